@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config, on N MI355X of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 metric   audio-sec/wall-sec (RTF^-1): seconds of 24 kHz audio whose mel spectrogram the hot path produces per wall second
@@ -12,10 +12,16 @@ workload configs[1]: one utterance per GPU, 64 text tokens, 16 AR candidates x 2
 step     one utterance through the whole hot path (tortoise_tts_amd/inference.py: inference.py:331-413 of the reference).
 N > 1    weak scaling: every rank runs its own utterance (BASELINE configs[2]); the only exchange is one RCCL all-gather of
          the sampled candidate ids per utterance (the hand-off to candidate scoring); value = N * audio / max-rank time.
-Also reported: `roofline` of the dominant kernel (HIP events inside libttk, see ttk_prof_*) with `roofline.phases` (AR decode
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else runs.  With --full it also reports
+`roofline` of the dominant kernel (HIP events inside libttk, see ttk_prof_*) with `roofline.phases` (AR decode
 against the HBM peak, latent pass and DDIM loop against the MFMA peak, from device events around the phases of one more
-un-instrumented step and SURVEY.md section 8d's algorithmic work), and `cpu_baseline` (the CPU oracle on a bounded sample of the
-same workload, rank 0, N = 1 only).
+un-instrumented step and SURVEY.md section 8d's algorithmic work), the informational `latent_k1_variant`, `pipelined_lines` and
+`stop_live` lines (rank 0, N = 1), and `cpu_baseline` (the CPU oracle on a bounded sample of the same workload, rank 0, N = 1 only);
+--no-roofline / --no-cpu-baseline leave parts of that out.  Those fields are null in a plain run.
+--dump-outputs DIR  after the timed steps, rank 0 writes what the last timed step returned (the mels and the aux arrays of
+         TTSHotPath.inference, per line with --shard candidates, the waveform with --with-vocoder) as DIR/<name>.npy: floats as float32,
+         integers as float64, at most 64 MB in all (a seeded sample of each array past its share).  The inputs, the weights and the
+         sampling RNG (torch's default seeds) are the same from run to run with the same arguments.
 
 N > 1 failure behaviour: a first multi-GPU run either prints its line or ends non-zero within minutes WITH a reason.
          Every rank logs to stderr and to gpurun_out/rank{r}.err; a stage watchdog (a daemon thread per rank, STAGE_BUDGET_S below) ends a rank that does not reach
@@ -51,8 +57,10 @@ def parse():
 	ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32", "fp8w", "fp8"],
 					help="BASELINE config 5 -- fp8w: bf16 arithmetic, block GEMM weights in fp8-e4m3; fp8: also fp8 activations into the diffusion block GEMMs (fp8 MFMA)")
 	ap.add_argument("--with-vocoder", action="store_true", help="BASELINE config 5's tail: the BigVGAN vocoder (bf16) inside the step; off for the headline metric")
-	ap.add_argument("--no-cpu-baseline", action="store_true")
-	ap.add_argument("--no-roofline", action="store_true")
+	ap.add_argument("--full", action="store_true", help="also the roofline / phase passes, the informational variants and the CPU baseline after the timed steps (off: the headline line only)")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+	ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+	ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline pass and the informational variants out")
 	ap.add_argument("--small", action="store_true", help="tiny models (plumbing check only; the number is NOT the metric)")
 	ap.add_argument("--no-graph", action="store_true", help="eager token loop (counter passes under rocprofv3 --pmc, which crashes on captured graphs); never the timed configuration")
 	ap.add_argument("--preflight", action="store_true", help="internal: the one-collective pre-flight child of an N > 1 rank (see the docstring)")
@@ -309,6 +317,35 @@ def effective_floor(dtype_name, n_text=TEXT_TOKENS, n_cand=CANDIDATES, n_mel=MEL
 			"ddim_step_us": step_us, "decode_token_us_at_mean_ctx": tok_us}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, d, limit=DUMP_LIMIT_BYTES):
+	"""--dump-outputs: every tensor or number of `outputs` (name -> value; None is skipped) as d/<name>.npy -- floating point as float32 (float64 stays
+	float64), integers and booleans as float64 (exact for ids).  When the whole exceeds `limit` bytes, every array larger than an even share of it is
+	replaced by a fixed sample of its flattened elements (sorted indices from numpy's Generator seeded 0: the same for every build at the same shape).
+	Returns {name: shape written}."""
+	import numpy as np
+	import torch
+	arrs = {}
+	for k, v in outputs.items():
+		if isinstance(v, torch.Tensor):
+			x = v.detach().cpu()
+			arrs[k] = (x.float() if x.is_floating_point() and x.dtype != torch.float64 else x.double()).numpy()
+		elif isinstance(v, (int, float)):
+			arrs[k] = np.array(v, dtype=np.float64)
+	if sum(x.nbytes for x in arrs.values()) > limit:
+		share = limit // len(arrs)
+		for k, x in arrs.items():
+			if x.nbytes > share:
+				idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+				arrs[k] = x.reshape(-1)[idx]
+	os.makedirs(d, exist_ok=True)
+	for k, x in arrs.items():
+		np.save(os.path.join(d, f"{k}.npy"), x)
+	return {k: tuple(x.shape) for k, x in arrs.items()}
+
+
 def log(msg):
 	line = f"[bench] {msg}"
 	print(line, file=sys.stderr, flush=True)
@@ -357,6 +394,10 @@ class StageWatchdog:
 		import threading
 		self.rank, self.world = rank, world
 		self.budgets = list(stage_budgets(a))
+		if os.environ.get("TTK_BENCH_STALL_AT") and int(os.environ.get("TTK_BENCH_STALL_RANK", "-1")) != rank:
+			# tests only: the ranks NOT made to stall wait in a collective for the one that is, with budgets armed at about the same instant; twice
+			# the budget makes the stalled rank's own watchdog the one that speaks, instead of whichever thread happens to poll first
+			self.budgets = [(n, 2 * b) for n, b in self.budgets]
 		self.elapsed = {}                      # marker -> seconds from the previous marker (goes into the result line: the first real N > 1 run calibrates the budgets)
 		self.last = time.monotonic()
 		self.i = 0
@@ -726,15 +767,25 @@ def main():
 	gdev = "cpu" if rehearsal else dev
 	gathered = [torch.empty((CANDIDATES, MEL_TOKENS), dtype=torch.long, device=gdev) for _ in range(world)] if world > 1 and not by_cand else None
 
+	last = {}        # --dump-outputs: what the latest step returned, name -> tensor
+
 	def step(exchange=True, marks=None):
 		if by_cand:     # one long-form utterance: its lines sampled one after the other, each with its candidates sharded over the ranks; the lines' winners
 			# are diffused as one ragged batch on their owner (TTSHotPath.inference_sharded_lines: each line's mel equals its own call's)
 			skw = {k: v for k, v in kw.items() if k != "candidates"}
 			res = tts.inference_sharded_lines(lines, ar_lat, df_lat, candidates=n_cand * world, phase_marks=marks, **skw)
+			if a.dump_outputs:
+				last.clear()
+				for i, (m, _, x) in enumerate(res):
+					last.update({f"line{i}_mels": m, **{f"line{i}_{k}": v for k, v in x.items()}})
 			return sum(r[1] for r in res)
 		mels, seconds, aux = tts.inference(text, ar_lat, df_lat, phase_marks=marks, **kw)
+		wav = None
 		if voc is not None:
-			voc.inference(mels)
+			wav = voc.inference(mels)
+		if a.dump_outputs:
+			last.clear()
+			last.update(mels=mels, wav=wav, **aux)
 		if world > 1 and exchange:   # hand the candidate ids to the scoring rank (RCCL all-gather over xGMI, 32 KB per rank)
 			dist.all_gather(gathered, aux["codes"].contiguous().to(gdev))
 		return seconds
@@ -762,8 +813,10 @@ def main():
 
 	mark("timed done")
 	log(f"timed {a.steps} steps in {dt:.3f}s")
+	if a.dump_outputs and rank == 0:
+		log(f"outputs of the last timed step: {dump_outputs(last, a.dump_outputs)}")
 	roof = None
-	if not a.no_roofline and (rank == 0 or by_cand):
+	if a.full and not a.no_roofline and (rank == 0 or by_cand):
 		# configs[1]/[2]: rank 0 alone (no collective in these passes).  configs[3]: the sharded step IS collectives, so every rank runs the two
 		# extra steps and rank 0 reports its own GPU's phases (it owns the diffused candidate: no scorer is attached, candidate 0 wins).
 		from tortoise_tts_amd import profiling
@@ -776,7 +829,7 @@ def main():
 	# informational, never `value`: the k = 1 variant SURVEY.md 8d row 2 asks to be reported beside the headline -- the candidate is chosen first and
 	# only its row goes through the dense latent pass (same bits out; the reference runs all 16, inference.py:370-379, and so does `value`)
 	k1 = None
-	if rank == 0 and world == 1 and not a.no_roofline and not by_cand:
+	if a.full and rank == 0 and world == 1 and not a.no_roofline and not by_cand:
 		kw1 = dict(kw, latents_for="winner")
 		tts.inference(text, ar_lat, df_lat, **kw1)
 		torch.cuda.synchronize()
@@ -790,7 +843,7 @@ def main():
 	# identical to the per-line calls.  Built on its own handle (max_batch = 4 x candidates) AFTER the headline was measured; `value` above
 	# stays the one-utterance-at-a-time figure of configs[1].
 	piped = None
-	if rank == 0 and world == 1 and not a.no_roofline and not by_cand:
+	if a.full and rank == 0 and world == 1 and not a.no_roofline and not by_cand:
 		n_lines, per_batch = 8, 4
 		lens = [64, 48, 88, 56, 72, 40, 80, 64][:n_lines]          # text lengths vary from line to line (mean 64): one captured token step serves them all
 		gl = torch.Generator().manual_seed(4321)
@@ -813,7 +866,7 @@ def main():
 	# a second handle's synthetic weights, so its probability is exactly 0, the length stays 250 and the ids must equal the headline's -- and the loop runs
 	# with the stopping test live: one event per token, the pinned flag read LAG tokens late (autoregressive.py `_token_loop`).
 	live = None
-	if rank == 0 and world == 1 and not a.no_roofline and not by_cand:
+	if a.full and rank == 0 and world == 1 and not a.no_roofline and not by_cand:
 		sd = W.synth_state_dict(W.ar_shapes(ar_cfg), 0)
 		sd["mel_head.bias"] = sd["mel_head.bias"].clone()
 		sd["mel_head.bias"][ar_cfg.stop_mel_token] = -1e9
@@ -833,9 +886,9 @@ def main():
 				"ids_equal_headline": bool(got_codes.shape == ref_codes.shape and torch.equal(got_codes, ref_codes)), "mel_tokens": int(got_codes.shape[1]),
 				"note": "stop token live (not suppressed, unreachable through mel_head.bias[stop] = -1e9): HF's per-token stopping test runs as the lagged pinned flag; not the headline metric"}
 		del tts_l, ar_l
-	log("roofline pass done; cpu baseline")
 	cpu = None
-	if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.small:
+	if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.small:
+		log("roofline pass done; cpu baseline")
 		cpu = cpu_baseline(1234, n_text, n_cand, n_mel, n_ddim, n_lines, light=True) if by_cand else cpu_baseline(1234)
 
 	if rank == 0:

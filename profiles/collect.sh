@@ -6,7 +6,7 @@ TAG=${1:-r01}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
-python3 bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.log
+python3 bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.log
 tail -1 $OUT/bench_$TAG.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof_$TAG $OUT/pmc_fetch_$TAG $OUT/pmc_write_$TAG

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_rank_candidate_sharded_bench_prints_one_line_with_phases():
 	env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
 	env["TTK_BENCH_REHEARSAL"] = "1"
-	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shard", "candidates", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shard", "candidates", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
 					   env=env, capture_output=True, text=True, timeout=900)
 	assert r.returncode == 0, r.stderr[-3000:]
 	lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -33,7 +33,7 @@ def test_two_rank_utterance_sharded_bench_prints_one_line():
 	whole-job value = 2 utterances' audio over the slower rank's time"""
 	env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
 	env["TTK_BENCH_REHEARSAL"] = "1"
-	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+	r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
 					   env=env, capture_output=True, text=True, timeout=900)
 	assert r.returncode == 0, r.stderr[-3000:]
 	lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

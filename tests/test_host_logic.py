@@ -326,3 +326,25 @@ def test_every_batch_a_handle_accepts_requests_no_more_fragment_rows_than_create
 		assert lib.ttk_ar_decode_geometry(dtype, cap + 1, 1, out) != 0 and lib.ttk_ar_decode_geometry(dtype, 8, 9, out) != 0
 	assert (True, 4) in seen and lib.ttk_ar_decode_geometry(_lib.DTYPES["bf16"], 48, 48, out) == 0 and out[0] == 48 and out[2] == 48      # round 3's faulting case (now a 3-tile form)
 	assert lib.ttk_ar_decode_geometry(_lib.DTYPES["bf16"], 64, 40, out) == 0 and out[0] == 64 and out[1] == 3 and out[2] == 48
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+	"""`bench.py --dump-outputs`: floats as float32 (float64 kept), ids as float64 (exact), numbers as 0-d arrays, None skipped; past the byte limit every array
+	over its even share becomes the same seeded sample of its elements on every call (two builds compare sample for sample)."""
+	import sys
+	sys.path.insert(0, ROOT)
+	import bench
+	codes = torch.randint(0, 8194, (16, 250))
+	out = {"mels": torch.randn(1, 100, 64, dtype=torch.bfloat16), "codes": codes, "x64": torch.randn(3, dtype=torch.float64), "best": 3, "scores": None}
+	shapes = bench.dump_outputs(out, str(tmp_path / "a"))
+	assert shapes == {"mels": (1, 100, 64), "codes": (16, 250), "x64": (3,), "best": ()} and sorted(os.listdir(tmp_path / "a")) == ["best.npy", "codes.npy", "mels.npy", "x64.npy"]
+	got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+	assert got["mels"].dtype == np.float32 and np.array_equal(got["mels"], out["mels"].float().numpy())
+	assert got["codes"].dtype == np.float64 and np.array_equal(got["codes"], codes.numpy()) and got["x64"].dtype == np.float64 and float(got["best"]) == 3.0
+	big = {"big": torch.randn(100_000), "small": torch.randn(10)}
+	for d in ("b", "c"):
+		bench.dump_outputs(big, str(tmp_path / d), limit=40_000)
+	b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+	assert b.shape == (5_000,) and np.array_equal(b, c) and np.isin(b, big["big"].numpy()).all()
+	assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), big["small"].numpy())
+	assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 40_000 + 2 * 128      # + the .npy headers
