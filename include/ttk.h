@@ -341,6 +341,30 @@ int ttk_cond_encode(ttk_cond* h, const float* mel, int b, int T, float* out, voi
  * then carries the tensor scale; 0 = none).  N % 128 == 0, K % 32 / 64 / 128 == 0.  No reference counterpart: exposed so the kernel behind every
  * conv / linear of both networks can be tested against a plain matmul of the same operands. */
 int ttk_gemm_nt(int dtype, const void* A, const void* W, int M, int N, int K, float out_scale, const float* bias, float* C, void* stream);
+/* Every form of the same kernel: the general descriptor, field for field what the networks' launches fill in (up to 12 segments -- row-shifted
+ * taps of a convolution, a channel concatenation -- an activation, a residual that may alias C, 16-bit output, the transposed [b][N][rows_per_batch]
+ * output and the fused GroupNorm32 statistics).  The tile and role choice is the one every product launch gets.
+ *   C = epi( sum_s shift_s(A_s) [M, K] . W_s [N, K]^T ),  W_s = W + w_off_s elements, rows [0, round_up(N, 128)) of ldw elements readable;
+ *   shift_s: row m reads A_s row m + shift_s if that stays inside m's batch element of rows_per_batch rows, else zeros;
+ *   epi: x out_scale (0 = none), + bias [N], act (0 none, 1 gelu_new, 2 SiLU), + residual f32 [M][ldr] (out_f32 only), in that order;
+ *   C: out_f32 ? f32 : the operand type (bf16 for TTK_FP8), [M][ldc]; transpose_out: f32 [M / rows_per_batch][N][rows_per_batch];
+ *   gn_part (f32 C only): one (count, mean, M2) triple per (batch element of gn_T rows, group of 32 channels, 64-row chunk) of C,
+ *   [ceil(M / gn_T)][32][gn_T / 64][3], only for the shapes whose tiles produce them (N == 1024, M and gn_T multiples of 64, not the 64-row tile).
+ * Returns TTK_E_ARG with a message when a precondition the kernels rely on fails. */
+typedef struct { const void* A; int64_t lda; int shift; int64_t w_off; } ttk_gemm_seg;
+typedef struct {
+	int nseg;
+	ttk_gemm_seg seg[12];
+	const void* W; int64_t ldw;
+	int M, N, K;                              /* K per segment: % 32 (f32), % 64 (bf16 / f16), % 128 (fp8) */
+	int rows_per_batch;                       /* > 0 when any shift != 0 or transpose_out */
+	int act;
+	const float* bias; const float* residual; int64_t ldr;
+	void* C; int64_t ldc;
+	float out_scale; int out_f32; int transpose_out;
+	int gn_T; float* gn_part;
+} ttk_gemm_desc;
+int ttk_gemm(int dtype, const ttk_gemm_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ mel front-ends of the conditioning path
  * TorchMelSpectrogram (models/arch_utils.py:361-395) and TacotronSTFT (:662-700 over STFT :560-623) as one handle type: reflect-padded

@@ -49,7 +49,8 @@ def test_role_kernels_equal_the_generic_kernel_bit_for_bit(diff_sd, monkeypatch,
 
 
 def test_role_kernels_in_a_ragged_line_batch(diff_sd, monkeypatch):
-	"""two lines as one batch (M = 4 x 1088 rows: 128 x 128 tiles for the 1024-wide roles; the shorter line's statistics come from the separate launch)"""
+	"""two lines as one batch (M = 4 x 1088 rows: 256 x 128 tiles for every role -- the wide-tile rule of launch_gemm_t, 272 tiles of 128 x 128 being two
+	rounds against one of 256 x 128; the shorter line's statistics come from the separate launch)"""
 	from tortoise_tts_amd.diffusion import get_diffuser
 	Ts = (1088, 1000)
 	noises = [torch.randn(1, 100, t, generator=gen(5 + i)).to(DEV) for i, t in enumerate(Ts)]

@@ -57,6 +57,19 @@ class SampleArgs(C.Structure):
 				("hist_ld", C.c_int64), ("hist_off", C.c_int64), ("live_rows", C.c_void_p), ("all_done", C.c_void_p), ("typical_mass", C.c_float)]
 
 
+class GemmSeg(C.Structure):
+	"""ttk_gemm_seg (include/ttk.h)"""
+	_fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("shift", C.c_int), ("w_off", C.c_int64)]
+
+
+class GemmDesc(C.Structure):
+	"""ttk_gemm_desc (include/ttk.h)"""
+	_fields_ = [("nseg", C.c_int), ("seg", GemmSeg * 12), ("W", C.c_void_p), ("ldw", C.c_int64), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+				("rows_per_batch", C.c_int), ("act", C.c_int), ("bias", C.c_void_p), ("residual", C.c_void_p), ("ldr", C.c_int64),
+				("C", C.c_void_p), ("ldc", C.c_int64), ("out_scale", C.c_float), ("out_f32", C.c_int), ("transpose_out", C.c_int),
+				("gn_T", C.c_int), ("gn_part", C.c_void_p)]
+
+
 class ProfResult(C.Structure):
 	_fields_ = [("ms", C.c_double), ("launches", C.c_int64), ("work", C.c_double)]
 
@@ -98,6 +111,7 @@ SYMBOLS = {
 	"ttk_mel_forward": (_I, [_P, _P, _I, _I, _P, _P]),
 	"ttk_resample_fir": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
 	"ttk_gemm_nt": (_I, [_I, _P, _P, _I, _I, _I, C.c_float, _P, _P, _P]),
+	"ttk_gemm": (_I, [_I, C.POINTER(GemmDesc), _P]),
 	"ttk_fp8_round_weights": (_I, [_P, _L, C.POINTER(C.c_float), _P]),
 	"ttk_sample_step": (_I, [_P, _L, _I, _I, _P, _L, _P, C.c_float, _L, _P, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P]),
 	"ttk_ar_decode_geometry": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),

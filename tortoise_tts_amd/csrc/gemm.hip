@@ -1308,12 +1308,15 @@ static void launch_tile_role(int role, const GemmParams& p, hipStream_t s, hipEv
 }
 
 int g_force_tile = -1;   // TTK_GEMM_TILE=0|1|2 (tuning only)
+// read on first use by EITHER of its readers: gemm_fuses_gn_stats may be asked before the first launch (a handle deciding where its statistics come from)
+static void read_force_tile() { if (g_force_tile < 0) { const char* e = getenv("TTK_GEMM_TILE"); g_force_tile = e ? atoi(e) + 100 : 99; } }
 static int pick_tile(int M, int N) {
 	const int t128 = ((M + 127) / 128) * ((N + 127) / 128);
 	const int t12864 = ((M + 127) / 128) * ((N + 63) / 64);
 	return t128 >= 256 ? 0 : (t12864 >= 128 ? 1 : 2);
 }
 bool gemm_fuses_gn_stats(int M, int N, int C, int T) {
+	read_force_tile();
 	if (g_force_tile >= 100 && g_force_tile - 100 == 2) return false;
 	return C == 1024 && N == C && T % 64 == 0 && M % 64 == 0 && pick_tile(M, N) != 2;
 }
@@ -1324,7 +1327,7 @@ bool gemm_fuses_gn_stats(int M, int N, int C, int T) {
 // 335-520 TF/s), 64x64 for tiny M.
 template <typename T>
 static void launch_gemm_t(const GemmParams& p, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-	if (g_force_tile < 0) { const char* e = getenv("TTK_GEMM_TILE"); g_force_tile = e ? atoi(e) + 100 : 99; }
+	read_force_tile();
 	int tile;
 	if (g_force_tile >= 100) tile = g_force_tile - 100;
 	else {

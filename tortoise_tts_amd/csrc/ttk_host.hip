@@ -187,3 +187,55 @@ extern "C" int ttk_gemm_nt(int dtype, const void* A, const void* W, int M, int N
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
+
+// Every form of the dense GEMM on caller-provided operands (include/ttk.h): the descriptor is GemmParams field for field, and launch_gemm picks tile and role
+// exactly as for the handles' launches.  What is checked here is what the kernels take for granted and cannot check themselves.
+static_assert(sizeof(ttk_gemm_seg) == 32 && sizeof(ttk_gemm_desc) == 496, "ttk_gemm_desc layout (tortoise_tts_amd/_lib.py mirrors it)");
+extern "C" int ttk_gemm(int dtype, const ttk_gemm_desc* d, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_gemm: null descriptor");
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16 || dtype == TTK_F16 || dtype == TTK_FP8, TTK_E_ARG, "ttk_gemm: dtype must be TTK_F32, TTK_BF16, TTK_F16 or TTK_FP8 (fp8-e4m3 bytes), got %d", dtype);
+	const int es = dtype == TTK_FP8 ? 1 : (dtype == TTK_F32 ? 4 : 2);
+	const int kmul = dtype == TTK_FP8 ? 128 : (dtype == TTK_F32 ? 32 : 64);
+	const int epc = 16 / es;      // elements per 16-byte staging chunk: row strides and offsets are whole chunks
+	auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+	TTK_REQUIRE(d->nseg >= 1 && d->nseg <= 12, TTK_E_ARG, "ttk_gemm: nseg must be 1..12, got %d", d->nseg);
+	TTK_REQUIRE(d->M >= 1 && d->N >= 1 && d->K >= kmul && d->K % kmul == 0, TTK_E_ARG, "ttk_gemm: need M >= 1, N >= 1, K %% %d == 0 (got M=%d N=%d K=%d)", kmul, d->M, d->N, d->K);
+	TTK_REQUIRE(d->act >= 0 && d->act <= 2, TTK_E_ARG, "ttk_gemm: act must be 0 (none), 1 (gelu_new) or 2 (SiLU), got %d", d->act);
+	TTK_REQUIRE(d->W && al16(d->W) && d->ldw >= d->K && d->ldw % epc == 0, TTK_E_ARG, "ttk_gemm: W must be 16-byte aligned with ldw >= K and ldw %% %d == 0 (ldw=%lld)", epc, (long long)d->ldw);
+	TTK_REQUIRE(d->rows_per_batch >= 0, TTK_E_ARG, "ttk_gemm: rows_per_batch < 0");
+	const int64_t npad = ((int64_t)d->N + 127) / 128 * 128;      // the kernels read W rows up to the next multiple of 128 (buffer offsets are 32-bit)
+	bool shifted = false;
+	for (int j = 0; j < d->nseg; ++j) {
+		const ttk_gemm_seg& sg = d->seg[j];
+		TTK_REQUIRE(sg.A && al16(sg.A) && sg.lda >= d->K && sg.lda % epc == 0, TTK_E_ARG, "ttk_gemm: segment %d: A must be 16-byte aligned with lda >= K and lda %% %d == 0 (lda=%lld)", j, epc, (long long)sg.lda);
+		TTK_REQUIRE(sg.w_off >= 0 && sg.w_off % epc == 0, TTK_E_ARG, "ttk_gemm: segment %d: w_off must be >= 0 and a multiple of %d", j, epc);
+		TTK_REQUIRE((int64_t)d->M * sg.lda * es < (1ll << 31) && (sg.w_off + (npad - 1) * d->ldw + d->K) * es < (1ll << 31), TTK_E_ARG,
+					"ttk_gemm: segment %d: A or W spans 2 GiB or more (32-bit buffer offsets)", j);
+		shifted |= sg.shift != 0;
+	}
+	TTK_REQUIRE(!(shifted || d->transpose_out) || d->rows_per_batch > 0, TTK_E_ARG, "ttk_gemm: shifted segments and transpose_out need rows_per_batch > 0");
+	TTK_REQUIRE(d->C && ((uintptr_t)d->C & 3) == 0, TTK_E_ARG, "ttk_gemm: C must be 4-byte aligned");
+	if (d->transpose_out) {
+		TTK_REQUIRE(d->out_f32 && d->M % d->rows_per_batch == 0 && !d->residual, TTK_E_ARG,
+					"ttk_gemm: transpose_out writes f32 [M / rows_per_batch][N][rows_per_batch]: needs out_f32, M %% rows_per_batch == 0 and no residual");
+	} else {
+		TTK_REQUIRE(d->ldc >= d->N, TTK_E_ARG, "ttk_gemm: ldc < N");
+	}
+	TTK_REQUIRE(!d->residual || (d->out_f32 && d->ldr >= d->N), TTK_E_ARG, "ttk_gemm: a residual needs out_f32 and ldr >= N (the 16-bit epilogue has none)");
+	if (d->gn_part) {
+		TTK_REQUIRE(d->gn_T > 0 && d->out_f32 && !d->transpose_out && gemm_fuses_gn_stats(d->M, d->N, d->N, d->gn_T), TTK_E_ARG,
+					"ttk_gemm: gn_part needs f32 row-major output and a shape whose tiles produce the statistics (N == 1024, M %% 64 == 0, gn_T %% 64 == 0, "
+					"no 64-row tile; got M=%d N=%d gn_T=%d)", d->M, d->N, d->gn_T);
+	}
+	GemmParams g = {};
+	g.nseg = d->nseg;
+	for (int j = 0; j < d->nseg; ++j) g.seg[j] = {d->seg[j].A, d->seg[j].lda, d->seg[j].shift, d->seg[j].w_off};
+	g.W = d->W; g.ldw = d->ldw; g.M = d->M; g.N = d->N; g.K = d->K; g.rows_per_batch = d->rows_per_batch; g.act = d->act;
+	g.bias = d->bias; g.residual = d->residual; g.ldr = d->ldr; g.C = d->C; g.ldc = d->ldc;
+	g.out_scale = d->out_scale; g.out_f32 = d->out_f32; g.transpose_out = d->transpose_out;
+	g.gn_T = d->gn_part ? d->gn_T : 0; g.gn_part = d->gn_part;
+	launch_gemm(dtype, g, (hipStream_t)stream);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
