@@ -294,6 +294,31 @@ int ttk_voc_destroy(ttk_voc* h);
  * padding frames of -11.5129 and the trimming of their 10 hops happen inside.                                             */
 int ttk_voc_inference(ttk_voc* h, const float* mel, int B, int T, float* audio, void* stream);
 
+/* ------------------------------------------------------------------ UnivNet vocoder (vocoder_type="vocoder")
+ * UnivNetGenerator of models/vocoder.py (:227-314): conv_pre, one LVCBlock per stride (convt_pre, KernelPredictor, the dilated convs
+ * and the location-variable convolutions with their gated updates), conv_post.  Weights: the generator's state_dict with weight norm
+ * folded into plain `weight` tensors (tortoise_tts_amd/univnet.py does that).                                                        */
+typedef struct ttk_univnet ttk_univnet;
+typedef struct {
+	int num_mels;                             /* 100 */
+	int noise_dim;                            /* 64 */
+	int channels;                             /* channel_size c_g: 16 or 32 */
+	int n_blocks;                             /* LVC blocks = number of strides, 1..4 */
+	int strides[4];                           /* 1..16 each; their product must equal hop_length */
+	int n_layers;                             /* dilations per block, 1..4 */
+	int dilations[4];
+	int kpnet_hidden;                         /* 64 */
+	int kpnet_conv_size;                      /* odd, <= 11 (3) */
+	int conv_kernel_size;                     /* LVC kernel size: 3 only */
+	int hop_length;                           /* 256 */
+	int dtype;                                /* TTK_F32 | TTK_BF16 */
+} ttk_univnet_config;
+int ttk_univnet_create(ttk_univnet** out, const ttk_univnet_config* cfg, const ttk_weight_view* weights, int n_weights);
+int ttk_univnet_destroy(ttk_univnet* h);
+/* UnivNetGenerator.inference(c, z) :302-314: mel [B, num_mels, T] f32 (denormalised log-mel), z [B, noise_dim, T + 10] f32 (the caller
+ * draws it) -> audio [B, 1, T * hop] f32 in [-1, 1]; the 10 padding frames of -11.5129 and the trimming of their hops happen inside. */
+int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int B, int T, float* audio, void* stream);
+
 /* ------------------------------------------------------------------ CLVP candidate scoring
  * models/clvp.py:21-136 (x-transformers branch): weights = CLVP.state_dict() with each attention's to_q / to_k / to_v stacked into
  * "<attn>.__qkv.weight" [3 * dim, dim] and "__rotary_inv_freq" [16] (RotaryEmbedding(32).inv_freq), as tortoise_tts_amd/clvp.py packs. */

@@ -100,6 +100,9 @@ SYMBOLS = {
 	"ttk_voc_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_voc_destroy": (_I, [_P]),
 	"ttk_voc_inference": (_I, [_P, _P, _I, _I, _P, _P]),
+	"ttk_univnet_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
+	"ttk_univnet_destroy": (_I, [_P]),
+	"ttk_univnet_inference": (_I, [_P, _P, _P, _I, _I, _P, _P]),
 	"ttk_clvp_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_clvp_destroy": (_I, [_P]),
 	"ttk_clvp_score": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),

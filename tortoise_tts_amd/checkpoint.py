@@ -288,6 +288,18 @@ def load_bigvgan(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key:
 	return BigVGAN(sd, cfg or VocoderConfig(), dtype=dtype, device=device)
 
 
+def load_univnet(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = "model_g"):
+	"""`load_model("vocoder")` (models/__init__.py:139-142): UnivNet's `vocoder.pth` keeps the generator under 'model_g'; weight norm is
+	folded and the config defaults to UnivNetGenerator's own (weights.UNIVNET_FULL)."""
+	from .univnet import UnivNet
+	from .weights import UnivNetConfig
+	obj = read_checkpoint(path)
+	if state_dict_key is not None and not (isinstance(obj, Mapping) and state_dict_key in obj):
+		state_dict_key = None                      # a bare generator state_dict
+	sd = unwrap_state_dict(obj, state_dict_key)
+	return UnivNet(sd, cfg or UnivNetConfig(), dtype=dtype, device=device)
+
+
 def load_clvp(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = None):
 	"""`load_model("clvp")` (models/__init__.py:111-113): `clvp2.pth` is a plain state_dict of the x-transformers CLVP."""
 	from .clvp import CLVP

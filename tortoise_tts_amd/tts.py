@@ -27,8 +27,9 @@ def set_seed(seed=None) -> int:
 
 class TTS:
 	def __init__(self, autoregressive, diffusion, tokenizer, *, vocoder=None, clvp=None, conditioning_encoder=None, contextual_embedder=None,
-				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None):
+				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None):
 		self.hot = TTSHotPath(autoregressive, diffusion, vocoder=vocoder, clvp=clvp)
+		self.univnet = univnet          # tortoise_tts_amd.UnivNet: the vocoder of vocoder_type="vocoder"
 		self.tokenizer = tokenizer
 		self.conditioning_encoder, self.contextual_embedder, self.tms, self.stft = conditioning_encoder, contextual_embedder, tms, stft
 		self.device = autoregressive.device
@@ -58,13 +59,17 @@ class TTS:
 	def inference(self, text: str, references, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
 				  seed=None, candidates=1, references_sr: int = 22050) -> Tuple[torch.Tensor, int]:
-		"""inference.py:142-425 (the BigVGAN branch): every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict
-		`encode_audio` returns) -> (wav [1, 1, samples] -- the lines concatenated in time -- , 24000)."""
-		if vocoder_type != "bigvgan":
-			raise NotImplementedError("only the BigVGAN vocoder path is built (the HiFiGAN streaming branch, inference.py:263-320, is not)")
+		"""inference.py:142-425 (the BigVGAN and UnivNet branches): every line of `text` spoken in the voice of `references` (clip tensor(s), or
+		the dict `encode_audio` returns) -> (wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the
+		`vocoder=` part, "vocoder" the `univnet=` part (see `_univnet_wav` for its noise)."""
+		if vocoder_type not in ("bigvgan", "vocoder"):
+			raise NotImplementedError("only the BigVGAN and UnivNet vocoder paths are built (the HiFiGAN streaming branch, inference.py:263-320, is not)")
 		if beam_width != 1:
 			raise NotImplementedError("beam search is not on the inference path (num_beams=1, inference.py:343)")
-		if self.hot.vocoder is None:
+		if vocoder_type == "vocoder":
+			if self.univnet is None:
+				raise ValueError("TTS was built without a UnivNet vocoder (univnet=)")
+		elif self.hot.vocoder is None:
 			raise ValueError("TTS was built without a vocoder")
 		ar_latent, diff_latent = self.encode_audio(references, references_sr)["latent"]
 		set_seed(seed)
@@ -76,10 +81,19 @@ class TTS:
 			lines.append(tokens)
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
 				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates)
+		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
 		if len(lines) > 1 and diffusion_sampler == "ddim":
 			# several lines: their sampling as one decode batch, the diffusion of a line under the sampling of later ones (TTSHotPath.inference_lines:
 			# the same waveforms as the line-by-line loop of inference.py:237-422, which is what the else branch runs)
-			wavs = [self.hot.vocoder.inference(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, **kw)]
+			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, **kw)]
 		else:
-			wavs = [self.hot.inference_to_wav(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)[0] for tokens in lines]
+			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)[0]) for tokens in lines]
 		return torch.concat(wavs, dim=-1), SAMPLE_RATE
+
+	def _univnet_wav(self, mels: torch.Tensor) -> torch.Tensor:
+		"""UnivNet on one line's mel [1, 100, T] with the noise the reference draws for that line: `generate` reseeds every generator to 0 per
+		line (`setup_seed(0)`, stream_generator.py:36-45, 296), nothing after it draws from the CPU generator (AR sampling and the diffusion noise
+		use the device one), so `vocoder.inference`'s `torch.randn` (models/vocoder.py:309) is the first draw after `torch.manual_seed(0)`.
+		The batched-lines path does not reseed per line, so the draw is made here from a generator in that state, on every path."""
+		z = self.univnet.draw_noise(mels.shape[0], mels.shape[-1], generator=torch.Generator().manual_seed(0))
+		return self.univnet.inference(mels, z)

@@ -97,6 +97,30 @@ class VocoderConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class UnivNetConfig:
+	"""`UnivNetGenerator.__init__` defaults (models/vocoder.py:234-236), the generator TorToiSe's `vocoder.pth` holds (key `model_g`)."""
+	num_mels: int = 100
+	noise_dim: int = 64
+	channel_size: int = 32
+	strides: Tuple[int, ...] = (8, 8, 4)
+	dilations: Tuple[int, ...] = (1, 3, 9, 27)
+	kpnet_hidden: int = 64
+	kpnet_conv_size: int = 3
+	conv_kernel_size: int = 3
+	lrelu_slope: float = 0.2
+	hop_length: int = 256
+	sampling_rate: int = 24000
+
+	def cond_hops(self):
+		"""cond_hop_length of each LVCBlock: the running product of the strides"""
+		out, h = [], 1
+		for s in self.strides:
+			h *= s
+			out.append(h)
+		return out
+
+
+@dataclasses.dataclass(frozen=True)
 class CLVPConfig:
 	"""`CLVP.__init__` defaults, models/clvp.py:29-46 (the x-transformers branch, `use_xformers=True`)."""
 	dim: int = 768                      # dim_text = dim_speech = dim_latent
@@ -117,6 +141,8 @@ CLVP_FULL = CLVPConfig()
 VOC_SMALL = VocoderConfig(upsample_rates=(4, 2), upsample_kernel_sizes=(8, 4), upsample_initial_channel=128,
 						  resblock_kernel_sizes=(3, 7), resblock_dilation_sizes=((1, 3, 5), (1, 3, 5)))
 VOC_FULL = VocoderConfig()
+UNIVNET_FULL = UnivNetConfig()
+UNIVNET_SMALL = UnivNetConfig(channel_size=16, strides=(4, 4), dilations=(1, 3), hop_length=16)
 AR_FULL = ARConfig()
 DIFF_SMALL = DiffusionConfig(model_channels=128, num_layers=2, in_latent_channels=128, num_heads=2)
 DIFF_FULL = DiffusionConfig()
@@ -242,6 +268,40 @@ def vocoder_shapes(c: VocoderConfig) -> Dict[str, Tuple[int, ...]]:
 	return s
 
 
+def univnet_shapes(c: UnivNetConfig) -> Dict[str, Tuple[int, ...]]:
+	"""`UnivNetGenerator.state_dict()` with weight norm folded (plain `weight` instead of `weight_g` / `weight_v`)."""
+	C, H, kc, nl = c.channel_size, c.kpnet_hidden, c.kpnet_conv_size, len(c.dilations)
+	s: Dict[str, Tuple[int, ...]] = {}
+	for i, st in enumerate(c.strides):
+		p = f"res_stack.{i}."
+		kp = p + "kernel_predictor."
+		s[kp + "input_conv.0.weight"] = (H, c.num_mels, 5); s[kp + "input_conv.0.bias"] = (H,)
+		for j in range(3):
+			for m in (1, 3):
+				s[kp + f"residual_convs.{j}.{m}.weight"] = (H, H, kc); s[kp + f"residual_convs.{j}.{m}.bias"] = (H,)
+		s[kp + "kernel_conv.weight"] = (nl * C * 2 * C * c.conv_kernel_size, H, kc); s[kp + "kernel_conv.bias"] = (nl * C * 2 * C * c.conv_kernel_size,)
+		s[kp + "bias_conv.weight"] = (nl * 2 * C, H, kc); s[kp + "bias_conv.bias"] = (nl * 2 * C,)
+		s[p + "convt_pre.1.weight"] = (C, C, 2 * st); s[p + "convt_pre.1.bias"] = (C,)          # ConvTranspose1d: [in, out, k]
+		for n in range(nl):
+			s[p + f"conv_blocks.{n}.1.weight"] = (C, C, c.conv_kernel_size); s[p + f"conv_blocks.{n}.1.bias"] = (C,)
+	s["conv_pre.weight"] = (C, c.noise_dim, 7); s["conv_pre.bias"] = (C,)
+	s["conv_post.1.weight"] = (1, C, 7); s["conv_post.1.bias"] = (1,)
+	return s
+
+
+def weight_norm_names(shapes: Dict[str, Tuple[int, ...]]) -> Dict[str, Tuple[int, ...]]:
+	"""The same keys as a checkpoint of `nn.utils.weight_norm` modules spells them: every conv `weight` becomes `weight_g` [out, 1, 1]
+	and `weight_v` (the norm is over every dimension but the first)."""
+	out: Dict[str, Tuple[int, ...]] = {}
+	for k, v in shapes.items():
+		if k.endswith(".weight") and len(v) == 3:
+			out[k[:-len("weight")] + "weight_g"] = (v[0], 1, 1)
+			out[k[:-len("weight")] + "weight_v"] = v
+		else:
+			out[k] = v
+	return out
+
+
 def clvp_shapes(c: CLVPConfig) -> Dict[str, Tuple[int, ...]]:
 	"""`CLVP.state_dict()` without the constant rotary `inv_freq` buffers.  Layer 2i is attention, 2i+1 feed-forward; index `.0.0` is the
 	pre-branch RMSNorm, `.1.wrap` the block inside arch_utils.CheckpointedLayer."""
@@ -296,6 +356,8 @@ def _gain_for(name: str, shape: Tuple[int, ...]) -> Tuple[str, float]:
 		for s in shape[1:]:
 			fan_in *= s
 	gain = 1.0
+	if "kernel_predictor.kernel_conv" in name:   # UnivNet: each predicted kernel meets in * k = 96 samples; keep the LVC output O(1)
+		gain = 0.1
 	if name.endswith("c_proj.weight") or "proj_out" in name or "out_layers.3" in name:
 		gain = 0.5
 	if "emb_layers" in name:
