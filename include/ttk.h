@@ -319,6 +319,31 @@ int ttk_univnet_destroy(ttk_univnet* h);
  * draws it) -> audio [B, 1, T * hop] f32 in [-1, 1]; the 10 padding frames of -11.5129 and the trimming of their hops happen inside. */
 int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int B, int T, float* audio, void* stream);
 
+/* ------------------------------------------------------------------ HiFiGAN vocoder (vocoder_type="hifigan")
+ * HifiganGenerator of models/hifigan.py (:161-305), resblock_type "1", with a cond_layer: the AR model's final_norm latents, one per
+ * mel token, to audio -- no diffusion.  Weights: the generator's state_dict with weight norm folded into plain `weight` tensors
+ * (tortoise_tts_amd/hifigan.py does that).  One utterance per call.                                                                 */
+typedef struct ttk_hifigan ttk_hifigan;
+typedef struct {
+	int in_channels;                          /* 1024: the latent width */
+	int cond_channels;                        /* 1024: the conditioning latent's width; 0 (no cond_layer) is refused */
+	int upsample_initial_channel;             /* 512; halves per stage, every stage a multiple of 8 */
+	int n_ups;                                /* <= 8 */
+	int up_rate[8], up_kernel[8];             /* kernel % rate == 0, (kernel - rate) even */
+	int n_kernels;                            /* ResBlocks per stage, 1..4 */
+	int rb_kernel[4];                         /* odd, <= 11 */
+	int rb_dil[4][3];
+	int resblock_type;                        /* 1 only */
+	int dtype;                                /* TTK_F32 | TTK_BF16 */
+} ttk_hifigan_config;
+int ttk_hifigan_create(ttk_hifigan** out, const ttk_hifigan_config* cfg, const ttk_weight_view* weights, int n_weights);
+int ttk_hifigan_destroy(ttk_hifigan* h);
+/* once per utterance: g f32 [cond_channels] on the device, the AR conditioning latent; cond_layer(g) is folded into conv_pre's bias */
+int ttk_hifigan_set_cond(ttk_hifigan* h, const float* g, void* stream);
+/* HifiganGenerator.inference(c, g) :270-296: latents f32 [n, in_channels] -> audio f32 [hop * F], F = floor(4 n * 24000 / 22050) frames
+ * (the two linear interpolations happen inside), hop = the product of the upsample rates.                                         */
+int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* audio, void* stream);
+
 /* ------------------------------------------------------------------ CLVP candidate scoring
  * models/clvp.py:21-136 (x-transformers branch): weights = CLVP.state_dict() with each attention's to_q / to_k / to_v stacked into
  * "<attn>.__qkv.weight" [3 * dim, dim] and "__rotary_inv_freq" [16] (RotaryEmbedding(32).inv_freq), as tortoise_tts_amd/clvp.py packs. */

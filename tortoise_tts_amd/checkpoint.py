@@ -300,6 +300,15 @@ def load_univnet(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key:
 	return UnivNet(sd, cfg or UnivNetConfig(), dtype=dtype, device=device)
 
 
+def load_hifigan(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = None):
+	"""`load_model("hifigan")` (models/__init__.py:126-138): `hifigan.pth` is a plain state_dict of the weight-normed HifiganGenerator; weight
+	norm is folded and the config defaults to the one the reference builds it with (weights.HIFIGAN_FULL)."""
+	from .hifigan import HiFiGAN
+	from .weights import HiFiGANConfig
+	sd = unwrap_state_dict(read_checkpoint(path), state_dict_key)
+	return HiFiGAN(sd, cfg or HiFiGANConfig(), dtype=dtype, device=device)
+
+
 def load_clvp(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = None):
 	"""`load_model("clvp")` (models/__init__.py:111-113): `clvp2.pth` is a plain state_dict of the x-transformers CLVP."""
 	from .clvp import CLVP

@@ -27,9 +27,10 @@ def set_seed(seed=None) -> int:
 
 class TTS:
 	def __init__(self, autoregressive, diffusion, tokenizer, *, vocoder=None, clvp=None, conditioning_encoder=None, contextual_embedder=None,
-				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None):
+				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None, hifigan=None):
 		self.hot = TTSHotPath(autoregressive, diffusion, vocoder=vocoder, clvp=clvp)
 		self.univnet = univnet          # tortoise_tts_amd.UnivNet: the vocoder of vocoder_type="vocoder"
+		self.hifigan = hifigan          # tortoise_tts_amd.HiFiGAN: the vocoder of vocoder_type="hifigan" (AR latents -> audio, no diffusion)
 		self.tokenizer = tokenizer
 		self.conditioning_encoder, self.contextual_embedder, self.tms, self.stft = conditioning_encoder, contextual_embedder, tms, stft
 		self.device = autoregressive.device
@@ -59,14 +60,19 @@ class TTS:
 	def inference(self, text: str, references, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
 				  seed=None, candidates=1, references_sr: int = 22050) -> Tuple[torch.Tensor, int]:
-		"""inference.py:142-425 (the BigVGAN and UnivNet branches): every line of `text` spoken in the voice of `references` (clip tensor(s), or
-		the dict `encode_audio` returns) -> (wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the
-		`vocoder=` part, "vocoder" the `univnet=` part (see `_univnet_wav` for its noise)."""
-		if vocoder_type not in ("bigvgan", "vocoder"):
-			raise NotImplementedError("only the BigVGAN and UnivNet vocoder paths are built (the HiFiGAN streaming branch, inference.py:263-320, is not)")
+		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
+		(wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the `vocoder=` part, "vocoder" the
+		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
+		diffusion model (see `_hifigan_wav`; the reference returns [1, samples] on that branch, here the shape is that of the other two)."""
+		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
+			raise NotImplementedError(f"vocoder_type {vocoder_type!r} is unknown ('bigvgan', 'vocoder', 'hifigan')")
+		if vocoder_type == "hifigan" and self.hifigan is None:
+			raise NotImplementedError("TTS was built without a HiFiGAN vocoder (hifigan=): the streaming branch, inference.py:250-329, needs one")
 		if beam_width != 1:
 			raise NotImplementedError("beam search is not on the inference path (num_beams=1, inference.py:343)")
-		if vocoder_type == "vocoder":
+		if vocoder_type == "hifigan":
+			pass
+		elif vocoder_type == "vocoder":
 			if self.univnet is None:
 				raise ValueError("TTS was built without a UnivNet vocoder (univnet=)")
 		elif self.hot.vocoder is None:
@@ -79,6 +85,10 @@ class TTS:
 			if tokens.shape[1] == 0:
 				raise ValueError("empty line (the reference fails inside the embedding here)")
 			lines.append(tokens)
+		if vocoder_type == "hifigan":
+			wavs = [self._hifigan_wav(tokens, ar_latent, max_ar_steps=max_ar_steps, ar_temp=ar_temp, top_p=top_p, top_k=top_k,
+									  repetition_penalty=repetition_penalty, length_penalty=length_penalty) for tokens in lines]
+			return torch.concat(wavs, dim=-1), SAMPLE_RATE
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
 				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
@@ -97,3 +107,27 @@ class TTS:
 		The batched-lines path does not reseed per line, so the draw is made here from a generator in that state, on every path."""
 		z = self.univnet.draw_noise(mels.shape[0], mels.shape[-1], generator=torch.Generator().manual_seed(0))
 		return self.univnet.inference(mels, z)
+
+	def hifigan_chunks(self, tokens: torch.Tensor, ar_latent: torch.Tensor, *, max_ar_steps=500, ar_temp=0.8, top_p=1.0, top_k=0, repetition_penalty=1.0,
+					   length_penalty=1.0):
+		"""One line of the HiFiGAN branch (inference.py:250-320) as a generator of waveform chunks [1, samples]: `compute_embeddings` ->
+		`get_generator` -> `HiFiGAN.stream`.  The first chunk is there after 60 tokens, while sampling goes on.  `max_length` is
+		min(500, prefix + max_ar_steps): the reference hard-codes 500 in total (stream_generator defaults) and ignores `max_ar_steps`; the
+		default call is the same."""
+		ar = self.hot.autoregressive
+		inputs = ar.compute_embeddings(ar_latent, tokens)
+		pairs = ar.get_generator(inputs=inputs, max_length=min(500, inputs.shape[1] + max_ar_steps), top_k=top_k, top_p=top_p, temperature=ar_temp,
+								 do_sample=True, num_return_sequences=1, length_penalty=length_penalty, repetition_penalty=repetition_penalty)
+		chunks = self.hifigan.stream(pairs, ar_latent)
+		while True:
+			with torch.inference_mode():      # per step, not around the yield: the consumer's own mode is its own between two chunks
+				try:
+					chunk = next(chunks)
+				except StopIteration:
+					return
+			yield chunk
+
+	def _hifigan_wav(self, tokens: torch.Tensor, ar_latent: torch.Tensor, **kw) -> torch.Tensor:
+		"""a line's chunks concatenated, [1, 1, samples].  `candidates` and `max_diffusion_steps` play no part (one sequence, no diffusion), nor
+		does `seed`: the token loop reseeds to 0 per line (stream_generator.py:36-45, 296) and nothing else draws."""
+		return torch.concat(list(self.hifigan_chunks(tokens, ar_latent, **kw)), dim=-1)[None]

@@ -11,6 +11,7 @@ so any subset can be regenerated bit-identically on any machine without the refe
 from __future__ import annotations
 
 import dataclasses
+import math
 import zlib
 from typing import Dict, Tuple
 
@@ -121,6 +122,31 @@ class UnivNetConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class HiFiGANConfig:
+	"""`HifiganGenerator(...)` as models/__init__.py:126-138 builds it for `hifigan.pth` (out_channels is 1)."""
+	in_channels: int = 1024
+	cond_channels: int = 1024
+	upsample_initial_channel: int = 512
+	upsample_factors: Tuple[int, ...] = (8, 8, 2, 2)
+	upsample_kernel_sizes: Tuple[int, ...] = (16, 16, 4, 4)
+	resblock_type: str = "1"
+	resblock_kernel_sizes: Tuple[int, ...] = (3, 7, 11)
+	resblock_dilation_sizes: Tuple[Tuple[int, ...], ...] = ((1, 3, 5), (1, 3, 5), (1, 3, 5))
+	sampling_rate: int = 24000
+
+	@property
+	def hop_length(self):
+		h = 1
+		for u in self.upsample_factors:
+			h *= u
+		return h
+
+	def frames(self, n: int) -> int:
+		"""frames after the two interpolations of `inference` (models/hifigan.py:285-294): floor(floor(n * 4) * 24000 / 22050), in double as torch computes it"""
+		return int(math.floor(float(4 * n) * (24000 / 22050)))
+
+
+@dataclasses.dataclass(frozen=True)
 class CLVPConfig:
 	"""`CLVP.__init__` defaults, models/clvp.py:29-46 (the x-transformers branch, `use_xformers=True`)."""
 	dim: int = 768                      # dim_text = dim_speech = dim_latent
@@ -144,6 +170,9 @@ VOC_FULL = VocoderConfig()
 UNIVNET_FULL = UnivNetConfig()
 UNIVNET_SMALL = UnivNetConfig(channel_size=16, strides=(4, 4), dilations=(1, 3), hop_length=16)
 AR_FULL = ARConfig()
+HIFIGAN_FULL = HiFiGANConfig()
+# latents of AR_SMALL (128 wide); stages of 64 and 32 channels, so both widths of the narrow-channel MFMA convolution are reached
+HIFIGAN_SMALL = HiFiGANConfig(in_channels=128, cond_channels=128, upsample_initial_channel=128, upsample_factors=(4, 2), upsample_kernel_sizes=(8, 4))
 DIFF_SMALL = DiffusionConfig(model_channels=128, num_layers=2, in_latent_channels=128, num_heads=2)
 DIFF_FULL = DiffusionConfig()
 
@@ -286,6 +315,27 @@ def univnet_shapes(c: UnivNetConfig) -> Dict[str, Tuple[int, ...]]:
 			s[p + f"conv_blocks.{n}.1.weight"] = (C, C, c.conv_kernel_size); s[p + f"conv_blocks.{n}.1.bias"] = (C,)
 	s["conv_pre.weight"] = (C, c.noise_dim, 7); s["conv_pre.bias"] = (C,)
 	s["conv_post.1.weight"] = (1, C, 7); s["conv_post.1.bias"] = (1,)
+	return s
+
+
+def hifigan_shapes(c: HiFiGANConfig) -> Dict[str, Tuple[int, ...]]:
+	"""`HifiganGenerator.state_dict()` with weight norm folded (plain `weight` instead of `weight_g` / `weight_v`; `cond_layer` carries none)."""
+	ch0 = c.upsample_initial_channel
+	s: Dict[str, Tuple[int, ...]] = {"conv_pre.weight": (ch0, c.in_channels, 7), "conv_pre.bias": (ch0,)}
+	nk = len(c.resblock_kernel_sizes)
+	ch = ch0
+	for i, (u, k) in enumerate(zip(c.upsample_factors, c.upsample_kernel_sizes)):
+		cin, ch = ch0 // (2 ** i), ch0 // (2 ** (i + 1))
+		s[f"ups.{i}.weight"] = (cin, ch, k)                   # ConvTranspose1d: [in, out, k]
+		s[f"ups.{i}.bias"] = (ch,)
+		for j, kk in enumerate(c.resblock_kernel_sizes):
+			p = f"resblocks.{i * nk + j}."
+			for m in range(3):
+				s[p + f"convs1.{m}.weight"] = (ch, ch, kk); s[p + f"convs1.{m}.bias"] = (ch,)
+				s[p + f"convs2.{m}.weight"] = (ch, ch, kk); s[p + f"convs2.{m}.bias"] = (ch,)
+	s["conv_post.weight"] = (1, ch, 7); s["conv_post.bias"] = (1,)
+	if c.cond_channels > 0:
+		s["cond_layer.weight"] = (ch0, c.cond_channels, 1); s["cond_layer.bias"] = (ch0,)
 	return s
 
 
