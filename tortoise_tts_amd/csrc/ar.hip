@@ -125,6 +125,11 @@ struct ttk_ar {
 	WsBuf ws_x, ws_a, ws_qkv, ws_ao, ws_h;
 	int B = 0, P = 0, k = 0, ready = 0;
 	int Pmax = 0;           // longest prefix of the batch (capacity checks); == P for one line
+	~ttk_ar() {             // also the failure path of ttk_ar_create: whatever was made so far; the workspaces and the arena free themselves after this
+		for (int i = 0; i < 3; ++i) { if (side[i]) (void)hipStreamDestroy(side[i]); if (ev_join[i]) (void)hipEventDestroy(ev_join[i]); }
+		if (ev_fork) (void)hipEventDestroy(ev_fork);
+		attn_pos_slot_release(pos_slot);
+	}
 };
 
 // Debug aid: per-call scratch must not outlive its call.  A captured token step that kept reading one of these buffers would see
@@ -289,77 +294,74 @@ int ttk_ar_create(ttk_ar** out, const ttk_ar_config* cfg, const ttk_weight_view*
 	TTK_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= (cfg->dtype == TTK_F32 ? 32 : 64), TTK_E_ARG,
 				"ttk_ar_create: max_batch %d out of range", cfg->max_batch);
 	TTK_REQUIRE(cfg->max_ctx >= 8, TTK_E_ARG, "ttk_ar_create: max_ctx %d too small", cfg->max_ctx);
-	ttk_ar* h = new ttk_ar();
+	std::unique_ptr<ttk_ar> h(new ttk_ar());
 	h->cfg = *cfg;
 	h->wdt = cfg->dtype;
 	h->dt = kernel_dtype(cfg->dtype);
 	h->es = dtype_size(h->dt);
 	WeightMap wm(w, n_w);
 	const int d = cfg->model_dim;
-	int rc = TTK_OK;
-	auto fail = [&](int code) { attn_pos_slot_release(h->pos_slot); h->arena.release(); delete h; return code; };
-#define AR_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
 	h->L.resize(cfg->layers);
 	for (int l = 0; l < cfg->layers; ++l) {
 		const std::string p = "gpt.h." + std::to_string(l) + ".";
 		ARLayer& L = h->L[l];
-		AR_TRY(upload_f32(h->arena, wm, p + "ln_1.weight", d, &L.ln1_g));
-		AR_TRY(upload_f32(h->arena, wm, p + "ln_1.bias", d, &L.ln1_b));
-		AR_TRY(upload_f32(h->arena, wm, p + "ln_2.weight", d, &L.ln2_g));
-		AR_TRY(upload_f32(h->arena, wm, p + "ln_2.bias", d, &L.ln2_b));
-		AR_TRY(upload_mat(h->arena, wm, h->wdt, p + "attn.c_attn.weight", p + "attn.c_attn.bias", PK_KN, 3 * d, d, true, &L.attn));
-		AR_TRY(upload_mat(h->arena, wm, h->wdt, p + "attn.c_proj.weight", p + "attn.c_proj.bias", PK_KN, d, d, true, &L.proj));
-		AR_TRY(upload_mat(h->arena, wm, h->wdt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", PK_KN, 4 * d, d, true, &L.fc));
-		AR_TRY(upload_mat(h->arena, wm, h->wdt, p + "mlp.c_proj.weight", p + "mlp.c_proj.bias", PK_KN, d, 4 * d, true, &L.proj2));
+		TTK_TRY(upload_f32(h->arena, wm, p + "ln_1.weight", d, &L.ln1_g));
+		TTK_TRY(upload_f32(h->arena, wm, p + "ln_1.bias", d, &L.ln1_b));
+		TTK_TRY(upload_f32(h->arena, wm, p + "ln_2.weight", d, &L.ln2_g));
+		TTK_TRY(upload_f32(h->arena, wm, p + "ln_2.bias", d, &L.ln2_b));
+		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "attn.c_attn.weight", p + "attn.c_attn.bias", PK_KN, 3 * d, d, true, &L.attn));
+		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "attn.c_proj.weight", p + "attn.c_proj.bias", PK_KN, d, d, true, &L.proj));
+		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", PK_KN, 4 * d, d, true, &L.fc));
+		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "mlp.c_proj.weight", p + "mlp.c_proj.bias", PK_KN, d, 4 * d, true, &L.proj2));
 		{   // (fp8 weights: the fold is taken of the rounded matrices and kept in bf16 -- TTK_FP8W stays "bf16 on the rounded weights")
-			AR_TRY(fold_layernorm(h->arena, wm, h->dt, p + "attn.c_attn.weight", p + "attn.c_attn.bias", p + "ln_1.weight", p + "ln_1.bias", &L.attn));
-			AR_TRY(fold_layernorm(h->arena, wm, h->dt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", p + "ln_2.weight", p + "ln_2.bias", &L.fc));
+			TTK_TRY(fold_layernorm(h->arena, wm, h->dt, p + "attn.c_attn.weight", p + "attn.c_attn.bias", p + "ln_1.weight", p + "ln_1.bias", &L.attn));
+			TTK_TRY(fold_layernorm(h->arena, wm, h->dt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", p + "ln_2.weight", p + "ln_2.bias", &L.fc));
 		}
 	}
-	AR_TRY(upload_f32(h->arena, wm, "gpt.ln_f.weight", d, &h->lnf_g));
-	AR_TRY(upload_f32(h->arena, wm, "gpt.ln_f.bias", d, &h->lnf_b));
-	AR_TRY(upload_f32(h->arena, wm, "final_norm.weight", d, &h->fn_g));
-	AR_TRY(upload_f32(h->arena, wm, "final_norm.bias", d, &h->fn_b));
-	AR_TRY(upload_mat(h->arena, wm, h->dt, "mel_head.weight", "mel_head.bias", PK_NK, cfg->number_mel_codes, d, true, &h->head));
-	AR_TRY(upload_f32(h->arena, wm, "text_embedding.weight", (int64_t)cfg->number_text_tokens_p1 * d, &h->text_emb));
-	AR_TRY(upload_f32(h->arena, wm, "mel_embedding.weight", (int64_t)cfg->number_mel_codes * d, &h->mel_emb));
-	AR_TRY(upload_f32(h->arena, wm, "mel_pos_embedding.emb.weight", (int64_t)cfg->max_mel_seq_len * d, &h->mel_pos));
-	AR_TRY(upload_f32(h->arena, wm, "text_pos_embedding.emb.weight", (int64_t)cfg->max_text_seq_len * d, &h->text_pos));
+	TTK_TRY(upload_f32(h->arena, wm, "gpt.ln_f.weight", d, &h->lnf_g));
+	TTK_TRY(upload_f32(h->arena, wm, "gpt.ln_f.bias", d, &h->lnf_b));
+	TTK_TRY(upload_f32(h->arena, wm, "final_norm.weight", d, &h->fn_g));
+	TTK_TRY(upload_f32(h->arena, wm, "final_norm.bias", d, &h->fn_b));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "mel_head.weight", "mel_head.bias", PK_NK, cfg->number_mel_codes, d, true, &h->head));
+	TTK_TRY(upload_f32(h->arena, wm, "text_embedding.weight", (int64_t)cfg->number_text_tokens_p1 * d, &h->text_emb));
+	TTK_TRY(upload_f32(h->arena, wm, "mel_embedding.weight", (int64_t)cfg->number_mel_codes * d, &h->mel_emb));
+	TTK_TRY(upload_f32(h->arena, wm, "mel_pos_embedding.emb.weight", (int64_t)cfg->max_mel_seq_len * d, &h->mel_pos));
+	TTK_TRY(upload_f32(h->arena, wm, "text_pos_embedding.emb.weight", (int64_t)cfg->max_text_seq_len * d, &h->text_pos));
 	h->kv_layer_stride = (size_t)cfg->max_batch * cfg->heads * cfg->max_ctx * 64;
-	AR_TRY(h->arena.alloc(&h->kc, h->kv_layer_stride * cfg->layers * h->es));
-	AR_TRY(h->arena.alloc(&h->vc, h->kv_layer_stride * cfg->layers * h->es));
-	AR_TRY(h->arena.alloc((void**)&h->d_pos, (size_t)(4 + 2 * cfg->max_batch) * sizeof(int)));
+	TTK_TRY(h->arena.alloc(&h->kc, h->kv_layer_stride * cfg->layers * h->es));
+	TTK_TRY(h->arena.alloc(&h->vc, h->kv_layer_stride * cfg->layers * h->es));
+	TTK_TRY(h->arena.alloc((void**)&h->d_pos, (size_t)(4 + 2 * cfg->max_batch) * sizeof(int)));
 	h->d_rowinfo = (int2*)(h->d_pos + 4);
 	h->d_health = h->d_pos + 2;      // (words 2, 3 of the block are otherwise unused; zeroed with it below)
-	if (hipMemset(h->d_pos, 0, (size_t)(4 + 2 * cfg->max_batch) * sizeof(int)) != hipSuccess) return fail(TTK_E_HIP);
+	if (hipMemset(h->d_pos, 0, (size_t)(4 + 2 * cfg->max_batch) * sizeof(int)) != hipSuccess) return TTK_E_HIP;
 	{   // the two position words move into the decode attention's position line when a slot is free (csrc/attn.hip); row_info and the health word stay in the block above
 		int* words = nullptr;
 		h->pos_slot = attn_pos_slot_acquire(&words);
 		if (h->pos_slot >= 0) {
 			h->d_pos = words;
-			if (hipMemset(h->d_pos, 0, 2 * sizeof(int)) != hipSuccess) return fail(TTK_E_HIP);
+			if (hipMemset(h->d_pos, 0, 2 * sizeof(int)) != hipSuccess) return TTK_E_HIP;
 		}
 	}
-	AR_TRY(h->arena.alloc((void**)&h->d_ring, sizeof(int64_t)));
-	if (hipMemset(h->d_ring, 0, sizeof(int64_t)) != hipSuccess) return fail(TTK_E_HIP);
-	AR_TRY(h->arena.alloc((void**)&h->x, (size_t)cfg->max_batch * d * sizeof(float)));
-	AR_TRY(h->arena.alloc((void**)&h->qbuf, (size_t)cfg->max_batch * d * sizeof(float)));
+	TTK_TRY(h->arena.alloc((void**)&h->d_ring, sizeof(int64_t)));
+	if (hipMemset(h->d_ring, 0, sizeof(int64_t)) != hipSuccess) return TTK_E_HIP;
+	TTK_TRY(h->arena.alloc((void**)&h->x, (size_t)cfg->max_batch * d * sizeof(float)));
+	TTK_TRY(h->arena.alloc((void**)&h->qbuf, (size_t)cfg->max_batch * d * sizeof(float)));
 	// Fragment-order operands of the decode launches, [m_tile][k-step][lane]: the kernels are instantiated for 1, 2 or 4 sixteen-row tiles (csrc/gemv.hip:
 	// gemv_mt) and request EVERY tile of their instantiation, so 33..48 rows read a fourth tile: it must exist (each buffer is its own allocation; a
 	// read past its end is a fault whenever the driver has not mapped anything behind it) and hold zeros, like the padding rows inside a tile.
 	const size_t frag_rows = (size_t)16 * decode_row_tiles(cfg->max_batch);      // the SAME function the launchers pick their instantiation with
 	h->frag_rows = (int)frag_rows;
 	for (int B = 1; B <= cfg->max_batch; ++B)      // every batch this handle accepts: the tiles its launches request exist
-		if (16 * decode_row_tiles(B) > h->frag_rows) { set_error("ttk_ar_create: %d rows would request %d fragment rows, %d allocated", B, 16 * decode_row_tiles(B), h->frag_rows); return fail(TTK_E_STATE); }
-	AR_TRY(h->arena.alloc(&h->attn_out, frag_rows * d * h->es));
-	if (hipMemset(h->attn_out, 0, frag_rows * d * h->es) != hipSuccess) return fail(TTK_E_HIP);
-	AR_TRY(h->arena.alloc(&h->hbuf, frag_rows * 4 * d * h->es));
-	if (hipMemset(h->hbuf, 0, frag_rows * 4 * d * h->es) != hipSuccess) return fail(TTK_E_HIP);
-	AR_TRY(h->arena.alloc(&h->x_frag, frag_rows * d * h->es));
-	if (hipMemset(h->x_frag, 0, frag_rows * d * h->es) != hipSuccess) return fail(TTK_E_HIP);
-	AR_TRY(h->arena.alloc((void**)&h->slab, (size_t)4 * (d / 16) * 4 * 4 * 256 * sizeof(float)));
-	AR_TRY(h->arena.alloc((void**)&h->tickets, (size_t)4 * (d / 16) * sizeof(int)));
-	if (hipMemset(h->tickets, 0, (size_t)4 * (d / 16) * sizeof(int)) != hipSuccess) return fail(TTK_E_HIP);
+		if (16 * decode_row_tiles(B) > h->frag_rows) { set_error("ttk_ar_create: %d rows would request %d fragment rows, %d allocated", B, 16 * decode_row_tiles(B), h->frag_rows); return TTK_E_STATE; }
+	TTK_TRY(h->arena.alloc(&h->attn_out, frag_rows * d * h->es));
+	if (hipMemset(h->attn_out, 0, frag_rows * d * h->es) != hipSuccess) return TTK_E_HIP;
+	TTK_TRY(h->arena.alloc(&h->hbuf, frag_rows * 4 * d * h->es));
+	if (hipMemset(h->hbuf, 0, frag_rows * 4 * d * h->es) != hipSuccess) return TTK_E_HIP;
+	TTK_TRY(h->arena.alloc(&h->x_frag, frag_rows * d * h->es));
+	if (hipMemset(h->x_frag, 0, frag_rows * d * h->es) != hipSuccess) return TTK_E_HIP;
+	TTK_TRY(h->arena.alloc((void**)&h->slab, (size_t)4 * (d / 16) * 4 * 4 * 256 * sizeof(float)));
+	TTK_TRY(h->arena.alloc((void**)&h->tickets, (size_t)4 * (d / 16) * sizeof(int)));
+	if (hipMemset(h->tickets, 0, (size_t)4 * (d / 16) * sizeof(int)) != hipSuccess) return TTK_E_HIP;
 	{
 		const char* ep = getenv("TTK_DEBUG_POISON");
 		h->poison = ep && atoi(ep) != 0;
@@ -389,27 +391,21 @@ int ttk_ar_create(ttk_ar** out, const ttk_ar_config* cfg, const ttk_weight_view*
 		const char* e = getenv("TTK_AR_SPLIT");
 		h->nsplit = e ? atoi(e) : 1;
 		if (h->nsplit != 1 && h->nsplit != 2 && h->nsplit != 4) h->nsplit = 1;
-		if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) return fail(TTK_E_HIP);
+		if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) return TTK_E_HIP;
 		for (int i = 0; i < 3; ++i) {
-			if (hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking) != hipSuccess) return fail(TTK_E_HIP);
-			if (hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming) != hipSuccess) return fail(TTK_E_HIP);
+			if (hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking) != hipSuccess) return TTK_E_HIP;
+			if (hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming) != hipSuccess) return TTK_E_HIP;
 		}
 	}
-#undef AR_TRY
 	hipError_t e = hipDeviceSynchronize();
-	if (e != hipSuccess) { set_error("ttk_ar_create: %s", hipGetErrorString(e)); return fail(TTK_E_HIP); }
-	*out = h;
+	if (e != hipSuccess) { set_error("ttk_ar_create: %s", hipGetErrorString(e)); return TTK_E_HIP; }
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_ar_destroy(ttk_ar* h) {
 	if (!h) return TTK_OK;
 	(void)hipDeviceSynchronize();
-	for (int i = 0; i < 3; ++i) { if (h->side[i]) (void)hipStreamDestroy(h->side[i]); if (h->ev_join[i]) (void)hipEventDestroy(h->ev_join[i]); }
-	if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-	h->ws_x.release(); h->ws_a.release(); h->ws_qkv.release(); h->ws_ao.release(); h->ws_h.release();
-	attn_pos_slot_release(h->pos_slot);
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }

@@ -200,27 +200,21 @@ int ttk_clvp_create(ttk_clvp** out, const ttk_clvp_config* cfg, const ttk_weight
 	TTK_REQUIRE(cfg->dtype == TTK_F32 || cfg->dtype == TTK_BF16, TTK_E_ARG, "ttk_clvp_create: bad dtype %d", cfg->dtype);
 	TTK_REQUIRE(cfg->dim % 64 == 0 && cfg->heads * 64 == cfg->dim, TTK_E_ARG, "ttk_clvp_create: head width must be 64 with heads * 64 == dim (dim %d, heads %d)", cfg->dim, cfg->heads);
 	TTK_REQUIRE(cfg->inner % 64 == 0 && cfg->depth >= 1, TTK_E_ARG, "ttk_clvp_create: inner width %d / depth %d unsupported", cfg->inner, cfg->depth);
-	ttk_clvp* h = new ttk_clvp();
+	std::unique_ptr<ttk_clvp> h(new ttk_clvp());
 	h->cfg = *cfg;
 	h->dt = cfg->dtype;
 	h->es = dtype_size(h->dt);
 	WeightMap wm(w, n_w);
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define C_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
-	C_TRY(upload_f32(h->arena, wm, "__rotary_inv_freq", 16, &h->inv_freq));
-	C_TRY(upload_f32(h->arena, wm, "temperature", 1, &h->temperature));
-	C_TRY(upload_encoder(h, wm, "text", cfg->num_text_tokens, &h->text));
-	C_TRY(upload_encoder(h, wm, "speech", cfg->num_speech_tokens, &h->speech));
-#undef C_TRY
-	*out = h;
+	TTK_TRY(upload_f32(h->arena, wm, "__rotary_inv_freq", 16, &h->inv_freq));
+	TTK_TRY(upload_f32(h->arena, wm, "temperature", 1, &h->temperature));
+	TTK_TRY(upload_encoder(h.get(), wm, "text", cfg->num_text_tokens, &h->text));
+	TTK_TRY(upload_encoder(h.get(), wm, "speech", cfg->num_speech_tokens, &h->speech));
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_clvp_destroy(ttk_clvp* h) {
 	if (!h) return TTK_OK;
-	h->ws.release();
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }

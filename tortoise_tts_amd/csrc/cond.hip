@@ -225,7 +225,7 @@ int ttk_cond_create(ttk_cond** out, const ttk_cond_config* cfg, const ttk_weight
 				TTK_E_ARG, "ttk_cond_create: bad widths (channels %d, heads %d, in %d)", cfg->channels, cfg->num_heads, cfg->in_channels);
 	const int hd = cfg->channels / cfg->num_heads;
 	TTK_REQUIRE(hd == 64 || hd == 128, TTK_E_ARG, "ttk_cond_create: head width %d unsupported (64 or 128)", hd);
-	ttk_cond* h = new ttk_cond();
+	std::unique_ptr<ttk_cond> h(new ttk_cond());
 	h->cfg = *cfg;
 	h->dt = cfg->dtype;
 	h->es = dtype_size(h->dt);
@@ -233,37 +233,31 @@ int ttk_cond_create(ttk_cond** out, const ttk_cond_config* cfg, const ttk_weight
 	h->groups = gn_groups(cfg->channels);
 	const int C = cfg->channels;
 	WeightMap wm(w, n_w);
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define C_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
 	if (cfg->stem == TTK_COND_STEM_DOWN4) {
-		C_TRY(upload_mat(h->arena, wm, h->dt, "stem.0.weight", "stem.0.bias", PK_NK, C / 2, cfg->in_channels * 3, false, &h->stem0));
-		C_TRY(upload_mat(h->arena, wm, h->dt, "stem.1.weight", "stem.1.bias", PK_NK, C, (C / 2) * 3, false, &h->stem1));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, "stem.0.weight", "stem.0.bias", PK_NK, C / 2, cfg->in_channels * 3, false, &h->stem0));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, "stem.1.weight", "stem.1.bias", PK_NK, C, (C / 2) * 3, false, &h->stem1));
 	} else {
-		C_TRY(upload_mat(h->arena, wm, h->dt, "stem.0.weight", "stem.0.bias", PK_NK, C, cfg->in_channels, false, &h->stem0));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, "stem.0.weight", "stem.0.bias", PK_NK, C, cfg->in_channels, false, &h->stem0));
 	}
 	h->blocks.resize(cfg->num_blocks);
 	for (int i = 0; i < cfg->num_blocks; ++i) {
 		Block& B = h->blocks[i];
 		const std::string p = "blocks." + std::to_string(i) + ".";
-		C_TRY(upload_f32(h->arena, wm, p + "norm.weight", C, &B.gn_g));
-		C_TRY(upload_f32(h->arena, wm, p + "norm.bias", C, &B.gn_b));
-		C_TRY(upload_mat(h->arena, wm, h->dt, p + "qkv.weight", p + "qkv.bias", PK_NK, 3 * C, C, false, &B.qkv));
-		C_TRY(upload_mat(h->arena, wm, h->dt, p + "proj_out.weight", p + "proj_out.bias", PK_NK, C, C, false, &B.proj));
-		if (cfg->relpos) C_TRY(upload_f32(h->arena, wm, p + "__relbias", (int64_t)cfg->num_heads * 129, &B.relbias));
+		TTK_TRY(upload_f32(h->arena, wm, p + "norm.weight", C, &B.gn_g));
+		TTK_TRY(upload_f32(h->arena, wm, p + "norm.bias", C, &B.gn_b));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, p + "qkv.weight", p + "qkv.bias", PK_NK, 3 * C, C, false, &B.qkv));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, p + "proj_out.weight", p + "proj_out.bias", PK_NK, C, C, false, &B.proj));
+		if (cfg->relpos) TTK_TRY(upload_f32(h->arena, wm, p + "__relbias", (int64_t)cfg->num_heads * 129, &B.relbias));
 	}
-#undef C_TRY
 	hipError_t e = hipDeviceSynchronize();
-	if (e != hipSuccess) { set_error("ttk_cond_create: %s", hipGetErrorString(e)); return fail(TTK_E_HIP); }
-	*out = h;
+	if (e != hipSuccess) { set_error("ttk_cond_create: %s", hipGetErrorString(e)); return TTK_E_HIP; }
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_cond_destroy(ttk_cond* h) {
 	if (!h) return TTK_OK;
 	(void)hipDeviceSynchronize();
-	h->ws.release();
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }

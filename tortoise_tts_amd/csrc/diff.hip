@@ -55,6 +55,10 @@ struct ttk_diff {
 	// separate statistics launch, exactly as a batch of their own length would
 	int* d_tlen = nullptr; int* d_need = nullptr;
 	const int* tlen = nullptr; const int* need = nullptr;      // = d_tlen / d_need while a ragged loop runs, else null
+	~ttk_diff() {            // the side stream and events are made on first use; the workspaces and the arena free themselves after this
+		if (side) (void)hipStreamDestroy(side);
+		for (hipEvent_t e : {ev_fork, ev_int[0], ev_int[1], ev_free[0], ev_free[1]}) if (e) (void)hipEventDestroy(e);
+	}
 };
 
 // gn_T > 0: the output is a GroupNorm input of gn_T rows per batch element; its statistics are produced in the epilogue when the
@@ -251,7 +255,7 @@ int ttk_diff_create(ttk_diff** out, const ttk_diff_config* cfg, const ttk_weight
 				"ttk_diff_create: model_channels %d unsupported (128, 256, 512 or 1024)", cfg->model_channels);
 	TTK_REQUIRE(cfg->dtype == TTK_F32 || cfg->dtype == TTK_BF16 || cfg->dtype == TTK_F16 || cfg->dtype == TTK_FP8W || cfg->dtype == TTK_FP8, TTK_E_ARG, "ttk_diff_create: bad dtype %d", cfg->dtype);
 	TTK_REQUIRE(cfg->dtype != TTK_FP8 || cfg->model_channels % 128 == 0, TTK_E_ARG, "ttk_diff_create: fp8 GEMMs need channels %% 128 == 0");
-	ttk_diff* h = new ttk_diff();
+	std::unique_ptr<ttk_diff> h(new ttk_diff());
 	h->cfg = *cfg;
 	h->wdt = cfg->dtype;              // ResBlock / AttentionBlock GEMM weights: rounded to fp8-e4m3 in DT_FP8W (held exactly in bf16)
 	h->dt = kernel_dtype(cfg->dtype);
@@ -263,56 +267,46 @@ int ttk_diff_create(ttk_diff** out, const ttk_diff_config* cfg, const ttk_weight
 	{ const char* e = getenv("TTK_DIFF_PIPE"); h->pipe = e ? atoi(e) : 1; }
 	const int C = cfg->model_channels;
 	WeightMap wm(w, n_w);
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define D_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
-	D_TRY(upload_f32(h->arena, wm, "unconditioned_embedding", C, &h->uncond));
-	D_TRY(upload_f32(h->arena, wm, "__time_freqs", C / 2, &h->time_freqs));
-	D_TRY(upload_mat(h->arena, wm, h->dt, "inp_block.weight", "inp_block.bias", PK_CONV3, C, cfg->in_channels, false, &h->inp_block));
-	D_TRY(upload_mat(h->arena, wm, h->dt, "time_embed.0.weight", "time_embed.0.bias", PK_NK, C, C, false, &h->time0));
-	D_TRY(upload_mat(h->arena, wm, h->dt, "time_embed.2.weight", "time_embed.2.bias", PK_NK, C, C, false, &h->time2));
-	D_TRY(upload_f32(h->arena, wm, "code_norm.weight", C, &h->code_g));
-	D_TRY(upload_f32(h->arena, wm, "code_norm.bias", C, &h->code_b));
-	D_TRY(upload_mat(h->arena, wm, h->dt, "latent_conditioner.0.weight", "latent_conditioner.0.bias", PK_CONV3, C, cfg->in_latent_channels, false, &h->lat_conv));
-	for (int i = 0; i < 4; ++i) D_TRY(load_attn(h, wm, "latent_conditioner." + std::to_string(i + 1) + ".", &h->lat_attn[i]));
-	D_TRY(upload_mat(h->arena, wm, h->dt, "integrating_conv.weight", "integrating_conv.bias", PK_NK, C, 2 * C, false, &h->integ));
-	D_TRY(upload_f32(h->arena, wm, "out.0.weight", C, &h->out_g));
-	D_TRY(upload_f32(h->arena, wm, "out.0.bias", C, &h->out_b));
-	D_TRY(upload_mat(h->arena, wm, h->dt, "out.2.weight", "out.2.bias", PK_CONV3, cfg->out_channels, C, false, &h->out_conv));
+	TTK_TRY(upload_f32(h->arena, wm, "unconditioned_embedding", C, &h->uncond));
+	TTK_TRY(upload_f32(h->arena, wm, "__time_freqs", C / 2, &h->time_freqs));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "inp_block.weight", "inp_block.bias", PK_CONV3, C, cfg->in_channels, false, &h->inp_block));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "time_embed.0.weight", "time_embed.0.bias", PK_NK, C, C, false, &h->time0));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "time_embed.2.weight", "time_embed.2.bias", PK_NK, C, C, false, &h->time2));
+	TTK_TRY(upload_f32(h->arena, wm, "code_norm.weight", C, &h->code_g));
+	TTK_TRY(upload_f32(h->arena, wm, "code_norm.bias", C, &h->code_b));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "latent_conditioner.0.weight", "latent_conditioner.0.bias", PK_CONV3, C, cfg->in_latent_channels, false, &h->lat_conv));
+	for (int i = 0; i < 4; ++i) TTK_TRY(load_attn(h.get(), wm, "latent_conditioner." + std::to_string(i + 1) + ".", &h->lat_attn[i]));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "integrating_conv.weight", "integrating_conv.bias", PK_NK, C, 2 * C, false, &h->integ));
+	TTK_TRY(upload_f32(h->arena, wm, "out.0.weight", C, &h->out_g));
+	TTK_TRY(upload_f32(h->arena, wm, "out.0.bias", C, &h->out_b));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "out.2.weight", "out.2.bias", PK_CONV3, cfg->out_channels, C, false, &h->out_conv));
 	int slot = 0;
 	for (int i = 0; i < 3; ++i) {
 		const std::string p = "conditioning_timestep_integrator." + std::to_string(i) + ".";
-		D_TRY(load_res(h, wm, p + "resblk.", &h->integrator[i].res, slot++));
-		D_TRY(load_attn(h, wm, p + "attn.", &h->integrator[i].attn));
+		TTK_TRY(load_res(h.get(), wm, p + "resblk.", &h->integrator[i].res, slot++));
+		TTK_TRY(load_attn(h.get(), wm, p + "attn.", &h->integrator[i].attn));
 	}
 	h->layers.resize(cfg->num_layers);
 	for (int i = 0; i < cfg->num_layers; ++i) {
 		const std::string p = "layers." + std::to_string(i) + ".";
-		D_TRY(load_res(h, wm, p + "resblk.", &h->layers[i].res, slot++));
-		D_TRY(load_attn(h, wm, p + "attn.", &h->layers[i].attn));
+		TTK_TRY(load_res(h.get(), wm, p + "resblk.", &h->layers[i].res, slot++));
+		TTK_TRY(load_attn(h.get(), wm, p + "attn.", &h->layers[i].attn));
 	}
-	for (int i = 0; i < 3; ++i) D_TRY(load_res(h, wm, "layers." + std::to_string(cfg->num_layers + i) + ".", &h->tail[i], slot++));
+	for (int i = 0; i < 3; ++i) TTK_TRY(load_res(h.get(), wm, "layers." + std::to_string(cfg->num_layers + i) + ".", &h->tail[i], slot++));
 	h->n_emb = slot;
-	D_TRY(h->arena.alloc((void**)&h->d_tlen, 128 * sizeof(int)));
-	D_TRY(h->arena.alloc((void**)&h->d_need, 128 * sizeof(int)));
+	TTK_TRY(h->arena.alloc((void**)&h->d_tlen, 128 * sizeof(int)));
+	TTK_TRY(h->arena.alloc((void**)&h->d_need, 128 * sizeof(int)));
 	// all emb_layers.1 linears stacked into one [n_emb * 2C][C] matrix ("__emb_cat.*", built by the Python packer)
-	D_TRY(upload_mat(h->arena, wm, h->dt, "__emb_cat.weight", "__emb_cat.bias", PK_NK, h->n_emb * 2 * C, C, false, &h->emb_cat));
-#undef D_TRY
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "__emb_cat.weight", "__emb_cat.bias", PK_NK, h->n_emb * 2 * C, C, false, &h->emb_cat));
 	hipError_t e = hipDeviceSynchronize();
-	if (e != hipSuccess) { set_error("ttk_diff_create: %s", hipGetErrorString(e)); return fail(TTK_E_HIP); }
-	*out = h;
+	if (e != hipSuccess) { set_error("ttk_diff_create: %s", hipGetErrorString(e)); return TTK_E_HIP; }
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_diff_destroy(ttk_diff* h) {
 	if (!h) return TTK_OK;
 	(void)hipDeviceSynchronize();
-	WsBuf* all[] = {&h->cs, &h->cs2, &h->xs, &h->h0, &h->csT, &h->xcl, &h->outb, &h->ecl, &h->temb, &h->e1, &h->e2, &h->se, &h->emb_all, &h->lat_T, &h->ms_ecl, &h->hf0, &h->ms_hf0};
-	for (WsBuf* b : all) b->release();
-	for (Lane& L : h->lane) { L.a.release(); L.hf.release(); L.qkv.release(); L.ao.release(); L.ms.release(); }
-	if (h->side) (void)hipStreamDestroy(h->side);
-	for (hipEvent_t e : {h->ev_fork, h->ev_int[0], h->ev_int[1], h->ev_free[0], h->ev_free[1]}) if (e) (void)hipEventDestroy(e);
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }

@@ -5,8 +5,8 @@
 //
 // Layout: channels-last rows, one utterance per call.  The residual stream is f32 [L][C]; every GEMM operand is a T-typed copy whose
 // row holds round_up(C, 64) elements (the tail zero, it meets zero weight columns).  LeakyReLU is applied where such a copy is written,
-// never inside a GEMM.  conv_pre, the transposed convolutions (u phase GEMMs of k / u taps each, as in voc.hip) and, in f32 mode or at
-// C > 64, the ResBlock convolutions run on the segment GEMM of gemm.hip (one segment per tap).  New kernels:
+// never inside a GEMM.  conv_pre, the transposed convolutions (u phase GEMMs of k / u taps each) and, in f32 mode or at
+// C > 64, the ResBlock convolutions run on the segment GEMM of gemm.hip (ttk_conv.h: one segment per tap).  New kernels:
 //  - k_hifi_interp: both interpolations of inference :285-294 in one pass, [n][C] f32 -> [F][C] T-typed, F = floor(4 n * 24000 / 22050).
 //    align_corners=False with the scale factor itself as the coordinate scale: src = max((i + 0.5) / scale - 0.5, 0), right neighbour
 //    clamped to the last frame; when a stage keeps the length (the second one for n = 1, 2) torch copies, and so does this kernel.
@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 #include "ttk_kernels.h"
 
 using namespace ttk;
@@ -266,16 +266,6 @@ void launch_mean_t(float* const* y, int n, float div, int C, float* out, void* o
 	hipLaunchKernelGGL((k_hifi_mean<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, y[0], y[1], y[2], y[3], n, div, C, out, (T*)out_t, ldo, kSlope, rows);
 }
 
-// Conv1d(k taps, dilation) over rows on the segment GEMM: out f32 [M][N] = sum_j A[m + (j - (k-1)/2) * dil] * W_j^T + bias (+ residual)
-void conv_rows(int dt, const void* A, int lda, const Mat& w, const float* bias, int k, int dil, int L, const float* residual, float* C, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = k;
-	for (int j = 0; j < k; ++j) g.seg[j] = {A, lda, (j - (k - 1) / 2) * dil, (int64_t)j * w.Npad * w.Kpad};
-	g.W = w.w; g.ldw = w.Kpad; g.M = L; g.N = w.N; g.K = w.Kpad; g.rows_per_batch = L; g.bias = bias;
-	g.residual = residual; g.ldr = w.N; g.C = C; g.ldc = w.N; g.out_f32 = 1;
-	launch_gemm(dt, g, s);
-}
-
 void launch_narrow(int C, const void* a, int lda, const bf16* wfrag, const float* bias, int L, int k, int dil, int mode, const float* xres, float* xout,
 				   void* at_out, int ldo, float* mrf, hipStream_t s) {
 	const size_t lds = narrow_lds(C, k, dil);
@@ -331,7 +321,7 @@ int ttk_hifigan_create(ttk_hifigan** out, const ttk_hifigan_config* cfg, const t
 		for (int m = 0; m < 3; ++m)
 			TTK_REQUIRE(cfg->rb_dil[j][m] >= 1 && cfg->rb_dil[j][m] <= 4096, TTK_E_ARG, "ttk_hifigan_create: dilation %d unsupported", cfg->rb_dil[j][m]);
 	}
-	ttk_hifigan* h = new ttk_hifigan();
+	std::unique_ptr<ttk_hifigan> h(new ttk_hifigan());
 	h->cfg = *cfg;
 	h->dt = cfg->dtype;
 	h->es = dtype_size(h->dt);
@@ -339,21 +329,18 @@ int ttk_hifigan_create(ttk_hifigan** out, const ttk_hifigan_config* cfg, const t
 	const char* env = getenv("TTK_HIFI_NARROW");               // 0: the ResBlocks of every stage on the segment GEMM
 	const bool want_narrow = h->dt == DT_BF16 && !(env && atoi(env) == 0);
 	WeightMap wm(w, n_w);
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define H_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
 	const int ch0 = cfg->upsample_initial_channel;
-	H_TRY(upload_mat(h->arena, wm, h->dt, "conv_pre.weight", "conv_pre.bias", PK_CONVK, ch0, cfg->in_channels, false, &h->conv_pre, 7));
-	H_TRY(upload_f32(h->arena, wm, "cond_layer.weight", (int64_t)ch0 * cfg->cond_channels, &h->cond_w));
-	H_TRY(upload_f32(h->arena, wm, "cond_layer.bias", ch0, &h->cond_b));
-	H_TRY(h->arena.alloc((void**)&h->pre_bias, (size_t)ch0 * 4));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "conv_pre.weight", "conv_pre.bias", PK_CONVK, ch0, cfg->in_channels, false, &h->conv_pre, 7));
+	TTK_TRY(upload_f32(h->arena, wm, "cond_layer.weight", (int64_t)ch0 * cfg->cond_channels, &h->cond_w));
+	TTK_TRY(upload_f32(h->arena, wm, "cond_layer.bias", ch0, &h->cond_b));
+	TTK_TRY(h->arena.alloc((void**)&h->pre_bias, (size_t)ch0 * 4));
 	h->ups.resize(cfg->n_ups);
 	h->blocks.resize((size_t)cfg->n_ups * cfg->n_kernels);
 	h->narrow.assign(cfg->n_ups, 0);
 	ch = ch0;
 	for (int i = 0; i < cfg->n_ups; ++i) {
 		const std::string u = "ups." + std::to_string(i) + ".";
-		H_TRY(upload_mat(h->arena, wm, h->dt, u + "weight", u + "bias", PK_CONVT, ch / 2, ch, false, &h->ups[i], cfg->up_kernel[i]));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, u + "weight", u + "bias", PK_CONVT, ch / 2, ch, false, &h->ups[i], cfg->up_kernel[i]));
 		ch /= 2;
 		bool nar = want_narrow && (ch == 32 || ch == 64);
 		for (int j = 0; j < cfg->n_kernels && nar; ++j)
@@ -363,28 +350,24 @@ int ttk_hifigan_create(ttk_hifigan** out, const ttk_hifigan_config* cfg, const t
 			ResBlock& b = h->blocks[(size_t)i * cfg->n_kernels + j];
 			b.k = cfg->rb_kernel[j];
 			const std::string p = "resblocks." + std::to_string(i * cfg->n_kernels + j) + ".";
+			TTK_TRY(upload_resblock(h->arena, wm, h->dt, p, ch, b.k, b.c1, b.c2));
 			for (int m = 0; m < 3; ++m) {
 				b.dil[m] = cfg->rb_dil[j][m];
-				H_TRY(upload_mat(h->arena, wm, h->dt, p + "convs1." + std::to_string(m) + ".weight", p + "convs1." + std::to_string(m) + ".bias", PK_CONVK, ch, ch, false, &b.c1[m], b.k));
-				H_TRY(upload_mat(h->arena, wm, h->dt, p + "convs2." + std::to_string(m) + ".weight", p + "convs2." + std::to_string(m) + ".bias", PK_CONVK, ch, ch, false, &b.c2[m], b.k));
 				if (nar) {
-					H_TRY(pack_frag(h->arena, b.c1[m], ch, b.k, &b.f1[m]));
-					H_TRY(pack_frag(h->arena, b.c2[m], ch, b.k, &b.f2[m]));
+					TTK_TRY(pack_frag(h->arena, b.c1[m], ch, b.k, &b.f1[m]));
+					TTK_TRY(pack_frag(h->arena, b.c2[m], ch, b.k, &b.f2[m]));
 				}
 			}
 		}
 	}
-	H_TRY(upload_f32(h->arena, wm, "conv_post.weight", (int64_t)ch * 7, &h->post_w));
-	H_TRY(upload_f32(h->arena, wm, "conv_post.bias", 1, &h->post_b));
-#undef H_TRY
-	*out = h;
+	TTK_TRY(upload_f32(h->arena, wm, "conv_post.weight", (int64_t)ch * 7, &h->post_w));
+	TTK_TRY(upload_f32(h->arena, wm, "conv_post.bias", 1, &h->post_b));
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_hifigan_destroy(ttk_hifigan* h) {
 	if (!h) return TTK_OK;
-	h->ws.release();
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }
@@ -417,13 +400,12 @@ int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* au
 	}
 	TTK_REQUIRE(max_el * 4 < ((int64_t)1 << 31), TTK_E_ARG, "ttk_hifigan_inference: %d latents exceed the 2 GiB buffer range of one call", n);
 	const int nxb = std::max(c.n_kernels, 2);
-	size_t off = 0;
-	auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+	WsPlan ws;
 	const size_t f32b = (size_t)max_el * 4, tb = (size_t)max_el * es;
-	const size_t o_in = take((size_t)F * in_ld * es), o_xt = take(tb), o_at = take(tb), o_at2 = take(tb), o_y = take(f32b), o_h = take(f32b);
+	const size_t o_in = ws.take((size_t)F * in_ld * es), o_xt = ws.take(tb), o_at = ws.take(tb), o_at2 = ws.take(tb), o_y = ws.take(f32b), o_h = ws.take(f32b);
 	size_t o_xb[4];
-	for (int j = 0; j < 4; ++j) o_xb[j] = j < nxb ? take(f32b) : o_xb[0];
-	TTK_TRY(h->ws.reserve(off));
+	for (int j = 0; j < 4; ++j) o_xb[j] = j < nxb ? ws.take(f32b) : o_xb[0];
+	TTK_TRY(h->ws.reserve(ws.total));
 	char* base = (char*)h->ws.p;
 	void* in_t = base + o_in;          // T [F][in_ld]: the interpolated latents
 	void* xt = base + o_xt;            // T lrelu(stage input): the transposed conv's operand; then lrelu(y), the first operand of the stage's ResBlocks
@@ -441,25 +423,13 @@ int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* au
 		if (dt == DT_BF16) hipLaunchKernelGGL((k_hifi_interp<bf16>), dim3(grid), dim3(256), 0, s, latents, n, c.in_channels, F, rs2, (bf16*)in_t, in_ld);
 		else hipLaunchKernelGGL((k_hifi_interp<float>), dim3(grid), dim3(256), 0, s, latents, n, c.in_channels, F, rs2, (float*)in_t, in_ld);
 	}
-	conv_rows(dt, in_t, in_ld, h->conv_pre, h->pre_bias, 7, 1, F, nullptr, hb, s);           // conv_pre + cond_layer(g), f32 [F][ch0]
+	conv_taps(dt, in_t, in_ld, h->conv_pre, h->pre_bias, 7, -3, 1, F, F, nullptr, hb, 1, s);         // conv_pre + cond_layer(g), f32 [F][ch0]
 	int L = F, ch = ch0;
 	launch_act(dt, hb, ch, xt, round_up(ch, 64), L, s);
 	for (int i = 0; i < c.n_ups; ++i) {
-		const int u = c.up_rate[i], k = c.up_kernel[i], pd = (k - u) / 2, cout = ch / 2, ld_in = round_up(ch, 64);
-		const Mat& W = h->ups[i];
-		// transposed convolution, one GEMM per output phase r: y[u m + r] = sum_t x[m + (r + pd - j_t) / u] W[:, :, j_t],  j_t = (r + pd) % u + u t
-		for (int r = 0; r < u; ++r) {
-			GemmParams g = {};
-			g.nseg = k / u;
-			for (int t = 0; t < g.nseg; ++t) {
-				const int j = (r + pd) % u + u * t;
-				g.seg[t] = {xt, ld_in, (r + pd - j) / u, (int64_t)j * W.Npad * W.Kpad};
-			}
-			g.W = W.w; g.ldw = W.Kpad; g.M = L; g.N = cout; g.K = W.Kpad; g.rows_per_batch = L; g.bias = W.bias;
-			g.C = y + (size_t)r * cout; g.ldc = (int64_t)u * cout; g.out_f32 = 1;
-			launch_gemm(dt, g, s);
-		}
-		L *= u; ch = cout;
+		const int u = c.up_rate[i], k = c.up_kernel[i];
+		convt_phases(dt, xt, round_up(ch, 64), h->ups[i], k, u, (k - u) / 2, L, L, y, s);
+		L *= u; ch /= 2;
 		const int ld = round_up(ch, 64);
 		const bool last = i == c.n_ups - 1;
 		if (h->narrow[i]) {
@@ -480,9 +450,9 @@ int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* au
 				const float* cur = y;
 				for (int m = 0; m < 3; ++m) {
 					launch_act(dt, cur, ch, at, ld, L, s);
-					conv_rows(dt, at, ld, b.c1[m], b.c1[m].bias, b.k, b.dil[m], L, nullptr, hb, s);
+					conv_same(dt, at, ld, b.c1[m], b.k, b.dil[m], L, L, nullptr, hb, 1, s);
 					launch_act(dt, hb, ch, at, ld, L, s);
-					conv_rows(dt, at, ld, b.c2[m], b.c2[m].bias, b.k, 1, L, cur, xb[j], s);   // + bias + residual (aliases the output from m = 1 on)
+					conv_same(dt, at, ld, b.c2[m], b.k, 1, L, L, cur, xb[j], 1, s);   // + bias + residual (aliases the output from m = 1 on)
 					cur = xb[j];
 				}
 			}

@@ -97,28 +97,22 @@ int ttk_mel_create(ttk_mel** out, const ttk_mel_config* cfg, const ttk_weight_vi
 	TTK_REQUIRE(cfg->n_fft >= 64 && cfg->n_fft % 64 == 0 && cfg->hop >= 1 && cfg->n_mels >= 1, TTK_E_ARG,
 				"ttk_mel_create: bad sizes (n_fft %d must be a multiple of 64, hop %d, n_mels %d)", cfg->n_fft, cfg->hop, cfg->n_mels);
 	TTK_REQUIRE(cfg->power == 1 || cfg->power == 2, TTK_E_ARG, "ttk_mel_create: power must be 1 (magnitude) or 2, got %d", cfg->power);
-	ttk_mel* h = new ttk_mel();
+	std::unique_ptr<ttk_mel> h(new ttk_mel());
 	h->cfg = *cfg;
 	h->nb = cfg->n_fft / 2 + 1;
 	WeightMap wm(w, n_w);
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define M_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
-	M_TRY(upload_mat(h->arena, wm, DT_F32, "basis", "", PK_NK, 2 * h->nb, cfg->n_fft, false, &h->basis));
-	M_TRY(upload_mat(h->arena, wm, DT_F32, "mel_basis", "", PK_NK, cfg->n_mels, h->nb, false, &h->melb));
-	if (cfg->has_norms) M_TRY(upload_f32(h->arena, wm, "mel_norms", cfg->n_mels, &h->norms));
-#undef M_TRY
+	TTK_TRY(upload_mat(h->arena, wm, DT_F32, "basis", "", PK_NK, 2 * h->nb, cfg->n_fft, false, &h->basis));
+	TTK_TRY(upload_mat(h->arena, wm, DT_F32, "mel_basis", "", PK_NK, cfg->n_mels, h->nb, false, &h->melb));
+	if (cfg->has_norms) TTK_TRY(upload_f32(h->arena, wm, "mel_norms", cfg->n_mels, &h->norms));
 	hipError_t e = hipDeviceSynchronize();
-	if (e != hipSuccess) { set_error("ttk_mel_create: %s", hipGetErrorString(e)); return fail(TTK_E_HIP); }
-	*out = h;
+	if (e != hipSuccess) { set_error("ttk_mel_create: %s", hipGetErrorString(e)); return TTK_E_HIP; }
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_mel_destroy(ttk_mel* h) {
 	if (!h) return TTK_OK;
 	(void)hipDeviceSynchronize();
-	h->ws.release();
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }

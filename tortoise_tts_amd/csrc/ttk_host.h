@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -37,10 +38,14 @@ void set_error(const char* fmt, ...);
 		}                                \
 	} while (0)
 
-// owns every device allocation of a handle
+// owns every device allocation of a handle; freed with it (a handle is deleted, on the failure path of its create as well)
 struct Arena {
 	std::vector<void*> ptrs;
 	size_t bytes = 0;
+	Arena() = default;
+	Arena(const Arena&) = delete;
+	Arena& operator=(const Arena&) = delete;
+	~Arena() { release(); }
 	int alloc(void** out, size_t n) {
 		if (n == 0) n = 16;
 		TTK_HIP(hipMalloc(out, n));
@@ -58,6 +63,10 @@ struct Arena {
 struct WsBuf {
 	void* p = nullptr;
 	size_t cap = 0;
+	WsBuf() = default;
+	WsBuf(const WsBuf&) = delete;
+	WsBuf& operator=(const WsBuf&) = delete;
+	~WsBuf() { release(); }
 	int reserve(size_t n) {
 		if (n <= cap) return TTK_OK;
 		if (p) TTK_HIP(hipFree(p));

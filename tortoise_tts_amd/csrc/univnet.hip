@@ -5,10 +5,10 @@
 // location_variable_convolution :184-218, UnivNetGenerator.forward :269-284, inference :302-314.
 //
 // Layout: channels-last everywhere.  The residual stream x is f32 [B * L][c_g]; GEMM A operands are T-typed with their channel count
-// zero-padded to the weight matrix's Kpad (64), so no GEMM reads past a row.  Every Conv1d is the segment GEMM of voc.hip (one
+// zero-padded to the weight matrix's Kpad (64), so no GEMM reads past a row.  Every Conv1d is the segment GEMM of ttk_conv.h (one
 // segment per tap); the two reflect-padded convs (conv_pre, conv_post) run as 'valid' convolutions (shifts 0..6) over a copy of their
 // input with the 3 reflected rows written on each side, and read their outputs back at the padded row stride.  convt_pre
-// (ConvTranspose1d, kernel 2s, stride s) is s phase GEMMs of two taps each, as in voc.hip.  LeakyReLU(0.2) never runs inside a GEMM
+// (ConvTranspose1d, kernel 2s, stride s) is s phase GEMMs of two taps each (convt_phases).  LeakyReLU(0.2) never runs inside a GEMM
 // (gemm.hip has no such epilogue and stays as it is): it is applied where the next operand is written -- k_act_rows, or the LVC
 // epilogue, which writes lrelu(x) for whatever reads x next (the next layer's dilated conv, the next block's convt_pre).
 //
@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 #include "ttk_kernels.h"
 
 using namespace ttk;
@@ -78,15 +78,6 @@ __global__ void k_act_rows(ActRows p) {
 		}
 	}
 	((T*)p.outT)[idx] = cvt<T>(v);
-}
-
-// audio[b][t] = clamp(tanh(y[b * Lp + t]), -1, 1) for t < keep  (conv_post's Tanh, inference :312-313)
-__global__ void k_un_out(const float* y, int B, int Lp, int keep, float* audio) {
-	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= (int64_t)B * keep) return;
-	const int b = (int)(i / keep), t = (int)(i - (int64_t)b * keep);
-	const float v = tanhf(y[(int64_t)b * Lp + t]);
-	audio[i] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
 }
 
 // Location-variable convolution of layer `layer` + gated update (LVCBlock.forward :172-180, location_variable_convolution :184-218,
@@ -229,26 +220,6 @@ ActRows act_cl(const float* src, int64_t sb, int64_t st, int B, int L, int C, in
 	return p;
 }
 
-// 'same' Conv1d over rows: out[M][N] = sum_j A[m + (j - (k-1)/2) * dil] * W_j^T + bias   (zero rows outside a batch element)
-void conv_rows(int dt, const void* A, int lda, const Mat& w, int k, int dil, int M, int L, void* C, int out_f32, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = k;
-	for (int j = 0; j < k; ++j) g.seg[j] = {A, lda, (j - (k - 1) / 2) * dil, (int64_t)j * w.Npad * w.Kpad};
-	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.rows_per_batch = L; g.bias = w.bias;
-	g.C = C; g.ldc = w.N; g.out_f32 = out_f32;
-	launch_gemm(dt, g, s);
-}
-
-// 'valid' Conv1d of k taps over rows that already carry (k-1)/2 reflected rows on each side: out row b * Lp + t (t < Lp - k + 1)
-void conv_valid(int dt, const void* A, int lda, const Mat& w, int k, int M, int Lp, float* C, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = k;
-	for (int j = 0; j < k; ++j) g.seg[j] = {A, lda, j, (int64_t)j * w.Npad * w.Kpad};
-	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.rows_per_batch = Lp; g.bias = w.bias;
-	g.C = C; g.ldc = w.N; g.out_f32 = 1;
-	launch_gemm(dt, g, s);
-}
-
 template <typename T>
 void launch_lvc_t(int cg, const float* y, const void* kern, const float* kbias, float* x, void* at, int B, int L, int hop, int Tc, int layer,
 				  int kstride, int bstride, int lda, hipStream_t s) {
@@ -285,44 +256,38 @@ int ttk_univnet_create(ttk_univnet** out, const ttk_univnet_config* cfg, const t
 	TTK_REQUIRE(hop == cfg->hop_length, TTK_E_ARG, "ttk_univnet_create: the strides multiply to %d, not the hop length %d", hop, cfg->hop_length);
 	for (int n = 0; n < cfg->n_layers; ++n)
 		TTK_REQUIRE(cfg->dilations[n] >= 1 && cfg->dilations[n] <= 4096, TTK_E_ARG, "ttk_univnet_create: dilation %d unsupported", cfg->dilations[n]);
-	ttk_univnet* h = new ttk_univnet();
+	std::unique_ptr<ttk_univnet> h(new ttk_univnet());
 	h->cfg = *cfg;
 	h->dt = cfg->dtype;
 	h->es = dtype_size(h->dt);
 	WeightMap wm(w, n_w);
 	const int C = cfg->channels, H = cfg->kpnet_hidden, kc = cfg->kpnet_conv_size;
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define U_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
-	U_TRY(upload_mat(h->arena, wm, h->dt, "conv_pre.weight", "conv_pre.bias", PK_CONVK, C, cfg->noise_dim, false, &h->conv_pre, 7));
-	U_TRY(upload_mat(h->arena, wm, h->dt, "conv_post.1.weight", "conv_post.1.bias", PK_CONVK, 1, C, false, &h->conv_post, 7));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "conv_pre.weight", "conv_pre.bias", PK_CONVK, C, cfg->noise_dim, false, &h->conv_pre, 7));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "conv_post.1.weight", "conv_post.1.bias", PK_CONVK, 1, C, false, &h->conv_post, 7));
 	h->blocks.resize(cfg->n_blocks);
 	for (int i = 0; i < cfg->n_blocks; ++i) {
 		LvcBlock& B = h->blocks[i];
 		const std::string p = pfx(i), kp = p + "kernel_predictor.";
-		U_TRY(upload_mat(h->arena, wm, h->dt, p + "convt_pre.1.weight", p + "convt_pre.1.bias", PK_CONVT, C, C, false, &B.convt, 2 * cfg->strides[i]));
-		U_TRY(upload_mat(h->arena, wm, h->dt, kp + "input_conv.0.weight", kp + "input_conv.0.bias", PK_CONVK, H, cfg->num_mels, false, &B.kp.in, 5));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, p + "convt_pre.1.weight", p + "convt_pre.1.bias", PK_CONVT, C, C, false, &B.convt, 2 * cfg->strides[i]));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, kp + "input_conv.0.weight", kp + "input_conv.0.bias", PK_CONVK, H, cfg->num_mels, false, &B.kp.in, 5));
 		for (int j = 0; j < 3; ++j)
 			for (int m = 0; m < 2; ++m) {
 				const std::string r = kp + "residual_convs." + std::to_string(j) + "." + std::to_string(1 + 2 * m) + ".";
-				U_TRY(upload_mat(h->arena, wm, h->dt, r + "weight", r + "bias", PK_CONVK, H, H, false, &B.kp.res[j][m], kc));
+				TTK_TRY(upload_mat(h->arena, wm, h->dt, r + "weight", r + "bias", PK_CONVK, H, H, false, &B.kp.res[j][m], kc));
 			}
-		U_TRY(upload_mat(h->arena, wm, h->dt, kp + "kernel_conv.weight", kp + "kernel_conv.bias", PK_CONVK, cfg->n_layers * C * 2 * C * 3, H, false, &B.kp.kernel, kc));
-		U_TRY(upload_mat(h->arena, wm, h->dt, kp + "bias_conv.weight", kp + "bias_conv.bias", PK_CONVK, cfg->n_layers * 2 * C, H, false, &B.kp.bias, kc));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, kp + "kernel_conv.weight", kp + "kernel_conv.bias", PK_CONVK, cfg->n_layers * C * 2 * C * 3, H, false, &B.kp.kernel, kc));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, kp + "bias_conv.weight", kp + "bias_conv.bias", PK_CONVK, cfg->n_layers * 2 * C, H, false, &B.kp.bias, kc));
 		for (int n = 0; n < cfg->n_layers; ++n) {
 			const std::string c = p + "conv_blocks." + std::to_string(n) + ".1.";
-			U_TRY(upload_mat(h->arena, wm, h->dt, c + "weight", c + "bias", PK_CONVK, C, C, false, &B.conv[n], 3));
+			TTK_TRY(upload_mat(h->arena, wm, h->dt, c + "weight", c + "bias", PK_CONVK, C, C, false, &B.conv[n], 3));
 		}
 	}
-#undef U_TRY
-	*out = h;
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_univnet_destroy(ttk_univnet* h) {
 	if (!h) return TTK_OK;
-	h->ws.release();
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }
@@ -345,15 +310,13 @@ int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int 
 	const int64_t x_el = (int64_t)B * Lmax * C, at_el = (int64_t)B * (Lmax + 6) * lda;
 	TTK_REQUIRE(kern_el * (int64_t)es < ((int64_t)1 << 31) && at_el * 4 < ((int64_t)1 << 31), TTK_E_ARG,
 				"ttk_univnet_inference: %d x %d frames exceed the 2 GiB buffer range of one call", B, Tm);
-	// workspace, 256-byte aligned pieces
-	size_t off = 0;
-	auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-	const size_t o_kern = take((size_t)kern_el * es), o_kb = take((size_t)B * T1 * bst * 4);
-	const size_t o_x = take((size_t)x_el * 4), o_y = take((size_t)std::max(std::max<int64_t>(x_el, (int64_t)B * (Lmax + 6)), (int64_t)B * (T1 + 6) * C) * 4);
-	const size_t o_at = take((size_t)at_el * es), o_mel = take((size_t)B * T1 * mel_ld * es), o_z = take((size_t)B * (T1 + 6) * z_ld * es);
-	const size_t o_c = take((size_t)B * T1 * H * 4), o_tmp = take((size_t)B * T1 * H * 4), o_ct = take((size_t)B * T1 * hid_ld * es),
-				 o_ht = take((size_t)B * T1 * hid_ld * es);
-	TTK_TRY(h->ws.reserve(off));
+	WsPlan ws;
+	const size_t o_kern = ws.take((size_t)kern_el * es), o_kb = ws.take((size_t)B * T1 * bst * 4);
+	const size_t o_x = ws.take((size_t)x_el * 4), o_y = ws.take((size_t)std::max(std::max<int64_t>(x_el, (int64_t)B * (Lmax + 6)), (int64_t)B * (T1 + 6) * C) * 4);
+	const size_t o_at = ws.take((size_t)at_el * es), o_mel = ws.take((size_t)B * T1 * mel_ld * es), o_z = ws.take((size_t)B * (T1 + 6) * z_ld * es);
+	const size_t o_c = ws.take((size_t)B * T1 * H * 4), o_tmp = ws.take((size_t)B * T1 * H * 4), o_ct = ws.take((size_t)B * T1 * hid_ld * es),
+				 o_ht = ws.take((size_t)B * T1 * hid_ld * es);
+	TTK_TRY(h->ws.reserve(ws.total));
 	char* base = (char*)h->ws.p;
 	void* kern = base + o_kern;        // T [B*T'][kst]: predicted kernels of the current block
 	float* kb = (float*)(base + o_kb); // f32 [B*T'][bst]: predicted biases
@@ -383,43 +346,32 @@ int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int 
 	int L = T1, cond_hop = 1;
 	for (int i = 0; i < c.n_blocks; ++i) {
 		const LvcBlock& blk = h->blocks[i];
-		const int u = c.strides[i], pd = u / 2 + u % 2;
+		const int u = c.strides[i];
 		cond_hop *= u;
-		// convt_pre: output phase r of y[u m + r] = sum_tap x[m + (r + pd - j) / u] W_j,  j = (r + pd) % u + u tap  (two taps)
-		for (int r = 0; r < u; ++r) {
-			GemmParams g = {};
-			g.nseg = 2;
-			for (int tp = 0; tp < 2; ++tp) {
-				const int j = (r + pd) % u + u * tp;
-				g.seg[tp] = {at, lda, (r + pd - j) / u, (int64_t)j * blk.convt.Npad * blk.convt.Kpad};
-			}
-			g.W = blk.convt.w; g.ldw = blk.convt.Kpad; g.M = B * L; g.N = C; g.K = blk.convt.Kpad; g.rows_per_batch = L; g.bias = blk.convt.bias;
-			g.C = x + (size_t)r * C; g.ldc = (int64_t)u * C; g.out_f32 = 1;
-			launch_gemm(dt, g, s);
-		}
+		convt_phases(dt, at, lda, blk.convt, 2 * u, u, u / 2 + u % 2, B * L, L, x, s);       // convt_pre: kernel 2u, two taps per phase
 		L *= u;
 		const int M = B * L;
 		// kernel predictor at mel rate
 		{
 			const int M1 = B * T1;
-			conv_rows(dt, melt, mel_ld, blk.kp.in, 5, 1, M1, T1, ktmp, 1, s);
+			conv_same(dt, melt, mel_ld, blk.kp.in, 5, 1, M1, T1, nullptr, ktmp, 1, s);
 			ActRows p = act_cl(ktmp, (int64_t)T1 * H, H, B, T1, H, 1, 0, kct, hid_ld);
 			p.out32 = kc32;
 			launch_act(dt, p, s);                                                                     // c = lrelu(input_conv(mel))
 			for (int j = 0; j < 3; ++j) {
-				conv_rows(dt, kct, hid_ld, blk.kp.res[j][0], kc, 1, M1, T1, ktmp, 1, s);
+				conv_same(dt, kct, hid_ld, blk.kp.res[j][0], kc, 1, M1, T1, nullptr, ktmp, 1, s);
 				launch_act(dt, act_cl(ktmp, (int64_t)T1 * H, H, B, T1, H, 1, 0, kht, hid_ld), s);
-				conv_rows(dt, kht, hid_ld, blk.kp.res[j][1], kc, 1, M1, T1, ktmp, 1, s);
+				conv_same(dt, kht, hid_ld, blk.kp.res[j][1], kc, 1, M1, T1, nullptr, ktmp, 1, s);
 				ActRows q = act_cl(ktmp, (int64_t)T1 * H, H, B, T1, H, 1, 0, kct, hid_ld);
 				q.out32 = kc32; q.accumulate = 1;
 				launch_act(dt, q, s);                                                                 // c = c + lrelu(conv(...))
 			}
-			conv_rows(dt, kct, hid_ld, blk.kp.kernel, kc, 1, M1, T1, kern, 0, s);                     // T [B*T'][kst]
-			conv_rows(dt, kct, hid_ld, blk.kp.bias, kc, 1, M1, T1, kb, 1, s);                         // f32 [B*T'][bst]
+			conv_same(dt, kct, hid_ld, blk.kp.kernel, kc, 1, M1, T1, nullptr, kern, 0, s);                     // T [B*T'][kst]
+			conv_same(dt, kct, hid_ld, blk.kp.bias, kc, 1, M1, T1, nullptr, kb, 1, s);                         // f32 [B*T'][bst]
 		}
 		launch_act(dt, act_cl(x, (int64_t)L * C, C, B, L, C, 1, 0, at, lda), s);                     // lrelu(x), first layer's operand
 		for (int n = 0; n < c.n_layers; ++n) {
-			conv_rows(dt, at, lda, blk.conv[n], 3, c.dilations[n], M, L, y, 1, s);                    // y = conv_d(lrelu(x)), f32
+			conv_same(dt, at, lda, blk.conv[n], 3, c.dilations[n], M, L, nullptr, y, 1, s);                    // y = conv_d(lrelu(x)), f32
 			if (dt == DT_BF16) launch_lvc_t<bf16>(C, y, kern, kb, x, at, B, L, cond_hop, T1, n, kst, bst, lda, s);
 			else launch_lvc_t<float>(C, y, kern, kb, x, at, B, L, cond_hop, T1, n, kst, bst, lda, s);
 		}
@@ -428,11 +380,7 @@ int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int 
 	// conv_post: LeakyReLU, reflect pad 3, Conv1d(C -> 1, 7), Tanh; trim the padding frames' hops, clamp
 	launch_act(dt, act_cl(x, (int64_t)L * C, C, B, L, C, 1, 3, at, lda), s);
 	conv_valid(dt, at, lda, h->conv_post, 7, B * (L + 6), L + 6, y, s);
-	{
-		const int keep = Tm * hop;
-		const int64_t total = (int64_t)B * keep;
-		hipLaunchKernelGGL(k_un_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, y, B, L + 6, keep, audio);
-	}
+	hipLaunchKernelGGL(k_tanh_out<>, tanh_out_grid(B, Tm * hop), dim3(256), 0, s, y, B, L + 6, Tm * hop, audio);   // conv_post's Tanh, inference :312-313
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

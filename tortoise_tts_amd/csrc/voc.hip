@@ -4,12 +4,12 @@
 // Activation1d :158-181 (UpSample1d :113-136, DownSample1d :139-153, kaiser_sinc_filter1d :40-69), SnakeBeta :237-295.
 //
 // Layout: everything between the first and the last convolution is channels-last [B * L][C], f32 for the residual streams, T for
-// GEMM inputs.  Every Conv1d is the hot path's segment GEMM (one segment per tap, row shift = (tap - (k-1)/2) * dilation, zero rows
-// outside a batch element); channel counts below one k-tile read past the row into finite neighbouring data that meets zero-padded
-// weight columns.  A ConvTranspose1d of stride u is u such GEMMs, one per output phase, each seeing k / u taps and writing its phase
-// through the output row stride.  The anti-aliased snake activation (2x zero-stuffing up-sampler with a 12-tap Kaiser low-pass,
-// SnakeBeta, 12-tap low-pass + decimation by 2) is ONE kernel: each output sample evaluates the 12 up-sampled activations it needs
-// from 13 input rows held in registers.
+// GEMM inputs.  Every Conv1d is the hot path's segment GEMM (ttk_conv.h: one segment per tap, row shift = (tap - (k-1)/2) * dilation,
+// zero rows outside a batch element); channel counts below one k-tile read past the row into finite neighbouring data that meets
+// zero-padded weight columns.  A ConvTranspose1d of stride u is u such GEMMs, one per output phase, each seeing k / u taps and writing
+// its phase through the output row stride (convt_phases).  The anti-aliased snake activation (2x zero-stuffing up-sampler with a
+// 12-tap Kaiser low-pass, SnakeBeta, 12-tap low-pass + decimation by 2) is ONE kernel: each output sample evaluates the 12 up-sampled
+// activations it needs from 13 input rows held in registers.
 #include <math.h>
 #include <stdlib.h>
 
@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 #include "ttk_kernels.h"
 
 using namespace ttk;
@@ -114,15 +114,6 @@ __global__ void k_voc_mean(const float* y0, const float* y1, const float* y2, co
 	out_t[i] = cvt<T>(s);
 }
 
-// audio[b][t] = clamp(tanh(y[b * L + t]), -1, 1) for t < keep   (forward :507-508, inference :531-533)
-__global__ void k_voc_out(const float* y, int B, int L, int keep, float* audio) {
-	const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= (int64_t)B * keep) return;
-	const int b = (int)(i / keep), t = (int)(i - (int64_t)b * keep);
-	float v = tanhf(y[(int64_t)b * L + t]);
-	audio[i] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
-}
-
 struct Snake { float *a = nullptr, *invb = nullptr; };
 struct AmpBlock { Mat c1[3], c2[3]; Snake act[6]; int k = 3; int dil[3] = {1, 3, 5}; };
 
@@ -151,16 +142,6 @@ void launch_snake_t(const float* x, int L, int C, const Snake& sn, const float* 
 void launch_snake(int dt, const float* x, int L, int C, const Snake& sn, const float* g, void* y, int64_t rows, hipStream_t s) {
 	if (dt == DT_BF16) launch_snake_t<bf16>(x, L, C, sn, g, y, rows, s);
 	else launch_snake_t<float>(x, L, C, sn, g, y, rows, s);
-}
-
-// Conv1d(k taps, dilation) over rows: out[M][N] = sum_j A[m + (j - (k-1)/2) * dil] * W_j^T + bias (+ residual)
-void conv_rows(int dt, const void* A, int lda, const Mat& w, int k, int dil, int M, int L, const float* residual, void* C, int out_f32, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = k;
-	for (int j = 0; j < k; ++j) g.seg[j] = {A, lda, (j - (k - 1) / 2) * dil, (int64_t)j * w.Npad * w.Kpad};
-	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.rows_per_batch = L; g.bias = w.bias;
-	g.residual = residual; g.ldr = w.N; g.C = C; g.ldc = w.N; g.out_f32 = out_f32;
-	launch_gemm(dt, g, s);
 }
 
 int upload_snake(Arena& ar, const WeightMap& wm, const std::string& prefix, int C, bool logscale, Snake* out) {
@@ -201,46 +182,37 @@ int ttk_voc_create(ttk_voc** out, const ttk_voc_config* cfg, const ttk_weight_vi
 	}
 	for (int j = 0; j < cfg->n_kernels; ++j)
 		TTK_REQUIRE(cfg->rb_kernel[j] % 2 == 1 && cfg->rb_kernel[j] <= 11, TTK_E_ARG, "ttk_voc_create: resblock kernel %d unsupported (odd, <= 11)", cfg->rb_kernel[j]);
-	ttk_voc* h = new ttk_voc();
+	std::unique_ptr<ttk_voc> h(new ttk_voc());
 	h->cfg = *cfg;
 	h->dt = cfg->dtype;
 	h->es = dtype_size(h->dt);
 	WeightMap wm(w, n_w);
-	int rc = TTK_OK;
-	auto fail = [&](int code) { h->arena.release(); delete h; return code; };
-#define V_TRY(expr) do { rc = (expr); if (rc != TTK_OK) return fail(rc); } while (0)
-	V_TRY(upload_f32(h->arena, wm, "__aa_filter", 12, &h->filt));
-	V_TRY(upload_mat(h->arena, wm, h->dt, "conv_pre.weight", "conv_pre.bias", PK_CONVK, cfg->ch0, cfg->num_mels, false, &h->conv_pre, 7));
+	TTK_TRY(upload_f32(h->arena, wm, "__aa_filter", 12, &h->filt));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "conv_pre.weight", "conv_pre.bias", PK_CONVK, cfg->ch0, cfg->num_mels, false, &h->conv_pre, 7));
 	h->ups.resize(cfg->n_ups);
 	h->blocks.resize((size_t)cfg->n_ups * cfg->n_kernels);
 	ch = cfg->ch0;
 	for (int i = 0; i < cfg->n_ups; ++i) {
 		const std::string u = "ups." + std::to_string(i) + ".0.";
-		V_TRY(upload_mat(h->arena, wm, h->dt, u + "weight", u + "bias", PK_CONVT, ch / 2, ch, false, &h->ups[i], cfg->up_kernel[i]));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, u + "weight", u + "bias", PK_CONVT, ch / 2, ch, false, &h->ups[i], cfg->up_kernel[i]));
 		ch /= 2;
 		for (int j = 0; j < cfg->n_kernels; ++j) {
 			AmpBlock& b = h->blocks[(size_t)i * cfg->n_kernels + j];
 			b.k = cfg->rb_kernel[j];
 			const std::string p = "resblocks." + std::to_string(i * cfg->n_kernels + j) + ".";
-			for (int m = 0; m < 3; ++m) {
-				b.dil[m] = cfg->rb_dil[j][m];
-				V_TRY(upload_mat(h->arena, wm, h->dt, p + "convs1." + std::to_string(m) + ".weight", p + "convs1." + std::to_string(m) + ".bias", PK_CONVK, ch, ch, false, &b.c1[m], b.k));
-				V_TRY(upload_mat(h->arena, wm, h->dt, p + "convs2." + std::to_string(m) + ".weight", p + "convs2." + std::to_string(m) + ".bias", PK_CONVK, ch, ch, false, &b.c2[m], b.k));
-			}
-			for (int m = 0; m < 6; ++m) V_TRY(upload_snake(h->arena, wm, p + "activations." + std::to_string(m) + ".act.", ch, cfg->snake_logscale != 0, &b.act[m]));
+			for (int m = 0; m < 3; ++m) b.dil[m] = cfg->rb_dil[j][m];
+			TTK_TRY(upload_resblock(h->arena, wm, h->dt, p, ch, b.k, b.c1, b.c2));
+			for (int m = 0; m < 6; ++m) TTK_TRY(upload_snake(h->arena, wm, p + "activations." + std::to_string(m) + ".act.", ch, cfg->snake_logscale != 0, &b.act[m]));
 		}
 	}
-	V_TRY(upload_snake(h->arena, wm, "activation_post.act.", ch, cfg->snake_logscale != 0, &h->act_post));
-	V_TRY(upload_mat(h->arena, wm, h->dt, "conv_post.weight", "conv_post.bias", PK_CONVK, 1, ch, false, &h->conv_post, 7));
-#undef V_TRY
-	*out = h;
+	TTK_TRY(upload_snake(h->arena, wm, "activation_post.act.", ch, cfg->snake_logscale != 0, &h->act_post));
+	TTK_TRY(upload_mat(h->arena, wm, h->dt, "conv_post.weight", "conv_post.bias", PK_CONVK, 1, ch, false, &h->conv_post, 7));
+	*out = h.release();
 	return TTK_OK;
 }
 
 int ttk_voc_destroy(ttk_voc* h) {
 	if (!h) return TTK_OK;
-	h->ws.release();
-	h->arena.release();
 	delete h;
 	return TTK_OK;
 }
@@ -266,49 +238,40 @@ int ttk_voc_inference(ttk_voc* h, const float* mel, int B, int Tm, float* audio,
 	TTK_REQUIRE(max_el * 4 < ((int64_t)1 << 31), TTK_E_ARG, "ttk_voc_inference: %d x %d frames exceed the 2 GiB buffer range of one call", B, Tm);
 	const int mel_ld = h->conv_pre.Kpad;
 	const size_t f32b = (size_t)max_el * 4, tb = (size_t)max_el * es;
-	const size_t off_in = 0, off_xt = off_in + (size_t)B * L0 * mel_ld * es, off_at = off_xt + tb, off_y = off_at + tb, off_h = off_y + f32b, off_xb = off_h + f32b;
-	TTK_TRY(h->ws.reserve(off_xb + f32b * c.n_kernels + 256));
+	WsPlan ws;
+	const size_t o_in = ws.take((size_t)B * L0 * mel_ld * es), o_xt = ws.take(tb), o_at = ws.take(tb), o_y = ws.take(f32b), o_h = ws.take(f32b);
+	size_t o_xb[4];
+	for (int j = 0; j < 4; ++j) o_xb[j] = j < c.n_kernels ? ws.take(f32b) : o_xb[0];
+	TTK_TRY(h->ws.reserve(ws.total));
 	char* base = (char*)h->ws.p;
-	void* mel_t = base + off_in;      // T [B*L0][mel_ld]
-	void* xt = base + off_xt;         // T copy of the stage input (A operand of the transposed convolution)
-	void* at = base + off_at;         // T output of the activation kernel (A operand of the AMP convolutions)
-	float* y = (float*)(base + off_y);    // f32 transposed-conv output = input of the stage's AMP blocks; later the stage mean
-	float* hb = (float*)(base + off_h);   // f32 output of convs1
+	void* mel_t = base + o_in;        // T [B*L0][mel_ld]
+	void* xt = base + o_xt;           // T copy of the stage input (A operand of the transposed convolution)
+	void* at = base + o_at;           // T output of the activation kernel (A operand of the AMP convolutions)
+	float* y = (float*)(base + o_y);      // f32 transposed-conv output = input of the stage's AMP blocks; later the stage mean
+	float* hb = (float*)(base + o_h);     // f32 output of convs1
 	float* xb[4];
-	for (int j = 0; j < 4; ++j) xb[j] = (float*)(base + off_xb + f32b * (j < c.n_kernels ? j : 0));
+	for (int j = 0; j < 4; ++j) xb[j] = (float*)(base + o_xb[j]);
 
 	{
 		const int64_t total = (int64_t)B * L0 * mel_ld;
 		if (dt == DT_BF16) hipLaunchKernelGGL((k_voc_mel_in<bf16>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mel, B, c.num_mels, Tm, PAD, -11.5129f, (bf16*)mel_t, mel_ld);
 		else hipLaunchKernelGGL((k_voc_mel_in<float>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mel, B, c.num_mels, Tm, PAD, -11.5129f, (float*)mel_t, mel_ld);
 	}
-	conv_rows(dt, mel_t, mel_ld, h->conv_pre, 7, 1, B * L0, L0, nullptr, xt, 0, s);      // conv_pre -> T [B*L0][ch0]
+	conv_same(dt, mel_t, mel_ld, h->conv_pre, 7, 1, B * L0, L0, nullptr, xt, 0, s);      // conv_pre -> T [B*L0][ch0]
 	int L = L0, ch = c.ch0;
 	for (int i = 0; i < c.n_ups; ++i) {
-		const int u = c.up_rate[i], k = c.up_kernel[i], pd = (k - u) / 2, cout = ch / 2;
-		const Mat& W = h->ups[i];
-		// transposed convolution, one GEMM per output phase r: y[u*m + r] = sum_i x[m + (r + pd - j_i) / u] * W[:, :, j_i],  j_i = (r + pd) % u + u*i
-		for (int r = 0; r < u; ++r) {
-			GemmParams g = {};
-			g.nseg = k / u;
-			for (int t = 0; t < g.nseg; ++t) {
-				const int j = (r + pd) % u + u * t;
-				g.seg[t] = {xt, ch, (r + pd - j) / u, (int64_t)j * W.Npad * W.Kpad};
-			}
-			g.W = W.w; g.ldw = W.Kpad; g.M = B * L; g.N = cout; g.K = W.Kpad; g.rows_per_batch = L; g.bias = W.bias;
-			g.C = y + (size_t)r * cout; g.ldc = (int64_t)u * cout; g.out_f32 = 1;
-			launch_gemm(dt, g, s);
-		}
-		L *= u; ch = cout;
+		const int u = c.up_rate[i], k = c.up_kernel[i];
+		convt_phases(dt, xt, ch, h->ups[i], k, u, (k - u) / 2, B * L, L, y, s);
+		L *= u; ch /= 2;
 		const int M = B * L;
 		for (int j = 0; j < c.n_kernels; ++j) {
 			const AmpBlock& b = h->blocks[(size_t)i * c.n_kernels + j];
 			const float* cur = y;
 			for (int m = 0; m < 3; ++m) {
 				launch_snake(dt, cur, L, ch, b.act[2 * m], h->filt, at, M, s);
-				conv_rows(dt, at, ch, b.c1[m], b.k, b.dil[m], M, L, nullptr, hb, 1, s);
+				conv_same(dt, at, ch, b.c1[m], b.k, b.dil[m], M, L, nullptr, hb, 1, s);
 				launch_snake(dt, hb, L, ch, b.act[2 * m + 1], h->filt, at, M, s);
-				conv_rows(dt, at, ch, b.c2[m], b.k, 1, M, L, cur, xb[j], 1, s);          // + bias + residual (aliases the output from m = 1 on)
+				conv_same(dt, at, ch, b.c2[m], b.k, 1, M, L, cur, xb[j], 1, s);          // + bias + residual (aliases the output from m = 1 on)
 				cur = xb[j];
 			}
 		}
@@ -321,12 +284,8 @@ int ttk_voc_inference(ttk_voc* h, const float* mel, int B, int Tm, float* audio,
 	}
 	const int M = B * L;
 	launch_snake(dt, y, L, ch, h->act_post, h->filt, at, M, s);
-	conv_rows(dt, at, ch, h->conv_post, 7, 1, M, L, nullptr, hb, 1, s);                  // [M][1] f32
-	{
-		const int keep = Tm * hop;
-		const int64_t total = (int64_t)B * keep;
-		hipLaunchKernelGGL(k_voc_out, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, hb, B, L, keep, audio);
-	}
+	conv_same(dt, at, ch, h->conv_post, 7, 1, M, L, nullptr, hb, 1, s);                  // [M][1] f32
+	hipLaunchKernelGGL(k_tanh_out<>, tanh_out_grid(B, Tm * hop), dim3(256), 0, s, hb, B, L, Tm * hop, audio);      // forward :507-508, inference :531-533
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

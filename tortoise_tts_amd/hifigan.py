@@ -14,7 +14,7 @@ from typing import Iterable, Iterator, Mapping, Tuple
 import torch
 
 from . import _lib
-from .vocoder import fold_weight_norm
+from .vocoder import Vocoder
 from .weights import HiFiGANConfig, hifigan_shapes
 
 
@@ -46,38 +46,15 @@ def config_c(cfg: HiFiGANConfig, dtype: str) -> HiFiGANConfigC:
 	return c
 
 
-class HiFiGAN:
-	"""`vocoder = load_model("hifigan")` of the reference (HifiganGenerator, inference side only)."""
+class HiFiGAN(Vocoder):
+	"""`vocoder = load_model("hifigan")` of the reference (HifiganGenerator, inference side only).  A tensor the state dict lacks is
+	named by `ttk_hifigan_create`.  (The weight-norm fold of a ConvTranspose1d: dimension 0 is the input channel, and weight_norm's
+	dim=0 norms over the others there too.)"""
+	_abi, _config_c, _shapes = "hifigan", staticmethod(config_c), staticmethod(hifigan_shapes)
 
 	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg: HiFiGANConfig = HiFiGANConfig(), dtype: str = "bf16", device: str = "cuda:0"):
-		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
-		if dtype not in ("bf16", "bfloat16", "f32", "fp32", "float32"):
-			raise _lib.TTKError("the vocoder runs in 'bf16' or 'f32'")
-		self.lib = _lib.load()
+		super().__init__(state_dict, cfg, dtype, device)
 		self.hop_length = cfg.hop_length
-		c = config_c(cfg, dtype)
-		sd = fold_weight_norm(state_dict)       # ConvTranspose1d: dimension 0 is the input channel, and weight_norm's dim=0 norms over the others there too
-		names = list(hifigan_shapes(cfg).keys())
-		views, keep = _lib.weight_views({n: sd[n] for n in names if n in sd}, [n for n in names if n in sd])
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_hifigan_create(C.byref(self._h), C.byref(c), views, len(views)), "ttk_hifigan_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_hifigan_destroy(h)
-			self._h = None
-
-	def eval(self, inference: bool = False):
-		return self
-
-	def to(self, *a, **k):
-		return self
 
 	def samples(self, n: int) -> int:
 		"""samples `inference` returns for n latents"""

@@ -13,7 +13,7 @@ from typing import Mapping, Optional
 import torch
 
 from . import _lib
-from .vocoder import fold_weight_norm
+from .vocoder import Vocoder
 from .weights import UnivNetConfig, univnet_shapes
 
 MEL_PAD_FRAMES = 10          # inference :305-306
@@ -42,43 +42,15 @@ def config_c(cfg: UnivNetConfig, dtype: str) -> UnivNetConfigC:
 	return c
 
 
-class UnivNet:
+class UnivNet(Vocoder):
 	"""`vocoder = load_model("vocoder")` of the reference (UnivNetGenerator, inference side only)."""
+	_abi, _lacks, _config_c, _shapes = "univnet", "UnivNet", staticmethod(config_c), staticmethod(univnet_shapes)
 
 	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg: UnivNetConfig = UnivNetConfig(), dtype: str = "bf16", device: str = "cuda:0"):
-		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
-		if dtype not in ("bf16", "bfloat16", "f32", "fp32", "float32"):
-			raise _lib.TTKError("the vocoder runs in 'bf16' or 'f32'")
-		self.lib = _lib.load()
+		super().__init__(state_dict, cfg, dtype, device)
 		self.hop_length = cfg.hop_length
 		self.mel_channel = cfg.num_mels
 		self.noise_dim = cfg.noise_dim
-		c = config_c(cfg, dtype)
-		sd = fold_weight_norm(state_dict)
-		names = list(univnet_shapes(cfg).keys())
-		missing = [n for n in names if n not in sd]
-		if missing:
-			raise _lib.TTKError(f"state_dict lacks {len(missing)} UnivNet tensors, e.g. {missing[:3]}")
-		views, keep = _lib.weight_views({n: sd[n] for n in names}, names)
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_univnet_create(C.byref(self._h), C.byref(c), views, len(names)), "ttk_univnet_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_univnet_destroy(h)
-			self._h = None
-
-	def eval(self, inference: bool = False):
-		return self
-
-	def to(self, *a, **k):
-		return self
 
 	def draw_noise(self, B: int, T: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
 		"""The z of inference :309 for a [B, num_mels, T] mel: [B, noise_dim, T + 10] from `generator` (default: the CPU default generator)."""

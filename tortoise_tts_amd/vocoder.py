@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, Mapping
+from typing import Callable, Dict, Mapping, Optional
 
 import torch
 
@@ -65,10 +65,17 @@ class VocConfigC(C.Structure):
 				("dtype", C.c_int)]
 
 
-class BigVGAN:
-	"""`vocoder = load_model("bigvgan")` of the reference, inference side only."""
+class Vocoder:
+	"""What the three vocoder wrappers (BigVGAN here, univnet.UnivNet, hifigan.HiFiGAN) share: the handle `ttk_<abi>_create` makes from the
+	weight-norm-folded tensors `shapes(cfg)` names, and its lifetime.  The subclass says which library entry points (`_abi`), how its
+	config becomes the C struct (`_config_c`) and which tensors it takes (`_shapes`).  `_lacks` set: a missing tensor raises here, as
+	"state_dict lacks N <_lacks> tensors"; None: the tensors present are passed on and `ttk_<abi>_create` names the missing one."""
+	_abi: str
+	_lacks: Optional[str] = None
+	_config_c: Callable
+	_shapes: Callable
 
-	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg: VocoderConfig = VocoderConfig(), dtype: str = "bf16", device: str = "cuda:0"):
+	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg, dtype: str, device: str, extra: Optional[Mapping[str, torch.Tensor]] = None):
 		self.cfg = cfg
 		self.device = torch.device(device)
 		if self.device.type != "cuda":
@@ -76,17 +83,48 @@ class BigVGAN:
 		if dtype not in ("bf16", "bfloat16", "f32", "fp32", "float32"):
 			raise _lib.TTKError("the vocoder runs in 'bf16' or 'f32'")
 		self.lib = _lib.load()
+		c = self._config_c(cfg, dtype)
+		sd = fold_weight_norm(state_dict)
+		names = list(self._shapes(cfg).keys())
+		missing = [n for n in names if n not in sd]
+		if missing and self._lacks:
+			raise _lib.TTKError(f"state_dict lacks {len(missing)} {self._lacks} tensors, e.g. {missing[:3]}")
+		names = [n for n in names if n in sd]
+		sd = {n: sd[n] for n in names}
+		for n, t in (extra or {}).items():       # host-built constants the handle takes like weights
+			sd[n] = t
+			names.append(n)
+		views, keep = _lib.weight_views(sd, names)
+		self._h = C.c_void_p()
+		create = f"ttk_{self._abi}_create"
+		with torch.cuda.device(self.device):
+			_lib.check(getattr(self.lib, create)(C.byref(self._h), C.byref(c), views, len(names)), create)
+		del keep
+
+	def __del__(self):
+		h = getattr(self, "_h", None)
+		if h:
+			getattr(self.lib, f"ttk_{self._abi}_destroy")(h)
+			self._h = None
+
+	def eval(self, inference: bool = False):
+		return self
+
+	def to(self, *a, **k):
+		return self
+
+
+class BigVGAN(Vocoder):
+	"""`vocoder = load_model("bigvgan")` of the reference, inference side only."""
+	_abi, _lacks, _shapes = "voc", "vocoder", staticmethod(vocoder_shapes)
+
+	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg: VocoderConfig = VocoderConfig(), dtype: str = "bf16", device: str = "cuda:0"):
+		super().__init__(state_dict, cfg, dtype, device, extra={"__aa_filter": aa_filter()})
 		self.hop_length = cfg.hop_size
 		self.mel_channel = cfg.num_mels
-		sd = fold_weight_norm(state_dict)
-		names = list(vocoder_shapes(cfg).keys())
-		missing = [n for n in names if n not in sd]
-		if missing:
-			raise _lib.TTKError(f"state_dict lacks {len(missing)} vocoder tensors, e.g. {missing[:3]}")
-		sd = {n: sd[n] for n in names}
-		sd["__aa_filter"] = aa_filter()
-		names.append("__aa_filter")
-		views, keep = _lib.weight_views(sd, names)
+
+	@staticmethod
+	def _config_c(cfg: VocoderConfig, dtype: str) -> VocConfigC:
 		c = VocConfigC()
 		c.num_mels, c.n_ups, c.ch0, c.n_kernels = cfg.num_mels, len(cfg.upsample_rates), cfg.upsample_initial_channel, len(cfg.resblock_kernel_sizes)
 		for i, (u, k) in enumerate(zip(cfg.upsample_rates, cfg.upsample_kernel_sizes)):
@@ -96,22 +134,7 @@ class BigVGAN:
 			for m in range(3):
 				c.rb_dil[j][m] = d[m]
 		c.snake_logscale, c.dtype = int(cfg.snake_logscale), _lib.DTYPES[dtype]
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_voc_create(C.byref(self._h), C.byref(c), views, len(names)), "ttk_voc_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_voc_destroy(h)
-			self._h = None
-
-	def eval(self, inference: bool = False):
-		return self
-
-	def to(self, *a, **k):
-		return self
+		return c
 
 	@torch.inference_mode()
 	def inference(self, c: torch.Tensor, z=None) -> torch.Tensor:
