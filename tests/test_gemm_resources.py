@@ -49,8 +49,9 @@ def kernel_name(sym):
 	return f"k_gemm<{t},{bm},{bn},{nwm},{nwn},{ns},{ROLES[role]}{',LONGK' if longk else ''}>"
 
 
-def gemm_kernel_resources(tmp_path):
-	paths = {t: shutil.which(t, path=LLVM_BIN) for t in TOOLS}
+def gemm_code_object(tmp_path, tools=TOOLS):
+	"""(tool paths, path of the gfx950 code object taken out of csrc/build/gemm.o)"""
+	paths = {t: shutil.which(t, path=LLVM_BIN) for t in tools}
 	if not all(paths.values()):
 		pytest.skip(f"ROCm LLVM tools missing under {LLVM_BIN}: {[t for t, p in paths.items() if not p]}")
 	_lib.build()
@@ -58,6 +59,11 @@ def gemm_kernel_resources(tmp_path):
 	subprocess.run([paths["llvm-objcopy"], f"--dump-section=.hip_fatbin={fatbin}", GEMM_O, str(tmp_path / "discard.o")], check=True, capture_output=True)
 	subprocess.run([paths["clang-offload-bundler"], "--unbundle", "--type=o", f"--input={fatbin}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
 					f"--output={co}"], check=True, capture_output=True)
+	return paths, co
+
+
+def gemm_kernel_resources(tmp_path):
+	paths, co = gemm_code_object(tmp_path)
 	notes = subprocess.run([paths["llvm-readelf"], "--notes", co], check=True, capture_output=True, text=True).stdout
 	out = {}
 	for block in re.split(r"\n\s*- \.(?=agpr_count|args)", notes):
@@ -94,3 +100,29 @@ def test_kernel_name_reading():
 	assert kernel_name("_ZN3ttk6k_gemmIDF16_Li256ELi128ELi4ELi2ELi3ELi0ELb1EEEvNS_10GemmParamsE") == "k_gemm<f16,256,128,4,2,3,GR_NONE,LONGK>"
 	assert kernel_name("_ZN3ttk12k_gemm_mixedINS_2f8ELi4EEEvNS_10GemmParamsE") == "k_gemm_mixed<f8,GR_PROJ_RES>"
 	assert kernel_name("_ZN3ttk6k_gemmIfLi64ELi64ELi2ELi2ELi3ELi0ELb0EEEvNS_10GemmParamsE") == "k_gemm<f32,64,64,2,2,3,GR_NONE>"
+
+
+def test_gemm_kernels_touch_m0_only_by_scalar_moves(tmp_path):
+	"""The hand-ordered k-loops write M0 from inline asm without declaring it (csrc/gemm_prims.h, "M0 INVARIANT"): they save it in front of the loop, restore
+	it behind, and rely on the compiler using M0 nowhere in a GEMM kernel.  Held here on the disassembled code object: every instruction of a k_gemm* kernel
+	that names m0 is `s_mov_b32 m0, sN` (an LDS-DMA piece's base, or the restore) or `s_mov_b32 sN, m0` (the save)."""
+	paths, co = gemm_code_object(tmp_path, TOOLS + ("llvm-objdump",))
+	text = subprocess.run([paths["llvm-objdump"], "-d", "--no-show-raw-insn", co], check=True, capture_output=True, text=True).stdout
+	ok = re.compile(r"s_mov_b32 (m0, s\d+|s\d+, m0)$")
+	kernel, seen, writes, reads, bad = None, set(), 0, 0, []
+	for line in text.split("\n"):
+		label = re.match(r"[0-9a-f]+ <(\S+)>:$", line)
+		if label:
+			kernel = label.group(1) if re.match(r"_ZN3ttk\d+k_gemm", label.group(1)) else None
+			seen.add(kernel)
+			continue
+		ins = line.split("//")[0].strip()
+		if kernel and re.search(r"\bm0\b", ins):
+			if not ok.search(ins):
+				bad.append(f"{kernel_name(kernel)}: {ins}")
+			writes += " m0, " in ins
+			reads += ins.endswith(", m0")
+	seen.discard(None)
+	print(f"{len(seen)} GEMM kernels: {writes} moves into m0, {reads} moves out of m0")
+	assert len(seen) >= 80 and writes > 0 and reads > 0, f"{len(seen)} GEMM kernels, {writes} / {reads} m0 moves found in the disassembly"
+	assert not bad, "GEMM kernels use m0 other than by s_mov_b32 to / from an SGPR:\n" + "\n".join(bad[:40])

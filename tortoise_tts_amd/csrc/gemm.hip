@@ -4,7 +4,7 @@
 //   GPT-2 c_attn / c_proj / c_fc / mlp.c_proj (HF Conv1D, HF:pytorch_utils.py:95-120) for prefill + latent pass,
 //   mel_head, DiffusionTTS 1x1 convs (qkv, proj_out, in_layers.2, integrating_conv = 2 concatenated segments),
 //   k=3 convs (inp_block, latent_conditioner.0, out_layers.3, out.2 = 3 row-shifted segments, zero padded at the
-//   edges of each batch element), emb_layers / time_embed linears.   (/root/reference/tortoise_tts/models/diffusion.py:1316-1376,1517-1574)
+//   edges of each batch element), emb_layers / time_embed linears.   (tortoise_tts/models/diffusion.py:1316-1376,1517-1574)
 //
 // Tiling: 256 threads = 4 waves (2x2), BMxBN block tile, 128-byte-row LDS tiles (64 bf16 / 32 f32 of K) with XOR-swizzled
 // 16-byte chunks, 16x16 MFMA sub-tiles, f32 accumulate.  Operand staging is direct-to-LDS (`global_load_lds_dwordx4`, one
@@ -25,322 +25,9 @@
 
 #include <hip/hip_ext.h>
 
-#include "ttk_common.h"
-#include "ttk_kernels.h"
+#include "gemm_epilogue.h"
 
 namespace ttk {
-
-// One LDS-DMA piece: 64 lanes x 16 B from buffer offsets (per-lane voff + scalar soff) to LDS bytes [lds_dst, lds_dst + 1024).
-// Issued from inline asm on purpose: hipcc's waitcnt pass would otherwise put `s_waitcnt vmcnt(0)` in front of the first ds_read
-// of every k-step (it cannot prove that the ring stage being read is not the one being filled) and serialise the ring; hidden
-// from it, the only vmcnt waits in the k-loop are the counted ones below (cdna_hip_programming.md section 5.7, items 1-2).
-// M0 carries the LDS base; it is compiler-reserved, so it is saved and restored inside the statement.
-__device__ __forceinline__ void glds16(unsigned voff, __amdgpu_buffer_rsrc_t srd, unsigned soff, unsigned lds_dst /* wave-uniform */) {
-	unsigned keep;
-	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-				 : "=&s"(keep) : "s"(lds_dst), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-	return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-}
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// ------------------------------------------------------------------------------------------------ hand-ordered k-loop (16-bit operands, 3-stage ring)
-// What the compiler made of the C++ ping-pong (profiles/r06_gemm_kloop_isa_*_before.txt): `cur` and `nxt` in the SAME registers, the next tile's 12 ds_read_b128
-// sunk behind MFMA 9-16 and drained by lgkmcnt(0) in front of every barrier, all six DMA issues in front of MFMA 1 -- the measured "sum, not maximum" (VERDICT r05
-// weak #3).  Here the fragment reads, the DMA pieces and the waits are `asm volatile` statements (invisible to the waitcnt pass, like glds16), the MFMAs stay
-// builtins (the compiler knows the matrix pipe's write-back hazards: an all-asm first version let it copy accumulators between two loop bodies with no wait
-// states -- 5e-2 errors), and a full scheduling fence (`sched_barrier(0)`) behind every statement pins the order written below: the source order IS the
-// instruction stream.  The compiler still allocates the registers (two real fragment sets).  What stays ours: a read's data is used only behind the
-// `s_waitcnt lgkmcnt(0)` that ends the step it was issued in (any copy the register allocator might add at a loop edge lands behind that wait too); M0 is
-// written by the DMA statements only (saved in front of the loop, restored behind it; the compiler has no M0 use of its own in this kernel).
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-#define TTK_FENCE() __builtin_amdgcn_sched_barrier(0)
-template <int OFF> __device__ __forceinline__ void pipe_read16(u32x4& d, unsigned addr) {
-	static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field");
-	asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-	TTK_FENCE();
-}
-template <typename T> __device__ __forceinline__ void pipe_mfma(f32x4& c, const u32x4& a, const u32x4& b) {
-	union U { u32x4 q; typename Frag<T>::type v; __device__ U() {} } ua, ub;
-	ua.q = a; ub.q = b;
-	c = mma16<T>(ua.v, ub.v, c);
-	TTK_FENCE();
-}
-__device__ __forceinline__ void pipe_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); TTK_FENCE(); }
-__device__ __forceinline__ void pipe_glds16(unsigned voff, __amdgpu_buffer_rsrc_t srd, unsigned soff, unsigned lds_dst /* wave-uniform */) {
-	asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(lds_dst), "v"(voff), "s"(srd), "s"(soff) : "memory");
-	TTK_FENCE();
-}
-__device__ __forceinline__ unsigned pipe_m0_save() { unsigned k; asm volatile("s_mov_b32 %0, m0" : "=s"(k)); TTK_FENCE(); return k; }
-__device__ __forceinline__ void pipe_m0_restore(unsigned k) { asm volatile("s_mov_b32 m0, %0" :: "s"(k)); TTK_FENCE(); }
-template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-	if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
-}
-// placement knobs of the hand-ordered k-step (tuning builds: -DTTK_PIPE_...=n); gaps are counted in MFMAs of the step, 0 = behind the first one
-#ifndef TTK_GEMM_PIPE
-#define TTK_GEMM_PIPE 1
-#endif
-#ifndef TTK_PIPE_RPG
-#define TTK_PIPE_RPG 2      // fragment reads per MFMA gap
-#endif
-#ifndef TTK_PIPE_PREB
-#define TTK_PIPE_PREB 0     // MFMAs issued in front of the step's barrier (reads start behind it)
-#endif
-#ifndef TTK_PIPE_DPG
-#define TTK_PIPE_DPG 1      // DMA pieces per MFMA gap
-#endif
-#ifndef TTK_PIPE_DLATE
-#define TTK_PIPE_DLATE 0    // 1: the DMA pieces fill the LAST gaps of the step; 0: they start TTK_PIPE_D0 gaps behind the barrier (or as late as still fits)
-#endif
-#ifndef TTK_PIPE_D0
-#define TTK_PIPE_D0 6
-#endif
-#ifndef TTK_FP8_SCALED_MFMA
-#define TTK_FP8_SCALED_MFMA 1      // 0: the non-scaled 16x16x32 fp8 MFMA (A/B builds)
-#endif
-#ifndef TTK_GEMM_PIPE_H
-#define TTK_GEMM_PIPE_H 1   // the half-tile form of the hand-ordered loop for 64 x 64 wave blocks
-#endif
-#ifndef TTK_ROLE_STAGES
-#define TTK_ROLE_STAGES 3      // ring depth of the 128 x 64 role tiles
-#endif
-// (profiles/r06_chain_pipe_knobs.log, per layer of the replayed chain on hashed operands: 1 read per gap + pieces last 113.1 us; pieces first 113.9; 2 reads per gap 111.1;
-//  2 reads per gap + pieces from gap 6 111.6 with the shortest launch spans; 2 MFMAs in front of the barrier 112.8; 2 pieces per gap 114.2 -- the compiler-ordered loop 117.3)
-
-// Fused GroupNorm32 statistics of a wave's 64-row block (the values just written: the next op on this tensor is always a GroupNorm): NI/2 whole groups of 32
-// channels; exact two-pass (mean, then centred squares) in registers, two DPP wave reductions per group, one (count, mean, M2) triple per (batch, group,
-// 64-row chunk) for k_gn_apply to merge.  ONE function for the generic and the role epilogues, with the contraction written out (the squares accumulate
-// by fma, nothing else is fused): left to the compiler, two instantiations of the same source rounded M2 differently in the last bit -- found by
-// tests/diag/role_check.cpp -- and results must not depend on which instantiation a shape happens to select.
-template <int MI, int NI>
-__device__ __forceinline__ void gn_block_stats(const f32x4 (&acc)[MI][NI], float* part, int b, int group0, int nch, int chunk, int lane) {
-#pragma clang fp contract(off)
-#pragma unroll
-	for (int gq = 0; gq < NI / 2; ++gq) {
-		float sum = 0.f;
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-				for (int r = 0; r < 4; ++r) sum += acc[i][2 * gq + jj][r];
-		const float mean = wave_sum(sum) * (1.0f / 2048.0f);
-		float sq = 0.f;
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-				for (int r = 0; r < 4; ++r) { const float d = acc[i][2 * gq + jj][r] - mean; sq = __builtin_fmaf(d, d, sq); }
-		sq = wave_sum(sq);
-		if (lane == 0) {
-			float* o = part + (((int64_t)b * 32 + (group0 + gq)) * nch + chunk) * 3;
-			o[0] = 2048.0f; o[1] = mean; o[2] = sq;
-		}
-	}
-}
-
-// Accumulator (i, j) register r is row row0 + 16i + 4*(lane>>4) + r, column col0 + 16j + (lane&15).
-// MODE 0: T-typed C; 1: f32 C (+ f32 residual, which may alias C); 2: f32 C transposed to [batch][N][rows_per_batch].
-// All residual/bias loads are issued before the first store: with C aliasing the residual a load-store-load-store order would
-// serialise 64 dependent L2 round trips per lane.  GUARD = tile crosses the M or N edge.
-template <typename T, int MODE, bool GUARD, int MI, int NI>
-__device__ __forceinline__ void epilogue(const GemmParams& p, f32x4 (&acc)[MI][NI], int row0, int col0, int lane) {
-#pragma clang fp contract(off)      // scale, bias and residual stay three rounded operations in every instantiation (the role epilogue writes them the same way)
-	const int lr = 4 * (lane >> 4), lc = lane & 15;
-	typedef typename OutOf<T>::type OT;
-	if (p.out_scale != 0.f) {
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int j = 0; j < NI; ++j) acc[i][j] *= p.out_scale;
-	}
-	float bj[NI];
-#pragma unroll
-	for (int j = 0; j < NI; ++j) {
-		const int gn = col0 + 16 * j + lc;
-		bj[j] = (p.bias && (!GUARD || gn < p.N)) ? p.bias[gn] : 0.f;
-	}
-	// bias, then the activation under ONE uniform branch (not one per element)
-#pragma unroll
-	for (int i = 0; i < MI; ++i)
-#pragma unroll
-		for (int j = 0; j < NI; ++j)
-#pragma unroll
-			for (int r = 0; r < 4; ++r) acc[i][j][r] += bj[j];
-	if (p.act == ACT_GELU_NEW) {
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int j = 0; j < NI; ++j)
-#pragma unroll
-				for (int r = 0; r < 4; ++r) acc[i][j][r] = gelu_new_f(acc[i][j][r]);
-	} else if (p.act == ACT_SILU) {
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int j = 0; j < NI; ++j)
-#pragma unroll
-				for (int r = 0; r < 4; ++r) acc[i][j][r] = silu_f(acc[i][j][r]);
-	}
-	// residual loads all issued before the first store: the residual aliases C, so interleaving them serialises load -> store pairs
-	float res[MI][4][NI];
-	if (MODE == 1 && p.residual) {
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int r = 0; r < 4; ++r)
-#pragma unroll
-				for (int j = 0; j < NI; ++j) {
-					const int gm = row0 + 16 * i + lr + r, gn = col0 + 16 * j + lc;
-					res[i][r][j] = (!GUARD || (gm < p.M && gn < p.N)) ? p.residual[(int64_t)gm * p.ldr + gn] : 0.f;
-				}
-	} else {
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int r = 0; r < 4; ++r)
-#pragma unroll
-				for (int j = 0; j < NI; ++j) res[i][r][j] = 0.f;
-	}
-#pragma unroll
-	for (int i = 0; i < MI; ++i) {
-#pragma unroll
-		for (int r = 0; r < 4; ++r) {
-			const int gm = row0 + 16 * i + lr + r;
-			int bb = 0, t = 0;
-			if (MODE == 2) { bb = gm / p.rows_per_batch; t = gm - bb * p.rows_per_batch; }
-#pragma unroll
-			for (int j = 0; j < NI; ++j) {
-				const int gn = col0 + 16 * j + lc;
-				if (GUARD && (gm >= p.M || gn >= p.N)) continue;
-				const float v = acc[i][j][r] + res[i][r][j];
-				acc[i][j][r] = v;
-				if (MODE == 2) ((float*)p.C)[((int64_t)bb * p.N + gn) * p.rows_per_batch + t] = v;
-				else if (MODE == 1) ((float*)p.C)[(int64_t)gm * p.ldc + gn] = v;
-				else ((OT*)p.C)[(int64_t)gm * p.ldc + gn] = cvt<OT>(v);
-			}
-		}
-	}
-	if (MODE == 1 && p.gn_part && MI == 4 && row0 < p.M) {
-		const int b = row0 / p.gn_T, chunk = (row0 - b * p.gn_T) / 64, nch = p.gn_T / 64;
-		gn_block_stats<MI, NI>(acc, p.gn_part, b, col0 / 32, nch, chunk, lane);
-	}
-}
-
-// ------------------------------------------------------------------------------------------------ role-specialised form (GemmRole, ttk_kernels.h)
-// What the stamps of tests/diag/ddim_chain.cpp showed for the generic kernel inside the DDIM layer chain: 1.16-1.52 us from a wave's first instruction to its
-// first DMA request and 1.64-2.44 us of epilogue per launch -- 44 % of the four GEMMs' time outside their k-loops.  The first is ~350 instructions of run-time
-// shape arithmetic issued by one wave per SIMD (integer divisions by the m-tile count and by rows_per_batch, 64-bit address products, the segment table);
-// a role turns all of it into constants, shifts and three f32-reciprocal divisions, and reads a dozen argument words instead of the segment table.
-template <int ROLE> struct GRole { static constexpr bool on = false, RES = false, GN = false, CONV = false; static constexpr int N = 0, NSEG = 1, MODE = 0; };
-template <> struct GRole<GR_IN1x1> { static constexpr bool on = true, RES = false, GN = true, CONV = false; static constexpr int N = 1024, NSEG = 1, MODE = 1; };
-template <> struct GRole<GR_CONV3_RES> { static constexpr bool on = true, RES = true, GN = true, CONV = true; static constexpr int N = 1024, NSEG = 3, MODE = 1; };
-template <> struct GRole<GR_QKV> { static constexpr bool on = true, RES = false, GN = false, CONV = false; static constexpr int N = 3072, NSEG = 1, MODE = 0; };
-template <> struct GRole<GR_PROJ_RES> { static constexpr bool on = true, RES = true, GN = true, CONV = false; static constexpr int N = 1024, NSEG = 1, MODE = 1; };
-constexpr int GR_K = 1024;      // K = lda = ldw of every role
-
-// floor(x / d) for 0 <= x < 2^23 with inv = 1.0f / d: the f32 product is off by less than one, so one correction step either way makes it exact
-__device__ __forceinline__ int div_recip(int x, int d, float inv) {
-	int q = (int)((float)x * inv);
-	const int r = x - q * d;
-	q += (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
-	return q;
-}
-
-// The generic epilogue with the role's decisions taken at compile time: bias always, no activation, no scale; ldc = ldr = N; 32-bit element indices
-// (M * N < 2^30, checked by the dispatcher).  Same operations on every value in the same order: bit-identical results.
-// the residual values of a wave's block, one dword per accumulator register (GUARD: a row beyond M reads the clamped LAST row -- the request must leave, see below -- and its value is dropped in the epilogue)
-template <int ROLE, int MI, int NI, bool GUARD>
-__device__ __forceinline__ void load_residual_role(const GemmParams& p, float (&res)[MI][4][NI], int row0, int col0, int lane) {
-	constexpr int N = GRole<ROLE>::N;
-	const int lr = 4 * (lane >> 4), lc = lane & 15;
-#pragma unroll
-	for (int i = 0; i < MI; ++i)
-#pragma unroll
-		for (int r = 0; r < 4; ++r)
-#pragma unroll
-			for (int j = 0; j < NI; ++j) {
-				// GUARD: a row beyond M reads the LAST row instead (its value is dropped in the epilogue).  The request must leave unconditionally: the tail's waits
-				// count exactly RESN loads behind the last DMA request, and a wave whose rows all lie beyond M (wm = 1 of the last tile row when M % 128 == 64) would
-				// otherwise issue none -- vmcnt(PER_TILE + RESN) then waits for nothing and its barrier passes before the last two k-tiles have landed.
-				const int gm = row0 + 16 * i + lr + r;
-				const int gr = GUARD ? min(gm, p.M - 1) : gm;
-				res[i][r][j] = p.residual[(unsigned)(gr * N + col0 + 16 * j + lc)];
-			}
-}
-
-// PRE: `res` already holds the residual (requested under the last k-tiles, see the role kernels' tail)
-// `bj`: the NI bias values of this lane's columns, requested by the caller in front of the k-loop (round 6: fetched here they were an L2 round trip between the last MFMA and the first store)
-template <typename T, int ROLE, bool GUARD, int MI, int NI, bool PRE = false>
-__device__ __forceinline__ void epilogue_role(const GemmParams& p, f32x4 (&acc)[MI][NI], float (&res)[MI][4][NI], const float (&bj)[NI], int row0, int col0, int lane) {
-#pragma clang fp contract(off)
-	typedef GRole<ROLE> R;
-	typedef typename OutOf<T>::type OT;
-	constexpr int N = R::N;
-	const int lr = 4 * (lane >> 4), lc = lane & 15;
-	const float os = sizeof(T) == 1 ? p.out_scale : 1.f;      // fp8 operands: the weights' power-of-two tensor scale (16-bit roles have none)
-	if constexpr (R::RES && !PRE) {      // all residual loads before the first store: C aliases the residual
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int r = 0; r < 4; ++r)
-#pragma unroll
-				for (int j = 0; j < NI; ++j) {
-					const int gm = row0 + 16 * i + lr + r;
-					res[i][r][j] = (!GUARD || gm < p.M) ? p.residual[(unsigned)(gm * N + col0 + 16 * j + lc)] : 0.f;
-				}
-	}
-	if constexpr (R::MODE == 0 && sizeof(OT) == 2 && !R::RES) {
-		// 16-bit output (the q / k / v projection): a lane holds four ROWS of one column, so the plain form is 64 two-byte stores per lane (1.6 us of epilogue).  Neighbouring lanes
-		// hold neighbouring columns: one DPP swap per row pair gives the even lane both columns of the upper row and the odd lane both of the lower one -- 32 dword stores of the
-		// same converted values (round 6).
-		const bool odd = lc & 1;
-#pragma unroll
-		for (int i = 0; i < MI; ++i)
-#pragma unroll
-			for (int j = 0; j < NI; ++j)
-#pragma unroll
-				for (int rp = 0; rp < 2; ++rp) {
-					float v0 = acc[i][j][2 * rp], v1 = acc[i][j][2 * rp + 1];
-					if constexpr (sizeof(T) == 1) { v0 = v0 * os; v1 = v1 * os; }
-					v0 = v0 + bj[j]; v1 = v1 + bj[j];
-					acc[i][j][2 * rp] = v0; acc[i][j][2 * rp + 1] = v1;
-					const float mine = odd ? v1 : v0, give = odd ? v0 : v1;      // the row this lane stores / the row its neighbour stores
-					const float got = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(give), 0xB1, 0xF, 0xF, true));      // quad_perm [1,0,3,2]: the neighbour's value of MY row
-					const uint2 pk = pack4_16<OT>(odd ? got : mine, odd ? mine : got, 0.f, 0.f);      // (column order: even lane's column first)
-					const int gm = row0 + 16 * i + lr + 2 * rp + (odd ? 1 : 0);
-					if (GUARD && gm >= p.M) continue;
-					*(unsigned*)((OT*)p.C + (unsigned)(gm * N + col0 + 16 * j + (lc & ~1))) = pk.x;
-				}
-	} else {
-#pragma unroll
-	for (int i = 0; i < MI; ++i)
-#pragma unroll
-		for (int r = 0; r < 4; ++r) {
-			const int gm = row0 + 16 * i + lr + r;
-#pragma unroll
-			for (int j = 0; j < NI; ++j) {
-				float v = acc[i][j][r];
-				if constexpr (sizeof(T) == 1) v = v * os;
-				v = v + bj[j];
-				if constexpr (R::RES) v += (PRE && GUARD && gm >= p.M) ? 0.f : res[i][r][j];      // (PRE: rows beyond M hold the clamped row's value)
-				acc[i][j][r] = v;
-				if (GUARD && gm >= p.M) continue;
-				const unsigned o = (unsigned)(gm * N + col0 + 16 * j + lc);
-				if constexpr (R::MODE == 1) ((float*)p.C)[o] = v;
-				else ((OT*)p.C)[o] = cvt<OT>(v);
-			}
-		}
-	}
-	if constexpr (R::GN) {
-		if (MI == 4 && row0 < p.M) {
-			const int b = div_recip(row0, p.gn_T, p.inv_gn_T), chunk = (row0 - b * p.gn_T) >> 6, nch = p.gn_T >> 6;
-			gn_block_stats<MI, NI>(acc, p.gn_part, b, col0 / 32, nch, chunk, lane);
-		}
-	}
-}
 
 // ------------------------------------------------------------------------------------------------ k = 3 convolution on a SHARED activation image (round 6)
 // The three taps of out_layers.3 multiply the SAME activation rows shifted by -1 / 0 / +1.  The ring kernel stages a 128-row A tile per (tap, k-chunk): 3 x 16 KiB of a
@@ -354,9 +41,6 @@ __device__ __forceinline__ void epilogue_role(const GemmParams& p, f32x4 (&acc)[
 //   reads of trip t need; the image they need is older) the wave has requested, by tap of t: {image, W} / {W, image} / {W} -> the counted waits B_PC + A_PC, A_PC + B_PC, B_PC.
 //   Batch edges: a row whose frame is the first (last) of its batch element must see zeros on tap -1 (+1) although the image holds the neighbouring element's row there
 //   (another row's tap 0 needs it) -- those lanes' A fragments are cleared in registers behind the step's lgkmcnt(0), under a wave-uniform branch only waves with such a row take.
-#ifndef TTK_CONV_IMAGE
-#define TTK_CONV_IMAGE 1
-#endif
 template <typename T, int BM, int NWM, int NWN, int ROLE>
 __device__ __forceinline__ void conv3_image_tile(const GemmParams& p, const int m0, const int n0, const int wave) {
 	typedef GRole<ROLE> R;
@@ -430,7 +114,6 @@ __device__ __forceinline__ void conv3_image_tile(const GemmParams& p, const int 
 #pragma unroll
 		for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-	auto barrier = [&] { TTK_FENCE(); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); TTK_FENCE(); };
 	auto issue_image = [&](auto i_, auto slot_, unsigned kc) {
 		constexpr int i = decltype(i_)::value, slot = decltype(slot_)::value;
 		const int q = wave + NW * i;
@@ -475,7 +158,7 @@ __device__ __forceinline__ void conv3_image_tile(const GemmParams& p, const int 
 #pragma unroll
 		for (int ks = 0; ks < KSTEPS; ++ks) rb[ks] = fb[ks] + rd_slot;
 		const unsigned soffW = (unsigned)S_CUR * TAPB + kc_w * 128u;
-		if constexpr (RD || PER > 0) { wait_vmcnt<W>(); barrier(); }
+		if constexpr (RD || PER > 0) { wait_vmcnt<W>(); pipe_barrier(); }
 		static_for<0, NM>([&](auto m_) {
 			constexpr int m = decltype(m_)::value, ks = m / (MI * NI), i = (m % (MI * NI)) / NI, j = m % NI;
 			pipe_mfma<T>(acc[i][j], cur.a[ks][i], cur.b[ks][j]);
@@ -495,14 +178,14 @@ __device__ __forceinline__ void conv3_image_tile(const GemmParams& p, const int 
 	typedef std::integral_constant<int, 0> I0; typedef std::integral_constant<int, 1> I1; typedef std::integral_constant<int, 2> I2;
 	typedef std::true_type Y; typedef std::false_type N;
 
-	const unsigned m0_keep = pipe_m0_save();
+	PipeScope scope = pipe_begin();
 	// prologue, in the steady state's request order: image 0, weight tiles 0 .. 2, image 1
 	static_for<0, A_PC>([&](auto i_) { issue_image(i_, I0{}, 0u); });
 	static_for<0, 3>([&](auto t_) { static_for<0, B_PC>([&](auto i_) { issue_w(i_, (unsigned)decltype(t_)::value * TAPB, (unsigned)decltype(t_)::value * BT); }); });
 	static_for<0, A_PC>([&](auto i_) { issue_image(i_, I1{}, 1u); });
 	TTK_WSTAMP(stamps_, blockIdx.x, 1);
 	wait_vmcnt<2 * B_PC + A_PC>();      // image 0 and weight tile 0 have landed
-	barrier();
+	pipe_barrier();
 	TTK_WSTAMP(stamps_, blockIdx.x, 2);
 	PFrags f0, f1;
 	{
@@ -513,9 +196,7 @@ __device__ __forceinline__ void conv3_image_tile(const GemmParams& p, const int 
 	}
 	pipe_lgkm0();
 	clear_edges(I0{}, f0);
-#ifdef TTK_CLOCK_STAMPS
-	const unsigned long long clk0_ = __builtin_amdgcn_s_memtime(), rt0_ = __builtin_amdgcn_s_memrealtime();
-#endif
+	scope.clk = kclock_start();
 	typedef std::integral_constant<int, B_PC + A_PC> W01; typedef std::integral_constant<int, B_PC> W2;
 	// six trips per round: k-chunks kc (image slot 0) and kc + 1 (slot 1); tile t lives in f[t & 1]
 	// arguments of trip: wait count, reads?, image slot / tap of the tile read, weight tile requested?, tap of the current tile (= of the weight tile requested), image requested?, its slot
@@ -538,19 +219,15 @@ __device__ __forceinline__ void conv3_image_tile(const GemmParams& p, const int 
 		else load_residual_role<ROLE, MI, NI, true>(p, res_pre, row0, col0, lane);
 		asm volatile("" ::: "memory");
 		TTK_FENCE();
-		trip(std::integral_constant<int, B_PC + RESN>{}, Y{}, I1{}, I1{}, N{}, I0{}, N{}, I1{}, f1, f0, 0u, 0u);      // weight tile NT - 2 has landed; NT - 1 and the residual may be in flight
+		// weight tile NT - 2 has landed; NT - 1 and the residual may be in flight
+		trip(std::integral_constant<int, B_PC + RESN>{}, Y{}, I1{}, I1{}, N{}, I0{}, N{}, I1{}, f1, f0, 0u, 0u);
 		trip(std::integral_constant<int, RESN>{}, Y{}, I1{}, I2{}, N{}, I1{}, N{}, I1{}, f0, f1, 0u, 0u);              // weight tile NT - 1 has landed
 		trip(I0{}, N{}, I0{}, I0{}, N{}, I2{}, N{}, I0{}, f1, f0, 0u, 0u);                                            // the last tile's MFMAs
 	}
-	pipe_m0_restore(m0_keep);
-#ifdef TTK_CLOCK_STAMPS
-	if (stamps_ && lane == 0) {
-		unsigned long long* st_ = stamps_ + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8;
-		st_[6] = ((__builtin_amdgcn_s_memtime() - clk0_) << 32) | ((__builtin_amdgcn_s_memrealtime() - rt0_) & 0xffffffffull);
-	}
-#endif
+	pipe_end(scope, TTK_GEMM_STAMPS(p), lane);
 	TTK_WSTAMPD(stamps_, blockIdx.x, 3, acc[0][0][0]);
-	if (m0 + BM <= p.M) epilogue_role<T, ROLE, false, MI, NI, true>(p, acc, res_pre, bias_pre, row0, col0, lane); else epilogue_role<T, ROLE, true, MI, NI, true>(p, acc, res_pre, bias_pre, row0, col0, lane);
+	if (m0 + BM <= p.M) epilogue_role<T, ROLE, false, MI, NI, true>(p, acc, res_pre, bias_pre, row0, col0, lane);
+	else epilogue_role<T, ROLE, true, MI, NI, true>(p, acc, res_pre, bias_pre, row0, col0, lane);
 	TTK_WSTAMP(stamps_, blockIdx.x, 4);
 #if defined(TTK_STAMPS) && TTK_STAMPS == 2
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -656,7 +333,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 			}
 			return;
 		}
-		sg = __builtin_amdgcn_readfirstlane(sg);      // (wave-uniform by construction; said explicitly so that the descriptor is built in scalar registers -- the DMA instruction takes it from there only)
+		// (wave-uniform by construction; said explicitly so that the descriptor is built in scalar registers -- the DMA instruction takes it from there only)
+		sg = __builtin_amdgcn_readfirstlane(sg);
 		const int64_t lda = p.seg[sg].lda;
 		const int shift = p.seg[sg].shift;
 		srdA = __builtin_amdgcn_make_buffer_rsrc((void*)p.seg[sg].A, 0, (unsigned)((int64_t)p.M * lda * ES), 0x00020000);
@@ -673,7 +351,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 	auto next_tile = [&] {
 		if (seg_in) { if (++seg_i == NSEG) { seg_i = 0; ++kk_i; } }
 		else if (++kk_i == KT) { kk_i = 0; ++seg_i; }
-		seg_i = __builtin_amdgcn_readfirstlane(seg_i); kk_i = __builtin_amdgcn_readfirstlane(kk_i);      // (wave-uniform by construction; said explicitly: the DMA instruction takes its k offset and descriptor from scalar registers only)
+		// (wave-uniform by construction; said explicitly: the DMA instruction takes its k offset and descriptor from scalar registers only)
+		seg_i = __builtin_amdgcn_readfirstlane(seg_i); kk_i = __builtin_amdgcn_readfirstlane(kk_i);
 	};
 	auto issue = [&](int stage) {   // requests the next tile of the order above
 		if (seg_in || kk_i == 0) set_segment(seg_i);
@@ -684,7 +363,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 		for (int i = 0; i < A_PC; ++i) {
 #ifdef TTK_DIAG_SKIP
 			if ((TTK_DIAG_SKIP & 1) && (seg_i > 0 || kk_i > 1)) continue;   // diagnostic: stale A tiles
-			if ((TTK_DIAG_SKIP & 16) && seg_i > 0) continue;                // diagnostic: the traffic of a k = 3 conv whose taps share ONE staged activation image (A fetched for tap 0 only; results wrong on purpose)
+			// diagnostic 16: the traffic of a k = 3 conv whose taps share ONE staged activation image (A fetched for tap 0 only; results wrong on purpose)
+			if ((TTK_DIAG_SKIP & 16) && seg_i > 0) continue;
 #endif
 			glds16(va[i], srdA, soffA, As + (wave + NW * i) * 1024);
 		}
@@ -729,7 +409,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 	// so two sets fit beside the 64 accumulators.  Half-step H0 of tile kt multiplies its k-step 0 (set f0) while k-step 1 of the SAME tile is read into f1 (no barrier: the tile
 	// has landed); H1 waits for tile kt + 1, passes the barrier (every wave's reads of tile kt ended with H0), multiplies k-step 1 while k-step 0 of tile kt + 1 is read into f0,
 	// and requests tile kt + NSTAGE into the stage tile kt has left.  Same MFMA order per accumulator (k-step 0, then 1): same bits.
-	constexpr bool PIPE_H = TTK_GEMM_PIPE_H && ES == 2 && NSTAGE == 3 && ((R::on && !R::RES) || (!R::on && LONGK)) && MI * NI == 16 && KSTEPS == 2;      // (the residual roles keep the compiler-ordered loop at this tile: their epilogue needs 64 more registers and the allocator spills inside the hand-ordered stream)
+	// (the residual roles keep the compiler-ordered loop at this tile: their epilogue needs 64 more registers and the allocator spills inside the hand-ordered stream)
+	constexpr bool PIPE_H = TTK_GEMM_PIPE_H && ES == 2 && NSTAGE == 3 && ((R::on && !R::RES) || (!R::on && LONGK)) && MI * NI == 16 && KSTEPS == 2;
 	if constexpr (PIPE_H) {
 		constexpr int NM = MI * NI, NR = MI + NI, D0 = NM - PER_TILE - 1;      // 16 MFMAs, 8 reads (one per gap from the first), the DMA pieces in the last gaps
 		static_assert(NR <= NM && D0 >= 0, "reads and DMA pieces must fit the gaps of a half-step");
@@ -760,11 +441,10 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 			if constexpr (r < MI) pipe_read16<r * 2048>(fr.a[r], ra);
 			else pipe_read16<(r - MI) * 2048>(fr.b[r - MI], rb);
 		};
-		auto barrier = [&] { TTK_FENCE(); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); TTK_FENCE(); };
 		// one half-step: [wait for W loads at most + barrier] 16 MFMAs of `cur`; RD: 8 reads into `nxt` (addresses ra / rb), one per gap; ISSUE: the next tile's pieces in the last gaps
 		auto htrip = [&](auto bar_, auto w_, auto rd_, auto issue_, const HFrags& cur, HFrags& nxt, unsigned ra, unsigned rb) {
 			constexpr bool BAR = decltype(bar_)::value, RD = decltype(rd_)::value, ISSUE = decltype(issue_)::value;
-			if constexpr (BAR) { wait_vmcnt<decltype(w_)::value>(); barrier(); }
+			if constexpr (BAR) { wait_vmcnt<decltype(w_)::value>(); pipe_barrier(); }
 			static_for<0, NM>([&](auto m_) {
 				constexpr int m = decltype(m_)::value, i = m / NI, j = m % NI;
 				pipe_mfma<T>(acc[i][j], cur.a[i], cur.b[j]);
@@ -774,19 +454,17 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 			if constexpr (RD) pipe_lgkm0();
 		};
 		typedef std::true_type Y; typedef std::false_type N; typedef std::integral_constant<int, 0> W0;
-		const unsigned m0_keep = pipe_m0_save();
+		PipeScope scope = pipe_begin();
 #pragma unroll
 		for (int st = 0; st < NSTAGE; ++st) { issue_prep(st * STAGE); static_for<0, PER_TILE>(issue_piece); }
 		TTK_WSTAMP(stamps_, blockIdx.x, 1);
 		wait_vmcnt<(NSTAGE - 1) * PER_TILE>();      // tile 0 has landed
-		barrier();
+		pipe_barrier();
 		TTK_WSTAMP(stamps_, blockIdx.x, 2);
 		HFrags f0, f1;
 		static_for<0, NR>([&](auto r_) { read_one(r_, f0, fa[0], fb[0]); });
 		pipe_lgkm0();
-#ifdef TTK_CLOCK_STAMPS
-		const unsigned long long clk0_ = __builtin_amdgcn_s_memtime(), rt0_ = __builtin_amdgcn_s_memrealtime();
-#endif
+		scope.clk = kclock_start();
 		unsigned cur_off = 0, nxt_off = STAGE;      // stages of tile kt and tile kt + 1
 		auto advance = [&] { cur_off = nxt_off; nxt_off = nxt_off == (NSTAGE - 1) * STAGE ? 0u : nxt_off + STAGE; };
 		for (int kt = 0; kt < NT - NSTAGE; ++kt) {      // tiles whose second half-step requests a tile
@@ -802,13 +480,7 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 		});
 		htrip(N{}, W0{}, Y{}, N{}, f0, f1, fa[1] + cur_off, fb[1] + cur_off);      // the last tile
 		htrip(N{}, W0{}, N{}, N{}, f1, f0, 0u, 0u);
-		pipe_m0_restore(m0_keep);
-#ifdef TTK_CLOCK_STAMPS
-		if (stamps_ && lane == 0) {
-			unsigned long long* st_ = stamps_ + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8;
-			st_[6] = ((__builtin_amdgcn_s_memtime() - clk0_) << 32) | ((__builtin_amdgcn_s_memrealtime() - rt0_) & 0xffffffffull);
-		}
-#endif
+		pipe_end(scope, TTK_GEMM_STAMPS(p), lane);
 	} else if constexpr (PIPE) {
 		constexpr int NM = KSTEPS * MI * NI, NR = KSTEPS * (MI + NI);
 		constexpr int PREB = TTK_PIPE_PREB, DPG = TTK_PIPE_DPG;
@@ -885,8 +557,10 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 			});
 			pipe_lgkm0();
 		};
-		auto barrier = [&] { TTK_FENCE(); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); TTK_FENCE(); };
 
+		auto barrier = [&] { TTK_FENCE(); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); TTK_FENCE(); };
+		// (this loop keeps its own barrier lambda, M0 save / restore and clock tail instead of pipe_barrier / pipe_begin / pipe_end: with either shared form the
+		// residual roles' instantiations come out with another compiler-placed vmcnt and register assignment; the other two hand-ordered loops do not care)
 		const unsigned m0_keep = pipe_m0_save();
 #pragma unroll
 		for (int st = 0; st < NSTAGE; ++st)
@@ -1049,7 +723,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 		// did: ~1050 cycles per k-tile for 256 cycles of MFMA and 384 of LDS reads).  Hence the peeled last tile below.
 		auto step = [&](int kt, const Frags& cur, Frags& nxt) {
 			wait_tiles(min(NSTAGE - 2, NTILES - 2 - kt));          // tile kt+1 has landed; up to NSTAGE-2 younger ones stay in flight
-	#if !(defined(TTK_DIAG_SKIP) && (TTK_DIAG_SKIP & 32))         // diagnostic 32: what the drain of this wave's fragment reads in front of the barrier costs (only meaningful with 3: no DMA overwrites anything)
+			// diagnostic 32: what the drain of this wave's fragment reads in front of the barrier costs (only meaningful with 3: no DMA overwrites anything)
+	#if !(defined(TTK_DIAG_SKIP) && (TTK_DIAG_SKIP & 32))
 			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 	#endif
 	#if !(defined(TTK_DIAG_SKIP) && (TTK_DIAG_SKIP & 64))         // diagnostic 64: no workgroup barrier in the k-loop (with 3)
@@ -1120,7 +795,8 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 	TTK_WSTAMPD(stamps_, blockIdx.x, 3, acc[0][0][0]);
 
 	if constexpr (R::on) {
-		if (m0 + BM <= p.M) epilogue_role<T, ROLE, false, MI, NI, PRE_RES>(p, acc, res_pre, bias_pre, row0, col0, lane); else epilogue_role<T, ROLE, true, MI, NI, PRE_RES>(p, acc, res_pre, bias_pre, row0, col0, lane);
+		if (m0 + BM <= p.M) epilogue_role<T, ROLE, false, MI, NI, PRE_RES>(p, acc, res_pre, bias_pre, row0, col0, lane);
+		else epilogue_role<T, ROLE, true, MI, NI, PRE_RES>(p, acc, res_pre, bias_pre, row0, col0, lane);
 		TTK_WSTAMP(stamps_, blockIdx.x, 4);
 #if defined(TTK_STAMPS) && TTK_STAMPS == 2
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1137,6 +813,14 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int m0, con
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	TTK_WSTAMP(stamps_, blockIdx.x, 5);
 #endif
+}
+
+// XCD-aware tile order (cdna_hip_programming.md T1, bijective form): workgroups are dealt round-robin over the 8 XCDs, so give
+// each XCD label (block % 8) a CONTIGUOUS run of the n-major tile order = a few n-tiles x all m-tiles.  Its private 4 MiB
+// L2 then holds that weight slice while the activations stream through once, instead of every XCD caching all of W.
+template <typename B> __device__ __forceinline__ int xcd_tile_id(B block, int nwg) {      // (B: blockIdx.x is unsigned, k_gemm_mixed's block index an int)
+	const int xcd = block & 7, q = nwg >> 3, r = nwg & 7;
+	return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (block >> 3);
 }
 
 // NWM x NWN waves per workgroup; 8 waves (2 per SIMD) let one wave's MFMAs run under another's LDS reads and DMA issue.
@@ -1160,14 +844,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, 2) void k_gemm(GemmParams p) {
 #endif
 	TTK_WSTAMP(stamps_, blockIdx.x, 0);
 	const int tiles_m = R::on ? p.tiles_m : (p.M + BM - 1) / BM;
-	// XCD-aware tile order (cdna_hip_programming.md T1, bijective form): workgroups are dealt round-robin over the 8 XCDs, so give
-	// each XCD label (blockIdx % 8) a CONTIGUOUS run of the n-major tile order = a few n-tiles x all m-tiles.  Its private 4 MiB
-	// L2 then holds that weight slice while the activations stream through once, instead of every XCD caching all of W.
-	int tile_id;
-	{
-		const int nwg = R::on ? tiles_m * (R::N / BN) : (int)gridDim.x, xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-		tile_id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-	}
+	const int tile_id = xcd_tile_id(blockIdx.x, R::on ? tiles_m * (R::N / BN) : (int)gridDim.x);
 	// p.m_major: the XCD's run of tiles is a few m-tiles x ALL n-tiles instead -- its L2 then holds the whole weight matrix plus an eighth of
 	// the activations, which is the smaller working set when the matrix (N x K) is smaller than the activation panel (M x K)
 	int m0, n0;
@@ -1191,7 +868,8 @@ template <typename T, int ROLE>
 __global__ __launch_bounds__(256, 2) void k_gemm_mixed(GemmParams p) {
 	typedef GRole<ROLE> R;
 	static_assert(R::on && R::N == 1024, "mixed grids serve the 1024-wide roles");
-	if constexpr (R::CONV) TTK_PIN_ARGS(TTK_S(p.M), TTK_S(p.W), TTK_S(p.seg[0].A), TTK_S(p.mix_full), TTK_S(p.mix_fm), TTK_S(p.inv_tiles_m), TTK_S(p.rows_per_batch), TTK_S(p.inv_rpb));
+	if constexpr (R::CONV) TTK_PIN_ARGS(TTK_S(p.M), TTK_S(p.W), TTK_S(p.seg[0].A), TTK_S(p.mix_full), TTK_S(p.mix_fm), TTK_S(p.inv_tiles_m),
+										TTK_S(p.rows_per_batch), TTK_S(p.inv_rpb));
 	else TTK_PIN_ARGS(TTK_S(p.M), TTK_S(p.W), TTK_S(p.seg[0].A), TTK_S(p.mix_full), TTK_S(p.mix_fm), TTK_S(p.inv_tiles_m));
 	const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 #ifdef TTK_STAMPS
@@ -1200,11 +878,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mixed(GemmParams p) {
 	TTK_WSTAMP(stamps_, blockIdx.x, 0);
 	const int b = blockIdx.x;
 	if (b < p.mix_full) {      // full tiles, XCD-aware n-major order over mix_fm x 16 tiles (p.inv_tiles_m = 1 / mix_fm)
-		const int nwg = p.mix_full, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-		const int tile_id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+		const int tile_id = xcd_tile_id(b, p.mix_full);
 		const int tn = div_recip(tile_id, p.mix_fm, p.inv_tiles_m);
 		gemm_tile<T, 128, 64, 2, 2, TTK_ROLE_STAGES, ROLE>(p, (tile_id - tn * p.mix_fm) * 128, tn * 64, wave);
-	} else {                   // half-height tiles of the remaining rows: j = row block * 16 + (n-tile & 1) * 8 + XCD, n-tile = 2 * XCD + (n-tile & 1) -- the XCD whose L2 holds that weight slice
+	} else {
+		// half-height tiles of the remaining rows: j = row block * 16 + (n-tile & 1) * 8 + XCD, n-tile = 2 * XCD + (n-tile & 1) -- the XCD whose L2 holds that weight slice
 		// (64 x 32 tiles on ONE wave each, over 64 CUs, were tried as well: a lone wave's k-loop is slower than the full tile beside it -- 116.0 against 114.5 us per
 		// layer, 130.0 against 128.3 ms per loop; profiles/r04_ddim_chain_mixed_quarter.log)
 		// HARDWARE RELIANCE: waves 2 and 3 end here while waves 0 and 1 go on to execute s_barrier in every k-step.  HIP leaves a barrier reached by part
@@ -1217,22 +895,32 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mixed(GemmParams p) {
 	}
 }
 
+// More than 64 KiB of dynamic LDS needs the opt-in, once per kernel.  `done` is a function-static flag of the launcher instantiation, process-wide: assumes ONE
+// device per process (this design: one process per GPU); a second device in the same process would need the attribute set again.
+static void opt_in_lds_once(bool& done, const void* kernel, int lds) {
+	if (done) return;
+	if (lds > 64 * 1024) (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+	done = true;
+}
+// the GemmParams fields the host derives for the kernels (reciprocals for div_recip), filled per launch
+static void fill_derived(GemmParams& p, int tiles_m) {
+	p.tiles_m = tiles_m;
+	p.inv_tiles_m = 1.0f / (float)tiles_m;
+	p.inv_rpb = p.rows_per_batch > 0 ? 1.0f / (float)p.rows_per_batch : 0.f;
+	p.inv_gn_T = p.gn_T > 0 ? 1.0f / (float)p.gn_T : 0.f;
+}
+
 template <typename T, int BM, int BN, int NWM, int NWN, int NSTAGE, int ROLE = GR_NONE, bool LONGK = false>
 static void launch_tile(const GemmParams& p_in, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
 	constexpr int LDS = NSTAGE * (BM + BN) * 128;
-	if constexpr (!LONGK && ROLE == GR_NONE && sizeof(T) == 2 && BM == 256 && BN == 128 && NSTAGE == 3) {      // the generic 64 x 64-wave-block tile: the half-tile hand-ordered loop when the k-loop is longer than the ring
+	// the generic 64 x 64-wave-block tile: the half-tile hand-ordered loop when the k-loop is longer than the ring
+	if constexpr (!LONGK && ROLE == GR_NONE && sizeof(T) == 2 && BM == 256 && BN == 128 && NSTAGE == 3) {
 		if (TTK_GEMM_PIPE_H && (p_in.K / 64) * p_in.nseg > NSTAGE) return launch_tile<T, BM, BN, NWM, NWN, NSTAGE, ROLE, true>(p_in, s, ea, eb);
 	}
-	static bool attr_set = false;      // per instantiation, process-wide: assumes ONE device per process (this design: one process per GPU); a second device in the same process would need the attribute set again
-	if (!attr_set) {   // > 64 KiB of dynamic LDS needs the opt-in
-		if (LDS > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_gemm<T, BM, BN, NWM, NWN, NSTAGE, ROLE, LONGK>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-		attr_set = true;
-	}
+	static bool attr_set = false;
+	opt_in_lds_once(attr_set, (const void*)k_gemm<T, BM, BN, NWM, NWN, NSTAGE, ROLE, LONGK>, LDS);
 	GemmParams p = p_in;
-	p.tiles_m = (p.M + BM - 1) / BM;
-	p.inv_tiles_m = 1.0f / (float)p.tiles_m;
-	p.inv_rpb = p.rows_per_batch > 0 ? 1.0f / (float)p.rows_per_batch : 0.f;
-	p.inv_gn_T = p.gn_T > 0 ? 1.0f / (float)p.gn_T : 0.f;
+	fill_derived(p, (p.M + BM - 1) / BM);
 	const int grid = p.tiles_m * ((p.N + BN - 1) / BN);
 	hipExtLaunchKernelGGL((k_gemm<T, BM, BN, NWM, NWN, NSTAGE, ROLE, LONGK>), dim3(grid), dim3(64 * NWM * NWN), (unsigned)LDS, s, ea, eb, 0, p);
 }
@@ -1248,14 +936,12 @@ static bool mixed_grid_applies(const GemmParams& p) {
 template <typename T, int ROLE>
 static void launch_mixed(const GemmParams& p_in, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
 	constexpr int LDS = TTK_ROLE_STAGES * (128 + 64) * 128;
-	static bool attr_set = false;      // (one device per process, as in launch_tile)
-	if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_gemm_mixed<T, ROLE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); attr_set = true; }
+	static_assert(LDS > 64 * 1024, "the mixed grid's ring needs the LDS opt-in");
+	static bool attr_set = false;
+	opt_in_lds_once(attr_set, (const void*)k_gemm_mixed<T, ROLE>, LDS);
 	GemmParams p = p_in;
 	p.mix_fm = 16; p.mix_full = 256;
-	p.tiles_m = p.mix_fm;
-	p.inv_tiles_m = 1.0f / (float)p.mix_fm;
-	p.inv_rpb = p.rows_per_batch > 0 ? 1.0f / (float)p.rows_per_batch : 0.f;
-	p.inv_gn_T = p.gn_T > 0 ? 1.0f / (float)p.gn_T : 0.f;
+	fill_derived(p, p.mix_fm);
 	const int blocks64 = (p.M - 128 * p.mix_fm) / 64;
 	hipExtLaunchKernelGGL((k_gemm_mixed<T, ROLE>), dim3(p.mix_full + blocks64 * 16), dim3(256), (unsigned)LDS, s, ea, eb, 0, p);
 }
@@ -1263,7 +949,11 @@ static void launch_mixed(const GemmParams& p_in, hipStream_t s, hipEvent_t ea, h
 // The role of a launch, or GR_NONE: every field a role fixes at compile time must have exactly that value (TTK_GEMM_ROLE=0 switches the roles off: A/B runs and
 // the test that the specialised kernels give the generic kernel's bits; read again by gemm_roles_refresh at every handle creation).
 int g_gemm_roles = -1;
-void gemm_roles_refresh() { g_mixed_mode = -1; const char* e = getenv("TTK_GEMM_ROLE"); g_gemm_roles = e ? (atoi(e) == 1 ? 0x1E : atoi(e)) : 0x1E; }      // 0 = off, 1 = all, else a bit mask of GemmRole values
+void gemm_roles_refresh() {      // 0 = off, 1 = all, else a bit mask of GemmRole values
+	g_mixed_mode = -1;
+	const char* e = getenv("TTK_GEMM_ROLE");
+	g_gemm_roles = e ? (atoi(e) == 1 ? 0x1E : atoi(e)) : 0x1E;
+}
 static int gemm_role_of_unmasked(const GemmParams& p, int es);
 static int gemm_role_of(const GemmParams& p, int es) {
 	const int r = gemm_role_of_unmasked(p, es);
@@ -1272,7 +962,8 @@ static int gemm_role_of(const GemmParams& p, int es) {
 static int gemm_role_of_unmasked(const GemmParams& p, int es) {
 	if (g_gemm_roles < 0) gemm_roles_refresh();
 	// (fp8 operands, es == 1: the same roles with the weights' tensor scale in the epilogue; 16-bit launches carry no scale)
-	if ((es != 2 && es != 1) || p.K != GR_K || p.ldw != GR_K || !p.bias || p.act != ACT_NONE || (es == 2) != (p.out_scale == 0.f) || p.transpose_out || p.m_major) return GR_NONE;
+	if ((es != 2 && es != 1) || p.K != GR_K || p.ldw != GR_K || !p.bias || p.act != ACT_NONE || (es == 2) != (p.out_scale == 0.f)) return GR_NONE;
+	if (p.transpose_out || p.m_major) return GR_NONE;
 	if (p.M < 1 || p.M > (1 << 19) || p.seg[0].lda != GR_K || p.seg[0].w_off != 0) return GR_NONE;      // 32-bit byte offsets and M * N < 2^30 element indices
 	if (p.nseg == 1 && p.seg[0].shift == 0) {
 		if (p.N == 3072 && !p.out_f32 && p.ldc == 3072 && !p.residual && !p.gn_part) return GR_QKV;
@@ -1286,21 +977,22 @@ static int gemm_role_of_unmasked(const GemmParams& p, int es) {
 	}
 	return GR_NONE;
 }
+// the role ladder, written once: f(std::integral_constant<int, role>) when `role` is one of the three 1024-wide statistics roles
+static bool is_stat_role(int role) { return role == GR_IN1x1 || role == GR_CONV3_RES || role == GR_PROJ_RES; }
+template <typename F> static void with_stat_role(int role, F&& f) {
+	if (role == GR_IN1x1) f(std::integral_constant<int, GR_IN1x1>{});
+	else if (role == GR_CONV3_RES) f(std::integral_constant<int, GR_CONV3_RES>{});
+	else if (role == GR_PROJ_RES) f(std::integral_constant<int, GR_PROJ_RES>{});
+}
 template <typename T, int BM, int BN, int NWM, int NWN, int NSTAGE>
 static void launch_tile_role(int role, const GemmParams& p, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
 	if constexpr (sizeof(T) <= 2) {
 		if constexpr (BM == 128 && BN == 64) {      // a few tiles more than CUs: the surplus rows as half-height tiles (k_gemm_mixed)
-			if ((role == GR_IN1x1 || role == GR_CONV3_RES || role == GR_PROJ_RES) && mixed_grid_applies(p)) {
-				if (role == GR_IN1x1) return launch_mixed<T, GR_IN1x1>(p, s, ea, eb);
-				if (role == GR_CONV3_RES) return launch_mixed<T, GR_CONV3_RES>(p, s, ea, eb);
-				return launch_mixed<T, GR_PROJ_RES>(p, s, ea, eb);
-			}
+			if (is_stat_role(role) && mixed_grid_applies(p)) return with_stat_role(role, [&](auto r) { launch_mixed<T, decltype(r)::value>(p, s, ea, eb); });
 		}
 		constexpr int NS = (BM == 128 && BN == 64 && sizeof(T) == 2) ? TTK_ROLE_STAGES : NSTAGE;
 		if constexpr (BN <= 128) {      // the 1024-wide roles run 128 x 64 (one utterance), 128 x 128 or 256 x 128 tiles (longer utterances, line batches)
-			if (role == GR_IN1x1) return launch_tile<T, BM, BN, NWM, NWN, NS, GR_IN1x1>(p, s, ea, eb);
-			if (role == GR_CONV3_RES) return launch_tile<T, BM, BN, NWM, NWN, NS, GR_CONV3_RES>(p, s, ea, eb);
-			if (role == GR_PROJ_RES) return launch_tile<T, BM, BN, NWM, NWN, NS, GR_PROJ_RES>(p, s, ea, eb);
+			if (is_stat_role(role)) return with_stat_role(role, [&](auto r) { launch_tile<T, BM, BN, NWM, NWN, NS, decltype(r)::value>(p, s, ea, eb); });
 		}
 		if (role == GR_QKV) return launch_tile<T, BM, BN, NWM, NWN, NS, GR_QKV>(p, s, ea, eb);
 	}
@@ -1340,14 +1032,17 @@ static void launch_gemm_t(const GemmParams& p, hipStream_t s, hipEvent_t ea, hip
 	// Round 4: the same choice by ROUNDS, statistics GEMMs included.  Both tiles run one workgroup per CU (96 / 144 KiB of LDS), so a launch lasts rounds x tile time, a
 	// 256 x 128 tile taking ~1.5 x a 128 x 128 one (twice the work at the 64 x 64 wave block's better LDS economy): take the wide tile when ceil(t256 / 256) x 1.5 is
 	// more than a tenth below ceil(t128 / 256).  One line of T = 2176 (M = 4352, N = 1024: 272 tiles of 128 x 128 = two rounds for 6 % more than one; QKV 816 = four
-	// rounds) runs 40 DDIM steps in 124.7 ms with wide tiles against 133.7 ms (tests/diag/ddim_ab.py, TTK_AB_T=2176); the benchmarked T = 1088 and the latent pass choose as before.
+	// rounds) runs 40 DDIM steps in 124.7 ms with wide tiles against 133.7 ms (tests/diag/ddim_ab.py, TTK_AB_T=2176); the benchmarked T = 1088 and the latent pass
+	// choose as before.
 	static const int wide = [] { const char* e = getenv("TTK_GEMM_TILE_WIDE"); return e ? atoi(e) : -2; }();
 	if (g_force_tile < 100 && tile == 0) {
 		const int t128 = ((p.M + 127) / 128) * ((p.N + 127) / 128), t256 = ((p.M + 255) / 256) * ((p.N + 127) / 128);
 		if (wide >= 0) { if (p.N >= 3072) tile = wide; }
 		else if (wide == -2 && sizeof(T) <= 2 && t128 > 256) {
 			const int r128 = (t128 + 255) / 256, r256 = (t256 + 255) / 256;
-			if (15 * r256 <= 9 * r128) tile = 8;      // 1.5 r256 <= 0.9 r128 (round 6: "<=" -- the wide tile runs the half-tile hand-ordered loop now; the latent pass's c_fc, 5 rounds of 128 x 128 against 3 of 256 x 128, 78.9 us, is the case on the line)
+			// 1.5 r256 <= 0.9 r128 (round 6: "<=" -- the wide tile runs the half-tile hand-ordered loop now; the latent pass's c_fc, 5 rounds of 128 x 128 against
+			// 3 of 256 x 128, 78.9 us, is the case on the line)
+			if (15 * r256 <= 9 * r128) tile = 8;
 		}
 	}
 	const int role = gemm_role_of(p, (int)sizeof(T));
@@ -1360,7 +1055,8 @@ static void launch_gemm_t(const GemmParams& p, hipStream_t s, hipEvent_t ea, hip
 	else if (tile == 7) launch_tile<T, 256, 64, 4, 2, 3>(p, s, ea, eb);   // 8 waves, wave block 64 x 32, 120 KiB: one workgroup per CU
 	else if (tile == 8) launch_tile_role<T, 256, 128, 4, 2, 3>(role, p, s, ea, eb);  // 8 waves, wave block 64 x 64, 144 KiB: one workgroup per CU
 	else if (tile == 9) launch_tile<T, 128, 128, 2, 4, 2>(p, s, ea, eb);  // as 0 with a 2-stage ring (64 KiB: two workgroups per CU)
-	// (128 x 64 as TWO waves of 64 x 64 -- a third less fragment traffic out of LDS per flop -- 158.9 ms per DDIM loop against 138.9 for tile 1 everywhere; with a 4-stage ring 213.7: not kept)
+	// (128 x 64 as TWO waves of 64 x 64 -- a third less fragment traffic out of LDS per flop -- 158.9 ms per DDIM loop against 138.9 for tile 1 everywhere; with a
+	// 4-stage ring 213.7: not kept)
 	else launch_tile<T, 64, 64, 2, 2, 3>(p, s, ea, eb);
 }
 
