@@ -198,6 +198,56 @@ int ttk_exponential_like_torch(float* out, int64_t numel, int64_t seed, int64_t 
 int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* text, const int* text_len, int n_lines, int rows_per_line,
 						 float* logits_out, void* stream);
 
+/* Beam search (`TTS.inference(beam_width=N)`, inference.py:161,342: generate(num_beams=N); HF:generation/utils.py `_beam_search` :3208-3509 with
+ * do_sample=True is the behaviour restated).
+ *
+ * ttk_ar_reorder_cache = `_reorder_cache` (unified_voice.py:257-265; HF :3477-3489): beam_idx = device int64 [B], B the prefilled rows (<= 16);
+ * new candidate slice b takes the K/V history of old slice beam_idx[b].  In place, one launch: a thread owns one 16-byte piece of one cache row,
+ * loads it from every source slice and only then stores the destinations.  Only rows [shared prefix, valid rows) move -- both bounds are
+ * the handle's device position words, so the launch may be captured; the shared prefix (ttk_ar_prefill) is one copy for all beams and stays.
+ * An identity beam_idx returns before the first load; an entry outside [0, B) moves nothing.  TTK_E_STATE before a prefill and after
+ * ttk_ar_prefill_lines.                                                                                                                  */
+int ttk_ar_reorder_cache(ttk_ar* h, const int64_t* beam_idx, void* stream);
+
+/* One step of `_beam_search` for one text line, steps b to g (HF:generation/utils.py:3386-3508), batch_size 1, early_stopping False,
+ * pad = eos = stop_token.  With c = col[0] tokens generated so far:
+ *   b. per beam row: log_softmax(logits) (:3388), then the processors and warpers ON THE LOG-PROBS in HF's order (:3389; the semantics of
+ *      ttk_sample_step_warped): repetition penalty over {prefix_ids, that beam's own c tokens}, suppress, temperature, top-k, top-p -- the
+ *      last two with min_tokens_to_keep = 2, as `_get_logits_processor` builds them for num_beams > 1 (:1297-1322) -- plus running score (:3419);
+ *   c. `_get_top_k_continuations` (:3077-3129): multinomial WITHOUT replacement of 2 * num_beams from softmax over the flat [num_beams * V]
+ *      = the 2 * num_beams largest of softmax / q in descending order, q the caller's Exp(1) noise of that flat tensor (ATen's no-replacement
+ *      path; ttk_ar_set_noise with a candidate count of num_beams draws exactly it); beam = idx / V, token = idx % V;
+ *   d. a continuation hits the stopping criteria with token == stop_token or c + 1 == max_new (MaxLengthCriteria);
+ *   e. `_get_running_beams_for_next_iteration` (:3131-3151);  f. `_update_finished_beams` (:3153-3204) with length_penalty;
+ *   g. tok [num_beams] / beam_idx [num_beams] for the next forward and ttk_ar_reorder_cache (:3481), `_check_early_stop_heuristic`
+ *      (:3008-3052), `_beam_search_has_unfinished_sequences` (:3055-3075): when the search is over, c + 1 goes to state[2 * num_beams + 1] and to
+ *      *all_done (optional; device or pinned host int, zeroed by the caller), and every later call is a no-op.
+ * Exact ties (softmax / q, and the scores of e. and f.) go to the lowest index: torch leaves that order unspecified (entries of probability
+ * exactly 0 -- the -1e9 beams of the first step, everything top-k / top-p cut -- tie at 0), so this is the library's choice, not the reference's;
+ * callers keep top_k == 0 or >= 2 * num_beams.  Scalar divisions are ATen's GPU form, x * (1 / f32(s)).
+ * State, all device memory the caller initialises once per generation (L = max_new):
+ *   col    int64 [num_beams], zeros: tokens generated so far (every entry is advanced; also the draw counter of ttk_ar_set_noise);
+ *   seqs   int64 [2][2][num_beams][L], stop_token: generated tokens of {running, finished} beams, read from half c & 1 and written to the other
+ *          (after n steps the finished beams are seqs[n & 1][1], best first; row b holds state[num_beams + b] tokens, then stop_token);
+ *   scores f32 [2][num_beams]: running_beam_scores = {0, -1e9, ...} and beam_scores = {-1e9, ...} (:3332-3334);
+ *   state  int [2 * num_beams + 2]: is_sent_finished [num_beams] = 0, finished lengths [num_beams] = 0, heuristic bit = 1, done word = 0;
+ *   acc    f32 [num_beams * V] and work int [4 * num_beams^2 + 2 * num_beams + 1] (zeroed once): scratch between the two launches.
+ * Enqueues two kernels; capturable.  num_beams 2..16, 2 * num_beams <= V <= 9216.                                                         */
+typedef struct {
+	const float* logits; int64_t ld; int num_beams, V;
+	const float* q;                           /* Exp(1) noise, flat [num_beams * V] */
+	const unsigned char* suppress;            /* [V] byte mask or NULL */
+	float temperature;                        /* > 0 */
+	int top_k; float top_p; float repetition_penalty, length_penalty;
+	int64_t stop_token, prefix_ids[2];        /* what the penalty sees in front of the generated tokens: {1, start_mel} (unified_voice.py:647-649) */
+	int max_new;
+	int64_t *col, *seqs; float* scores; int* state;
+	float* acc; int* work;
+	int64_t *tok, *beam_idx;                  /* out [num_beams] */
+	int* all_done;                            /* optional */
+} ttk_beam_args;
+int ttk_beam_step(const ttk_beam_args* a, void* stream);
+
 /* hipGraphLaunch of an instantiated graph the caller captured around libttk launches (torch.cuda.CUDAGraph.raw_cuda_graph_exec()): the
  * token step replayed without torch.cuda.CUDAGraph.replay()'s prologue, which fills the generator's seed / offset tensors -- two launches per
  * token -- whether or not the captured work draws random numbers.  With ttk_ar_set_noise it does not.                                      */

@@ -57,6 +57,15 @@ class SampleArgs(C.Structure):
 				("hist_ld", C.c_int64), ("hist_off", C.c_int64), ("live_rows", C.c_void_p), ("all_done", C.c_void_p), ("typical_mass", C.c_float)]
 
 
+class BeamArgs(C.Structure):
+	"""ttk_beam_args (include/ttk.h)"""
+	_fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("num_beams", C.c_int), ("V", C.c_int), ("q", C.c_void_p), ("suppress", C.c_void_p),
+				("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("repetition_penalty", C.c_float), ("length_penalty", C.c_float),
+				("stop_token", C.c_int64), ("prefix_ids", C.c_int64 * 2), ("max_new", C.c_int), ("col", C.c_void_p), ("seqs", C.c_void_p),
+				("scores", C.c_void_p), ("state", C.c_void_p), ("acc", C.c_void_p), ("work", C.c_void_p), ("tok", C.c_void_p), ("beam_idx", C.c_void_p),
+				("all_done", C.c_void_p)]
+
+
 class GemmSeg(C.Structure):
 	"""ttk_gemm_seg (include/ttk.h)"""
 	_fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("shift", C.c_int), ("w_off", C.c_int64)]
@@ -95,6 +104,8 @@ SYMBOLS = {
 	"ttk_graph_launch": (_I, [_P, _P]),
 	"ttk_exponential_like_torch": (_I, [_P, _L, _L, _L, _L, _L, _L, _P]),
 	"ttk_ar_sample_next": (_I, [_P, C.POINTER(SampleArgs), _P]),
+	"ttk_ar_reorder_cache": (_I, [_P, _P, _P]),
+	"ttk_beam_step": (_I, [C.POINTER(BeamArgs), _P]),
 	"ttk_sample_step_warped": (_I, [C.POINTER(SampleArgs), _P]),
 	"ttk_ar_latents": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
 	"ttk_voc_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),

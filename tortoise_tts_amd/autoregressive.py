@@ -13,6 +13,9 @@ What runs where
     (seed 0 on every call) and is left where torch's draws would have left it; typical sampling (rare, off by default)
     runs inside the kernel too since round 3 (sampling.py keeps the torch-op forms for `hf_exact_top_p`).
   * the per-token loop .............................................. here; one HIP-graph replay per token.
+  * beam search (num_beams > 1) ..................................... libttk  (csrc/beam.hip: the beam step -- log-softmax, warpers, the
+    multinomial without replacement over num_beams * V, HF's running / finished bookkeeping -- and the in-place KV-cache reorder); the loop
+    here enqueues {beam step, reorder, decode} per token and polls the done word.
 """
 from __future__ import annotations
 
@@ -197,6 +200,18 @@ class UnifiedVoice:
 		row (the gather pads with the stop token, as the unsharded loop does for finished rows)."""
 		if text_inputs.shape[0] != 1:
 			raise NotImplementedError("one text line per call, as inference.py:244-246 does")
+		num_beams = hf_generate_kwargs.get("num_beams", 1) or 1
+		if num_beams != 1:
+			# the beam-sample branch of `generate` (HF `_beam_search`, do_sample=True): csrc/beam.hip
+			if not hf_generate_kwargs.get("do_sample", False):
+				raise NotImplementedError("beam search is implemented for the sampling branch only (do_sample=True, as TTS.inference passes it)")
+			if input_tokens is not None:
+				raise NotImplementedError("beam search takes no input_tokens (prompted continuation runs on the sampling branch, num_beams=1)")
+			if candidate_shard is not None:
+				raise NotImplementedError("beam search is not sharded over ranks: the beams of a line exchange histories every token (candidate_shard needs num_beams=1)")
+			if typical_sampling:
+				raise NotImplementedError("typical_sampling together with beam search is not implemented (num_beams=1 has it)")
+			return self._beam_generate(speech_conditioning_latent, text_inputs, int(num_beams), num_return_sequences, max_generate_length, hf_generate_kwargs)
 		prompt = None
 		if input_tokens is not None:
 			# Prompted continuation (unified_voice.py:651-656; `TTS.inference` never passes it).  The reference tiles the fake prefix and the prompts to
@@ -213,8 +228,8 @@ class UnifiedVoice:
 				raise ValueError("input_tokens must not contain the stop token")
 		# omitted keywords mean HF GenerationConfig defaults in the reference (stream_generator.py:262-276): do_sample False (greedy
 		# search, not on the hot path: TTS.inference always samples, inference.py:336), top_k 50, temperature / top_p / penalty 1
-		if hf_generate_kwargs.get("num_beams", 1) not in (None, 1) or not hf_generate_kwargs.get("do_sample", False):
-			raise NotImplementedError("only the sampling branch (do_sample=True, num_beams=1) is implemented; pass do_sample=True")
+		if not hf_generate_kwargs.get("do_sample", False):
+			raise NotImplementedError("only the sampling branches (do_sample=True) are implemented; pass do_sample=True")
 		gen, _ = self._generate(speech_conditioning_latent, text_inputs, num_return_sequences if prompt is None else prompt.shape[0], max_generate_length,
 								typical_mass if typical_sampling else None, hf_generate_kwargs, stream=False, shard=candidate_shard, prompt=prompt)
 		return gen
@@ -227,8 +242,10 @@ class UnifiedVoice:
 		[num_return_sequences, V] multinomial noise (the reference reseeds to 0 per line), and line g is cut where its own last row finished.
 		`self.last_generate_lines[g]` says where the generator stands after line g's sampling in the reference (steps, rng_start, rng_step):
 		a caller that draws per line afterwards (TTSHotPath.inference_lines) re-positions it with `position_rng_after_line(g)`."""
-		if hf_generate_kwargs.get("num_beams", 1) not in (None, 1) or not hf_generate_kwargs.get("do_sample", False):
-			raise NotImplementedError("only the sampling branch (do_sample=True, num_beams=1) is implemented; pass do_sample=True")
+		if hf_generate_kwargs.get("num_beams", 1) not in (None, 1):
+			raise NotImplementedError("beam search over a batch of lines is not implemented: call inference_speech(num_beams=N) per line")
+		if not hf_generate_kwargs.get("do_sample", False):
+			raise NotImplementedError("only the sampling branch (do_sample=True) is implemented; pass do_sample=True")
 		texts = list(texts)
 		if any(t.dim() != 2 or t.shape[0] != 1 for t in texts):
 			raise NotImplementedError("texts: a list of [1, Tt] id tensors, one per line")
@@ -295,6 +312,72 @@ class UnifiedVoice:
 			self.position_rng_after_line(G - 1)
 			self.last_generate = dict(self.last_generate_lines[-1])
 			return out
+
+	def _beam_generate(self, cond, text, N, R, max_generate_length, kw):
+		"""HF `_beam_search` with do_sample=True (HF:generation/utils.py:3208-3509) for one text line: N beams prefilled on the shared prefix, then per
+		token {ttk_beam_step; ttk_ar_reorder_cache; ttk_ar_decode of the chosen tokens}.  Returns `sequences[:R]` behind the prompt, cropped to the
+		longest returned beam and padded with the stop token (step 5, :3510-3523).  The search ends on the device (the done word of ttk_beam_step);
+		the host looks at it LAG tokens late, and the steps enqueued past the end are no-ops that draw nothing from the torch generator."""
+		c = self.cfg
+		self._require_idle()
+		if R > N:
+			raise ValueError(f"`num_return_sequences` ({R}) has to be smaller or equal to `num_beams` ({N}).")
+		if N > min(16, self.max_batch):
+			raise _lib.TTKError(f"{N} beams exceed min(16, max_batch={self.max_batch})")
+		top_k = kw.get("top_k", 50) or 0
+		if 0 < top_k < 2 * N:
+			raise ValueError(f"top_k={top_k} keeps fewer tokens than the 2 * num_beams = {2 * N} continuations a beam step selects; which of the removed "
+							 "(probability 0) ones torch.multinomial would pick is unspecified: use top_k=0 or top_k >= 2 * num_beams")
+		Tt = text.shape[1]
+		max_new = (c.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
+		if Tt + 4 + max_new > self.max_ctx or max_new + 2 > c.max_mel_seq_len:
+			raise _lib.TTKError(f"prefix {Tt + 4} + {max_new} new tokens exceed max_ctx={self.max_ctx} or the mel position table ({c.max_mel_seq_len})")
+		if max_new < 1:
+			raise ValueError("max_generate_length must be at least 1")
+		LAG = 2
+		with torch.cuda.device(self.device):
+			st = _BeamState(self, N, max_new, kw)
+			setup_seed(kw.get("seed", 0))
+			gen = torch.cuda.default_generators[self.device.index or 0]
+			off_start = gen.get_offset()
+			if st.own_rng:
+				st.arm_noise(gen)
+			try:
+				st.logits.copy_(self._prefill(cond, text, N))
+				n, events = 0, []
+				while True:
+					st.step()
+					n += 1
+					if n >= max_new:
+						break
+					if st.own_rng:
+						ev = torch.cuda.Event()
+						ev.record()
+						events.append(ev)
+						if len(events) > LAG:
+							events.pop(0).synchronize()          # the step LAG tokens back is complete: its done word is visible
+							if int(st.done[0]):
+								break
+					else:                                        # torch draws the noise: a step past the end would consume generator state
+						torch.cuda.synchronize(self.device)
+						if int(st.done[0]):
+							break
+					_lib.check(self.lib.ttk_ar_reorder_cache(self._h, st.beam_idx.data_ptr(), _lib.stream_ptr()), "ttk_ar_reorder_cache")
+					self._decode(st.tok, st.logits)
+			finally:
+				if st.own_rng:
+					_lib.check(self.lib.ttk_ar_set_noise(self._h, None, None, None), "ttk_ar_set_noise")
+			torch.cuda.synchronize(self.device)
+			state = st.state.tolist()
+			steps = state[2 * N + 1]
+			if steps <= 0:
+				raise _lib.TTKError("beam search did not end within max_generate_length steps (the done word of ttk_beam_step is unset)")
+			if st.own_rng:
+				gen.set_offset(off_start + steps * st.noise_step)      # what the torch.multinomial of every step would have consumed
+			self.last_generate = dict(steps=steps, rng_start=off_start, rng_step=(gen.get_offset() - off_start) // steps)
+			self._check_health()
+			length = max(state[N:N + R])
+			return st.seqs[steps & 1, 1, :R, :length].clone()
 
 	def _require_idle(self):
 		"""one generation at a time per handle: the KV cache, the noise arming and the latent ring of an open streamed generation are the handle's (the
@@ -696,3 +779,66 @@ class _GenState:
 			else:
 				self.q.exponential_(1)
 		_lib.check(self.model.lib.ttk_ar_sample_next(self.model._h, _lib.C.byref(a), _lib.stream_ptr()), "ttk_ar_sample_next")
+
+
+class _BeamState:
+	"""Device state of one beam search (include/ttk.h: ttk_beam_args) and the noise arming of its flat [num_beams * V] multinomial."""
+
+	def __init__(self, model: UnifiedVoice, N, max_new, kw):
+		c, dev = model.cfg, model.device
+		V = c.number_mel_codes
+		self.model, self.N = model, N
+		self.logits = torch.empty((N, V), device=dev, dtype=torch.float32)
+		self.q = torch.empty((1, N * V), device=dev, dtype=torch.float32)      # the tensor torch.multinomial draws its noise for: [batch 1, N * V]
+		self.noise_rows = 1
+		self.col = torch.zeros(N, dtype=torch.long, device=dev)
+		self.seqs = torch.full((2, 2, N, max_new), c.stop_mel_token, dtype=torch.long, device=dev)
+		self.scores = torch.full((2, N), -1e9, dtype=torch.float32, device=dev)
+		self.scores[0, 0] = 0.0
+		self.state = torch.zeros(2 * N + 2, dtype=torch.int32, device=dev)
+		self.state[2 * N] = 1
+		self.acc = torch.empty(N * V, dtype=torch.float32, device=dev)
+		self.work = torch.zeros(4 * N * N + 2 * N + 1, dtype=torch.int32, device=dev)
+		self.tok = torch.zeros(N, dtype=torch.long, device=dev)
+		self.beam_idx = torch.arange(N, dtype=torch.long, device=dev)
+		self.done = torch.zeros(1, dtype=torch.int32).pin_memory()
+		self.rng = torch.zeros(6, dtype=torch.long, device=dev)
+		self.own_rng = os.environ.get("TTK_AR_OWN_RNG", "1") != "0" and self._noise_matches_torch(model, dev)
+		suppress = tuple(kw.get("suppress_tokens") or ())
+		self.suppress_mask = None
+		if suppress:
+			self.suppress_mask = torch.zeros(V, dtype=torch.uint8, device=dev)
+			self.suppress_mask[list(suppress)] = 1
+		a = _lib.BeamArgs()
+		a.logits, a.ld, a.num_beams, a.V = self.logits.data_ptr(), self.logits.stride(0), N, V
+		a.q, a.suppress = self.q.data_ptr(), _lib.ptr(self.suppress_mask)
+		a.temperature = float(kw.get("temperature", 1.0) or 1.0)
+		a.top_k = int(kw.get("top_k", 50) or 0)
+		top_p, penalty = kw.get("top_p", 1.0), kw.get("repetition_penalty", 1.0)
+		a.top_p = 1.0 if top_p is None else float(top_p)
+		a.repetition_penalty = 1.0 if penalty is None else float(penalty)
+		lp = kw.get("length_penalty", 1.0)
+		a.length_penalty = 1.0 if lp is None else float(lp)
+		a.stop_token = c.stop_mel_token
+		a.prefix_ids[0], a.prefix_ids[1] = 1, c.start_mel_token      # the fake prefix ids are all 1 with start_mel last (unified_voice.py:647-649)
+		a.max_new = max_new
+		a.col, a.seqs, a.scores, a.state = self.col.data_ptr(), self.seqs.data_ptr(), self.scores.data_ptr(), self.state.data_ptr()
+		a.acc, a.work, a.tok, a.beam_idx = self.acc.data_ptr(), self.work.data_ptr(), self.tok.data_ptr(), self.beam_idx.data_ptr()
+		a.all_done = self.done.data_ptr()
+		self.args = a
+
+	_noise_geometry = _GenState._noise_geometry
+	_noise_matches_torch = _GenState._noise_matches_torch
+
+	def arm_noise(self, gen):
+		"""the mel-head launches of this search write q for their logits: N rows of V = the flat tensor, numbered by the step counter"""
+		seed = gen.initial_seed()
+		seed = seed - (1 << 64) if seed >= (1 << 63) else seed
+		self.rng.copy_(torch.tensor([seed, gen.get_offset(), self.noise_threads, self.noise_step, 0, 0], dtype=torch.long))
+		m = self.model
+		_lib.check(m.lib.ttk_ar_set_noise(m._h, self.rng.data_ptr(), self.col.data_ptr(), self.q.data_ptr()), "ttk_ar_set_noise")
+
+	def step(self):
+		if not self.own_rng:
+			self.q.exponential_(1)
+		_lib.check(self.model.lib.ttk_beam_step(_lib.C.byref(self.args), _lib.stream_ptr()), "ttk_beam_step")

@@ -559,6 +559,15 @@ int ttk_ar_sample_next(ttk_ar* h, const ttk_sample_args* a, void* stream) {
 							  (hipStream_t)stream, "ttk_ar_sample_next");
 }
 
+int ttk_ar_reorder_cache(ttk_ar* h, const int64_t* beam_idx, void* stream) {
+	TTK_REQUIRE(h && beam_idx, TTK_E_ARG, "ttk_ar_reorder_cache: null argument");
+	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_reorder_cache: call ttk_ar_prefill first");
+	TTK_REQUIRE(!h->lines_mode, TTK_E_STATE, "ttk_ar_reorder_cache: the candidates of a line batch (ttk_ar_prefill_lines) keep their own histories");
+	// rows [d_pos[1], d_pos[0]) of every slice; the shared prefix lives in slice 0 alone and is what every beam reads, whatever the order
+	return launch_kv_reorder(h->kc, h->vc, h->cfg.layers, h->cfg.max_batch, h->cfg.heads, h->cfg.max_ctx, h->es, h->d_pos, beam_idx, h->B, (hipStream_t)stream,
+							 "ttk_ar_reorder_cache");
+}
+
 int ttk_ar_set_noise(ttk_ar* h, const int64_t* rng_args, const int64_t* draws, float* q) {
 	TTK_REQUIRE(h, TTK_E_ARG, "ttk_ar_set_noise: null handle");
 	TTK_REQUIRE((rng_args && draws && q) || (!rng_args && !draws && !q), TTK_E_ARG, "ttk_ar_set_noise: pass all three pointers or none");

@@ -115,6 +115,10 @@ int fold_layernorm(Arena& ar, const WeightMap& wm, int dt, const std::string& wn
 int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 					   hipStream_t stream, const char* who);
 
+// beam.hip: the in-place gather of the KV cache's candidate slices that beam search needs per token (ttk_ar_reorder_cache)
+int launch_kv_reorder(void* kc, void* vc, int layers, int max_batch, int H, int max_ctx, size_t es, const int* d_pos, const int64_t* beam_idx, int B,
+					  hipStream_t s, const char* who);
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 }  // namespace ttk

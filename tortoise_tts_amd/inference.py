@@ -187,14 +187,16 @@ class TTSHotPath:
 	def inference(self, text_tokens: torch.Tensor, autoregressive_latents: torch.Tensor, diffusion_latents: torch.Tensor, *,
 				  max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, diffusion_sampler="ddim", cond_free=True, candidates=1,
-				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all"):
+				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1):
 		"""text_tokens [1, Tt] int64; latents from the reference's conditioning encoders ([1,1024], [1,2048]).
 		latents_for: "all" = the latent pass over every candidate, as the reference runs it before scoring (inference.py:370-379; the benchmarked
 		workload); "winner" = the k = 1 variant: the candidate is chosen first and only its row goes through the dense
 		pass (the reference's own to-do at :370) -- rows of the pass are independent, so the result is the same bits.
 		Returns the denormalised mel [1, 100, T] (input of the vocoder) and the audio seconds it represents.
 		phase_marks (measurement only): a list that receives (name, torch.cuda.Event) at the phase boundaries -- start, after the AR
-		sampling, after the latent pass, after the diffusion -- for bench.py's per-phase roofline."""
+		sampling, after the latent pass, after the diffusion -- for bench.py's per-phase roofline.
+		beam_width: `num_beams=max(1, beam_width)` of the reference's call (inference.py:342); above 1 the `candidates` best finished beams come back
+		(candidates <= beam_width) and `length_penalty` ranks them."""
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
 
@@ -208,7 +210,7 @@ class TTSHotPath:
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		extra = {"suppress_tokens": suppress_tokens} if suppress_tokens else {}
 		codes = ar.inference_speech(autoregressive_latents, text_tokens, do_sample=True, top_k=top_k, top_p=top_p,
-									temperature=ar_temp, num_return_sequences=candidates, num_beams=1,
+									temperature=ar_temp, num_return_sequences=candidates, num_beams=max(1, beam_width),
 									length_penalty=length_penalty, repetition_penalty=repetition_penalty,
 									max_generate_length=max_ar_steps, **extra)
 		mark("ar_decode")

@@ -63,13 +63,16 @@ class TTS:
 		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
 		(wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the `vocoder=` part, "vocoder" the
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
-		diffusion model (see `_hifigan_wav`; the reference returns [1, samples] on that branch, here the shape is that of the other two)."""
+		diffusion model (see `_hifigan_wav`; the reference returns [1, samples] on that branch, here the shape is that of the other two).
+		beam_width > 1 (inference.py:342: num_beams) samples every line by beam search -- `candidates` <= beam_width finished beams come back, ranked
+		with `length_penalty` -- on the "bigvgan" and "vocoder" branches, line by line; the streaming "hifigan" branch takes no beams."""
 		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
 			raise NotImplementedError(f"vocoder_type {vocoder_type!r} is unknown ('bigvgan', 'vocoder', 'hifigan')")
 		if vocoder_type == "hifigan" and self.hifigan is None:
 			raise NotImplementedError("TTS was built without a HiFiGAN vocoder (hifigan=): the streaming branch, inference.py:250-329, needs one")
-		if beam_width != 1:
-			raise NotImplementedError("beam search is not on the inference path (num_beams=1, inference.py:343)")
+		beam_width = max(1, int(beam_width))                  # inference.py:342
+		if beam_width != 1 and vocoder_type == "hifigan":
+			raise NotImplementedError("beam search is not available on the HiFiGAN streaming branch: its token generator yields one sequence as it is sampled (beam_width=1)")
 		if vocoder_type == "hifigan":
 			pass
 		elif vocoder_type == "vocoder":
@@ -92,7 +95,9 @@ class TTS:
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
 				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
-		if len(lines) > 1 and diffusion_sampler == "ddim":
+		if beam_width != 1:                                   # the beams of a line exchange histories every token: lines are sampled one by one
+			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
+		elif len(lines) > 1 and diffusion_sampler == "ddim":
 			# several lines: their sampling as one decode batch, the diffusion of a line under the sampling of later ones (TTSHotPath.inference_lines:
 			# the same waveforms as the line-by-line loop of inference.py:237-422, which is what the else branch runs)
 			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, **kw)]
