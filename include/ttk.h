@@ -394,6 +394,32 @@ int ttk_hifigan_set_cond(ttk_hifigan* h, const float* g, void* stream);
  * (the two linear interpolations happen inside), hop = the product of the upsample rates.                                         */
 int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* audio, void* stream);
 
+/* ------------------------------------------------------------------ DiscreteVAE: mel -> mel codes -> mel
+ * The default DiscreteVAE of models/dvae.py (:116-219; 1-D, two stride-2 k = 3 layers, ReLU, no encoder norm, nearest x2 + conv upsampling, the
+ * `Quantize` codebook :12-72), inference side.  Weights: the module's state_dict ("encoder.N...", "decoder.N...", "codebook.embed" [dim, tokens]).
+ * The convolutions run in `dtype`; the quantizer runs in f32 in every dtype (codes are ids: a 16-bit distance over thousands of candidates moves them). */
+typedef struct ttk_dvae ttk_dvae;
+typedef struct {
+	int channels;                             /* 80 mel bands */
+	int hidden_dim;                           /* 512; the two encoder layers give hidden_dim and 2 * hidden_dim channels; multiple of 8 */
+	int codebook_dim;                         /* 512; one of 32, 64, 128, 256, 512 */
+	int num_tokens;                           /* 8192 */
+	int num_resnet_blocks;                    /* 3; 1..8 */
+	int dtype;                                /* TTK_F32 | TTK_BF16 | TTK_F16 */
+} ttk_dvae_config;
+int ttk_dvae_create(ttk_dvae** out, const ttk_dvae_config* cfg, const ttk_weight_view* weights, int n_weights);
+int ttk_dvae_destroy(ttk_dvae* h);
+/* get_codebook_indices :239-246: mel f32 [B, channels, T] -> codes int64 [B, T4], T4 = T passed twice through L -> (L - 1) / 2 + 1; z_out
+ * (optional) f32 [B, T4, codebook_dim]: the encoder output the codes were taken from. */
+int ttk_dvae_encode(ttk_dvae* h, const float* mel, int B, int T, int64_t* codes_out, float* z_out, void* stream);
+/* Quantize.forward :29-39, the index alone: z f32 [M, codebook_dim] -> codes int64 [M], the argmin over j of |e_j|^2 - 2 z . e_j in f32 (the
+ * reference's distance less the row constant |z|^2); ties go to the lowest index; the same bits on every run. */
+int ttk_dvae_quantize(ttk_dvae* h, const float* z, int M, int64_t* codes_out, void* stream);
+/* decode :248-270: codes int64 [B, n] (device) -> mel f32 [B, channels, 4 n] and (optional) the last hidden activation f32 [B, hidden_dim, 4 n].
+ * The codes are copied to the host and checked first (this call synchronises `stream`): one outside [0, num_tokens) returns TTK_E_ARG and
+ * nothing is launched. */
+int ttk_dvae_decode(ttk_dvae* h, const int64_t* codes, int B, int n, float* mel_out, float* hidden_out, void* stream);
+
 /* ------------------------------------------------------------------ CLVP candidate scoring
  * models/clvp.py:21-136 (x-transformers branch): weights = CLVP.state_dict() with each attention's to_q / to_k / to_v stacked into
  * "<attn>.__qkv.weight" [3 * dim, dim] and "__rotary_inv_freq" [16] (RotaryEmbedding(32).inv_freq), as tortoise_tts_amd/clvp.py packs. */

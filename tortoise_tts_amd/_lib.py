@@ -118,6 +118,11 @@ SYMBOLS = {
 	"ttk_hifigan_destroy": (_I, [_P]),
 	"ttk_hifigan_set_cond": (_I, [_P, _P, _P]),
 	"ttk_hifigan_inference": (_I, [_P, _P, _I, _P, _P]),
+	"ttk_dvae_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
+	"ttk_dvae_destroy": (_I, [_P]),
+	"ttk_dvae_encode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+	"ttk_dvae_quantize": (_I, [_P, _P, _I, _P, _P]),
+	"ttk_dvae_decode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
 	"ttk_clvp_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_clvp_destroy": (_I, [_P]),
 	"ttk_clvp_score": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),

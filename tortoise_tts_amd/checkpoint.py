@@ -309,6 +309,22 @@ def load_hifigan(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key:
 	return HiFiGAN(sd, cfg or HiFiGANConfig(), dtype=dtype, device=device)
 
 
+def load_dvae_state(path, *, cfg=None, state_dict_key: Optional[str] = None):
+	"""`dvae.pth` -> (the tensors the handle reads, config): the reference's state_dict keys (`encoder.N...`, `decoder.N...`, `codebook.embed`),
+	shape-checked; the codebook's EMA buffers `codebook.cluster_size` / `codebook.embed_avg` (training state) and anything else are ignored."""
+	from .weights import DVAE_FULL, dvae_shapes
+	cfg = cfg or DVAE_FULL
+	sd = unwrap_state_dict(read_checkpoint(path), state_dict_key)
+	return select_hot_path(sd, dvae_shapes(cfg), "dvae"), cfg
+
+
+def load_dvae(path, *, cfg=None, dtype="f32", device="cuda", state_dict_key: Optional[str] = None):
+	"""`load_model("dvae")` (models/__init__.py): `dvae.pth` is a plain state_dict of the default DiscreteVAE (weights.DVAE_FULL).  f32 by default: codes are ids."""
+	from .dvae import DiscreteVAE
+	sd, cfg = load_dvae_state(path, cfg=cfg, state_dict_key=state_dict_key)
+	return DiscreteVAE(sd, cfg, dtype=dtype, device=device)
+
+
 def load_clvp(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = None):
 	"""`load_model("clvp")` (models/__init__.py:111-113): `clvp2.pth` is a plain state_dict of the x-transformers CLVP."""
 	from .clvp import CLVP

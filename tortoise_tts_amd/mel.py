@@ -237,15 +237,21 @@ def format_diffusion_conditioning(sample: torch.Tensor, stft: TacotronSTFT) -> t
 
 
 @torch.inference_mode()
-def encode(wav: torch.Tensor, sr: int, *, tms: TorchMelSpectrogram, stft: TacotronSTFT, conditioning_encoder, contextual_embedder, rng=None) -> dict:
-	"""emb/mel.py:84-109 without the dvae codes (training data, not needed to speak): one mono clip [1, n] at `sr` ->
-	{"conds": (ar mel [1, 1, 80, F], diffusion mel [1, 1, 100, F']), "latent": ([1, 1024], [1, 2048]), "metadata": {...}}."""
+def encode(wav: torch.Tensor, sr: int, *, tms: TorchMelSpectrogram, stft: TacotronSTFT, conditioning_encoder, contextual_embedder, rng=None, dvae=None) -> dict:
+	"""emb/mel.py:84-109: one mono clip [1, n] at `sr` ->
+	{"conds": (ar mel [1, 1, 80, F], diffusion mel [1, 1, 100, F']), "latent": ([1, 1024], [1, 2048]), "metadata": {...}}.
+	With `dvae` (tortoise_tts_amd.DiscreteVAE) also "codes": the mel codes int64 [1, F4] of the WHOLE clip's AR mel (:90,95: `format_autoregressive_conditioning(wav, 0)`,
+	no crop or padding) -- what `UnifiedVoice.inference_speech(input_tokens=...)` continues from.  Without one the dict has no such key."""
 	n = wav.shape[-1]
 	wav = resample(wav, sr, 22050, device=str(tms.device))
 	ar_conds = torch.stack([format_autoregressive_conditioning(wav, tms, rng=rng)], dim=1)
 	diff_conds = torch.stack([format_diffusion_conditioning(wav, stft)], dim=1)
-	return {
+	out = {}
+	if dvae is not None:
+		out["codes"] = dvae.get_codebook_indices(format_autoregressive_conditioning(wav, tms, cond_length=0))
+	out.update({
 		"conds": (ar_conds, diff_conds),
 		"latent": (conditioning_encoder.get_conditioning(ar_conds), contextual_embedder.get_conditioning(diff_conds)),
 		"metadata": {"original_length": n, "sample_rate": sr, "duration": n / sr},
-	}
+	})
+	return out

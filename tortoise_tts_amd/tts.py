@@ -27,10 +27,11 @@ def set_seed(seed=None) -> int:
 
 class TTS:
 	def __init__(self, autoregressive, diffusion, tokenizer, *, vocoder=None, clvp=None, conditioning_encoder=None, contextual_embedder=None,
-				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None, hifigan=None):
+				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None, hifigan=None, dvae=None):
 		self.hot = TTSHotPath(autoregressive, diffusion, vocoder=vocoder, clvp=clvp)
 		self.univnet = univnet          # tortoise_tts_amd.UnivNet: the vocoder of vocoder_type="vocoder"
 		self.hifigan = hifigan          # tortoise_tts_amd.HiFiGAN: the vocoder of vocoder_type="hifigan" (AR latents -> audio, no diffusion)
+		self.dvae = dvae                # tortoise_tts_amd.DiscreteVAE: `encode_audio` then returns the clip's mel codes as well (emb/mel.py:95)
 		self.tokenizer = tokenizer
 		self.conditioning_encoder, self.contextual_embedder, self.tms, self.stft = conditioning_encoder, contextual_embedder, tms, stft
 		self.device = autoregressive.device
@@ -45,16 +46,26 @@ class TTS:
 
 	def encode_audio(self, wav: Union[dict, torch.Tensor, Sequence[torch.Tensor]], sr: int = 22050) -> dict:
 		"""inference.py:113-124 over emb/mel.py:84-137 (`encode` / `encode_from_files`): a mono clip [1, n] (or a list of them, concatenated
-		in time like `encode_from_files`) -> {"conds", "latent", "metadata"}; a dict produced earlier is passed through."""
+		in time like `encode_from_files`) -> {"conds", "latent", "metadata"}; a dict produced earlier is passed through.  Built with `dvae=`, the
+		dict also has "codes": the mel codes [1, F4] of the clip, or for a list of clips a list with one entry per clip (emb/mel.py:95; each clip stays usable as a
+		continuation prompt of its own, where the reference codes the concatenation)."""
 		if isinstance(wav, dict):
 			return wav
 		if any(p is None for p in (self.tms, self.stft, self.conditioning_encoder, self.contextual_embedder)):
 			raise ValueError("TTS was built without the conditioning parts (tms, stft, conditioning_encoder, contextual_embedder)")
+		clips = None
 		if not isinstance(wav, torch.Tensor):
-			wav = torch.cat([w[:1] if w.dim() == 2 else w[None] for w in wav], dim=-1)
+			clips = [w[:1] if w.dim() == 2 else w[None] for w in wav]
+			wav = torch.cat(clips, dim=-1)
 		if wav.dim() == 1:
 			wav = wav[None]
-		return M.encode(wav[:1], sr, tms=self.tms, stft=self.stft, conditioning_encoder=self.conditioning_encoder, contextual_embedder=self.contextual_embedder)
+		parts = dict(tms=self.tms, stft=self.stft, conditioning_encoder=self.conditioning_encoder, contextual_embedder=self.contextual_embedder)
+		out = M.encode(wav[:1], sr, dvae=None if clips is not None else self.dvae, **parts)
+		if clips is not None and self.dvae is not None:
+			codes = [self.dvae.get_codebook_indices(M.format_autoregressive_conditioning(M.resample(c, sr, 22050, device=str(self.tms.device)), self.tms, cond_length=0))
+					 for c in clips]
+			out = {"codes": codes, **out}
+		return out
 
 	@torch.inference_mode()
 	def inference(self, text: str, references, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,

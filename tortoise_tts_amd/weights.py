@@ -147,6 +147,33 @@ class HiFiGANConfig:
 
 
 @dataclasses.dataclass(frozen=True)
+class DVAEConfig:
+	"""`DiscreteVAE.__init__` defaults, models/dvae.py:117-137: what `load_model("dvae")` builds and `dvae.pth` holds.  Only the default structure is
+	built (tortoise_tts_amd/dvae.py refuses the rest with a reason); the sizes may vary."""
+	channels: int = 80
+	hidden_dim: int = 512
+	codebook_dim: int = 512
+	num_tokens: int = 8192
+	num_resnet_blocks: int = 3
+	num_layers: int = 2
+	stride: int = 2
+	kernel_size: int = 3
+	positional_dims: int = 1
+	use_transposed_convs: bool = False
+	encoder_norm: bool = False
+	activation: str = "relu"
+	normalization: object = None
+	record_codes: bool = False
+	use_lr_quantizer: bool = False
+
+	def code_frames(self, T: int) -> int:
+		"""codes per clip of T mel frames: T through L -> (L - 1) // 2 + 1 once per stride-2 layer"""
+		for _ in range(self.num_layers):
+			T = (T - 1) // 2 + 1
+		return T
+
+
+@dataclasses.dataclass(frozen=True)
 class CLVPConfig:
 	"""`CLVP.__init__` defaults, models/clvp.py:29-46 (the x-transformers branch, `use_xformers=True`)."""
 	dim: int = 768                      # dim_text = dim_speech = dim_latent
@@ -173,6 +200,9 @@ AR_FULL = ARConfig()
 HIFIGAN_FULL = HiFiGANConfig()
 # latents of AR_SMALL (128 wide); stages of 64 and 32 channels, so both widths of the narrow-channel MFMA convolution are reached
 HIFIGAN_SMALL = HiFiGANConfig(in_channels=128, cond_channels=128, upsample_initial_channel=128, upsample_factors=(4, 2), upsample_kernel_sizes=(8, 4))
+DVAE_FULL = DVAEConfig()
+# 200 codes: no multiple of the quantizer's 16-code tile or 64-code workgroup range, and within AR_SMALL's mel-code count
+DVAE_SMALL = DVAEConfig(channels=80, hidden_dim=32, codebook_dim=32, num_tokens=200, num_resnet_blocks=1)
 DIFF_SMALL = DiffusionConfig(model_channels=128, num_layers=2, in_latent_channels=128, num_heads=2)
 DIFF_FULL = DiffusionConfig()
 
@@ -337,6 +367,38 @@ def hifigan_shapes(c: HiFiGANConfig) -> Dict[str, Tuple[int, ...]]:
 	if c.cond_channels > 0:
 		s["cond_layer.weight"] = (ch0, c.cond_channels, 1); s["cond_layer.bias"] = (ch0,)
 	return s
+
+
+def dvae_shapes(c: DVAEConfig) -> Dict[str, Tuple[int, ...]]:
+	"""`DiscreteVAE.state_dict()` (models/dvae.py:164-210) without the codebook's EMA buffers (`codebook.cluster_size`, `codebook.embed_avg`: training state)."""
+	H, C2, R, k = c.hidden_dim, 2 * c.hidden_dim, c.num_resnet_blocks, c.kernel_size
+	s: Dict[str, Tuple[int, ...]] = {"encoder.0.0.weight": (H, c.channels, k), "encoder.0.0.bias": (H,), "encoder.1.0.weight": (C2, H, k), "encoder.1.0.bias": (C2,)}
+
+	def res(p):
+		s[p + "net.0.weight"] = (C2, C2, 3); s[p + "net.0.bias"] = (C2,)
+		s[p + "net.2.weight"] = (C2, C2, 3); s[p + "net.2.bias"] = (C2,)
+		s[p + "net.4.weight"] = (C2, C2, 1); s[p + "net.4.bias"] = (C2,)
+	for i in range(R):
+		res(f"encoder.{2 + i}.")
+	s[f"encoder.{2 + R}.weight"] = (c.codebook_dim, C2, 1); s[f"encoder.{2 + R}.bias"] = (c.codebook_dim,)
+	s["decoder.0.weight"] = (C2, c.codebook_dim, 1); s["decoder.0.bias"] = (C2,)
+	for i in range(R):
+		res(f"decoder.{1 + i}.")
+	s[f"decoder.{1 + R}.0.conv.weight"] = (C2, C2, k); s[f"decoder.{1 + R}.0.conv.bias"] = (C2,)
+	s[f"decoder.{2 + R}.0.conv.weight"] = (H, C2, k); s[f"decoder.{2 + R}.0.conv.bias"] = (H,)
+	s[f"decoder.{3 + R}.weight"] = (c.channels, H, 1); s[f"decoder.{3 + R}.bias"] = (c.channels,)
+	s["codebook.embed"] = (c.codebook_dim, c.num_tokens)
+	return s
+
+
+def dvae_codebook(mean: torch.Tensor, std: torch.Tensor, num_tokens: int, seed: int) -> torch.Tensor:
+	"""A synthetic `codebook.embed` [dim, num_tokens] at the scale of an encoder's output: column j = mean + std * (a seeded normal draw), per channel.
+	`Quantize`'s own initialisation (randn) against a randomly initialised encoder makes |e|^2 decide every distance -- every frame gets the same code,
+	and a broken quantizer passes; the DVAE fixtures (tools/make_golden_dvae.py) and tests draw the codebook here, from the statistics of the encoder's output."""
+	g = torch.Generator(device="cpu")
+	g.manual_seed((seed * 1000003 + zlib.crc32(b"codebook.embed")) % (2 ** 63 - 1))
+	mean, std = torch.as_tensor(mean, dtype=torch.float32), torch.as_tensor(std, dtype=torch.float32)
+	return mean[:, None] + std[:, None] * torch.randn((mean.shape[0], num_tokens), generator=g, dtype=torch.float32)
 
 
 def weight_norm_names(shapes: Dict[str, Tuple[int, ...]]) -> Dict[str, Tuple[int, ...]]:
