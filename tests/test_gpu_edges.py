@@ -370,3 +370,48 @@ def test_two_stream_ddim_loop_equals_the_sequential_one(monkeypatch):
 		noise = torch.randn(1, 100, T, generator=g).to(DEV)
 		outs = [get_diffuser(steps, cf).sample_loop(m, (1, 100, T), sampler="ddim", noise=noise, model_kwargs={"precomputed_aligned_embeddings": E}) for m in (seq, pip, pip)]
 		assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1]) and torch.equal(outs[1], outs[2]), (T, steps, cf)
+
+
+def _stream_ids(model, cond, text, **kw):
+	ids = model.compute_embeddings(cond, text)
+	return torch.stack([tok for tok, _ in model.get_generator(inputs=ids, max_length=ids.shape[1] + 8, **kw)], 1)
+
+
+@pytest.mark.parametrize("own", ["1", "0"])
+@pytest.mark.parametrize("entry", ["inference_speech", "inference_speech_lines", "beam", "get_generator"])
+def test_a_host_error_inside_an_armed_generation_leaves_the_model_usable(entry, own, monkeypatch):
+	"""a text id outside the embedding table is `_check_ids`' IndexError, raised on the host inside the generation session (state reset, noise armed,
+	for the stream the handle marked busy) before any launch of the call: the session disarms and frees the handle on its way out, so the same model then
+	gives, for a valid text, the ids of a freshly built model and leaves the torch generator where that one leaves it.  Every entry point, with the noise
+	drawn in the mel-head launch and by torch.  5 text tokens, 3 candidates, 8 new tokens, max_batch=4 -- but the beam call returns its one best beam of
+	two (HF refuses num_return_sequences > num_beams), and the batch of two lines has 2 x 3 rows, so its models are built with max_batch=8."""
+	from tortoise_tts_amd.autoregressive import UnifiedVoice
+	monkeypatch.setenv("TTK_AR_OWN_RNG", own)
+	cfg = W.AR_SMALL
+	sd = W.synth_state_dict(W.ar_shapes(cfg), 31)
+	text = torch.randint(1, 255, (1, 5), generator=gen(90)).to(DEV)
+	other = torch.randint(1, 255, (1, 4), generator=gen(91)).to(DEV)
+	cond = torch.randn(1, 128, generator=gen(92)).to(DEV)
+	bad = text.clone()
+	bad[0, 2] = 300
+	kw = dict(do_sample=True, temperature=0.9)
+	call = {
+		"inference_speech": lambda m, t: [m.inference_speech(cond, t, num_return_sequences=3, max_generate_length=8, **kw)],
+		"inference_speech_lines": lambda m, t: m.inference_speech_lines(cond, [other, t], num_return_sequences=3, max_generate_length=8, **kw),
+		"beam": lambda m, t: [m.inference_speech(cond, t, num_beams=2, top_k=0, max_generate_length=8, **kw)],
+		"get_generator": lambda m, t: [_stream_ids(m, cond, t, num_return_sequences=3, **kw)],
+	}[entry]
+	res = []
+	for fails_first in (True, False):
+		model = UnifiedVoice(sd, cfg, dtype="f32", device=DEV, max_batch=8 if entry == "inference_speech_lines" else 4, max_ctx=160)
+		if fails_first:
+			with pytest.raises(IndexError, match="text token ids"):
+				call(model, bad)
+			model._require_idle()
+		ids = call(model, text)
+		res.append((ids, torch.cuda.default_generators[0].get_offset()))
+		if entry != "beam":      # (a beam state lives for its call only)
+			assert next(iter(model._states.values())).own_rng == (own == "1")      # the self-check against torch passed on this device
+	(got, off_got), (want, off_want) = res
+	assert len(got) == len(want) and all(torch.equal(a, b) for a, b in zip(got, want))
+	assert off_got == off_want

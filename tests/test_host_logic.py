@@ -106,6 +106,39 @@ def test_product_path_has_no_cpu_fallback():
 	assert "tortoise_oracle" not in src and "import oracle" not in src
 
 
+def test_handle_del_without_a_live_handle_is_a_no_op():
+	"""`_lib.Handle.__del__` also runs on an object whose __init__ raised before `_create` (no `_h`, no `_abi`, perhaps no `lib`) and on one that was
+	destroyed already (`_h` None): neither may raise or reach the library; a live handle is destroyed once, by `ttk_<abi>_destroy`"""
+	calls = []
+
+	class Lib:
+		def __getattr__(self, name):
+			return lambda *a: calls.append((name, a))
+
+	class Raises(_lib.Handle):
+		def __init__(self):
+			raise ValueError("before the handle exists")
+
+	with pytest.raises(ValueError):
+		Raises()
+	bare = object.__new__(Raises)
+	_lib.Handle.__del__(bare)
+	bare.lib = Lib()
+	_lib.Handle.__del__(bare)
+	gone = object.__new__(_lib.Handle)
+	gone.lib, gone._abi, gone._h = Lib(), "ar", None
+	_lib.Handle.__del__(gone)
+	failed = object.__new__(_lib.Handle)      # what a failed ttk_<abi>_create leaves: a null pointer
+	failed.lib, failed._abi, failed._h = Lib(), "ar", ctypes.c_void_p()
+	_lib.Handle.__del__(failed)
+	assert calls == []
+	live = object.__new__(_lib.Handle)
+	live.lib, live._abi, live._h = Lib(), "dvae", ctypes.c_void_p(64)
+	_lib.Handle.__del__(live)
+	_lib.Handle.__del__(live)
+	assert [c[0] for c in calls] == ["ttk_dvae_destroy"] and calls[0][1][0].value == 64 and live._h is None
+
+
 def test_bench_launches_its_own_ranks_when_started_without_a_distributed_environment():
 	"""`python bench.py --gpus 2` as the driver starts it (no torchrun, no WORLD_SIZE): the parent starts the ranks as child processes under
 	torch.distributed.run, relays rank 0's ONE line and exits with their status (VERDICT r02 missing #1).  TTK_BENCH_PROBE=1 makes the ranks

@@ -198,6 +198,41 @@ def require_cuda(*tensors: torch.Tensor):
 			raise TTKError("libttk takes device tensors; got a CPU tensor (the HIP path has no CPU fallback)")
 
 
+def cuda_device(device) -> torch.device:
+	dev = torch.device(device)
+	if dev.type != "cuda":
+		raise TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
+	return dev
+
+
+class Handle:
+	"""What every wrapper of a libttk handle shares: the device it lives on, the library, the handle `ttk_<abi>_create` makes from a config struct
+	and named f32 tensors, and its lifetime.  The subclass prepares its weights, says which tensors are missing in its own words and calls `_create`."""
+
+	def __init__(self, device):
+		self.device = cuda_device(device)
+		self.lib = load()
+
+	def _create(self, abi: str, config: C.Structure, tensors: Dict[str, torch.Tensor], names: Sequence[str]):
+		views, keep = weight_views(tensors, names)      # `keep` lives until the create call has copied the tensors
+		self._abi, self._h = abi, C.c_void_p()
+		create = f"ttk_{abi}_create"
+		with torch.cuda.device(self.device):
+			check(getattr(self.lib, create)(C.byref(self._h), C.byref(config), views, len(names)), create)
+
+	def __del__(self):
+		h = getattr(self, "_h", None)          # absent when __init__ raised before `_create`, empty when the create call failed
+		if h:
+			getattr(self.lib, f"ttk_{self._abi}_destroy")(h)
+			self._h = None
+
+	def eval(self, *a, **k):
+		return self
+
+	def to(self, *a, **k):
+		return self
+
+
 def weight_views(sd: Dict[str, torch.Tensor], names: Sequence[str]):
 	"""(array of ttk_weight_view, keepalive list) for f32 contiguous tensors (host or device)."""
 	keep: List[torch.Tensor] = []

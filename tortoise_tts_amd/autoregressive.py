@@ -16,11 +16,23 @@ What runs where
   * beam search (num_beams > 1) ..................................... libttk  (csrc/beam.hip: the beam step -- log-softmax, warpers, the
     multinomial without replacement over num_beams * V, HF's running / finished bookkeeping -- and the in-place KV-cache reorder); the loop
     here enqueues {beam step, reorder, decode} per token and polls the done word.
+
+How the host layer is laid out: four drivers -- `_generate` (+ `_token_loop`), `_generate_lines`, `_beam_generate`, `_loop_stream` -- differ in their loop and
+in how they account for the torch generator; what they share is written once:
+  * `_session` ........ one generation on the handle: refusal while a stream is open, device guard, reseed, state reset, noise armed; disarmed again
+                        however the body ends, health flags read
+  * `_capture_step` ... the token step into a HIP graph (the non-streamed and the streamed loop each keep their own capture per state)
+  * `_StopPoll` ....... the look, LAG steps late, at the end-of-generation word the device writes
+  * `_max_new`, `_pipe_key` ... the new-token budget; what of the sampling keywords a state is keyed by
+  * `_NoiseState` ..... base of `_GenState` and `_BeamState`: the self-check of the head-drawn noise against torch, arming and disarming it
+The handle itself (creation from named tensors, destruction) is `_lib.Handle`'s, as for every other libttk wrapper.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import os
+import sys
 import warnings
 from typing import Dict, Iterator, Optional, Tuple
 
@@ -30,8 +42,10 @@ from . import _lib
 from .sampling import LogitsPipeline, multinomial1, setup_seed
 from .weights import ARConfig, ar_shapes
 
+LAG = 2      # steps the host runs ahead of the device-side end-of-generation word it polls
 
-class UnifiedVoice:
+
+class UnifiedVoice(_lib.Handle):
 	def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: ARConfig = ARConfig(), dtype: str = "bf16",
 				 device: str = "cuda:0", max_batch: int = 16, max_ctx: Optional[int] = None, use_graph: bool = True,
 				 hf_exact_top_p: bool = False):
@@ -40,10 +54,7 @@ class UnifiedVoice:
 		rounding (csrc/sample.hip; tests/test_gpu_parity.py::test_top_p_boundary_stress); costs the per-token torch launches the kernel removed."""
 		self.hf_exact_top_p = hf_exact_top_p
 		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
-		self.lib = _lib.load()
+		super().__init__(device)
 		self.dtype = _lib.DTYPES[dtype]
 		if self.dtype == _lib.TTK_FP8:      # the decode GEMVs have 16 rows: fp8 activations buy nothing there; 'fp8' means fp8 weights
 			self.dtype = _lib.TTK_FP8W
@@ -61,32 +72,16 @@ class UnifiedVoice:
 		missing = [n for n in names if n not in state_dict]
 		if missing:
 			raise _lib.TTKError(f"state_dict lacks {len(missing)} hot-path tensors, e.g. {missing[:3]}")
-		views, keep = _lib.weight_views(state_dict, names)
 		c = _lib.ARConfigC(cfg.layers, cfg.model_dim, cfg.heads, cfg.max_mel_seq_len, cfg.max_text_seq_len,
 						   cfg.number_text_tokens + 1, cfg.number_mel_codes, cfg.start_text_token, cfg.stop_text_token,
 						   cfg.start_mel_token, cfg.stop_mel_token, self.dtype, max_batch, self.max_ctx)
-		self._h = _lib.C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_ar_create(_lib.C.byref(self._h), _lib.C.byref(c), views, len(names)), "ttk_ar_create")
-		del keep
+		self._create("ar", c, state_dict, names)
 		self._states: Dict[tuple, "_GenState"] = {}
 		self._prefix = None
 		self._streaming = False          # a streamed generation is open on this handle (its KV cache, noise and latent ring belong to it)
 
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_ar_destroy(h)
-			self._h = None
-
 	def parameters(self):
 		yield torch.empty(0, device=self.device)
-
-	def to(self, *a, **k):
-		return self
-
-	def eval(self):
-		return self
 
 	# ------------------------------------------------------------------ C-ABI calls
 	def _check_ids(self, ids: torch.Tensor, n: int, what: str):
@@ -271,6 +266,43 @@ class UnifiedVoice:
 		setup_seed(info["seed"])
 		torch.cuda.default_generators[self.device.index or 0].set_offset(info["rng_start"] + info["steps"] * info["rng_step"])
 
+	def _max_new(self, prefix_tokens, max_generate_length):
+		"""the number of new tokens a call may generate behind a prefix of `prefix_tokens` cached rows"""
+		c = self.cfg
+		max_new = (c.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
+		if prefix_tokens + max_new > self.max_ctx or max_new + 2 > c.max_mel_seq_len:
+			raise _lib.TTKError(f"prefix {prefix_tokens} + {max_new} new tokens exceed max_ctx={self.max_ctx} or the mel position table ({c.max_mel_seq_len})")
+		return max_new
+
+	def _pipe_key(self, kw, typical_mass):
+		"""(what of the keywords is baked into a generation state, whether the stop token can be sampled at all)"""
+		suppress = tuple(kw.get("suppress_tokens") or ())
+		pipe_key = (kw.get("temperature", 1.0), kw.get("top_k", 50), kw.get("top_p", 1.0), kw.get("repetition_penalty", 1.0), suppress, typical_mass)
+		return pipe_key, self.cfg.stop_mel_token not in suppress
+
+	@contextlib.contextmanager
+	def _session(self, seed, make_state, prompt=None, arm=(), streamed=False):
+		"""One generation on the handle, from the reseed to the noise switched off again: yields (state, the device's torch generator, its offset
+		behind the reseed).  The body runs the loop and does its own accounting of what the reference's draws would have consumed; the noise is disarmed
+		however the body ends, and the health flags are read when it ends well (`streamed`: always -- a consumer may walk away from a stream)."""
+		self._require_idle()            # (a generator body runs at its first next(): two generators may have been created, only one may run)
+		with torch.cuda.device(self.device):
+			st = make_state()
+			setup_seed(seed)
+			gen = torch.cuda.default_generators[self.device.index or 0]
+			off_start = gen.get_offset()
+			st.reset(self.cfg, prompt)
+			if st.own_rng:
+				st.arm_noise(gen, *arm)
+			health = streamed
+			try:
+				yield st, gen, off_start
+				health = True
+			finally:
+				st.disarm_noise()
+				if health:
+					self._check_health()
+
 	def _generate_lines(self, cond, texts, C, max_generate_length, kw, typical_mass=None):
 		c = self.cfg
 		self._require_idle()            # a line batch rewrites the KV cache, the noise arming and (through the ring) an open stream's latent buffer
@@ -278,29 +310,12 @@ class UnifiedVoice:
 		B = G * C
 		if B > self.max_batch:
 			raise _lib.TTKError(f"{G} lines x {C} candidates exceed max_batch={self.max_batch}")
-		Tmax = max(int(t.shape[1]) for t in texts)
-		max_new = (c.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
-		if Tmax + 4 + max_new > self.max_ctx or max_new + 2 > c.max_mel_seq_len:
-			raise _lib.TTKError(f"prefix {Tmax + 4} + {max_new} new tokens exceed max_ctx={self.max_ctx} or the mel position table ({c.max_mel_seq_len})")
-		suppress = tuple(kw.get("suppress_tokens") or ())
-		pipe_key = (kw.get("temperature", 1.0), kw.get("top_k", 50), kw.get("top_p", 1.0), kw.get("repetition_penalty", 1.0), suppress, typical_mass)
-		can_stop = c.stop_mel_token not in suppress
+		max_new = self._max_new(max(int(t.shape[1]) for t in texts) + 4, max_generate_length)
+		pipe_key, can_stop = self._pipe_key(kw, typical_mass)
 		seed = kw.get("seed", 0)
-		with torch.cuda.device(self.device):
-			st = self._gen_state(B, max_new, pipe_key, C, 0, lines=G)
-			setup_seed(seed)
-			gen = torch.cuda.default_generators[self.device.index or 0]
-			off_start = gen.get_offset()
-			st.reset(c)
-			if st.own_rng:
-				st.arm_noise(gen, 0)
-			try:
-				n = self._token_loop(st, gen, off_start, lambda: self._prefill_lines(cond, texts, C), max_new, can_stop)
-			finally:
-				if st.own_rng:
-					_lib.check(self.lib.ttk_ar_set_noise(self._h, None, None, None), "ttk_ar_set_noise")
+		with self._session(seed, lambda: self._gen_state(B, max_new, pipe_key, C, 0, lines=G), arm=(0,)) as (st, gen, off_start):
+			n = self._token_loop(st, gen, off_start, lambda: self._prefill_lines(cond, texts, C), max_new, can_stop)
 			step = st.noise_step if st.own_rng else (gen.get_offset() - off_start) // max(n, 1)
-			self._check_health()
 			ids = st.ids[:, :n]
 			first_stop = torch.where((ids == c.stop_mel_token).any(dim=1), (ids == c.stop_mel_token).float().argmax(dim=1), torch.full((B,), n, device=ids.device)).view(G, C)
 			done = bool(can_stop) & (first_stop < n).all(dim=1)
@@ -318,7 +333,6 @@ class UnifiedVoice:
 		token {ttk_beam_step; ttk_ar_reorder_cache; ttk_ar_decode of the chosen tokens}.  Returns `sequences[:R]` behind the prompt, cropped to the
 		longest returned beam and padded with the stop token (step 5, :3510-3523).  The search ends on the device (the done word of ttk_beam_step);
 		the host looks at it LAG tokens late, and the steps enqueued past the end are no-ops that draw nothing from the torch generator."""
-		c = self.cfg
 		self._require_idle()
 		if R > N:
 			raise ValueError(f"`num_return_sequences` ({R}) has to be smaller or equal to `num_beams` ({N}).")
@@ -328,45 +342,26 @@ class UnifiedVoice:
 		if 0 < top_k < 2 * N:
 			raise ValueError(f"top_k={top_k} keeps fewer tokens than the 2 * num_beams = {2 * N} continuations a beam step selects; which of the removed "
 							 "(probability 0) ones torch.multinomial would pick is unspecified: use top_k=0 or top_k >= 2 * num_beams")
-		Tt = text.shape[1]
-		max_new = (c.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
-		if Tt + 4 + max_new > self.max_ctx or max_new + 2 > c.max_mel_seq_len:
-			raise _lib.TTKError(f"prefix {Tt + 4} + {max_new} new tokens exceed max_ctx={self.max_ctx} or the mel position table ({c.max_mel_seq_len})")
+		max_new = self._max_new(text.shape[1] + 4, max_generate_length)
 		if max_new < 1:
 			raise ValueError("max_generate_length must be at least 1")
-		LAG = 2
-		with torch.cuda.device(self.device):
-			st = _BeamState(self, N, max_new, kw)
-			setup_seed(kw.get("seed", 0))
-			gen = torch.cuda.default_generators[self.device.index or 0]
-			off_start = gen.get_offset()
-			if st.own_rng:
-				st.arm_noise(gen)
-			try:
-				st.logits.copy_(self._prefill(cond, text, N))
-				n, events = 0, []
-				while True:
-					st.step()
-					n += 1
-					if n >= max_new:
-						break
-					if st.own_rng:
-						ev = torch.cuda.Event()
-						ev.record()
-						events.append(ev)
-						if len(events) > LAG:
-							events.pop(0).synchronize()          # the step LAG tokens back is complete: its done word is visible
-							if int(st.done[0]):
-								break
-					else:                                        # torch draws the noise: a step past the end would consume generator state
-						torch.cuda.synchronize(self.device)
-						if int(st.done[0]):
-							break
-					_lib.check(self.lib.ttk_ar_reorder_cache(self._h, st.beam_idx.data_ptr(), _lib.stream_ptr()), "ttk_ar_reorder_cache")
-					self._decode(st.tok, st.logits)
-			finally:
+		with self._session(kw.get("seed", 0), lambda: _BeamState(self, N, max_new, kw)) as (st, gen, off_start):
+			st.logits.copy_(self._prefill(cond, text, N))
+			n, poll = 0, _StopPoll()
+			while True:
+				st.step()
+				n += 1
+				if n >= max_new:
+					break
 				if st.own_rng:
-					_lib.check(self.lib.ttk_ar_set_noise(self._h, None, None, None), "ttk_ar_set_noise")
+					ended = poll.step_complete() and int(st.done[0])
+				else:                                        # torch draws the noise: a step past the end would consume generator state
+					torch.cuda.synchronize(self.device)
+					ended = int(st.done[0])
+				if ended:
+					break
+				_lib.check(self.lib.ttk_ar_reorder_cache(self._h, st.beam_idx.data_ptr(), _lib.stream_ptr()), "ttk_ar_reorder_cache")
+				self._decode(st.tok, st.logits)
 			torch.cuda.synchronize(self.device)
 			state = st.state.tolist()
 			steps = state[2 * N + 1]
@@ -375,7 +370,6 @@ class UnifiedVoice:
 			if st.own_rng:
 				gen.set_offset(off_start + steps * st.noise_step)      # what the torch.multinomial of every step would have consumed
 			self.last_generate = dict(steps=steps, rng_start=off_start, rng_step=(gen.get_offset() - off_start) // steps)
-			self._check_health()
 			length = max(state[N:N + R])
 			return st.seqs[steps & 1, 1, :R, :length].clone()
 
@@ -405,7 +399,6 @@ class UnifiedVoice:
 
 	# ------------------------------------------------------------------ the token loop
 	def _generate(self, cond, text, num_return_sequences, max_generate_length, typical_mass, kw, stream, shard=None, prompt=None):
-		c = self.cfg
 		self._require_idle()
 		n_in = 0 if prompt is None else int(prompt.shape[1])
 		if stream and n_in:
@@ -419,39 +412,45 @@ class UnifiedVoice:
 		B = hi - lo
 		if B > self.max_batch:
 			raise _lib.TTKError(f"{B} candidates exceed max_batch={self.max_batch}")
-		Tt = text.shape[1]
-		trunc_index = Tt + 4
-		max_new = (c.max_mel_tokens - 1) if max_generate_length is None else int(max_generate_length)
-		if trunc_index + max_new > self.max_ctx or max_new + 2 > c.max_mel_seq_len:
-			raise _lib.TTKError(f"prefix {trunc_index} + {max_new} new tokens exceed max_ctx={self.max_ctx} "
-								f"or the mel position table ({c.max_mel_seq_len})")
+		max_new = self._max_new(text.shape[1] + 4, max_generate_length)
 		if n_in >= max_new:      # HF's stopping criterion is only looked at after a token has been appended: the reference would still sample one
 			raise ValueError(f"{n_in} prompt tokens leave no room below max_generate_length={max_new}")
-		suppress = tuple(kw.get("suppress_tokens") or ())
-		pipe_key = (kw.get("temperature", 1.0), kw.get("top_k", 50), kw.get("top_p", 1.0), kw.get("repetition_penalty", 1.0),
-					suppress, typical_mass)
+		pipe_key, can_stop = self._pipe_key(kw, typical_mass)
 		if stream:
-			return self._loop_stream(cond, text, B, max_new, pipe_key, c.stop_mel_token not in suppress)
-		can_stop = c.stop_mel_token not in suppress
-		with torch.cuda.device(self.device):
-			st = self._gen_state(B, max_new, pipe_key, C, lo)
-			setup_seed(kw.get("seed", 0))
-			gen = torch.cuda.default_generators[self.device.index or 0]
-			off_start = gen.get_offset()
-			st.reset(c, prompt)
-			if st.own_rng:
-				st.arm_noise(gen, lo, n_in)
-			try:
-				n = self._token_loop(st, gen, off_start, lambda: self._prefill(cond, text, B, prompt), max_new, can_stop, n_in)
-			finally:
-				if st.own_rng:
-					_lib.check(self.lib.ttk_ar_set_noise(self._h, None, None, None), "ttk_ar_set_noise")
+			return self._loop_stream(cond, text, B, max_new, pipe_key, can_stop)
+		with self._session(kw.get("seed", 0), lambda: self._gen_state(B, max_new, pipe_key, C, lo), prompt, arm=(lo, n_in)) as (st, gen, off_start):
+			n = self._token_loop(st, gen, off_start, lambda: self._prefill(cond, text, B, prompt), max_new, can_stop, n_in)
 			if st.own_rng:
 				gen.set_offset(off_start + (n - n_in) * st.noise_step)        # what the n - n_in torch draws would have consumed
 			# what the sampling consumed from the generator: dist.py aligns a shard's stream with the unsharded run's from this
 			self.last_generate = dict(steps=n - n_in, rng_start=off_start, rng_step=(gen.get_offset() - off_start) // max(n - n_in, 1))
-			self._check_health()
 			return st.ids[:, :n].clone(), None
+
+	def _capture_step(self, st):
+		"""the token step {ttk_ar_decode_next; [typical warper]; exponential_; ttk_ar_sample_next} as it is issued right now (with or without the hidden
+		ring set), captured into a HIP graph.  The caller has run the step eagerly before (warm kernels)."""
+		torch.cuda.synchronize(self.device)
+		g = torch.cuda.CUDAGraph()
+		# thread-local capture mode: another host thread may be enqueuing (and allocating for) the previous
+		# line's diffusion meanwhile (TTSHotPath.inference_lines); in the default global mode its hipMalloc /
+		# hipFree would invalidate this capture.
+		# capture_begin / capture_end run OUTSIDE inference mode whatever the caller's mode: torch creates the
+		# generator's graph-side seed / offset tensors at the first capture and updates them in place at every
+		# later capture and replay -- created under inference_mode they would make any later capture from a
+		# caller without it fail ("inplace update to inference tensor outside InferenceMode").
+		ctx = torch.cuda.graph(g, capture_error_mode="thread_local")
+		with torch.inference_mode(False):
+			ctx.__enter__()
+		try:
+			self._decode_next(st.logits)
+			st.sample(0)
+		except BaseException:
+			with torch.inference_mode(False):
+				ctx.__exit__(*sys.exc_info())
+			raise
+		with torch.inference_mode(False):
+			ctx.__exit__(None, None, None)
+		return g
 
 	def _token_loop(self, st, gen, off_start, prefill, max_new, can_stop, n0=0):
 		"""n0: id columns that are filled already (the prompt tokens of a prompted continuation); returns the filled columns at the end"""
@@ -474,12 +473,11 @@ class UnifiedVoice:
 			# becomes a flag the sampling kernel raises in pinned memory; the host looks at it LAG replays late, so the GPU
 			# always has work queued.  The <= LAG tokens generated past the true end are all padding; they are cut off below
 			# and the generator offset they consumed is handed back, so ids AND the RNG stream equal the reference's.
-			LAG = 2
 			st.sample(n0)
 			if st.rng_step is None:
 				st.rng_step = gen.get_offset() - off_start
 			n = n0 + 1
-			events = []
+			poll = _StopPoll()
 			stopped = can_stop and int(st.unfinished.max()) == 0
 			while n < max_new and not stopped:
 				if st.graph is None:
@@ -488,44 +486,18 @@ class UnifiedVoice:
 					n += 1
 					stopped = can_stop and int(st.unfinished.max()) == 0
 					if n < max_new and not stopped:
-						torch.cuda.synchronize(self.device)
-						g = torch.cuda.CUDAGraph()
-						# thread-local capture mode: another host thread may be enqueuing (and allocating for) the previous
-						# line's diffusion meanwhile (TTSHotPath.inference_lines); in the default global mode its hipMalloc /
-						# hipFree would invalidate this capture.
-						# capture_begin / capture_end run OUTSIDE inference mode whatever the caller's mode: torch creates the
-						# generator's graph-side seed / offset tensors at the first capture and updates them in place at every
-						# later capture and replay -- created under inference_mode they would make any later capture from a
-						# caller without it fail ("inplace update to inference tensor outside InferenceMode").
-						ctx = torch.cuda.graph(g, capture_error_mode="thread_local")
-						with torch.inference_mode(False):
-							ctx.__enter__()
-						try:
-							self._decode_next(st.logits)
-							st.sample(0)
-						except BaseException:
-							with torch.inference_mode(False):
-								ctx.__exit__(*__import__("sys").exc_info())
-							raise
-						with torch.inference_mode(False):
-							ctx.__exit__(None, None, None)
-						st.graph = g
+						st.graph = self._capture_step(st)
 						# no random numbers are drawn inside the captured step when the mel head draws the noise: launch the instantiated
 						# graph directly then -- CUDAGraph.replay() first refills the generator's seed / offset tensors, two launches per token
-						st.graph_exec = g.raw_cuda_graph_exec() if st.own_rng and os.environ.get("TTK_AR_RAW_REPLAY", "1") != "0" else None
+						st.graph_exec = st.graph.raw_cuda_graph_exec() if st.own_rng and os.environ.get("TTK_AR_RAW_REPLAY", "1") != "0" else None
 					continue
 				if st.graph_exec:
 					_lib.check(self.lib.ttk_graph_launch(st.graph_exec, _lib.stream_ptr()), "ttk_graph_launch")
 				else:
 					st.graph.replay()
 				n += 1
-				if can_stop:
-					ev = torch.cuda.Event()
-					ev.record()
-					events.append(ev)
-					if len(events) > LAG:
-						events.pop(0).synchronize()          # the replay LAG tokens back is complete: its flag is visible
-						stopped = int(st.done[0]) != 0
+				if can_stop and poll.step_complete():      # the replay LAG tokens back is complete: its flag is visible
+					stopped = int(st.done[0]) != 0
 			if can_stop:
 				# exact end: HF stops right after the token with which the last row finishes
 				torch.cuda.synchronize(self.device)
@@ -567,16 +539,7 @@ class UnifiedVoice:
 		token about to be yielded.  The yielded tensors are slots of two per-call buffers (tokens [max_new, B], latents [max_new, B, d]): like the
 		reference's fresh tensors they stay valid whatever runs on the model afterwards."""
 		c = self.cfg
-		LAG = 2
-		self._require_idle()            # (a generator body runs at its first next(): two generators may have been created, only one may run)
-		with torch.cuda.device(self.device):
-			st = self._gen_state(B, max_new, pipe_key, B, 0)
-			setup_seed(0)
-			gen = torch.cuda.default_generators[self.device.index or 0]
-			off_start = gen.get_offset()
-			st.reset(c)
-			if st.own_rng:
-				st.arm_noise(gen, 0)
+		with self._session(0, lambda: self._gen_state(B, max_new, pipe_key, B, 0), arm=(0,), streamed=True) as (st, gen, off_start):
 			hid = torch.empty((max_new, B, c.model_dim), device=self.device, dtype=torch.float32)
 			# the yielded tokens get this call's lifetime too, as the reference's fresh tensors have (stream_generator.py:1172): `st.ids` belongs to the
 			# cached generation state, which the next generation of the same shape -- streamed or not -- refills
@@ -599,21 +562,8 @@ class UnifiedVoice:
 							_lib.check(self.lib.ttk_graph_launch(st.stream_graph_exec, _lib.stream_ptr()), "ttk_graph_launch")
 						elif fast and produced >= 2:
 							# capture {decode_next into the ring; sample}: step 1 ran eagerly (warm kernels), the stream is idle of other work
-							torch.cuda.synchronize(self.device)
-							g = torch.cuda.CUDAGraph()
-							ctx = torch.cuda.graph(g, capture_error_mode="thread_local")
-							with torch.inference_mode(False):
-								ctx.__enter__()
-							try:
-								self._decode_next(st.logits)
-								st.sample(0)
-							except BaseException:
-								with torch.inference_mode(False):
-									ctx.__exit__(*__import__("sys").exc_info())
-								raise
-							with torch.inference_mode(False):
-								ctx.__exit__(None, None, None)
-							st.stream_graph, st.stream_graph_exec = g, g.raw_cuda_graph_exec()
+							st.stream_graph = self._capture_step(st)
+							st.stream_graph_exec = st.stream_graph.raw_cuda_graph_exec()
 							continue
 						else:
 							self._decode_next(st.logits)
@@ -632,25 +582,95 @@ class UnifiedVoice:
 			finally:
 				self._streaming = False
 				_lib.check(self.lib.ttk_ar_set_hidden_ring(self._h, None, None, 0, _lib.stream_ptr()), "ttk_ar_set_hidden_ring")
+				# the generator where the reference's loop leaves it: one draw per token it produced (steps sampled ahead of an early end drew nothing
+				# from torch; without the head-drawn noise they did, and are handed back)
 				if st.own_rng:
-					_lib.check(self.lib.ttk_ar_set_noise(self._h, None, None, None), "ttk_ar_set_noise")
-					# the generator where the reference's loop leaves it: one draw per token it produced (steps sampled ahead of an early end drew nothing
-					# from torch; without the head-drawn noise they did, and are handed back)
 					gen.set_offset(off_start + n_done * st.noise_step)
 				elif st.rng_step:
 					gen.set_offset(off_start + n_done * st.rng_step)
-				self._check_health()
 
 
-class _GenState:
+class _StopPoll:
+	"""The late look at a device-written end-of-generation word: the loop records an event behind every step it enqueues and waits for the one LAG
+	steps back, so the GPU always has work queued while the host reads a word that step has certainly written."""
+
+	def __init__(self):
+		self.events = []
+
+	def step_complete(self) -> bool:
+		"""call once behind each enqueued step; True when the step LAG back has completed (then its done word is visible)"""
+		ev = torch.cuda.Event()
+		ev.record()
+		self.events.append(ev)
+		if len(self.events) <= LAG:
+			return False
+		self.events.pop(0).synchronize()
+		return True
+
+
+class _NoiseState:
+	"""What a generation state owns of the multinomial noise: torch's `q.exponential_(1)` restated inside the mel-head launch (include/ttk.h:
+	ttk_ar_set_noise) -- one launch per token less.  Relied on (`own_rng`) only after a bitwise comparison with torch's own draw on this device, for the
+	very [rows, cols] tensor torch would draw; TTK_AR_OWN_RNG=0 leaves the draw to torch."""
+
+	def _init_noise(self, model: UnifiedVoice, rows, cols):
+		self.model, self.noise_rows = model, rows
+		self.rng = torch.zeros(6, dtype=torch.long, device=model.device)          # RngArgs {seed, offset0, threads, step, row0, candidates per line or 0}
+		self.own_rng = os.environ.get("TTK_AR_OWN_RNG", "1") != "0" and self._noise_matches_torch(rows, cols)
+
+	@staticmethod
+	def _signed_seed(gen):
+		"""the generator's seed as the int64 the C ABI takes"""
+		seed = gen.initial_seed()
+		return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+	def _noise_geometry(self, numel):
+		"""(threads, offset step per draw) of ATen's launch for `exponential_()` on `numel` values (ATen/native/cuda/DistributionTemplates.h:
+		distribution_nullary_kernel -- 256-thread blocks, a grid capped at the resident blocks of the device, four values per Philox call)"""
+		props = torch.cuda.get_device_properties(self.model.device)
+		grid = min(props.multi_processor_count * (props.max_threads_per_multi_processor // 256), (numel + 255) // 256)
+		threads = 256 * grid
+		return threads, ((numel - 1) // (threads * 4) + 1) * 4
+
+	def _noise_matches_torch(self, rows, cols):
+		dev = self.model.device
+		gen = torch.cuda.default_generators[dev.index or 0]
+		keep = gen.get_state()
+		try:
+			threads, step = self._noise_geometry(rows * cols)
+			seed, off = self._signed_seed(gen), gen.get_offset()
+			want = [torch.empty((rows, cols), device=dev).exponential_(1) for _ in range(2)]
+			if gen.get_offset() - off != 2 * step:
+				return False
+			got = torch.empty((rows, cols), device=dev)
+			for draw in range(2):
+				_lib.check(self.model.lib.ttk_exponential_like_torch(got.data_ptr(), got.numel(), seed, off, threads, step, draw, _lib.stream_ptr()),
+						   "ttk_exponential_like_torch")
+				if not torch.equal(got.view(torch.int32), want[draw].view(torch.int32)):
+					return False
+			self.noise_threads, self.noise_step = threads, step
+			return True
+		finally:
+			gen.set_state(keep)
+
+	def _arm(self, gen, offset, row0, per_line, q: torch.Tensor):
+		"""point the mel-head launches at q: draws numbered by the column counter `self.col`, the first one at generator offset `offset`"""
+		self.rng.copy_(torch.tensor([self._signed_seed(gen), offset, self.noise_threads, self.noise_step, row0, per_line], dtype=torch.long))
+		_lib.check(self.model.lib.ttk_ar_set_noise(self.model._h, self.rng.data_ptr(), self.col.data_ptr(), q.data_ptr()), "ttk_ar_set_noise")
+
+	def disarm_noise(self):
+		if self.own_rng:
+			_lib.check(self.model.lib.ttk_ar_set_noise(self.model._h, None, None, None), "ttk_ar_set_noise")
+
+
+class _GenState(_NoiseState):
 	"""Persistent device buffers of one generation shape, so a captured token step can be replayed across calls (and across text
 	lengths: nothing in it depends on the prefix length)."""
 
 	def __init__(self, model: UnifiedVoice, B, max_new, pipe_key, C=None, lo=0, lines=1):
 		c, dev = model.cfg, model.device
 		C = B if C is None else C
-		self.lines, self.noise_rows = lines, C                          # lines > 1: B = lines * C rows, every line draws the same [C, V] noise
-		self.model = model
+		self.lines = lines                                              # lines > 1: B = lines * C rows, every line draws the same [C, V] noise
 		self.B, self.max_new = B, max_new
 		self.pipe = LogitsPipeline(temperature=pipe_key[0], top_k=pipe_key[1], top_p=pipe_key[2], repetition_penalty=pipe_key[3],
 								   suppress_tokens=pipe_key[4], typical_mass=pipe_key[5], vocab=c.number_mel_codes, device=dev)
@@ -667,10 +687,7 @@ class _GenState:
 		self.live = torch.zeros(1, dtype=torch.int32, device=dev)        # unfinished rows, decremented on the device
 		self.done = torch.zeros(1, dtype=torch.int32).pin_memory()       # raised by the row that finishes last; polled by the host
 		self.rng_step = None                                             # generator offset consumed by one sample() call
-		# torch's `q.exponential_(1)` restated inside the mel-head launch (include/ttk.h: ttk_ar_set_noise) -- one launch per token less.
-		# Relied on only after a bitwise comparison with torch's own draw on this device, for this very shape (below).
-		self.rng = torch.zeros(6, dtype=torch.long, device=dev)          # RngArgs {seed, offset0, threads, step, row0, candidates per line or 0}
-		self.own_rng = os.environ.get("TTK_AR_OWN_RNG", "1") != "0" and self._noise_matches_torch(model, dev)
+		self._init_noise(model, C, c.number_mel_codes)
 		# input_ids as the repetition penalty sees them: the fake prefix ids are all 1 with start_mel last (unified_voice.py:647-649),
 		# i.e. the SET {1, start_mel} whatever the text length (the penalty acts once per distinct id), then the sampled tokens
 		self.history = None
@@ -705,45 +722,10 @@ class _GenState:
 		self.stream_graph = None          # the streaming generator's captured step (it also fills the hidden ring)
 		self.stream_graph_exec = None
 
-	def _noise_geometry(self, dev):
-		"""(threads, offset step per draw) of ATen's launch for `self.q.exponential_()` (ATen/native/cuda/DistributionTemplates.h:
-		distribution_nullary_kernel -- 256-thread blocks, a grid capped at the resident blocks of the device, four values per Philox call)"""
-		props = torch.cuda.get_device_properties(dev)
-		numel = self.noise_rows * self.q.shape[1]
-		grid = min(props.multi_processor_count * (props.max_threads_per_multi_processor // 256), (numel + 255) // 256)
-		threads = 256 * grid
-		return threads, ((numel - 1) // (threads * 4) + 1) * 4
-
-	def _noise_matches_torch(self, model, dev):
-		gen = torch.cuda.default_generators[dev.index or 0]
-		keep = gen.get_state()
-		try:
-			threads, step = self._noise_geometry(dev)
-			seed, off = gen.initial_seed(), gen.get_offset()
-			seed = seed - (1 << 64) if seed >= (1 << 63) else seed
-			shape = (self.noise_rows, self.q.shape[1])
-			want = [torch.empty(shape, device=dev).exponential_(1) for _ in range(2)]
-			if gen.get_offset() - off != 2 * step:
-				return False
-			got = torch.empty(shape, device=dev)
-			for draw in range(2):
-				_lib.check(model.lib.ttk_exponential_like_torch(got.data_ptr(), got.numel(), seed, off, threads, step, draw, _lib.stream_ptr()),
-						   "ttk_exponential_like_torch")
-				if not torch.equal(got.view(torch.int32), want[draw].view(torch.int32)):
-					return False
-			self.noise_threads, self.noise_step = threads, step
-			return True
-		finally:
-			gen.set_state(keep)
-
 	def arm_noise(self, gen, lo, n0=0):
 		"""point the mel-head launches of this call at q, starting from the generator's current state.  n0: id columns filled before the first draw (prompt
 		tokens): the launches number their draws by the column counter, so the first offset is moved back by n0 draws"""
-		seed = gen.initial_seed()
-		seed = seed - (1 << 64) if seed >= (1 << 63) else seed
-		self.rng.copy_(torch.tensor([seed, gen.get_offset() - n0 * self.noise_step, self.noise_threads, self.noise_step, lo, self.noise_rows if self.lines > 1 else 0], dtype=torch.long))
-		m = self.model
-		_lib.check(m.lib.ttk_ar_set_noise(m._h, self.rng.data_ptr(), self.col.data_ptr(), self.q[lo].data_ptr()), "ttk_ar_set_noise")
+		self._arm(gen, gen.get_offset() - n0 * self.noise_step, lo, self.noise_rows if self.lines > 1 else 0, self.q[lo])
 
 	def reset(self, c, prompt=None):
 		self.ids.fill_(self.stop)
@@ -781,16 +763,15 @@ class _GenState:
 		_lib.check(self.model.lib.ttk_ar_sample_next(self.model._h, _lib.C.byref(a), _lib.stream_ptr()), "ttk_ar_sample_next")
 
 
-class _BeamState:
+class _BeamState(_NoiseState):
 	"""Device state of one beam search (include/ttk.h: ttk_beam_args) and the noise arming of its flat [num_beams * V] multinomial."""
 
 	def __init__(self, model: UnifiedVoice, N, max_new, kw):
 		c, dev = model.cfg, model.device
 		V = c.number_mel_codes
-		self.model, self.N = model, N
+		self.N = N
 		self.logits = torch.empty((N, V), device=dev, dtype=torch.float32)
 		self.q = torch.empty((1, N * V), device=dev, dtype=torch.float32)      # the tensor torch.multinomial draws its noise for: [batch 1, N * V]
-		self.noise_rows = 1
 		self.col = torch.zeros(N, dtype=torch.long, device=dev)
 		self.seqs = torch.full((2, 2, N, max_new), c.stop_mel_token, dtype=torch.long, device=dev)
 		self.scores = torch.full((2, N), -1e9, dtype=torch.float32, device=dev)
@@ -802,8 +783,7 @@ class _BeamState:
 		self.tok = torch.zeros(N, dtype=torch.long, device=dev)
 		self.beam_idx = torch.arange(N, dtype=torch.long, device=dev)
 		self.done = torch.zeros(1, dtype=torch.int32).pin_memory()
-		self.rng = torch.zeros(6, dtype=torch.long, device=dev)
-		self.own_rng = os.environ.get("TTK_AR_OWN_RNG", "1") != "0" and self._noise_matches_torch(model, dev)
+		self._init_noise(model, 1, N * V)
 		suppress = tuple(kw.get("suppress_tokens") or ())
 		self.suppress_mask = None
 		if suppress:
@@ -827,16 +807,12 @@ class _BeamState:
 		a.all_done = self.done.data_ptr()
 		self.args = a
 
-	_noise_geometry = _GenState._noise_geometry
-	_noise_matches_torch = _GenState._noise_matches_torch
+	def reset(self, c, prompt=None):
+		"""(a beam state is built per call, in its start state)"""
 
 	def arm_noise(self, gen):
 		"""the mel-head launches of this search write q for their logits: N rows of V = the flat tensor, numbered by the step counter"""
-		seed = gen.initial_seed()
-		seed = seed - (1 << 64) if seed >= (1 << 63) else seed
-		self.rng.copy_(torch.tensor([seed, gen.get_offset(), self.noise_threads, self.noise_step, 0, 0], dtype=torch.long))
-		m = self.model
-		_lib.check(m.lib.ttk_ar_set_noise(m._h, self.rng.data_ptr(), self.col.data_ptr(), self.q.data_ptr()), "ttk_ar_set_noise")
+		self._arm(gen, gen.get_offset(), 0, 0, self.q)
 
 	def step(self):
 		if not self.own_rng:

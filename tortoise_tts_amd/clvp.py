@@ -29,40 +29,21 @@ class CLVPConfigC(C.Structure):
 	_fields_ = [(n, C.c_int) for n in ("dim", "heads", "depth", "inner", "num_text_tokens", "num_speech_tokens", "dtype")]
 
 
-class CLVP:
+class CLVP(_lib.Handle):
 	"""`clvp = load_model("clvp")` of the reference, scoring side only (eval mode: the random token masks of training are off)."""
 
 	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg: CLVPConfig = CLVPConfig(), dtype: str = "bf16", device: str = "cuda:0"):
 		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
+		super().__init__(device)
 		if dtype not in ("bf16", "bfloat16", "f32", "fp32", "float32"):
 			raise _lib.TTKError("CLVP runs in 'bf16' or 'f32'")
-		self.lib = _lib.load()
 		missing = [n for n in clvp_shapes(cfg) if n not in state_dict]
 		if missing:
 			raise _lib.TTKError(f"state_dict lacks {len(missing)} CLVP tensors, e.g. {missing[:3]}")
 		sd = pack_state_dict(state_dict, cfg)
 		names = [n for n in sd if not n.endswith(("to_q.weight", "to_k.weight", "to_v.weight"))]
-		views, keep = _lib.weight_views(sd, names)
 		c = CLVPConfigC(cfg.dim, cfg.heads, cfg.depth, cfg.inner, cfg.num_text_tokens, cfg.num_speech_tokens, _lib.DTYPES[dtype])
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_clvp_create(C.byref(self._h), C.byref(c), views, len(names)), "ttk_clvp_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_clvp_destroy(h)
-			self._h = None
-
-	def eval(self):
-		return self
-
-	def to(self, *a, **k):
-		return self
+		self._create("clvp", c, sd, names)
 
 	@torch.inference_mode()
 	def forward(self, text: torch.Tensor, speech_tokens: torch.Tensor, return_loss: bool = False) -> torch.Tensor:

@@ -4,7 +4,6 @@ both over `ttk_cond_*`.  One-off per voice: the results are the `cond_latent [b,
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Mapping
 
 import torch
@@ -27,31 +26,11 @@ def _pack_blocks(sd: Mapping[str, torch.Tensor], src: str, first: int, n: int, h
 	return out
 
 
-class _CondEncoder:
+class _CondEncoder(_lib.Handle):
 	def __init__(self, packed: Dict[str, torch.Tensor], cfgc: _lib.CondConfigC, device: str):
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
-		self.lib = _lib.load()
+		super().__init__(device)
 		self.in_channels, self.channels = cfgc.in_channels, cfgc.channels
-		names = list(packed.keys())
-		views, keep = _lib.weight_views(packed, names)
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_cond_create(C.byref(self._h), C.byref(cfgc), views, len(names)), "ttk_cond_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_cond_destroy(h)
-			self._h = None
-
-	def eval(self):
-		return self
-
-	def to(self, *a, **k):
-		return self
+		self._create("cond", cfgc, packed, list(packed.keys()))
 
 	@torch.inference_mode()
 	def forward(self, mel: torch.Tensor) -> torch.Tensor:

@@ -81,45 +81,25 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: DiffusionConfig) -> Dict[s
 
 
 # ------------------------------------------------------------------------------------------------ the network
-class DiffusionTTS:
+class DiffusionTTS(_lib.Handle):
 	def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: DiffusionConfig = DiffusionConfig(), dtype: str = "bf16",
 				 device: str = "cuda:0"):
 		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
-		self.lib = _lib.load()
+		super().__init__(device)
 		self.dtype = _lib.DTYPES[dtype]
 		self.in_channels, self.out_channels, self.model_channels = cfg.in_channels, cfg.out_channels, cfg.model_channels
 		missing = [n for n in diffusion_shapes(cfg) if n not in state_dict]
 		if missing:
 			raise _lib.TTKError(f"state_dict lacks {len(missing)} hot-path tensors, e.g. {missing[:3]}")
 		packed = pack_state_dict(state_dict, cfg)
-		names = list(packed.keys())
-		views, keep = _lib.weight_views(packed, names)
 		c = _lib.DiffConfigC(cfg.model_channels, cfg.num_layers, cfg.in_channels, cfg.in_latent_channels, cfg.out_channels,
 							 cfg.num_heads, self.dtype)
-		self._h = _lib.C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_diff_create(_lib.C.byref(self._h), _lib.C.byref(c), views, len(names)), "ttk_diff_create")
-		del keep
+		self._create("diff", c, packed, list(packed.keys()))
 		self._idx_cache: Dict[tuple, torch.Tensor] = {}
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_diff_destroy(h)
-			self._h = None
 
 	def parameters(self):
 		"""`next(model.parameters()).device` is queried by the sampler (diffusion.py:788)."""
 		yield torch.empty(0, device=self.device)
-
-	def to(self, *a, **k):
-		return self
-
-	def eval(self):
-		return self
 
 	def timestep_independent(self, aligned_conditioning, conditioning_latent, expected_seq_len, return_code_pred=False):
 		"""diffusion.py:1487-1510, latent conditioning: [b, M, C_latent] f32, [b, 2C] -> [b, C, T] f32."""

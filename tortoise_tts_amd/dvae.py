@@ -39,38 +39,19 @@ def check_config(cfg: DVAEConfig) -> None:
 			raise NotImplementedError("DiscreteVAE: " + why)
 
 
-class DiscreteVAE:
+class DiscreteVAE(_lib.Handle):
 	"""`DiscreteVAE()` of the reference with its `state_dict` ("encoder.N...", "decoder.N...", "codebook.embed"), inference side."""
 
 	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg: DVAEConfig = DVAE_FULL, dtype: str = "f32", device: str = "cuda:0"):
 		check_config(cfg)
 		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
+		super().__init__(device)
 		if _lib.DTYPES.get(dtype) not in (_lib.TTK_F32, _lib.TTK_BF16, _lib.TTK_F16):
 			raise _lib.TTKError("the DiscreteVAE runs in 'f32', 'bf16' or 'f16'")
-		self.lib = _lib.load()
 		self.num_tokens, self.num_layers, self.positional_dims = cfg.num_tokens, cfg.num_layers, cfg.positional_dims
 		c = DVAEConfigC(cfg.channels, cfg.hidden_dim, cfg.codebook_dim, cfg.num_tokens, cfg.num_resnet_blocks, _lib.DTYPES[dtype])
 		names = [n for n in dvae_shapes(cfg) if n in state_dict]      # ttk_dvae_create names a missing tensor
-		views, keep = _lib.weight_views(state_dict, names)
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_dvae_create(C.byref(self._h), C.byref(c), views, len(names)), "ttk_dvae_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_dvae_destroy(h)
-			self._h = None
-
-	def eval(self):
-		return self
-
-	def to(self, *a, **k):
-		return self
+		self._create("dvae", c, state_dict, names)
 
 	def forward(self, *a, **k):
 		raise NotImplementedError("DiscreteVAE.forward is the training pass (reconstruction and commitment losses, EMA codebook update); "

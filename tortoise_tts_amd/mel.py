@@ -107,9 +107,7 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, device: str = "cu
 	[..., n] -> [..., ceil(new * n / orig)] f32."""
 	if int(orig_freq) == int(new_freq):
 		return wav
-	dev = torch.device(device)
-	if dev.type != "cuda":
-		raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
+	dev = _lib.cuda_device(device)
 	kernels, width, orig, new = sinc_resample_kernel(orig_freq, new_freq)
 	shape = wav.shape
 	x = wav.reshape(-1, shape[-1]).to(dev, torch.float32).contiguous()
@@ -133,37 +131,16 @@ def pad_or_truncate(t: torch.Tensor, length: int) -> torch.Tensor:
 	return t[..., :length]
 
 
-class _MelFrontEnd:
+class _MelFrontEnd(_lib.Handle):
 	def __init__(self, n_fft: int, hop: int, n_mels: int, power: int, clip: bool, mel_matrix: np.ndarray, mel_norms: Optional[torch.Tensor], device: str):
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
-		self.lib = _lib.load()
+		super().__init__(device)
 		self.n_fft, self.hop_length, self.n_mel_channels = n_fft, hop, n_mels
 		sd = {"basis": torch.from_numpy(dft_basis(n_fft, hann_periodic(n_fft))).float(), "mel_basis": torch.from_numpy(mel_matrix).float()}
 		if mel_norms is not None:
 			if mel_norms.numel() != n_mels:
 				raise _lib.TTKError(f"mel_norms has {mel_norms.numel()} entries, expected {n_mels}")
 			sd["mel_norms"] = mel_norms.detach().float().reshape(n_mels).cpu()
-		names = list(sd.keys())
-		views, keep = _lib.weight_views(sd, names)
-		c = MelConfigC(n_fft, hop, n_mels, power, int(clip), int(mel_norms is not None))
-		self._h = C.c_void_p()
-		with torch.cuda.device(self.device):
-			_lib.check(self.lib.ttk_mel_create(C.byref(self._h), C.byref(c), views, len(names)), "ttk_mel_create")
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			self.lib.ttk_mel_destroy(h)
-			self._h = None
-
-	def to(self, *a, **k):
-		return self
-
-	def eval(self):
-		return self
+		self._create("mel", MelConfigC(n_fft, hop, n_mels, power, int(clip), int(mel_norms is not None)), sd, list(sd.keys()))
 
 	@torch.inference_mode()
 	def _run(self, wav: torch.Tensor) -> torch.Tensor:

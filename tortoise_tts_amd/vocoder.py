@@ -65,9 +65,9 @@ class VocConfigC(C.Structure):
 				("dtype", C.c_int)]
 
 
-class Vocoder:
+class Vocoder(_lib.Handle):
 	"""What the three vocoder wrappers (BigVGAN here, univnet.UnivNet, hifigan.HiFiGAN) share: the handle `ttk_<abi>_create` makes from the
-	weight-norm-folded tensors `shapes(cfg)` names, and its lifetime.  The subclass says which library entry points (`_abi`), how its
+	weight-norm-folded tensors `shapes(cfg)` names.  The subclass says which library entry points (`_abi`), how its
 	config becomes the C struct (`_config_c`) and which tensors it takes (`_shapes`).  `_lacks` set: a missing tensor raises here, as
 	"state_dict lacks N <_lacks> tensors"; None: the tensors present are passed on and `ttk_<abi>_create` names the missing one."""
 	_abi: str
@@ -77,12 +77,9 @@ class Vocoder:
 
 	def __init__(self, state_dict: Mapping[str, torch.Tensor], cfg, dtype: str, device: str, extra: Optional[Mapping[str, torch.Tensor]] = None):
 		self.cfg = cfg
-		self.device = torch.device(device)
-		if self.device.type != "cuda":
-			raise _lib.TTKError("tortoise_tts_amd runs on an MI355X only (device must be cuda:N)")
+		super().__init__(device)
 		if dtype not in ("bf16", "bfloat16", "f32", "fp32", "float32"):
 			raise _lib.TTKError("the vocoder runs in 'bf16' or 'f32'")
-		self.lib = _lib.load()
 		c = self._config_c(cfg, dtype)
 		sd = fold_weight_norm(state_dict)
 		names = list(self._shapes(cfg).keys())
@@ -94,24 +91,7 @@ class Vocoder:
 		for n, t in (extra or {}).items():       # host-built constants the handle takes like weights
 			sd[n] = t
 			names.append(n)
-		views, keep = _lib.weight_views(sd, names)
-		self._h = C.c_void_p()
-		create = f"ttk_{self._abi}_create"
-		with torch.cuda.device(self.device):
-			_lib.check(getattr(self.lib, create)(C.byref(self._h), C.byref(c), views, len(names)), create)
-		del keep
-
-	def __del__(self):
-		h = getattr(self, "_h", None)
-		if h:
-			getattr(self.lib, f"ttk_{self._abi}_destroy")(h)
-			self._h = None
-
-	def eval(self, inference: bool = False):
-		return self
-
-	def to(self, *a, **k):
-		return self
+		self._create(self._abi, c, sd, names)
 
 
 class BigVGAN(Vocoder):
