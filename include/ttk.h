@@ -492,6 +492,42 @@ typedef struct {
 } ttk_gemm_desc;
 int ttk_gemm(int dtype, const ttk_gemm_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ the attention kernels (head dim 64) on caller-provided operands
+ * No reference counterpart: exposed so every launch form of csrc/attn.hip can be tested against a float64 softmax(q k^T) v of the same operands.
+ * ttk_attn_fwd: out[b][q][h*64 + d] = sum_k softmax_k(scale * q.k + bias[h][clamp(k - q, -64, 64) + 64]) v_k over keys k < tlen[b] (k <= q when causal),
+ *   for queries q < tlen[b] of sequence b, which occupies rows [b*T, b*T + T) of qkv [nb*T][ld] and of out [nb*T][ldo]; element (h, d) of q / k / v is
+ *   column q_off / k_off / v_off + h * head_stride + d.  dtype: TTK_F32, TTK_BF16 or TTK_F16 (qkv and out; out_f8, bf16 only: out is fp8-e4m3 bytes).
+ *   tlen: null (every sequence has T rows) or device int [nb], each 1..T.  bias: null or device f32 [H][129]; not together with causal.
+ *   form: 0 = the launcher's own choice from nb x H x T (what every product launch gets), 1 = 64-query blocks, 2 = 128-query blocks,
+ *   3 = 8 waves x 16 queries (non-causal), 4 = balanced (non-causal, no tlen, 256 % (nb*H) == 0, at most 9 16-query tiles per workgroup).
+ * ttk_attn_decode: one query per (candidate, head) over the cache rows [start, min(d_pos[0] + 1, max_ctx)): qbuf f32 [B][H*64] (already scaled),
+ *   kcache / vcache dtype [B][H][max_ctx][64], d_pos device int[2] = {last valid row, rows of the shared prefix}, out dtype [B][H*64] or (out_frag) the
+ *   skinny GEMV's fragment order [ceil(B / 16)][H*2][64][8].  row_info: null or device int [B][2] = {start, first candidate of b's line}.
+ *   shared_rows != 0: rows [start, d_pos[1]) are read from the first candidate's slice (candidate 0 without row_info).
+ *   variant: 0 = default, 1 = 4 waves x 4 groups, 2 = 8 x 6 (1 and 2: bf16 only).  pos_line != 0: the two words travel through a slot of the position
+ *   line (copied there on `stream`; refused when all 8 slots are taken).
+ * Both return TTK_E_ARG with a message when a precondition the kernels rely on fails. */
+typedef struct {
+	const void* qkv; int64_t ld;
+	int q_off, k_off, v_off, head_stride;
+	void* out; int64_t ldo;
+	int out_f8;
+	int nb, T, H, causal;
+	const int* tlen;
+	const float* bias;
+	float scale;
+	int form;
+} ttk_attn_desc;
+int ttk_attn_fwd(int dtype, const ttk_attn_desc* d, void* stream);
+typedef struct {
+	const float* qbuf; const void* kcache; const void* vcache; const int* d_pos;
+	int B, H, max_ctx, out_frag;
+	void* out;
+	const int* row_info;
+	int shared_rows, variant, pos_line;
+} ttk_attn_decode_desc;
+int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ mel front-ends of the conditioning path
  * TorchMelSpectrogram (models/arch_utils.py:361-395) and TacotronSTFT (:662-700 over STFT :560-623) as one handle type: reflect-padded
  * frames x "basis" [2 * (n_fft/2 + 1), n_fft] (windowed DFT, Re rows then Im rows) -> |.|^power -> x "mel_basis" [n_mels, n_fft/2 + 1] ->

@@ -79,6 +79,20 @@ class GemmDesc(C.Structure):
 				("gn_T", C.c_int), ("gn_part", C.c_void_p)]
 
 
+class AttnDesc(C.Structure):
+	"""ttk_attn_desc (include/ttk.h)"""
+	_fields_ = [("qkv", C.c_void_p), ("ld", C.c_int64), ("q_off", C.c_int), ("k_off", C.c_int), ("v_off", C.c_int), ("head_stride", C.c_int),
+				("out", C.c_void_p), ("ldo", C.c_int64), ("out_f8", C.c_int), ("nb", C.c_int), ("T", C.c_int), ("H", C.c_int), ("causal", C.c_int),
+				("tlen", C.c_void_p), ("bias", C.c_void_p), ("scale", C.c_float), ("form", C.c_int)]
+
+
+class AttnDecodeDesc(C.Structure):
+	"""ttk_attn_decode_desc (include/ttk.h)"""
+	_fields_ = [("qbuf", C.c_void_p), ("kcache", C.c_void_p), ("vcache", C.c_void_p), ("d_pos", C.c_void_p),
+				("B", C.c_int), ("H", C.c_int), ("max_ctx", C.c_int), ("out_frag", C.c_int), ("out", C.c_void_p), ("row_info", C.c_void_p),
+				("shared_rows", C.c_int), ("variant", C.c_int), ("pos_line", C.c_int)]
+
+
 class ProfResult(C.Structure):
 	_fields_ = [("ms", C.c_double), ("launches", C.c_int64), ("work", C.c_double)]
 
@@ -135,6 +149,8 @@ SYMBOLS = {
 	"ttk_resample_fir": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _I, _P]),
 	"ttk_gemm_nt": (_I, [_I, _P, _P, _I, _I, _I, C.c_float, _P, _P, _P]),
 	"ttk_gemm": (_I, [_I, C.POINTER(GemmDesc), _P]),
+	"ttk_attn_fwd": (_I, [_I, C.POINTER(AttnDesc), _P]),
+	"ttk_attn_decode": (_I, [_I, C.POINTER(AttnDecodeDesc), _P]),
 	"ttk_fp8_round_weights": (_I, [_P, _L, C.POINTER(C.c_float), _P]),
 	"ttk_sample_step": (_I, [_P, _L, _I, _I, _P, _L, _P, C.c_float, _L, _P, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P]),
 	"ttk_ar_decode_geometry": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),

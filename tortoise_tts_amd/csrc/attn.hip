@@ -409,7 +409,34 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void k_attn_fwd(AttnPar
 }
 
 template <typename T>
-static void launch_attn_fwd_t(const AttnParams& p, hipStream_t s) {
+static void launch_attn_fwd_t(const AttnParams& p, hipStream_t s, int form) {
+	auto launch_w8 = [&] {
+		dim3 grid((p.T + 127) / 128, p.H, p.nb);
+		if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1, 8>), grid, dim3(512), 0, s, p);
+		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1, 8>), grid, dim3(512), 0, s, p);
+	};
+	auto launch_bal = [&](int G) {
+		dim3 grid(G, p.H, p.nb);
+		if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1, 9>), grid, dim3(576), 0, s, p);
+		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1, 9>), grid, dim3(576), 0, s, p);
+	};
+	auto launch_blocks = [&](bool big) {
+		if (big) {
+			dim3 grid((p.T + 127) / 128, p.H, p.nb);
+			if (p.causal) hipLaunchKernelGGL((k_attn_fwd<T, true, false, 2>), grid, dim3(256), 0, s, p);
+			else if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 2>), grid, dim3(256), 0, s, p);
+			else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 2>), grid, dim3(256), 0, s, p);
+		} else {
+			dim3 grid((p.T + 63) / 64, p.H, p.nb);
+			if (p.causal) hipLaunchKernelGGL((k_attn_fwd<T, true, false, 1>), grid, dim3(256), 0, s, p);
+			else if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1>), grid, dim3(256), 0, s, p);
+			else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1>), grid, dim3(256), 0, s, p);
+		}
+	};
+	// an explicit form (ttk_attn_fwd: kernel-level tests) overrides the knobs below; the caller has asked attn_fwd_form_refusal first
+	if (form == 1 || form == 2) return launch_blocks(form == 2);
+	if (form == 3) return launch_w8();
+	if (form == 4) return launch_bal(256 / (p.nb * p.H));
 	static const int force_qt = [] { const char* e = getenv("TTK_ATTN_QT"); return e ? atoi(e) : 0; }();   // tuning knob
 	const bool big = force_qt ? force_qt == 2 : (int64_t)((p.T + 127) / 128) * p.H * p.nb >= 512;   // enough 128-query blocks for 2 waves per SIMD
 	// 128-query blocks as 8 waves x 16 queries once they cover most of the chip (TTK_ATTN_W8=0: off); non-causal only: a causal block of 8 waves
@@ -417,40 +444,33 @@ static void launch_attn_fwd_t(const AttnParams& p, hipStream_t s) {
 	// (measured at T = 1088: 141.3 vs 139.9 ms per DDIM loop -- 288 such blocks on 256 CUs leave 32 CUs with two, the same quantisation that
 	// costs the 64-query form 544 blocks on 768 slots; kept as a knob, off by default)
 	static const int w8 = [] { const char* e = getenv("TTK_ATTN_W8"); return e ? atoi(e) : 0; }();
-	if (w8 && !big && !force_qt && !p.causal && (int64_t)((p.T + 127) / 128) * p.H * p.nb >= 192) {
-		dim3 grid((p.T + 127) / 128, p.H, p.nb);
-		if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1, 8>), grid, dim3(512), 0, s, p);
-		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1, 8>), grid, dim3(512), 0, s, p);
-		return;
-	}
+	if (w8 && !big && !force_qt && !p.causal && (int64_t)((p.T + 127) / 128) * p.H * p.nb >= 192) return launch_w8();
 	// balanced form: batch x heads x G workgroups == 256 (the CUs), each with 8..9 tiles
 	static const int bal = [] { const char* e = getenv("TTK_ATTN_BAL"); return e ? atoi(e) : 1; }();
 	if (bal && !force_qt && !p.causal && !p.tlen && p.nb * p.H <= 256 && 256 % (p.nb * p.H) == 0) {
 		const int G = 256 / (p.nb * p.H), tiles = (p.T + 15) / 16;
-		if ((tiles + G - 1) / G <= 9 && tiles / G >= 6) {
-			dim3 grid(G, p.H, p.nb);
-			if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1, 9>), grid, dim3(576), 0, s, p);
-			else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1, 9>), grid, dim3(576), 0, s, p);
-			return;
-		}
+		if ((tiles + G - 1) / G <= 9 && tiles / G >= 6) return launch_bal(G);
 	}
-	if (big) {
-		dim3 grid((p.T + 127) / 128, p.H, p.nb);
-		if (p.causal) hipLaunchKernelGGL((k_attn_fwd<T, true, false, 2>), grid, dim3(256), 0, s, p);
-		else if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 2>), grid, dim3(256), 0, s, p);
-		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 2>), grid, dim3(256), 0, s, p);
-	} else {
-		dim3 grid((p.T + 63) / 64, p.H, p.nb);
-		if (p.causal) hipLaunchKernelGGL((k_attn_fwd<T, true, false, 1>), grid, dim3(256), 0, s, p);
-		else if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1>), grid, dim3(256), 0, s, p);
-		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1>), grid, dim3(256), 0, s, p);
-	}
+	launch_blocks(big);
 }
-void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s) {
+// what an explicit form needs for its result to be right (null: nothing stands against it).  The launcher's own choice (form 0) tests the same conditions
+// itself, plus those that only decide which form is faster.
+const char* attn_fwd_form_refusal(const AttnParams& p, int form) {
+	if (form < 0 || form > 4) return "form must be 0 (the launcher's choice), 1 (64-query blocks), 2 (128-query blocks), 3 (8 waves x 16 queries) or 4 (balanced)";
+	if (form == 3 && p.causal) return "form 3 (8 waves x 16 queries) has no causal kernel";
+	if (form == 4) {
+		if (p.causal || p.tlen) return "form 4 (balanced) is non-causal and takes no tlen (a workgroup's tile share is computed from T)";
+		if ((int64_t)p.nb * p.H > 256 || 256 % (p.nb * p.H) != 0) return "form 4 (balanced) needs 256 % (nb * H) == 0";
+		const int G = 256 / (p.nb * p.H), tiles = (p.T + 15) / 16;
+		if ((tiles + G - 1) / G > 9) return "form 4 (balanced) has 9 waves: at most 9 16-query tiles per workgroup, ceil(ceil(T / 16) / (256 / (nb * H))) <= 9";
+	}
+	return nullptr;
+}
+void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s, int form) {
 	ProfScope prof(PROF_ATTN_FWD, 4.0 * p.nb * p.H * (double)p.T * p.T * HD * (p.causal ? 0.5 : 1.0), s);
-	if (dt == DT_BF16) launch_attn_fwd_t<bf16>(p, s);
-	else if (dt == DT_F16) launch_attn_fwd_t<f16>(p, s);
-	else launch_attn_fwd_t<float>(p, s);
+	if (dt == DT_BF16) launch_attn_fwd_t<bf16>(p, s, form);
+	else if (dt == DT_F16) launch_attn_fwd_t<f16>(p, s, form);
+	else launch_attn_fwd_t<float>(p, s, form);
 }
 
 // ------------------------------------------------------------------------------------------------ decode
@@ -633,10 +653,11 @@ static void launch_attn_decode_t(const AttnDecodeParams& p, hipStream_t s, hipEv
 	else if (slot) hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN, false, true>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p);
 	else hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p);
 }
-void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s) {
+void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s, int force_variant) {
 	hipEvent_t ea = nullptr, eb = nullptr;      // kernel start / stop timestamps when profiling (prof_pair)
 	if (g_prof_on) prof_pair(PROF_ATTN_DECODE, 2.0 * p.B * p.H * (double)p.ctx_hint * HD * dtype_size(dt), &ea, &eb);
-	static const int variant = [] { const char* e = getenv("TTK_ATTN_DECODE"); return e ? atoi(e) : 0; }();   // tuning knob: 0 = default
+	static const int env_variant = [] { const char* e = getenv("TTK_ATTN_DECODE"); return e ? atoi(e) : 0; }();   // tuning knob: 0 = default
+	const int variant = force_variant ? force_variant : env_variant;      // an explicit variant (ttk_attn_decode: kernel-level tests) overrides the knob
 	if (dt == DT_BF16) {
 		// 250-token AR loop, B=16, one box: 4 waves x 4 groups (first version, 128 keys per round trip) 261.9 ms; 8 x 6 257.5 ms;
 		// 16 x 3 256.8 ms

@@ -239,3 +239,67 @@ extern "C" int ttk_gemm(int dtype, const ttk_gemm_desc* d, void* stream) {
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
+
+// Every launch form of the attention kernels on caller-provided operands (include/ttk.h): the descriptors are AttnParams / AttnDecodeParams without the prefetch and
+// diagnostic fields, plus the host-only form / variant.  With form = 0 / variant = 0 the launchers choose exactly as for the handles' launches.
+static_assert(sizeof(ttk_attn_desc) == 96 && sizeof(ttk_attn_decode_desc) == 80, "ttk_attn_desc / ttk_attn_decode_desc layout (tortoise_tts_amd/_lib.py mirrors it)");
+extern "C" int ttk_attn_fwd(int dtype, const ttk_attn_desc* d, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_attn_fwd: null descriptor");
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16 || dtype == TTK_F16, TTK_E_ARG, "ttk_attn_fwd: dtype must be TTK_F32, TTK_BF16 or TTK_F16, got %d", dtype);
+	const int epc = dtype == TTK_F32 ? 4 : 8;      // elements per 16 bytes: every fragment and staging chunk is read as whole 16-byte words
+	auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+	TTK_REQUIRE(d->qkv && d->out, TTK_E_ARG, "ttk_attn_fwd: null qkv or out");
+	TTK_REQUIRE(d->T >= 1 && d->nb >= 1 && d->H >= 1, TTK_E_ARG, "ttk_attn_fwd: need T >= 1, nb >= 1, H >= 1 (got T=%d nb=%d H=%d)", d->T, d->nb, d->H);
+	TTK_REQUIRE(al16(d->qkv) && d->ld > 0 && d->ld % epc == 0 && d->q_off >= 0 && d->k_off >= 0 && d->v_off >= 0 && d->head_stride >= 0 &&
+				d->q_off % epc == 0 && d->k_off % epc == 0 && d->v_off % epc == 0 && d->head_stride % epc == 0, TTK_E_ARG,
+				"ttk_attn_fwd: qkv must be 16-byte aligned, ld, q_off, k_off, v_off and head_stride multiples of %d elements (ld=%lld q_off=%d k_off=%d v_off=%d head_stride=%d)",
+				epc, (long long)d->ld, d->q_off, d->k_off, d->v_off, d->head_stride);
+	const int64_t last_col = (int64_t)(d->H - 1) * d->head_stride + 64;
+	TTK_REQUIRE(d->q_off + last_col <= d->ld && d->k_off + last_col <= d->ld && d->v_off + last_col <= d->ld, TTK_E_ARG, "ttk_attn_fwd: a head's 64 columns end past ld");
+	TTK_REQUIRE(d->ldo >= (int64_t)64 * d->H, TTK_E_ARG, "ttk_attn_fwd: ldo < 64 H");
+	TTK_REQUIRE(!d->out_f8 || dtype == TTK_BF16, TTK_E_ARG, "ttk_attn_fwd: out_f8 only with TTK_BF16");
+	TTK_REQUIRE(d->out_f8 ? (((uintptr_t)d->out & 3) == 0 && d->ldo % 4 == 0) : ((uintptr_t)d->out & (dtype == TTK_F32 ? 3 : 1)) == 0, TTK_E_ARG,
+				"ttk_attn_fwd: out is misaligned (out_f8 stores 4 bytes at a time: out and ldo multiples of 4)");
+	TTK_REQUIRE(!(d->causal && d->bias), TTK_E_ARG, "ttk_attn_fwd: causal together with bias: there is no such kernel (the launcher would drop the bias)");
+	AttnParams a = {};
+	a.qkv = d->qkv; a.ld = d->ld; a.q_off = d->q_off; a.k_off = d->k_off; a.v_off = d->v_off; a.head_stride = d->head_stride;
+	a.out = d->out; a.ldo = d->ldo; a.out_f8 = d->out_f8; a.nb = d->nb; a.T = d->T; a.H = d->H; a.causal = d->causal ? 1 : 0;
+	a.tlen = d->tlen; a.bias = d->bias; a.scale = d->scale;
+	const char* why = attn_fwd_form_refusal(a, d->form);
+	TTK_REQUIRE(!why, TTK_E_ARG, "ttk_attn_fwd: %s (form=%d causal=%d tlen=%s nb=%d H=%d T=%d)", why, d->form, a.causal, a.tlen ? "set" : "null", a.nb, a.H, a.T);
+	launch_attn_fwd(dtype, a, (hipStream_t)stream, d->form);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+extern "C" int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_attn_decode: null descriptor");
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16 || dtype == TTK_F16, TTK_E_ARG, "ttk_attn_decode: dtype must be TTK_F32, TTK_BF16 or TTK_F16, got %d", dtype);
+	TTK_REQUIRE(d->qbuf && d->kcache && d->vcache && d->d_pos && d->out, TTK_E_ARG, "ttk_attn_decode: null qbuf, kcache, vcache, d_pos or out");
+	TTK_REQUIRE(d->B >= 1 && d->H >= 1 && d->max_ctx >= 1, TTK_E_ARG, "ttk_attn_decode: need B >= 1, H >= 1, max_ctx >= 1 (got B=%d H=%d max_ctx=%d)", d->B, d->H, d->max_ctx);
+	TTK_REQUIRE(d->B <= 65535, TTK_E_ARG, "ttk_attn_decode: B > 65535 (the grid's y dimension)");
+	TTK_REQUIRE(((uintptr_t)d->qbuf & 15) == 0 && ((uintptr_t)d->kcache & 15) == 0 && ((uintptr_t)d->vcache & 15) == 0 && ((uintptr_t)d->d_pos & 7) == 0 &&
+				((uintptr_t)d->out & (dtype == TTK_F32 ? 3 : 1)) == 0 && ((uintptr_t)d->row_info & 7) == 0, TTK_E_ARG,
+				"ttk_attn_decode: qbuf, kcache and vcache must be 16-byte aligned, d_pos and row_info 8-byte aligned (both words are one request)");
+	TTK_REQUIRE(!d->out_frag || (64 * d->H) % 32 == 0, TTK_E_ARG, "ttk_attn_decode: out_frag needs 64 H %% 32 == 0");
+	TTK_REQUIRE(d->variant >= 0 && d->variant <= 2, TTK_E_ARG, "ttk_attn_decode: variant must be 0 (default), 1 (4 x 4) or 2 (8 x 6), got %d", d->variant);
+	TTK_REQUIRE(d->variant == 0 || dtype == TTK_BF16, TTK_E_ARG, "ttk_attn_decode: variants 1 and 2 are bf16 only");
+	AttnDecodeParams a = {};
+	a.qbuf = d->qbuf; a.kcache = d->kcache; a.vcache = d->vcache; a.d_pos = d->d_pos; a.B = d->B; a.H = d->H; a.max_ctx = d->max_ctx; a.ctx_hint = d->max_ctx;
+	a.out = d->out; a.out_frag = d->out_frag ? 1 : 0; a.row_info = (const int2*)d->row_info; a.shared_rows = d->shared_rows ? 1 : 0;
+	int slot = -1;
+	if (d->pos_line) {      // the two words through a slot of the position line, as a handle that owns one keeps them
+		int* words = nullptr;
+		slot = attn_pos_slot_acquire(&words);
+		TTK_REQUIRE(slot >= 0, TTK_E_ARG, "ttk_attn_decode: pos_line: no free slot in the position line (8 decode handles hold them)");
+		const hipError_t e = hipMemcpyAsync(words, d->d_pos, 2 * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+		if (e != hipSuccess) { attn_pos_slot_release(slot); set_error("ttk_attn_decode: copy into the position line failed: %s", hipGetErrorString(e)); return TTK_E_HIP; }
+		a.d_pos = words; a.pos_slot_p1 = slot + 1;
+	}
+	launch_attn_decode(dtype, a, (hipStream_t)stream, d->variant);
+	if (slot >= 0) attn_pos_slot_release(slot);      // enqueued: a later user of the slot writes it behind this launch on the same stream
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}

@@ -207,7 +207,10 @@ struct AttnParams {
 	unsigned long long* stamps;   // diagnostic build only
 #endif
 };
-void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s);
+// form (host only, never a kernel argument): 0 = the launcher's choice from nb x H x T and the TTK_ATTN_* knobs; 1 = 64-query blocks, 2 = 128-query blocks,
+// 3 = 8 waves x 16 queries, 4 = balanced -- an explicit form overrides the knobs and is legal only where attn_fwd_form_refusal returns null
+void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s, int form = 0);
+const char* attn_fwd_form_refusal(const AttnParams& p, int form);
 
 struct AttnDecodeParams {
 	const float* qbuf;        // f32 [B][H*64], already scaled
@@ -229,7 +232,8 @@ struct AttnDecodeParams {
 	unsigned long long* stamps;   // diagnostic build only
 #endif
 };
-void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s);
+// variant (host only): 0 = the default (waves, unroll) shape or what TTK_ATTN_DECODE asks for; 1 = 4 x 4, 2 = 8 x 6 (both bf16 only)
+void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s, int variant = 0);
 // the position line (csrc/attn.hip): up to 8 decode handles keep {valid cache rows, shared-prefix rows} in one 64-byte line of the code object.  acquire returns the slot
 // (and the device address of its two words), or -1 when all are taken -- the handle then keeps the words in its own allocation and the kernel reads them through d_pos
 int attn_pos_slot_acquire(int** words_out);
