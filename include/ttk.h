@@ -121,8 +121,7 @@ int ttk_ar_health(ttk_ar* h, int* flags_out, void* stream);
  * advances (the `col` of ttk_sample_args: tokens sampled so far), so step n's rows land in slot n of a [slots, B, D] buffer although the
  * captured launch arguments never change -- what the streaming generator (unified_voice.py:670-679, stream_generator.py:1172) yields next to
  * token n.  The base is uploaded to a device word on `stream` and read from there by the launches, so a token step captured during one
- * generation writes into the buffer of whichever generation replays it.  Pass base = NULL to switch it off.  Needs the default decode form
- * (TTK_AR_HEAD_SPLIT=1, TTK_AR_SPLIT=1).                                                                                                 */
+ * generation writes into the buffer of whichever generation replays it.  Pass base = NULL to switch it off.                            */
 int ttk_ar_set_hidden_ring(ttk_ar* h, float* base, const int64_t* index, int64_t stride, void* stream);
 
 /* One sampled token per candidate, the body of HF `_sample` that stream_generator.py drives (warpers :56-101; HF:generation/

@@ -1,5 +1,5 @@
 """Diagnostic: wall time of the 250-token AR loop (configs[1] shape), repeated, for A/B runs on ONE box:
-   python tests/diag/ar_ab.py [reps]          (env TTK_LIB / TTK_AR_NARROW / ... select the variant)"""
+   python tests/diag/ar_ab.py [reps]          (env TTK_LIB / TTK_AR_LEAN / TTK_AR_LNFOLD / ... select the variant)"""
 import os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -4,7 +4,7 @@
 // timestamps of EVERY wave of the five kernels of one layer in the middle of the chain: the boundary between two kernels (last wave end ->
 // first wave start of the next), the start spread of a launch, and the phases inside the waves.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DTTK_STAMPS=2 -I tortoise_tts_amd/csrc tests/diag/ar_chain.cpp -o tests/diag/ar_chain.bin
-//   tests/diag/ar_chain.bin [ctx=190] [replays=40]          env: CH_WV_QKV / CH_WV_PROJ / CH_WV_FC / CH_WV_PROJ2 (waves), CH_NARROW, CH_LAYERS
+//   tests/diag/ar_chain.bin [ctx=190] [replays=40]          env: CH_WV_QKV / CH_WV_PROJ / CH_WV_FC / CH_WV_PROJ2 (waves of k_skinny, CH_LEAN=0), CH_LAYERS
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,7 +41,6 @@ int main(int argc, char** argv) {
 	const int d = 1024, B = 16, H = 16, max_ctx = 336;
 	const int NL = envi("CH_LAYERS", 30), SL = NL / 2;
 	const int wv_qkv = envi("CH_WV_QKV", 4), wv_proj = envi("CH_WV_PROJ", 4), wv_fc = envi("CH_WV_FC", 4), wv_proj2 = envi("CH_WV_PROJ2", 8);
-	const int narrow = envi("CH_NARROW", 4);
 	const int lean = envi("CH_LEAN", 1);      // 1: the specialised launches of gemv.hip; 0: k_skinny
 	struct Layer { void *wqkv, *wproj, *wfc, *wproj2, *kc, *vc; };
 	std::vector<Layer> L(NL);
@@ -69,7 +68,7 @@ int main(int argc, char** argv) {
 
 	auto layer = [&](int i, unsigned long long* st) {
 		SkinnyParams p = {};
-		p.Wp = L[i].wqkv; p.N = 3 * d; p.K = d; p.M = B; p.bias = bias; p.g1 = bias; p.a = xfrag; p.lda = d; p.a_frag = 1;
+		p.Wp = L[i].wqkv; p.N = 3 * d; p.K = d; p.M = B; p.bias = bias; p.g1 = bias; p.a = xfrag;
 		p.mode = SK_QKV; p.qbuf = qbuf; p.kcache = L[i].kc; p.vcache = L[i].vc; p.d_pos = dpos; p.max_ctx = max_ctx; p.H = H; p.q_scale = 0.125f;
 		p.stamps = st ? st + 0 * SLOTS : nullptr;
 		GemvParams gq = {};
@@ -80,21 +79,21 @@ int main(int argc, char** argv) {
 		a.qbuf = qbuf; a.kcache = L[i].kc; a.vcache = L[i].vc; a.d_pos = dpos; a.pos_slot_p1 = pos_slot + 1; a.B = B; a.H = H; a.max_ctx = max_ctx; a.ctx_hint = ctx; a.out = ao; a.out_frag = 1; a.shared_rows = 1;
 		a.stamps = st ? st + 1 * SLOTS : nullptr;
 		launch_attn_decode(DT_BF16, a, s);
-		p = {}; p.Wp = L[i].wproj; p.N = d; p.K = d; p.M = B; p.bias = bias; p.a = ao; p.lda = d; p.a_frag = 1;
-		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.narrow = narrow; p.out_T = xfrag; p.stamps = st ? st + 2 * SLOTS : nullptr;
+		p = {}; p.Wp = L[i].wproj; p.N = d; p.K = d; p.M = B; p.bias = bias; p.a = ao;
+		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = xfrag; p.stamps = st ? st + 2 * SLOTS : nullptr;
 		GemvParams gp = {};
 		gp.Wp = p.Wp; gp.a = ao; gp.bias = bias; gp.out_f32 = x; gp.out_T = xfrag; gp.M = B; gp.N = d; gp.K = d; gp.stamps = p.stamps;
-		if (!(lean && narrow == 4 && launch_gemv(DT_BF16, GV_PROJ, gp, s))) launch_skinny(DT_BF16, p, wv_proj, s);
-		p = {}; p.Wp = L[i].wfc; p.N = 4 * d; p.K = d; p.M = B; p.bias = bias; p.g1 = bias; p.a = xfrag; p.lda = d; p.a_frag = 1;
-		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hb; p.out_frag = 1; p.stamps = st ? st + 3 * SLOTS : nullptr;
+		if (!(lean && launch_gemv(DT_BF16, GV_PROJ, gp, s))) launch_skinny(DT_BF16, p, wv_proj, s);
+		p = {}; p.Wp = L[i].wfc; p.N = 4 * d; p.K = d; p.M = B; p.bias = bias; p.g1 = bias; p.a = xfrag;
+		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hb; p.stamps = st ? st + 3 * SLOTS : nullptr;
 		GemvParams gf = {};
 		gf.Wp = p.Wp; gf.a = xfrag; gf.bias = bias; gf.csum = bias; gf.out_T = hb; gf.M = B; gf.N = 4 * d; gf.K = d; gf.stamps = p.stamps;
 		if (!(lean && launch_gemv(DT_BF16, GV_FC, gf, s))) launch_skinny(DT_BF16, p, wv_fc, s);
-		p = {}; p.Wp = L[i].wproj2; p.N = d; p.K = 4 * d; p.M = B; p.bias = bias; p.a = hb; p.lda = 4 * d; p.a_frag = 1;
-		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.narrow = narrow; p.out_T = xfrag; p.stamps = st ? st + 4 * SLOTS : nullptr;
+		p = {}; p.Wp = L[i].wproj2; p.N = d; p.K = 4 * d; p.M = B; p.bias = bias; p.a = hb;
+		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = xfrag; p.stamps = st ? st + 4 * SLOTS : nullptr;
 		GemvParams g2 = {};
 		g2.Wp = p.Wp; g2.a = hb; g2.bias = bias; g2.out_f32 = x; g2.out_T = xfrag; g2.M = B; g2.N = d; g2.K = 4 * d; g2.stamps = p.stamps;
-		if (!(lean && narrow == 4 && launch_gemv(DT_BF16, GV_PROJ, g2, s))) launch_skinny(DT_BF16, p, wv_proj2, s);
+		if (!(lean && launch_gemv(DT_BF16, GV_PROJ, g2, s))) launch_skinny(DT_BF16, p, wv_proj2, s);
 	};
 	for (int i = 0; i < NL; ++i) layer(i, nullptr);      // warm (code objects, first-touch)
 	CK(hipStreamSynchronize(s));
@@ -116,12 +115,12 @@ int main(int argc, char** argv) {
 		float ms; CK(hipEventElapsedTime(&ms, e0, e1));
 		if (rep >= 1) best = std::min(best, ms);
 	}
-	printf("chain: lean %d ctx %d, %d layers x %d replays, waves %d/%d/%d/%d narrow %d: %.3f us per layer (%.3f us per launch)\n", lean, ctx, NL, replays,
-		   wv_qkv, wv_proj, wv_fc, wv_proj2, narrow, best * 1e3 / (replays * NL), best * 1e3 / (replays * NL * 5));
+	printf("chain: lean %d ctx %d, %d layers x %d replays, waves %d/%d/%d/%d: %.3f us per layer (%.3f us per launch)\n", lean, ctx, NL, replays,
+		   wv_qkv, wv_proj, wv_fc, wv_proj2, best * 1e3 / (replays * NL), best * 1e3 / (replays * NL * 5));
 
 	// ---- stamps of layer SL inside the replayed chain (median over several replays of every statistic)
 	const char* names[5] = {"c_attn(fold)", "attention", "c_proj", "c_fc(fold)", "mlp.c_proj"};
-	const int grids[5] = {192, B * H, narrow ? (d / 16) * narrow : d / 16, 256, narrow ? (d / 16) * narrow : d / 16};
+	const int grids[5] = {192, B * H, (d / 16) * 4, 256, (d / 16) * 4};
 	const int waves[5] = {lean ? 4 : wv_qkv, 16, lean ? 4 : wv_proj, lean ? 4 : wv_fc, lean ? 8 : wv_proj2};
 	// stamp slots: skinny 0 start, 2 loads issued, 3 own MFMAs done, 4 after the barrier, 5 stores issued, 6 stores acknowledged
 	//              attention 0 start, 1 position + q known, 2 own keys reduced, 3 after the barrier, 5 stores issued, 6 acknowledged

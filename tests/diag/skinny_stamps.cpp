@@ -14,8 +14,7 @@ using namespace ttk;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 
 int main(int argc, char** argv) {
-	const int narrow = argc > 1 ? atoi(argv[1]) : 1;
-	const int fold = argc > 2 ? atoi(argv[2]) : 0;      // 1: ln1+qkv / ln2+fc with the LayerNorm folded (plain path over fragment-order rows)
+	const int fold = argc > 1 ? atoi(argv[1]) : 0;      // 1: ln1+qkv / ln2+fc with the LayerNorm folded (plain path over fragment-order rows)
 	const int d = 1024, B = 16, H = 16, max_ctx = 512;
 	// two alternating "layers" so weights are not L2-resident between launches: 40 distinct weight sets (> 256 MiB total)
 	const int NSET = 48;
@@ -26,35 +25,33 @@ int main(int argc, char** argv) {
 		CK(hipMemset(sets[i].wqkv, 0, (size_t)3 * d * d * 2)); CK(hipMemset(sets[i].wproj, 0, (size_t)d * d * 2));
 		CK(hipMemset(sets[i].wfc, 0, (size_t)4 * d * d * 2)); CK(hipMemset(sets[i].wproj2, 0, (size_t)4 * d * d * 2));
 	}
-	float *x, *qbuf, *bias, *g, *b, *slab; void *kc, *vc, *ao, *hb; int *dpos, *tickets; unsigned long long* stamps;
+	float *x, *qbuf, *bias, *g, *b; void *kc, *vc, *ao, *hb; int* dpos; unsigned long long* stamps;
 	CK(hipMalloc(&x, B * d * 4)); CK(hipMalloc(&qbuf, B * d * 4)); CK(hipMalloc(&bias, 4 * d * 4)); CK(hipMalloc(&g, d * 4)); CK(hipMalloc(&b, d * 4));
 	CK(hipMalloc(&kc, (size_t)B * H * max_ctx * 64 * 2)); CK(hipMalloc(&vc, (size_t)B * H * max_ctx * 64 * 2));
 	CK(hipMalloc(&ao, B * d * 2)); CK(hipMalloc(&hb, B * 4 * d * 2)); CK(hipMalloc(&dpos, 16)); CK(hipMalloc(&stamps, 512 * 8 * 8));
-	CK(hipMalloc(&slab, 64 * 4 * 4 * 256 * 4)); CK(hipMalloc(&tickets, 64 * 4)); CK(hipMemset(tickets, 0, 64 * 4));
 	CK(hipMemset(x, 0, B * d * 4)); CK(hipMemset(bias, 0, 4 * d * 4)); CK(hipMemset(g, 0, d * 4)); CK(hipMemset(b, 0, d * 4)); CK(hipMemset(dpos, 0, 16));
 	CK(hipMemset(ao, 0, B * d * 2)); CK(hipMemset(hb, 0, B * 4 * d * 2));
 	hipStream_t s; CK(hipStreamCreate(&s));
 	auto run_layer = [&](int i, unsigned long long* st, int which) {
 		SkinnyParams p = {};
 		p.Wp = sets[i].wqkv; p.N = 3 * d; p.K = d; p.M = B; p.bias = bias;
-		if (fold) { p.g1 = bias; p.a = ao; p.lda = d; p.a_frag = 1; } else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = g; p.b1 = b; }
+		if (fold) { p.g1 = bias; p.a = ao; } else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = g; p.b1 = b; }
 		p.mode = SK_QKV; p.qbuf = qbuf; p.kcache = kc; p.vcache = vc; p.d_pos = dpos; p.max_ctx = max_ctx; p.H = H; p.q_scale = 0.125f;
 		p.stamps = which == 0 ? st : nullptr;
 		launch_skinny(DT_BF16, p, 8, s);
-		p = {}; p.Wp = sets[i].wproj; p.N = d; p.K = d; p.M = B; p.bias = bias; p.a = ao; p.lda = d; p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.narrow = narrow; p.a_frag = 1; p.out_T = fold ? ao : nullptr;
+		p = {}; p.Wp = sets[i].wproj; p.N = d; p.K = d; p.M = B; p.bias = bias; p.a = ao; p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = fold ? ao : nullptr;
 		p.stamps = which == 1 ? st : nullptr;
 		launch_skinny(DT_BF16, p, 8, s);
 		p = {}; p.Wp = sets[i].wfc; p.N = 4 * d; p.K = d; p.M = B; p.bias = bias;
-		if (fold) { p.g1 = bias; p.a = ao; p.lda = d; p.a_frag = 1; } else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = g; p.b1 = b; }
-		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hb; p.out_frag = 1; p.stamps = which == 2 ? st : nullptr;
+		if (fold) { p.g1 = bias; p.a = ao; } else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = g; p.b1 = b; }
+		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hb; p.stamps = which == 2 ? st : nullptr;
 		launch_skinny(DT_BF16, p, 8, s);
-		p = {}; p.Wp = sets[i].wproj2; p.N = d; p.K = 4 * d; p.M = B; p.bias = bias; p.a = hb; p.lda = 4 * d; p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.a_frag = 1;
-		p.stamps = which == 3 ? st : nullptr; p.narrow = narrow;
-		if (!narrow) { p.ksplit = 4; p.slab = slab; p.tickets = tickets; }
-		launch_skinny(DT_BF16, p, narrow ? 16 : 8, s);
+		p = {}; p.Wp = sets[i].wproj2; p.N = d; p.K = 4 * d; p.M = B; p.bias = bias; p.a = hb; p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d;
+		p.stamps = which == 3 ? st : nullptr;
+		launch_skinny(DT_BF16, p, 16, s);
 	};
-	const char* names[4] = {"ln1+qkv (192 WG x 8 waves)", "c_proj (64 WG x 8)", "ln2+fc+gelu (256 WG x 8)", "mlp.c_proj (64x4 WG x 8)"};
-	const int grids[4] = {192, narrow ? 256 : 64, 256, 256};
+	const char* names[4] = {"ln1+qkv (192 WG x 8 waves)", "c_proj (64x4 WG x 8)", "ln2+fc+gelu (256 WG x 8)", "mlp.c_proj (64x4 WG x 16)"};
+	const int grids[4] = {192, 256, 256, 256};
 	for (int which = 0; which < 4; ++which) {
 		for (int i = 0; i < NSET; ++i) run_layer(i, nullptr, -1);   // warm
 		CK(hipStreamSynchronize(s));

@@ -7,6 +7,7 @@ geometry (csrc/skinny.hip: k_skinny, selected with TTK_AR_LEAN=0): same operands
         v_dot2c_f32_bf16 instead of an unpack / add / fma chain (a few ulp of mean and rstd), which moves some gelu outputs to the
         neighbouring bf16 value: logits within 3e-3 relative L2 of the generic kernel's (the bf16 bar against the f32 oracle is 3e-2).
   rows  M = 1, 16, 17 (second m-tile, rows 17..31 padding), 48 (third): each row's logits do not depend on what else is in the batch.
+  odd   model_dim = 192 (no fixture model): k_skinny's residual projections with a tile count that is no multiple of 8, against the oracle.
 GPU only; calls go through the C ABI."""
 import os
 
@@ -163,3 +164,51 @@ def test_folded_layernorm_on_outlier_channels_and_on_a_common_offset(ar_sd, dtyp
 		with pytest.warns(RuntimeWarning, match="TTK_AR_LNFOLD=0"):
 			m.inference_speech(cond.to(DEV), text.to(DEV), do_sample=True, temperature=0.8, top_k=0, num_return_sequences=16, max_generate_length=4)
 		assert m.last_health & 1
+
+
+# ---- k_skinny where no fixture model reaches it: a projection whose N / 16 is no multiple of 8
+ODD = W.ARConfig(layers=2, model_dim=192, heads=3)      # 12 column tiles in c_proj / mlp.c_proj; K = 192 and 768: 6 and 24 k-steps over 4 waves
+
+
+@pytest.fixture(scope="module")
+def odd_runs():
+	"""model_dim = 192: the residual projections have 12 n-tiles, so their four-workgroups-per-tile launches take the plain tile order (the XCD-grouped
+	one needs a multiple of 8 tiles -- every other model in the suite has one); K = 192 gives the four waves 1 / 2 / 1 / 2 k-steps, K = 768 six each, fewer
+	than one operand batch.  5 text tokens, the prefill and four forced decode steps, at B = 3 and B = 17 (second row tile, 15 padding rows), against the
+	oracle's dense teacher-forced pass (computed once for the 17 rows; the 3-row batch feeds its first three)."""
+	from tortoise_tts_amd.autoregressive import UnifiedVoice
+	import tortoise_oracle as O
+	sd = W.synth_state_dict(W.ar_shapes(ODD), 3)
+	g = torch.Generator().manual_seed(80)
+	text = torch.randint(1, 255, (1, 5), generator=g)
+	cond = torch.randn(1, ODD.model_dim, generator=g)
+	toks = torch.randint(0, 8192, (17, 4), generator=g)
+	out = {}
+	with torch.inference_mode():
+		out["ref"] = O.AROracle(sd, ODD).teacher_forced_logits(cond, text, toks, [0, 1, 2, 3, 4])
+		for dtype in ("f32", "bf16"):
+			for B in (3, 17):
+				m = UnifiedVoice(sd, ODD, dtype=dtype, device=DEV, max_batch=B, max_ctx=5 + 4 + 8)
+				out[dtype, B] = forced(m, cond, text, torch.cat([toks[:B], toks[:B, :1]], 1)).cpu()      # forced() feeds all but the last column
+	return out
+
+
+@pytest.mark.parametrize("B", [3, 17])
+def test_odd_tile_count_f32_equals_the_oracle(odd_runs, B):
+	"""the small model's f32 bar (tests/test_gpu_parity.py: max abs error < 1e-4)"""
+	err = (odd_runs["f32", B] - odd_runs["ref"][:B]).abs().max().item()
+	print(f"model_dim 192, f32, B={B}: max abs error {err:.3e}")
+	assert err < 1e-4, err
+
+
+@pytest.mark.parametrize("B", [3, 17])
+def test_odd_tile_count_bf16_within_the_bf16_bar(odd_runs, B):
+	"""the small model's bf16 bar (tests/test_gpu_parity.py: relative L2 < 3e-2)"""
+	err = relerr(odd_runs["bf16", B], odd_runs["ref"][:B])
+	print(f"model_dim 192, bf16, B={B}: relative L2 {err:.3e}")
+	assert err < 3e-2, err
+
+
+def test_odd_tile_count_row_0_is_the_same_bits_in_both_batches(odd_runs):
+	a, b = odd_runs["f32", 3][0], odd_runs["f32", 17][0]
+	assert torch.equal(a, b), (a - b).abs().max().item()

@@ -93,43 +93,22 @@ struct ttk_ar {
 	int2* d_rowinfo;        // per candidate {first cache row, first candidate of its line}: line batches (ttk_ar_prefill_lines), prefixes right-aligned
 	int lines_mode = 0;     // the current generation was started by ttk_ar_prefill_lines: the attention launches read d_rowinfo
 	float *x, *qbuf;        // decode residual stream / scaled queries [max_batch][d]
-	void *attn_out, *hbuf;  // T [max_batch][d], [max_batch][4d]
+	void *attn_out, *hbuf;  // T, A-fragment order: [frag_rows][d] (attention output; the head's normalised rows), [frag_rows][4d] (MLP activations)
 	void* x_frag = nullptr; // T copy of x in A-fragment order [m_tile][d/32][64][8]: operand of the folded-LayerNorm launches
 	int poison = 0;         // TTK_DEBUG_POISON=1: the dense passes' scratch (ws_*) is filled with 0xFF when a prefill / latent pass ends -- nothing may read it afterwards
 	int frag_rows = 0;      // rows attn_out / hbuf / x_frag were allocated (and zeroed) for: 16 * decode_row_tiles(max_batch)
 	int shared_rows = 0;    // leading cache rows that are identical for all candidates of the current generation (AttnDecodeParams.shared_rows)
-	int share_prefix = 1;   // TTK_AR_SHARE_PREFIX=0: every candidate reads its own copy
 	// multinomial noise drawn by the mel-head launch (ttk_ar_set_noise): device RngArgs, per-row draw counters, q rows of this handle's candidates
 	const int64_t* rng_args = nullptr; const int64_t* rng_draws = nullptr; float* rng_q = nullptr;
 	int* d_health = nullptr;  // GemvParams.health of the folded launches (ttk_ar_health reads and clears it)
 	float* ring_base = nullptr; const int64_t* ring_idx = nullptr; int64_t ring_stride = 0;      // ttk_ar_set_hidden_ring
 	int64_t* d_ring = nullptr;                                                                 // device word holding ring_base: what the (possibly captured) launch reads
-	int head_split = 1;     // decode head as LayerNorm launch + plain GEMV (TTK_AR_HEAD_SPLIT=0: norms inside the GEMV)
-	int lnfold = 1;         // ln_1 + c_attn and ln_2 + c_fc of the decode step with the LayerNorm folded into the matrix (TTK_AR_LNFOLD=0: LN prologue)
+	int lnfold = 1;         // ln_1 + c_attn and ln_2 + c_fc of the decode step with the LayerNorm folded into the matrix (TTK_AR_LNFOLD=0: LN prologue, normalises in f32 first)
 	int lean = 1;           // decode launches on the compile-time-specialised kernels of gemv.hip where one exists (TTK_AR_LEAN=0: k_skinny everywhere)
-	float* slab; int* tickets;   // split-K scratch of the mlp.c_proj decode GEMV, one set per row group
-	// Waves per workgroup of the decode GEMVs that read their rows in fragment order (TTK_AR_WV_PROJ / _PROJ2 / _LN).  A wave requests its
-	// operands in batches of 8 k-steps (bf16; 4 in f32), so K / 32 / waves should be a multiple of that: with 8 waves on K = 1024 every wave
-	// owned 4 k-steps and half of its 16 load instructions re-read the last fragment -- on a path that is bound by what a CU can take in.
-	// More than 8 waves lose again (16 partial tiles to merge through LDS): 4 / 4 / 8 measured best in the 250-token loop (bf16, B = 16).
-	int wv_proj = 4, wv_proj2 = 8;
-	int wv_ln = 4;                    // ln_1 + c_attn and ln_2 + c_fc with the LayerNorm folded in; the LN-prologue form (TTK_AR_LNFOLD=0) keeps 8
-	int wv_head = 4;                  // waves per workgroup of the ln_f + final_norm + mel_head launch (TTK_AR_WV_HEAD): 513 n-tiles; with 8-wave
-	                                  // workgroups two fit a CU (512 slots), so tile 513 ran as a second round on an empty chip; 4-wave ones fit four
-	int hfrag = 1;                // MLP activations of the decode step in MFMA-fragment order (TTK_AR_HFRAG=0: row-major)
-	int narrow2 = 4;              // same for mlp.c_proj (TTK_AR_NARROW2)
-	int narrow = 4;               // c_proj / mlp.c_proj decode GEMVs as 4-column workgroups without split-K (TTK_AR_NARROW=0: 16-column + split-K)
-	int nsplit = 1;               // row groups decoded concurrently (TTK_AR_SPLIT; measured slower: 283 -> 340 ms at 2, see below)
-	hipStream_t side[3] = {nullptr, nullptr, nullptr};
-	hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
 	WsBuf ws_x, ws_a, ws_qkv, ws_ao, ws_h;
 	int B = 0, P = 0, k = 0, ready = 0;
 	int Pmax = 0;           // longest prefix of the batch (capacity checks); == P for one line
-	~ttk_ar() {             // also the failure path of ttk_ar_create: whatever was made so far; the workspaces and the arena free themselves after this
-		for (int i = 0; i < 3; ++i) { if (side[i]) (void)hipStreamDestroy(side[i]); if (ev_join[i]) (void)hipEventDestroy(ev_join[i]); }
-		if (ev_fork) (void)hipEventDestroy(ev_fork);
-		attn_pos_slot_release(pos_slot);
-	}
+	~ttk_ar() { attn_pos_slot_release(pos_slot); }      // also the failure path of ttk_ar_create; the workspaces and the arena free themselves after this
 };
 
 // Debug aid: per-call scratch must not outlive its call.  A captured token step that kept reading one of these buffers would see
@@ -186,101 +165,101 @@ static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipSt
 	return TTK_OK;
 }
 
-// ln_f + final_norm + mel_head on the decode rows h->x [B][d]
-static void head_launch(ttk_ar* h, int B, float* logits, float* hidden_out, hipStream_t s) {
-	SkinnyParams p = {};
-	p.Wp = h->head.wfrag; p.N = h->cfg.number_mel_codes; p.K = h->cfg.model_dim; p.M = B; p.bias = h->head.bias;
-	p.ln_count = 2; p.x = h->x; p.ldx = h->cfg.model_dim;
-	p.g1 = h->lnf_g; p.b1 = h->lnf_b; p.g2 = h->fn_g; p.b2 = h->fn_b; p.ln_out = hidden_out;
-	p.mode = SK_STORE_F32; p.out_f32 = logits; p.ldc = h->cfg.number_mel_codes;
-	if (h->rng_q) { p.qbuf = h->rng_q; p.slab = (float*)h->rng_args; p.tickets = (int*)h->rng_draws; }
-	launch_skinny(h->dt, p, h->cfg.model_dim >= 1024 ? h->wv_head : 4, s);
+// ---- the weight-streaming launches of the decode step, each described once
+enum DecodeRole { DR_QKV = 0, DR_PROJ, DR_FC, DR_PROJ2, DR_HEAD };      // ln_1 + c_attn, c_proj + residual, ln_2 + c_fc + gelu_new, mlp.c_proj + residual, mel_head
+struct DecodeLaunch {
+	int role;
+	const Mat* W; int N, K;
+	const void* a;                   // rows, T-typed in A-fragment order: x_frag (DR_QKV / DR_FC: un-normalised, the LayerNorm is folded into W), attn_out, hbuf
+	const float *ln_g, *ln_b;        // the LayerNorm in front: DR_QKV / DR_FC (used as such only with TTK_AR_LNFOLD=0), the prefill's head (ln_f)
+	const float *ln2_g, *ln2_b;      // the prefill's head: final_norm behind ln_f
+	float* out_f32;                  // DR_PROJ / DR_PROJ2: the residual stream, updated in place; DR_HEAD: logits
+	void* out_T;                     // DR_FC: activations; DR_PROJ / DR_PROJ2 (optional): T copy of the updated rows; both in A-fragment order
+	void *kc, *vc;                   // DR_QKV: this layer's caches
+	bool bump;                       // DR_HEAD: the launch advances the cache length
+};
+
+// Waves per workgroup of the k_skinny launches (k_gemv's are template parameters that repeat them).  A wave requests its operands in batches of 8 k-steps
+// (4 in f32), so K / 32 / waves should be a multiple of that: with 8 waves on K = 1024 every bf16 wave owned 4 k-steps and half of its 16 load
+// instructions re-read the last fragment -- on a path bound by what a CU can take in.  More than 8 lose again (16 partial tiles to merge through LDS):
+// 4 (K = 1024) / 8 (K = 4096) measured best in the 250-token loop (bf16, B = 16).  f32: batches of 4 k-steps, 32 / 4 = 8 waves; K = 4096: 4 batches each.
+// LN prologue: 8 waves x 2 rows normalise 16 candidates in one pass.  The head has 513 n-tiles: two 8-wave workgroups fit a CU (512 slots), so tile 513
+// ran as a second round on an empty chip; five 4-wave ones fit and the tiles run as one round.  Small models: 4 everywhere.
+static int skinny_waves(int role, bool ln_prologue, int dt, int d) {
+	if (d < 1024 || role == DR_HEAD) return 4;
+	if (ln_prologue || dt == DT_F32) return 8;
+	return role == DR_PROJ2 ? 8 : 4;
 }
 
-// one row group [r0, r0 + nrows) of a decode step on stream s: 30 x {ln_1+c_attn+KV append, attention, c_proj+res, ln_2+c_fc+gelu,
-// mlp.c_proj+res} + ln_f/final_norm/mel_head
-static void decode_rows(ttk_ar* h, int r0, int nrows, int gi, float* logits_out, float* hidden_out, hipStream_t s, bool bump_pos) {
+// One launch on M rows: k_gemv where the lean kernels are allowed and have an instantiation for the geometry, else k_skinny on the same operands.
+static void decode_launch(ttk_ar* h, const DecodeLaunch& L, int M, hipStream_t s) {
 	const ttk_ar_config& c = h->cfg;
-	const int d = c.model_dim, H = c.heads, dt = h->dt;
-	const size_t es = h->es;
-	float* x = h->x + (size_t)r0 * d;
-	float* qbuf = h->qbuf + (size_t)r0 * d;
-	char* attn_out = (char*)h->attn_out + (size_t)r0 * d * es;
-	char* hbuf = (char*)h->hbuf + (size_t)r0 * 4 * d * es;
-	const size_t kv_row = (size_t)H * c.max_ctx * 64 * es;
-	const int wv_small = d >= 1024 ? h->wv_ln : 4;   // waves per workgroup that split K = d (folded LayerNorm: plain operand path)
-	const int wv_prologue = d >= 1024 ? 8 : 4;       // LayerNorm prologue form: 8 waves x 2 rows normalise the 16 candidates in one pass
-	const bool whole = r0 == 0 && nrows == h->B;      // fragment-order activations exist for the whole batch only
-	void* xf = whole ? h->x_frag : nullptr;
-	const bool lean = h->lean && whole && h->lnfold && h->hfrag;      // gemv.hip's specialised launches: the whole batch, fragment-order activations
+	const Mat& W = *L.W;
+	const bool fold = h->lnfold && (L.role == DR_QKV || L.role == DR_FC);      // x_frag times gamma o W, the norm finished in the epilogue
+	const bool prologue = L.ln_g && !fold;                                     // f32 rows of h->x normalised inside the launch
+	const bool residual = L.role == DR_PROJ || L.role == DR_PROJ2;
+	GemvParams g = {};
+	g.Wp = fold ? W.wfrag_fold : W.wfrag; g.bias = fold ? W.bias_fold : W.bias; g.csum = fold ? W.csum : nullptr;
+	g.w8 = fold ? 0 : W.w8; g.wscale = W.wscale;       // (fp8 weights: the fold is kept in bf16)
+	g.a = L.a; g.out_f32 = L.out_f32; g.out_T = L.out_T; g.M = M; g.N = L.N; g.K = L.K; g.row0 = 0;
+	if (fold) g.health = h->d_health;
+	if (L.role == DR_QKV) { g.qbuf = h->qbuf; g.kcache = L.kc; g.vcache = L.vc; g.d_pos = h->d_pos; g.max_ctx = c.max_ctx; g.H = c.heads; g.q_scale = 0.125f; }
+	if (L.role == DR_HEAD) { g.d_pos = L.bump ? h->d_pos : nullptr; g.noise = h->rng_q; g.rng = h->rng_args; g.draws = h->rng_draws; }
+	const int gv = L.role == DR_QKV ? GV_QKV : (L.role == DR_FC ? GV_FC : (L.role == DR_HEAD ? GV_HEAD : GV_PROJ));
+	// the ONE place that decides between the kernel families: launch_gemv declines (gemv_supported) what it has no instantiation for
+	if (h->lean && h->lnfold && !prologue && launch_gemv(h->dt, gv, g, s)) return;
+	SkinnyParams p = {};
+	p.Wp = g.Wp; p.w8 = g.w8; p.wscale = g.wscale; p.N = L.N; p.K = L.K; p.M = M; p.bias = g.bias;
+	if (prologue) { p.ln_count = L.ln2_g ? 2 : 1; p.x = h->x; p.ldx = c.model_dim; p.g1 = L.ln_g; p.b1 = L.ln_b; p.g2 = L.ln2_g; p.b2 = L.ln2_b; }
+	else { p.a = L.a; p.g1 = g.csum; }
+	p.mode = L.role == DR_QKV ? SK_QKV : (L.role == DR_FC ? SK_ACT_T : (residual ? SK_RESIDUAL : SK_STORE_F32));
+	p.act = L.role == DR_FC ? ACT_GELU_NEW : ACT_NONE;
+	p.out_f32 = L.out_f32; p.ldc = L.N; p.out_T = L.out_T;
+	p.qbuf = g.qbuf; p.kcache = g.kcache; p.vcache = g.vcache; p.max_ctx = g.max_ctx; p.H = g.H; p.q_scale = g.q_scale; p.d_pos = g.d_pos;
+	p.noise = g.noise; p.rng = g.rng; p.draws = g.draws;
+	launch_skinny(h->dt, p, skinny_waves(L.role, prologue, h->dt, c.model_dim), s);
+}
+
+// the prefill's head: ln_f + final_norm + mel_head on the f32 rows h->x [B][d], the norms inside the launch (once per utterance; the decode step splits them off)
+static void head_launch(ttk_ar* h, int B, float* logits, hipStream_t s) {
+	DecodeLaunch L = {DR_HEAD, &h->head, h->cfg.number_mel_codes, h->cfg.model_dim};
+	L.ln_g = h->lnf_g; L.ln_b = h->lnf_b; L.ln2_g = h->fn_g; L.ln2_b = h->fn_b; L.out_f32 = logits;
+	decode_launch(h, L, B, s);
+}
+
+// one decode step of the whole batch on stream s: layers x {ln_1+c_attn+KV append, attention, c_proj+res, ln_2+c_fc+gelu, mlp.c_proj+res} + ln_f/final_norm + mel_head
+static void decode_rows(ttk_ar* h, float* logits_out, float* hidden_out, hipStream_t s) {
+	const ttk_ar_config& c = h->cfg;
+	const int d = c.model_dim, B = h->B, dt = h->dt;
+	void* xf = h->lnfold ? h->x_frag : nullptr;      // T copy of the residual rows: written by the projections, operand of the folded launches
 	for (int l = 0; l < c.layers; ++l) {
 		const ARLayer& L = h->L[l];
-		char* kc = (char*)h->kc + (size_t)l * h->kv_layer_stride * es + r0 * kv_row;
-		char* vc = (char*)h->vc + (size_t)l * h->kv_layer_stride * es + r0 * kv_row;
-		SkinnyParams p = {};
-		p.Wp = L.attn.wfrag; p.w8 = L.attn.w8; p.wscale = L.attn.wscale; p.N = 3 * d; p.K = d; p.M = nrows; p.bias = L.attn.bias;
-		const bool fold_qkv = h->lnfold && whole && L.attn.wfrag_fold;
-		if (fold_qkv) { p.Wp = L.attn.wfrag_fold; p.w8 = 0; p.bias = L.attn.bias_fold; p.g1 = L.attn.csum; p.a = xf; p.lda = d; p.a_frag = 1; }
-		else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = L.ln1_g; p.b1 = L.ln1_b; }
-		p.mode = SK_QKV; p.qbuf = qbuf; p.kcache = kc; p.vcache = vc; p.d_pos = h->d_pos; p.max_ctx = c.max_ctx; p.H = H; p.q_scale = 0.125f;
-		GemvParams gq = {};
-		gq.Wp = p.Wp; gq.a = xf; gq.bias = p.bias; gq.csum = p.g1; gq.qbuf = qbuf; gq.kcache = kc; gq.vcache = vc; gq.d_pos = h->d_pos;
-		gq.M = nrows; gq.N = 3 * d; gq.K = d; gq.max_ctx = c.max_ctx; gq.H = H; gq.q_scale = 0.125f; gq.health = h->d_health;
-		if (!(lean && fold_qkv && launch_gemv(dt, GV_QKV, gq, s))) launch_skinny(dt, p, fold_qkv ? wv_small : wv_prologue, s);
+		char* kc = (char*)h->kc + (size_t)l * h->kv_layer_stride * h->es;
+		char* vc = (char*)h->vc + (size_t)l * h->kv_layer_stride * h->es;
+		DecodeLaunch qkv = {DR_QKV, &L.attn, 3 * d, d, h->x_frag, L.ln1_g, L.ln1_b};
+		qkv.kc = kc; qkv.vc = vc;
+		decode_launch(h, qkv, B, s);
 		AttnDecodeParams a = {};
-		a.qbuf = qbuf; a.kcache = kc; a.vcache = vc; a.d_pos = h->d_pos; a.pos_slot_p1 = h->pos_slot + 1; a.B = nrows; a.H = H; a.max_ctx = c.max_ctx; a.ctx_hint = h->P + 2 + h->k; a.out = attn_out; a.out_frag = h->hfrag && r0 == 0 && nrows == h->B; a.shared_rows = r0 == 0 && h->share_prefix && h->nsplit == 1;
-		a.row_info = h->lines_mode && r0 == 0 ? h->d_rowinfo : nullptr;
+		a.qbuf = h->qbuf; a.kcache = kc; a.vcache = vc; a.d_pos = h->d_pos; a.pos_slot_p1 = h->pos_slot + 1; a.B = B; a.H = c.heads; a.max_ctx = c.max_ctx; a.ctx_hint = h->P + 2 + h->k;
+		a.out = h->attn_out; a.out_frag = 1; a.shared_rows = 1; a.row_info = h->lines_mode ? h->d_rowinfo : nullptr;
 		launch_attn_decode(dt, a, s);
-		p = {};
-		p.Wp = L.proj.wfrag; p.w8 = L.proj.w8; p.wscale = L.proj.wscale; p.N = d; p.K = d; p.M = nrows; p.bias = L.proj.bias; p.a = attn_out; p.lda = d; p.a_frag = h->hfrag && r0 == 0 && nrows == h->B;
-		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.narrow = h->narrow; p.out_T = h->lnfold ? xf : nullptr;
-		GemvParams gp = {};
-		gp.Wp = p.Wp; gp.a = attn_out; gp.bias = p.bias; gp.out_f32 = x; gp.out_T = p.out_T; gp.M = nrows; gp.N = d; gp.K = d; gp.w8 = p.w8; gp.wscale = p.wscale;
-		if (!(lean && p.a_frag && h->narrow == 4 && launch_gemv(dt, GV_PROJ, gp, s))) launch_skinny(dt, p, d >= 1024 ? h->wv_proj : 4, s);
-		p = {};
-		p.Wp = L.fc.wfrag; p.w8 = L.fc.w8; p.wscale = L.fc.wscale; p.N = 4 * d; p.K = d; p.M = nrows; p.bias = L.fc.bias;
-		const bool fold_fc = h->lnfold && whole && L.fc.wfrag_fold;
-		if (fold_fc) { p.Wp = L.fc.wfrag_fold; p.w8 = 0; p.bias = L.fc.bias_fold; p.g1 = L.fc.csum; p.a = xf; p.lda = d; p.a_frag = 1; }
-		else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = L.ln2_g; p.b1 = L.ln2_b; }
-		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hbuf; p.out_frag = h->hfrag && r0 == 0 && nrows == h->B;
-		GemvParams gf = {};
-		gf.Wp = p.Wp; gf.a = xf; gf.bias = p.bias; gf.csum = p.g1; gf.out_T = hbuf; gf.M = nrows; gf.N = 4 * d; gf.K = d; gf.health = h->d_health;
-		if (!(lean && fold_fc && p.out_frag && launch_gemv(dt, GV_FC, gf, s))) launch_skinny(dt, p, fold_fc ? wv_small : wv_prologue, s);
-		p = {};
-		p.Wp = L.proj2.wfrag; p.w8 = L.proj2.w8; p.wscale = L.proj2.wscale; p.N = d; p.K = 4 * d; p.M = nrows; p.bias = L.proj2.bias; p.a = hbuf; p.lda = 4 * d; p.a_frag = h->hfrag && r0 == 0 && nrows == h->B;
-		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = h->lnfold ? xf : nullptr;
-		p.narrow = h->narrow2;
-		if (d >= 1024 && !h->narrow2) {   // 64 n-tiles x 4 K-slices = 256 workgroups; each row group has its own slab and tickets
-			p.ksplit = 4; p.slab = h->slab + (size_t)gi * (d / 16) * 4 * 4 * 256; p.tickets = h->tickets + (size_t)gi * (d / 16);
-		}
-		GemvParams g2 = {};
-		g2.Wp = p.Wp; g2.a = hbuf; g2.bias = p.bias; g2.out_f32 = x; g2.out_T = p.out_T; g2.M = nrows; g2.N = d; g2.K = 4 * d; g2.w8 = p.w8; g2.wscale = p.wscale;
-		if (!(lean && p.a_frag && h->narrow2 == 4 && launch_gemv(dt, GV_PROJ, g2, s))) launch_skinny(dt, p, d >= 1024 ? h->wv_proj2 : 4, s);
+		DecodeLaunch proj = {DR_PROJ, &L.proj, d, d, h->attn_out};
+		proj.out_f32 = h->x; proj.out_T = xf;
+		decode_launch(h, proj, B, s);
+		DecodeLaunch fc = {DR_FC, &L.fc, 4 * d, d, h->x_frag, L.ln2_g, L.ln2_b};
+		fc.out_T = h->hbuf;
+		decode_launch(h, fc, B, s);
+		DecodeLaunch proj2 = {DR_PROJ2, &L.proj2, d, 4 * d, h->hbuf};
+		proj2.out_f32 = h->x; proj2.out_T = xf;
+		decode_launch(h, proj2, B, s);
 	}
-	SkinnyParams p = {};
-	p.Wp = h->head.wfrag; p.N = c.number_mel_codes; p.K = d; p.M = nrows; p.bias = h->head.bias;
-	p.mode = SK_STORE_F32; p.out_f32 = logits_out + (size_t)r0 * c.number_mel_codes; p.ldc = c.number_mel_codes;
-	// the last launch of the step advances the cache length: every reader of *d_pos (c_attn epilogues, attention) is behind it on the
-	// stream, the next reader is the next step -- one 1-thread launch per token less (an otherwise unused field carries the pointer)
-	if (bump_pos) p.d_pos = h->d_pos;
-	if (h->rng_q) { p.qbuf = h->rng_q + (size_t)r0 * c.number_mel_codes; p.slab = (float*)h->rng_args; p.tickets = (int*)(h->rng_draws + r0); p.max_ctx = r0; }
-	float* hid = hidden_out ? hidden_out + (size_t)r0 * d : nullptr;
-	if (h->head_split && whole) {
-		// ln_f + final_norm ONCE (4 workgroups), the mel head as a plain 513-tile GEMV over the normalised rows in fragment order: with the
-		// norms inside the GEMV every one of the 513 workgroups normalised all 16 rows, two passes each -- 17 us for 16.8 MB of weights
-		if (h->ring_base && !hid) launch_layernorm(dt, x, d, nrows, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, h->attn_out, d, 0, s, 1, nullptr, h->ring_idx, h->ring_stride, h->d_ring);
-		else launch_layernorm(dt, x, d, nrows, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, h->attn_out, d, 0, s, 1, hid);
-		p.a = h->attn_out; p.lda = d; p.a_frag = 1;
-		GemvParams gh = {};
-		gh.Wp = p.Wp; gh.a = h->attn_out; gh.bias = p.bias; gh.out_f32 = p.out_f32; gh.d_pos = p.d_pos; gh.noise = p.qbuf; gh.rng = p.slab; gh.draws = (const int64_t*)p.tickets;
-		gh.M = nrows; gh.N = c.number_mel_codes; gh.K = d; gh.row0 = r0;
-		if (!(lean && launch_gemv(dt, GV_HEAD, gh, s)))
-			launch_skinny(dt, p, 4, s);      // 4-wave workgroups: five fit a CU, so the 513 tiles run as one round (two 8-wave ones fit: 512 slots)
-	} else {
-		p.ln_count = 2; p.x = x; p.ldx = d;
-		p.g1 = h->lnf_g; p.b1 = h->lnf_b; p.g2 = h->fn_g; p.b2 = h->fn_b; p.ln_out = hid;
-		launch_skinny(dt, p, d >= 1024 ? h->wv_head : 4, s);
-	}
+	// ln_f + final_norm ONCE (4 workgroups), the mel head as a plain 513-tile GEMV over the normalised rows in fragment order: with the norms inside the
+	// GEMV every one of the 513 workgroups normalised all 16 rows, two passes each -- 17 us for 16.8 MB of weights
+	if (h->ring_base && !hidden_out) launch_layernorm(dt, h->x, d, B, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, h->attn_out, d, 0, s, 1, nullptr, h->ring_idx, h->ring_stride, h->d_ring);
+	else launch_layernorm(dt, h->x, d, B, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, h->attn_out, d, 0, s, 1, hidden_out);
+	DecodeLaunch head = {DR_HEAD, &h->head, c.number_mel_codes, d, h->attn_out};
+	head.out_f32 = logits_out; head.bump = true;      // the last launch of the step advances the cache length
+	decode_launch(h, head, B, s);
 }
 
 extern "C" {
@@ -313,10 +292,9 @@ int ttk_ar_create(ttk_ar** out, const ttk_ar_config* cfg, const ttk_weight_view*
 		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "attn.c_proj.weight", p + "attn.c_proj.bias", PK_KN, d, d, true, &L.proj));
 		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", PK_KN, 4 * d, d, true, &L.fc));
 		TTK_TRY(upload_mat(h->arena, wm, h->wdt, p + "mlp.c_proj.weight", p + "mlp.c_proj.bias", PK_KN, d, 4 * d, true, &L.proj2));
-		{   // (fp8 weights: the fold is taken of the rounded matrices and kept in bf16 -- TTK_FP8W stays "bf16 on the rounded weights")
-			TTK_TRY(fold_layernorm(h->arena, wm, h->dt, p + "attn.c_attn.weight", p + "attn.c_attn.bias", p + "ln_1.weight", p + "ln_1.bias", &L.attn));
-			TTK_TRY(fold_layernorm(h->arena, wm, h->dt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", p + "ln_2.weight", p + "ln_2.bias", &L.fc));
-		}
+		// (fp8 weights: the fold is taken of the rounded matrices and kept in bf16 -- TTK_FP8W stays "bf16 on the rounded weights")
+		TTK_TRY(fold_layernorm(h->arena, wm, h->dt, p + "attn.c_attn.weight", p + "attn.c_attn.bias", p + "ln_1.weight", p + "ln_1.bias", &L.attn));
+		TTK_TRY(fold_layernorm(h->arena, wm, h->dt, p + "mlp.c_fc.weight", p + "mlp.c_fc.bias", p + "ln_2.weight", p + "ln_2.bias", &L.fc));
 	}
 	TTK_TRY(upload_f32(h->arena, wm, "gpt.ln_f.weight", d, &h->lnf_g));
 	TTK_TRY(upload_f32(h->arena, wm, "gpt.ln_f.bias", d, &h->lnf_b));
@@ -359,43 +337,13 @@ int ttk_ar_create(ttk_ar** out, const ttk_ar_config* cfg, const ttk_weight_view*
 	if (hipMemset(h->hbuf, 0, frag_rows * 4 * d * h->es) != hipSuccess) return TTK_E_HIP;
 	TTK_TRY(h->arena.alloc(&h->x_frag, frag_rows * d * h->es));
 	if (hipMemset(h->x_frag, 0, frag_rows * d * h->es) != hipSuccess) return TTK_E_HIP;
-	TTK_TRY(h->arena.alloc((void**)&h->slab, (size_t)4 * (d / 16) * 4 * 4 * 256 * sizeof(float)));
-	TTK_TRY(h->arena.alloc((void**)&h->tickets, (size_t)4 * (d / 16) * sizeof(int)));
-	if (hipMemset(h->tickets, 0, (size_t)4 * (d / 16) * sizeof(int)) != hipSuccess) return TTK_E_HIP;
 	{
 		const char* ep = getenv("TTK_DEBUG_POISON");
 		h->poison = ep && atoi(ep) != 0;
-		const char* en = getenv("TTK_AR_NARROW");
-		h->narrow = en ? atoi(en) : 4;                    // 0 = 16-column workgroups (+ split-K for mlp.c_proj), 2 / 4 = workgroups per tile
-		const char* ef = getenv("TTK_AR_HFRAG");
-		h->hfrag = ef ? (atoi(ef) != 0) : 1;
-		const char* en2 = getenv("TTK_AR_NARROW2");
-		h->narrow2 = en2 ? atoi(en2) : h->narrow;
-		const char* e1 = getenv("TTK_AR_WV_PROJ");
-		const char* e2 = getenv("TTK_AR_WV_PROJ2");
-		if (e1 && atoi(e1) >= 4 && atoi(e1) <= 16) h->wv_proj = atoi(e1);
-		if (h->dt == DT_F32) { h->wv_proj = 8; h->wv_ln = 8; h->wv_proj2 = 8; }      // batches of 4 k-steps: 32 / 4 = 8 waves; K = 4096: 4 batches each
-		if (e2 && atoi(e2) >= 4 && atoi(e2) <= 16) h->wv_proj2 = atoi(e2);
-		const char* e4 = getenv("TTK_AR_WV_LN");
-		if (e4 && atoi(e4) >= 4 && atoi(e4) <= 16) h->wv_ln = atoi(e4);
-		const char* e3 = getenv("TTK_AR_WV_HEAD");
-		if (e3 && (atoi(e3) == 4 || atoi(e3) == 8)) h->wv_head = atoi(e3);
-		const char* es = getenv("TTK_AR_SHARE_PREFIX");
-		h->share_prefix = es ? (atoi(es) != 0) : 1;
-		const char* eh = getenv("TTK_AR_HEAD_SPLIT");
-		h->head_split = eh ? (atoi(eh) != 0) : 1;
 		const char* el = getenv("TTK_AR_LNFOLD");
 		h->lnfold = el ? (atoi(el) != 0) : 1;
 		const char* eg = getenv("TTK_AR_LEAN");
 		h->lean = eg ? (atoi(eg) != 0) : 1;
-		const char* e = getenv("TTK_AR_SPLIT");
-		h->nsplit = e ? atoi(e) : 1;
-		if (h->nsplit != 1 && h->nsplit != 2 && h->nsplit != 4) h->nsplit = 1;
-		if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) return TTK_E_HIP;
-		for (int i = 0; i < 3; ++i) {
-			if (hipStreamCreateWithFlags(&h->side[i], hipStreamNonBlocking) != hipSuccess) return TTK_E_HIP;
-			if (hipEventCreateWithFlags(&h->ev_join[i], hipEventDisableTiming) != hipSuccess) return TTK_E_HIP;
-		}
 	}
 	hipError_t e = hipDeviceSynchronize();
 	if (e != hipSuccess) { set_error("ttk_ar_create: %s", hipGetErrorString(e)); return TTK_E_HIP; }
@@ -426,7 +374,7 @@ static int prefill_impl(ttk_ar* h, const float* cond_latent, int Bc, const int64
 	// the prefix is run ONCE and its cache rows live in candidate 0's slice only -- the decode attention reads rows [0, S) there for every
 	// candidate (AttnDecodeParams.shared_rows) -- and the last row / the logits are replicated.  (A prompt shared by all candidates is part of that
 	// prefix; with one prompt per candidate every candidate's rows are run and cached on their own.)
-	const bool shared = Bc == 1 && B > 1 && h->share_prefix && h->nsplit == 1 && (n_in == 0 || prompt_rows == 1);
+	const bool shared = Bc == 1 && B > 1 && (n_in == 0 || prompt_rows == 1);
 	const int Bp = shared ? 1 : B;
 	TTK_TRY(h->ws_x.reserve((size_t)Bp * S * d * sizeof(float)));
 	float* x = (float*)h->ws_x.p;
@@ -435,7 +383,7 @@ static int prefill_impl(ttk_ar* h, const float* cond_latent, int Bc, const int64
 					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, x, prompt, prompt_rows, n_in);
 	TTK_TRY(dense_forward(h, x, Bp, S, true, s));
 	launch_copy_rows(x + (size_t)(S - 1) * d, shared ? 0 : (int64_t)S * d, h->x, d, B, d, s);      // source stride 0: one row to all candidates
-	head_launch(h, B, logits_out, nullptr, s);
+	head_launch(h, B, logits_out, s);
 	launch_set_int(h->d_pos, S, s);
 	launch_set_int(h->d_pos + 1, shared ? S : 0, s);      // rows of the shared prefix (AttnDecodeParams.shared_rows): device-resident, like the cache length
 	TTK_TRY(poison_scratch(h, s));
@@ -467,7 +415,6 @@ int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* te
 	const ttk_ar_config& c = h->cfg;
 	const int B = n_lines * rows_per_line, d = c.model_dim;
 	TTK_REQUIRE(n_lines >= 1 && rows_per_line >= 1 && B <= c.max_batch, TTK_E_ARG, "ttk_ar_prefill_lines: %d lines x %d candidates exceed max_batch=%d", n_lines, rows_per_line, c.max_batch);
-	TTK_REQUIRE(h->share_prefix && h->nsplit == 1, TTK_E_STATE, "ttk_ar_prefill_lines: needs the shared-prefix decode (TTK_AR_SHARE_PREFIX=1, TTK_AR_SPLIT=1)");
 	int Smax = 0;
 	for (int g = 0; g < n_lines; ++g) {
 		const int Tt = text_len[g];
@@ -491,7 +438,7 @@ int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* te
 		launch_fill_int2((int*)(h->d_rowinfo + r0), start, r0, rows_per_line, s);
 		toff += Tt;
 	}
-	head_launch(h, B, logits_out, nullptr, s);
+	head_launch(h, B, logits_out, s);
 	launch_set_int(h->d_pos, Smax, s);
 	launch_set_int(h->d_pos + 1, Smax, s);
 	TTK_TRY(poison_scratch(h, s));
@@ -509,33 +456,13 @@ static int decode_impl(ttk_ar* h, const int64_t* tok, float* logits_out, float* 
 	TTK_REQUIRE(h->Pmax + 1 + h->k + 1 <= c.max_ctx, TTK_E_STATE, "%s: KV cache full (max_ctx=%d)", who, c.max_ctx);
 	TTK_REQUIRE(B <= c.max_batch && 16 * decode_row_tiles(B) <= h->frag_rows, TTK_E_STATE, "%s: %d rows request %d fragment rows, the handle holds %d (max_batch=%d)", who, B,
 				16 * decode_row_tiles(B), h->frag_rows, c.max_batch);
-	TTK_REQUIRE((h->lnfold && h->nsplit == 1) || B <= 32, TTK_E_STATE, "%s: the LayerNorm-prologue decode kernels (TTK_AR_LNFOLD=0 / TTK_AR_SPLIT) hold at most 32 candidates' rows in LDS; B=%d", who, B);
+	TTK_REQUIRE(h->lnfold || B <= 32, TTK_E_STATE, "%s: the LayerNorm-prologue decode kernels (TTK_AR_LNFOLD=0) hold at most 32 candidates' rows in LDS; B=%d", who, B);
 	TTK_REQUIRE(h->k + 2 < c.max_mel_seq_len, TTK_E_STATE, "%s: mel position table exhausted (%d rows)", who, c.max_mel_seq_len);
-	TTK_REQUIRE(!h->ring_base || (h->head_split && h->nsplit == 1), TTK_E_STATE, "%s: the hidden ring needs the default decode form (TTK_AR_HEAD_SPLIT=1, TTK_AR_SPLIT=1)", who);
 	hipStream_t s = (hipStream_t)stream;
 	// x[b] = mel_embedding[tok] + mel_pos[k + 1]; *d_pos = P + k rows are cached  =>  offset 1 - P   (unified_voice.py:213-214)
 	// (tok == null: ttk_ar_sample_next has written the rows already)
 	if (tok) launch_decode_embed(h->mel_emb, tok, h->mel_pos, h->d_pos, 1 - h->P, c.max_mel_seq_len, h->x, B, d, s, h->lnfold ? h->x_frag : nullptr, elem_kind(h->dt));
-	// Experiment kept behind TTK_AR_SPLIT (default 1 = off): cut the candidates into row groups whose launch chains run on forked
-	// streams.  Rows are independent, so results are unchanged -- but on MI355X it LOSES (B=16, 250 tokens: 283 ms -> 340 ms with
-	// 2 groups, 517 ms with 4): the LayerNorm kernels already hold one 8-wave workgroup per CU, so the second chain cannot
-	// co-reside and only the doubled weight traffic remains.
-	int nsplit = h->nsplit;
-	while (nsplit > 1 && B / nsplit < 1) nsplit >>= 1;
-	if (nsplit > 1) {
-		TTK_HIP(hipEventRecord(h->ev_fork, s));
-		for (int gi = 1; gi < nsplit; ++gi) TTK_HIP(hipStreamWaitEvent(h->side[gi - 1], h->ev_fork, 0));
-	}
-	for (int gi = 0; gi < nsplit; ++gi) {
-		hipStream_t gs = gi == 0 ? s : h->side[gi - 1];
-		const int r0 = (B * gi) / nsplit, r1 = (B * (gi + 1)) / nsplit;
-		decode_rows(h, r0, r1 - r0, gi, logits_out, hidden_out, gs, nsplit == 1);
-	}
-	for (int gi = 1; gi < nsplit; ++gi) {
-		TTK_HIP(hipEventRecord(h->ev_join[gi - 1], h->side[gi - 1]));
-		TTK_HIP(hipStreamWaitEvent(s, h->ev_join[gi - 1], 0));
-	}
-	if (nsplit > 1) launch_add_int(h->d_pos, 1, s);
+	decode_rows(h, logits_out, hidden_out, s);
 	h->k += 1;
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

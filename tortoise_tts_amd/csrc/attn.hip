@@ -485,19 +485,8 @@ void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s, int form) {
 __device__ __forceinline__ int64_t decode_out_index(const AttnDecodeParams& p, int b, int h, int e) {
 	if (!p.out_frag) return ((int64_t)b * p.H + h) * HD + e;
 	const int n = h * HD + e;
-	return ((((int64_t)(b >> 4) * (p.H * HD / 32) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (b & 15)) * 8 + (n & 7));
+	return TTK_FRAG_INDEX(b, n, p.H * HD / 32);
 }
-
-#if defined(TTK_STAMPS) && TTK_STAMPS == 2   // tests/diag/ar_chain.cpp: every wave stamps, [workgroup][wave (16 slots)][8]; slot 7 = XCC id
-#define TTK_ASTAMP(i) do { if (p.stamps && (threadIdx.x & 63) == 0) { unsigned long long* st_ = p.stamps + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (threadIdx.x >> 6)) * 8; \
-	st_[(i)] = __builtin_amdgcn_s_memrealtime(); if ((i) == 0) st_[7] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)); } } while (0)
-#define TTK_ASTAMPD(i, dep) do { if (p.stamps) { unsigned tmp_; unsigned long long t_; \
-	asm volatile("s_nop 7\n\tv_readfirstlane_b32 %0, %2\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(tmp_), "=s"(t_) : "v"(dep) : "memory"); \
-	if ((threadIdx.x & 63) == 0) p.stamps[((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (threadIdx.x >> 6)) * 8 + (i)] = t_; } } while (0)
-#else
-#define TTK_ASTAMP(i) do {} while (0)
-#define TTK_ASTAMPD(i, dep) do {} while (0)
-#endif
 
 // The position line (round 5).  Every K / V address of the decode attention depends on the cache length, which lives in device memory (one captured step serves every
 // token), behind a pointer that arrives with the kernel arguments: two DEPENDENT round trips -- arguments, then position -- before the first key is asked for (1.52 us from a
@@ -531,7 +520,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode(AttnDecodeParams p) {
 	const int h = blockIdx.x, b = blockIdx.y;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int slot = lane >> 3, dg = lane & 7;
-	TTK_ASTAMP(0);
+	TTK_WSTAMP(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 0);
 #ifdef TTK_ABL      // diagnostic builds only (tests/diag/ar_ablate.sh): 256 = the whole kernel, 128 = the K / V loads
 	if (TTK_ABL & 256) return;
 #endif
@@ -578,7 +567,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode(AttnDecodeParams p) {
 #pragma unroll
 		for (int j = 0; j < 8; ++j) q[j] = qp[j] * LOG2E;   // log2-domain scores: exp2 is a single v_exp_f32
 	}
-	TTK_ASTAMPD(1, (float)(n + shared) + q[0]);      // cache length, shared-prefix length and the query are there
+	TTK_WSTAMPD(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 1, (float)(n + shared) + q[0]);      // cache length, shared-prefix length and the query are there
 	float m = NEG_BIG, l = 0.f, acc[8];
 #pragma unroll
 	for (int j = 0; j < 8; ++j) acc[j] = 0.f;
@@ -604,7 +593,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode(AttnDecodeParams p) {
 		gb += NW * UN;
 		if (gb < groups) request(gb);
 	}
-	TTK_ASTAMPD(2, acc[0] + l);                      // this wave's keys are in and reduced
+	TTK_WSTAMPD(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 2, acc[0] + l);                      // this wave's keys are in and reduced
 	// merge the NP partial softmaxes through LDS in two levels.  Level 1 is wave-private: a wave folds its own 8 slots (lane = head dim) as soon as
 	// its keys are done -- no workgroup barrier in front of it, so it runs inside the time the wave would otherwise wait for the slowest one -- and
 	// publishes ONE partial; after the only barrier 64 threads fold the NW wave partials.  (First version: barrier, 4 waves folding 32 partials
@@ -627,7 +616,7 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode(AttnDecodeParams p) {
 		so2[wave][lane] = ot;
 	}
 	__syncthreads();
-	TTK_ASTAMP(3);
+	TTK_WSTAMP(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 3);
 	if (tid < HD) {
 		float mn = NEG_BIG;
 #pragma unroll
@@ -637,10 +626,10 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode(AttnDecodeParams p) {
 		for (int i = 0; i < NW; ++i) { const float a = __builtin_amdgcn_exp2f(sm2[i] - mn); lt += sl2[i] * a; ot += so2[i][tid] * a; }
 		((T*)p.out)[decode_out_index(p, b, h, tid)] = cvt<T>(ot / lt);
 	}
-	TTK_ASTAMP(5);
+	TTK_WSTAMP(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 5);
 #if defined(TTK_STAMPS) && TTK_STAMPS == 2
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	TTK_ASTAMP(6);
+	TTK_WSTAMP(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 6);
 #endif
 }
 

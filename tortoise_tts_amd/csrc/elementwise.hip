@@ -6,9 +6,7 @@
 namespace ttk {
 
 __global__ void k_set_int(int* p, int v) { *p = v; }
-__global__ void k_add_int(int* p, int v) { *p += v; }
 void launch_set_int(int* p, int v, hipStream_t s) { hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, p, v); }
-void launch_add_int(int* p, int v, hipStream_t s) { hipLaunchKernelGGL(k_add_int, dim3(1), dim3(1), 0, s, p, v); }
 __global__ void k_fill_int(int* p, int v, int n) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
 void launch_fill_int(int* p, int v, int n, hipStream_t s) { if (n > 0) hipLaunchKernelGGL(k_fill_int, dim3((n + 255) / 256), dim3(256), 0, s, p, v, n); }
 __global__ void k_fill_int2(int* p, int a, int b, int n) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) { p[2 * i] = a; p[2 * i + 1] = b; } }
@@ -44,7 +42,7 @@ __global__ void k_decode_embed(const float* emb, const int64_t* tok, const float
 	const float4 v = make_float4(e.x + w.x, e.y + w.y, e.z + w.z, e.w + w.w);
 	*(float4*)(out + (int64_t)b * d + c) = v;
 	if (frag) {
-		const int64_t fi = ((((int64_t)(b >> 4) * (d / 32) + (c >> 5)) * 64 + ((c >> 3) & 3) * 16 + (b & 15)) * 8 + (c & 7));
+		const int64_t fi = TTK_FRAG_INDEX(b, c, d / 32);
 		store4_kind(frag, fi, v, frag_f32);      // frag_f32: ttk::ElemKind of the copy
 	}
 }

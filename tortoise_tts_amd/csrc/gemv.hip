@@ -3,15 +3,16 @@
 //
 // Why a second kernel family beside k_skinny (skinny.hip): in-kernel timestamps of every wave (tests/diag/ar_chain.cpp, profiles/
 // r03_ar_chain_*.log) showed the generic kernel spending 1.2 - 1.5 us between a wave's first instruction and its first weight request -- as
-// long as the weights then take to arrive.  Its prologue is ~350 instructions of run-time shape arithmetic (integer divisions by ksplit / narrow /
-// waves, mode branches) issued by one wave per SIMD, and it reads its 248 bytes of kernel arguments in FOUR dependent scalar-load round trips
+// long as the weights then take to arrive.  Its prologue was ~350 instructions of run-time shape arithmetic (integer divisions by the waves per
+// workgroup and, then, by split-K and column-group counts; mode branches) issued by one wave per SIMD, and it read its 248 bytes of kernel arguments in FOUR dependent scalar-load round trips
 // (the compiler sinks each field's load next to its first use, behind branches), the second of which also waits for the cache-length word.
 // Here the role (epilogue), the waves per workgroup, the k-steps per wave and the tile geometry are template parameters, the arguments are 37
 // dwords pinned into SGPRs by ONE batch of scalar loads, and the first weight request leaves ~40 instructions after the wave starts.
 // The products are k_skinny's, operation for operation (same fragments, same k order per wave, same wave order in the cross-wave sum), so the
 // projections and the head are bit-identical to the generic kernel's; the folded launches differ from it only in how a lane sums its row
-// statistics (dot2 instructions, see fold_stats) -- a few ulp of mean / rstd.  k_skinny stays the path for every other geometry (small models,
-// row groups, LayerNorm-prologue form, split-K) and is what tests/test_gpu_gemv.py compares against.
+// statistics (dot2 instructions, see fold_stats) -- a few ulp of mean / rstd.  k_skinny stays the path for every other geometry (small models, the
+// LayerNorm-prologue form of TTK_AR_LNFOLD=0, the prefill's head) and, with TTK_AR_LEAN=0, is what tests/test_gpu_gemv.py compares against.  The
+// caller describes a launch once and fills both parameter blocks from it (ar.hip: decode_launch).
 //
 //   GV_QKV   ln_1 (folded) + c_attn + bias -> q (pre-scaled) / K, V appended to the cache   (HF:models/gpt2/modeling_gpt2.py:144-226)
 //   GV_PROJ  c_proj / mlp.c_proj + bias + residual, 4-column workgroups; also writes the T-typed fragment-order copy of the rows
@@ -26,41 +27,6 @@
 #include "ttk_rng.h"
 
 namespace ttk {
-
-#ifndef TTK_NT
-#define TTK_NT 1
-#endif
-#if TTK_NT
-#define GV_WLOAD(p) __builtin_nontemporal_load(p)
-#else
-#define GV_WLOAD(p) (*(p))
-#endif
-
-#if defined(TTK_STAMPS) && TTK_STAMPS == 2   // tests/diag/ar_chain.cpp: every wave stamps, [workgroup][wave (16 slots)][8]; slot 7 = XCC id
-#define GV_STAMP(i) do { if (p.stamps && (threadIdx.x & 63) == 0) { unsigned long long* st_ = p.stamps + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8; \
-	st_[(i)] = __builtin_amdgcn_s_memrealtime(); if ((i) == 0) st_[7] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)); } } while (0)
-#define GV_STAMPD(i, dep) do { if (p.stamps) { unsigned tmp_; unsigned long long t_; \
-	asm volatile("s_nop 7\n\tv_readfirstlane_b32 %0, %2\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(tmp_), "=s"(t_) : "v"(dep) : "memory"); \
-	if ((threadIdx.x & 63) == 0) p.stamps[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + (i)] = t_; } } while (0)
-#else
-#define GV_STAMP(i) do {} while (0)
-#define GV_STAMPD(i, dep) do {} while (0)
-#endif
-
-// weight fragment as stored: the MFMA operand, or (W8, bf16 arithmetic) 8 fp8-e4m3 bytes widened exactly next to their MFMA (skinny.hip: WFrag)
-template <typename T, bool W8> struct GvW {
-	typedef typename Frag<T>::type raw;
-	static __device__ __forceinline__ typename Frag<T>::type dec(raw r) { return r; }
-};
-template <> struct GvW<bf16, true> {
-	typedef unsigned raw __attribute__((ext_vector_type(2)));
-	static __device__ __forceinline__ bf16x8 dec(raw r) {
-		typedef float f2 __attribute__((ext_vector_type(2)));
-		const f2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[0], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[0], true);
-		const f2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[1], false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[1], true);
-		return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)b[0], (bf16)b[1], (bf16)c[0], (bf16)c[1], (bf16)d[0], (bf16)d[1]};
-	}
-};
 
 // Folded LayerNorm: a lane's contribution to its row's sum and sum of squares from the 8 elements of one A fragment.  16-bit types: two
 // v_dot2c_f32_{bf16,f16} per element pair (x.x and x.1, f32 accumulate) instead of unpack + add + fma per element -- 8 VALU issues per
@@ -94,7 +60,7 @@ template <> __device__ __forceinline__ void fold_stats<f16>(const f16x8& a, floa
 template <typename T, int MT, int ROLE, int NW, int KPW, bool W8>
 __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 	typedef typename Frag<T>::type FragT;
-	typedef GvW<T, W8> WF;
+	typedef WFrag<T, W8> WF;
 	typedef typename WF::raw WRaw;
 	constexpr int ES = sizeof(T);
 	constexpr bool FOLD = ROLE == GV_QKV || ROLE == GV_FC;
@@ -107,7 +73,7 @@ __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 	// use: four dependent round trips before the first weight request)
 	asm volatile("" :: "s"(p.Wp), "s"(p.a), "s"(p.bias), "s"(p.csum), "s"(p.out_f32), "s"(p.out_T), "s"(p.qbuf), "s"(p.kcache), "s"(p.vcache),
 				 "s"(p.d_pos), "s"(p.noise), "s"(p.rng), "s"(p.draws), "s"(p.health), "s"(p.M), "s"(p.N), "s"(p.max_ctx), "s"(p.H), "s"(p.row0), "s"(p.q_scale), "s"(p.wscale));
-	GV_STAMP(0);
+	TTK_WSTAMP(p.stamps, blockIdx.x, 0);
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	int nt, sub = 0;
 	if (NARROW) { const int b = blockIdx.x; nt = ((b >> 5) << 3) + (b & 7); sub = (b >> 3) & 3; }   // the 4 workgroups of a tile: ids equal mod 8 -> one XCD, one L2
@@ -163,13 +129,13 @@ __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 		const WRaw* wd = (const WRaw*)p.Wp + ((int64_t)nt * KS + ks0 + (lane >> 4)) * 64 + ((lane >> 2) & 3) * 16 + 4 * sub + (lane & 3);
 		WRaw wq[WL];
 #pragma unroll
-		for (int i = 0; i < WL; ++i) wq[i] = GV_WLOAD(wd + i * 4 * 64);
+		for (int i = 0; i < WL; ++i) wq[i] = TTK_WLOAD(wd + i * 4 * 64);
 		FragT a0[PRE][MT];
 #pragma unroll
 		for (int u = 0; u < PRE; ++u)
 #pragma unroll
 			for (int mt = 0; mt < MT; ++mt) a0[u][mt] = ap[((int64_t)mt * KS + u) * 64];
-		GV_STAMP(2);
+		TTK_WSTAMP(p.stamps, blockIdx.x, 2);
 		__builtin_amdgcn_sched_barrier(0);
 #pragma unroll
 		for (int i = 0; i < WL; ++i) wl[i * 64 + lane] = wq[i];
@@ -204,11 +170,11 @@ __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 		FragT a[PRE][MT];
 #pragma unroll
 		for (int u = 0; u < PRE; ++u) {
-			b[u] = GV_WLOAD(wp + (kb + u) * 64);
+			b[u] = TTK_WLOAD(wp + (kb + u) * 64);
 #pragma unroll
 			for (int mt = 0; mt < MT; ++mt) a[u][mt] = ap[((int64_t)mt * KS + kb + u) * 64];
 		}
-		if (kb == 0) GV_STAMP(2);
+		if (kb == 0) TTK_WSTAMP(p.stamps, blockIdx.x, 2);
 		__builtin_amdgcn_sched_barrier(0);      // keep the requests in front: sunk next to their MFMAs they become dependent round trips
 #pragma unroll
 		for (int u = 0; u < PRE; ++u)
@@ -227,12 +193,12 @@ __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 			if (lane < 16) *(float2*)(rstat + ((wave * MT + mt) * 16 + lane) * 2) = make_float2(fs1[mt], fs2[mt]);
 		}
 	}
-	GV_STAMPD(3, acc[0][0]);
+	TTK_WSTAMPD(p.stamps, blockIdx.x, 3, acc[0][0]);
 	// ---- cross-wave sum through LDS (wave order), epilogue by the first 256 threads
 #pragma unroll
 	for (int mt = 0; mt < MT; ++mt) *(f32x4*)(red + ((wave * MT + mt) * 64 + lane) * 4) = acc[mt];
 	__syncthreads();
-	GV_STAMP(4);
+	TTK_WSTAMP(p.stamps, blockIdx.x, 4);
 	if (!mine) return;
 #pragma unroll
 	for (int mt = 0; mt < MT; ++mt) {
@@ -268,9 +234,9 @@ __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 			}
 		} else if (ROLE == GV_PROJ) {
 			p.out_f32[(int64_t)m * p.N + n] = res[mt] + v;
-			if (p.out_T) ((T*)p.out_T)[((((int64_t)mt * (p.N >> 5) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (m & 15)) * 8 + (n & 7))] = cvt<T>(res[mt] + v);
+			if (p.out_T) ((T*)p.out_T)[TTK_FRAG_INDEX(m, n, p.N >> 5)] = cvt<T>(res[mt] + v);
 		} else if (ROLE == GV_FC) {
-			((T*)p.out_T)[((((int64_t)mt * (p.N >> 5) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (m & 15)) * 8 + (n & 7))] = cvt<T>(gelu_new_f(v));
+			((T*)p.out_T)[TTK_FRAG_INDEX(m, n, p.N >> 5)] = cvt<T>(gelu_new_f(v));
 		} else {   // GV_QKV: n in [0, 3d), d = 32 * KS
 			constexpr int d = 32 * KS;
 			const int which = n / d, c = n - which * d;
@@ -283,10 +249,10 @@ __global__ __launch_bounds__(64 * NW) void k_gemv(GemvParams p) {
 			}
 		}
 	}
-	GV_STAMP(5);
+	TTK_WSTAMP(p.stamps, blockIdx.x, 5);
 #if defined(TTK_STAMPS) && TTK_STAMPS == 2
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	GV_STAMP(6);
+	TTK_WSTAMP(p.stamps, blockIdx.x, 6);
 #endif
 }
 

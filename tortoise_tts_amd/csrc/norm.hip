@@ -78,7 +78,7 @@ __global__ void k_layernorm(const float* x, int64_t ldx, int rows, int d, const 
 		const int c = lane + 64 * i;
 		if (c < nchunk) {
 			const int n = 4 * c;
-			OT* o = frag ? out + ((((int64_t)(row >> 4) * (d / 32) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (row & 15)) * 8 + (n & 7)) : out + (int64_t)row * ldo + n;
+			OT* o = frag ? out + TTK_FRAG_INDEX(row, n, d / 32) : out + (int64_t)row * ldo + n;
 			o[0] = (OT)v[i].x; o[1] = (OT)v[i].y; o[2] = (OT)v[i].z; o[3] = (OT)v[i].w;
 			if (out2) *(float4*)(out2 + (int64_t)row * d + n) = v[i];
 		}

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step(SampleParams p) 
 			o[i] = v;
 			if (p.x_frag) {   // element (m = b, n = 4i + j) of [m_tile][d/32][lane = (n>>3 & 3) * 16 + (m & 15)][n & 7]: four consecutive n are contiguous
 				const int n = 4 * i;
-				const int64_t fi = ((((int64_t)(b >> 4) * (p.d / 32) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (b & 15)) * 8 + (n & 7));
+				const int64_t fi = TTK_FRAG_INDEX(b, n, p.d / 32);
 				store4_kind(p.x_frag, fi, v, p.x_frag_f32);      // x_frag_f32: ttk::ElemKind of the copy
 			}
 		}

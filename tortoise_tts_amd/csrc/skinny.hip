@@ -2,18 +2,25 @@
 //
 //   out[M, N] = epilogue( LN?(x)[M, K] * W[N, K]^T + bias )
 //
-// One workgroup per 16-column n-tile; its waves split K; every wave streams its slice of the weights exactly once,
-// straight from HBM into MFMA B-operand registers (no LDS round trip: "GEMV / M <= 16 decode weights" row of
-// cdna_hip_programming.md section 5).  Weights are stored in MFMA-fragment order  Wp[n_tile][k_step][lane][8]
-// so one wave instruction reads 1 KiB (bf16) of contiguous memory.  The batch rows are the MFMA M dimension
-// (16 candidates = one 16x16 tile, MT tiles for bigger shards).
+// One workgroup per 16-column n-tile (four per tile, 4 columns each, for the residual projections); its waves split K; every
+// wave streams its slice of the weights exactly once, straight from HBM into MFMA B-operand registers (no LDS round trip:
+// "GEMV / M <= 16 decode weights" row of cdna_hip_programming.md section 5).  Weights are stored in MFMA-fragment order
+// Wp[n_tile][k_step][lane][8] so one wave instruction reads 1 KiB (bf16) of contiguous memory.  The batch rows are the MFMA M
+// dimension (16 candidates = one 16x16 tile, MT tiles for bigger shards) and arrive either as f32 rows that the launch
+// normalises itself (LayerNorm prologue) or T-typed in A-fragment order (ttk_common.h: TTK_FRAG_INDEX).
+//
+// This is the generic kernel: any model_dim, any waves per workgroup.  The decode step at the benchmarked geometry runs on the
+// compile-time specialisations of gemv.hip, which repeat this kernel's arithmetic operation for operation; k_skinny serves the
+// small models, the LayerNorm-prologue form (TTK_AR_LNFOLD=0), the prefill's head, and TTK_AR_LEAN=0 -- the reference
+// tests/test_gpu_gemv.py holds k_gemv against.  Forms that measured slower and were removed are listed in DESIGN.md section 5.
 //
 // Fused prologues/epilogues (one launch per GPT-2 sub-block, reference ops in parentheses):
 //   LN1 + c_attn + bias -> q (pre-scaled) / K,V appended to the cache  (HF:models/gpt2/modeling_gpt2.py:144-226,
 //        DynamicCache.update)                                                         SK_QKV
 //   c_proj + bias + residual add                                                       SK_RESIDUAL
 //   LN2 + c_fc + bias + gelu_new  (HF:activations.py:59-66)                            SK_ACT_T
-//   ln_f + final_norm + mel_head  (unified_voice.py:106,239)                           SK_STORE_F32, ln_count = 2
+//   ln_f + final_norm + mel_head  (unified_voice.py:106,239)                           SK_STORE_F32, ln_count = 2 (prefill)
+//   mel_head over normalised rows (+ multinomial noise, + the cache-length bump)       SK_STORE_F32 (decode)
 // Algorithmic bytes per launch: N*K*sizeof(T) weight bytes (+ M*K*4 activations from L2).
 #include <hip/hip_ext.h>
 
@@ -23,18 +30,6 @@
 
 namespace ttk {
 
-// Diagnostic build only (-DTTK_STAMPS, tests/diag/skinny_stamps.cpp): wave 0 / lane 0 of every workgroup records a 100 MHz
-// timestamp per phase.  Expands to nothing in the product build.
-// weight-stream cache policy: non-temporal (streamed once per token) unless built with -DTTK_NT=0
-#ifndef TTK_NT
-#define TTK_NT 1
-#endif
-#if TTK_NT
-#define TTK_WLOAD(p) __builtin_nontemporal_load(p)
-#else
-#define TTK_WLOAD(p) (*(p))
-#endif
-
 // Diagnostic builds only (-DTTK_ABL=<bits>, tests/diag/ar_ablate.sh): leave out one part of the kernel to price it in the real decode loop
 // (results are then wrong on purpose).  1 LayerNorm statistics + affine, 2 gamma / beta loads, 4 cross-wave reduction, 8 weight loads,
 // 16 activation loads, 32 output stores, 64 the whole kernel.  Expands to nothing in the product build.
@@ -42,37 +37,15 @@ namespace ttk {
 #define TTK_ABL 0
 #endif
 
-#if defined(TTK_STAMPS) && TTK_STAMPS == 2   // tests/diag/ar_chain.cpp: every wave stamps, [workgroup][wave (16 slots)][8]; slot 7 = XCC id
-#define TTK_STAMP(i) do { if (p.stamps && (threadIdx.x & 63) == 0) { unsigned long long* st_ = p.stamps + ((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8; \
-	st_[(i)] = __builtin_amdgcn_s_memrealtime(); if ((i) == 0) st_[7] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)); } } while (0)
-// stamp taken only once `dep` (a VGPR value: an accumulator, a loaded word) is really there: the asm reads it, so the wave stalls on the MFMA /
-// the load that produces it first -- a bare s_memrealtime has no data dependency and floats above the arithmetic it is meant to follow
-#define TTK_STAMPD(i, dep) do { if (p.stamps) { unsigned tmp_; unsigned long long t_; \
-	asm volatile("s_nop 7\n\tv_readfirstlane_b32 %0, %2\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(tmp_), "=s"(t_) : "v"(dep) : "memory"); \
-	if ((threadIdx.x & 63) == 0) p.stamps[((size_t)blockIdx.x * 16 + (threadIdx.x >> 6)) * 8 + (i)] = t_; } } while (0)
-#elif defined(TTK_STAMPS)
-#define TTK_STAMP(i) do { if (p.stamps && threadIdx.x == 0) p.stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define TTK_STAMPD(i, dep) TTK_STAMP(i)
+// Diagnostic builds only: -DTTK_STAMPS=2 (tests/diag/ar_chain.cpp) every wave stamps (ttk_common.h); plain -DTTK_STAMPS (tests/diag/skinny_stamps.cpp)
+// wave 0 / lane 0 of every workgroup records a 100 MHz timestamp per phase, [workgroup][8].  Expands to nothing in the product build.
+#if defined(TTK_STAMPS) && TTK_STAMPS != 2
+#define SK_STAMP(i) do { if (p.stamps && threadIdx.x == 0) p.stamps[blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define SK_STAMPD(i, dep) SK_STAMP(i)
 #else
-#define TTK_STAMP(i) do {} while (0)
-#define TTK_STAMPD(i, dep) do {} while (0)
+#define SK_STAMP(i) TTK_WSTAMP(p.stamps, blockIdx.x, i)
+#define SK_STAMPD(i, dep) TTK_WSTAMPD(p.stamps, blockIdx.x, i, dep)
 #endif
-
-// Weight fragment as it sits in memory: the MFMA operand itself, or (W8, bf16 arithmetic only) 8 fp8-e4m3 bytes that are widened to
-// bf16 -- exactly, e4m3 has 3 mantissa bits -- next to their MFMA; the power-of-two tensor scale is applied to the f32 sums.
-template <typename T, bool W8> struct WFrag {
-	typedef typename Frag<T>::type raw;
-	static __device__ __forceinline__ typename Frag<T>::type dec(raw r) { return r; }
-};
-template <> struct WFrag<bf16, true> {
-	typedef unsigned raw __attribute__((ext_vector_type(2)));      // a clang vector: the non-temporal load builtin takes no HIP struct types
-	static __device__ __forceinline__ bf16x8 dec(raw r) {
-		typedef float f2 __attribute__((ext_vector_type(2)));
-		const f2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[0], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[0], true);
-		const f2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[1], false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[1], true);
-		return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)b[0], (bf16)b[1], (bf16)c[0], (bf16)c[1], (bf16)d[0], (bf16)d[1]};
-	}
-};
 
 // KC = float4 chunks of a row per lane in the LayerNorm prologue (K <= 256 * KC); LN kernels run <= 8 waves (2 per SIMD,
 // 256 VGPRs), plain ones up to 16.
@@ -89,21 +62,19 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 	extern __shared__ __attribute__((aligned(16))) char smem[];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
 	if (TTK_ABL & 64) return;
-	// Plain mode: ksplit workgroups share one 16-column n-tile.  Narrow mode (p.narrow = 4, or 2): that many workgroups share an n-tile, each
-	// owning 4 (8) of its columns over the whole of K -- 4x (2x) the workgroups streaming the matrix without any split-K combine.  The MFMA still runs
+	// One workgroup per 16-column n-tile.  The residual projections (N = d: 64 tiles at d = 1024) are "narrow": four workgroups share an n-tile, each
+	// owning 4 of its columns over the whole of K -- 4x the workgroups streaming the matrix, no combine between them.  The MFMA still runs
 	// 16 columns wide: lane (g, n) fetches the fragment of column 4*sub + (n & 3), so columns 4..15 of the product are copies that the
 	// epilogue ignores (matrix throughput is irrelevant here, the weight stream is the work).  The four workgroups of a tile read the
 	// same 128-byte lines, so they are given ids that are equal mod 8: round-robin dispatch then puts them on one XCD and its L2
-	// fetches every line once.
-	int nt, kslice = 0, sub = 0;
-	const int G = p.narrow > 1 ? p.narrow : 1;          // workgroups per 16-column tile (narrow mode: 2 or 4), 16 / G columns each
-	const int NC = 16 / G;
-	if (p.narrow) {
+	// fetches every line once (tile counts that are no multiple of 8 keep the plain order).
+	const int mode = FOLD ? (p.mode == SK_QKV ? SK_QKV : SK_ACT_T) : p.mode;      // a folded LayerNorm sits in front of c_attn and c_fc only
+	const bool narrow = !LN && mode == SK_RESIDUAL;      // (launch_skinny_mt sizes the grid by the same condition)
+	int nt = blockIdx.x, sub = 0;
+	if (narrow) {
 		const int b = blockIdx.x, ntiles = (p.N + 15) / 16;
-		if ((ntiles & 7) == 0) { nt = (b / (8 * G)) * 8 + (b & 7); sub = (b >> 3) % G; }
-		else { nt = b / G; sub = b % G; }
-	} else {
-		nt = blockIdx.x / p.ksplit; kslice = blockIdx.x - nt * p.ksplit;
+		if ((ntiles & 7) == 0) { nt = (b >> 5) * 8 + (b & 7); sub = (b >> 3) & 3; }
+		else { nt = b >> 2; sub = b & 3; }
 	}
 	const int KS = p.K / 32;
 	const int RS = p.K * ES + 16;                       // padded LDS row stride (bytes), LN mode only
@@ -199,23 +170,23 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 					dst[1] = cvt<T>(live ? v[j][i].y : 0.f);
 					dst[2] = cvt<T>(live ? v[j][i].z : 0.f);
 					dst[3] = cvt<T>(live ? v[j][i].w : 0.f);
-					if (p.ln_out && nt == 0 && live) *(float4*)(p.ln_out + (int64_t)r * p.K + 4 * c) = v[j][i];
 				}
 			}
 		}
 	};
-	TTK_STAMP(0);
+	SK_STAMP(0);
 	// the cache row the c_attn epilogue appends at: requested now (first in the vmcnt order), not as one more dependent round trip at the end
 	int kv_pos = 0;
-	if (p.mode == SK_QKV) kv_pos = *p.d_pos;
-	// mel_head launch of a decode step: one thread advances the cache length for the next step (nothing in this launch reads it)
-	if (p.mode == SK_STORE_F32 && p.d_pos && blockIdx.x == 0 && threadIdx.x == 0) *(int*)p.d_pos += 1;
+	if (mode == SK_QKV) kv_pos = *p.d_pos;
+	// mel_head launch of a decode step: one thread advances the cache length for the next step.  Every reader of *d_pos (c_attn epilogues, attention) is
+	// ahead of this launch on the stream and nothing in it reads the word: one 1-thread launch per token less
+	if (mode == SK_STORE_F32 && p.d_pos && blockIdx.x == 0 && threadIdx.x == 0) *(int*)p.d_pos += 1;
 	// Epilogue role of the first 256 threads: element (row 4*(l2>>4)+r of each m-tile, column l2&15) of the 16-wide output tile.  Its
 	// bias and, for the residual modes, the current value of the output are requested now, ahead of everything else, so the epilogue
 	// finds them in registers instead of paying one more dependent L2 round trip after the reduction.
 	const int l2 = tid & 63, r = tid >> 6;
-	const int n = p.narrow ? nt * 16 + NC * sub + (l2 & (NC - 1)) : nt * 16 + (l2 & 15);
-	const bool mine = tid < 256 && (!p.narrow || (l2 & 15) < NC) && n < p.N;
+	const int n = narrow ? nt * 16 + 4 * sub + (l2 & 3) : nt * 16 + (l2 & 15);
+	const bool mine = tid < 256 && (!narrow || (l2 & 15) < 4) && n < p.N;
 	float bias = 0.f, fcs = 0.f, res[MT];
 	RngArgs rng = {};           // mel head drawing the multinomial noise: generator state and this thread's draw counters
 	int64_t draw[MT];
@@ -223,23 +194,22 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 		const int nn = n < p.N ? n : p.N - 1;
 		if (p.bias) bias = p.bias[nn];
 		if (FOLD) fcs = p.g1[nn];            // column sum of the folded matrix (cold, like the bias: left to the epilogue it is a dependent trip to HBM)
-		const bool noise = p.mode == SK_STORE_F32 && p.qbuf;
-		if (noise) rng = *(const RngArgs*)p.slab;
+		const bool noise = mode == SK_STORE_F32 && p.noise;
+		if (noise) rng = *(const RngArgs*)p.rng;
 #pragma unroll
 		for (int mt = 0; mt < MT; ++mt) {
 			res[mt] = 0.f; draw[mt] = 0;
 			int m = mt * 16 + 4 * (l2 >> 4) + (r & 3);
 			m = m < p.M ? m : p.M - 1;
-			if (p.mode == SK_RESIDUAL) res[mt] = p.out_f32[(int64_t)m * p.ldc + nn];
-			if (noise) draw[mt] = ((const int64_t*)p.tickets)[m];
+			if (mode == SK_RESIDUAL) res[mt] = p.out_f32[(int64_t)m * p.ldc + nn];
+			if (noise) draw[mt] = p.draws[m];
 		}
 	}
 	if (LN) { ln_load(wave); ln_load_affine(); }
 
 	// ---- this wave's K slice of the weights; the first PRE fragments are requested now
-	const int kw0 = (KS * kslice) / p.ksplit, kw1 = (KS * (kslice + 1)) / p.ksplit;   // this workgroup's k-steps
-	const int ks0 = kw0 + ((kw1 - kw0) * wave) / nw, ks1 = kw0 + ((kw1 - kw0) * (wave + 1)) / nw;
-	const WRaw* wp = (const WRaw*)p.Wp + ((int64_t)nt * KS) * 64 + (p.narrow ? ((lane & ~15) | (NC * sub + (lane & (NC - 1)))) : lane);
+	const int ks0 = (KS * wave) / nw, ks1 = (KS * (wave + 1)) / nw;
+	const WRaw* wp = (const WRaw*)p.Wp + ((int64_t)nt * KS) * 64 + (narrow ? ((lane & ~15) | (4 * sub + (lane & 3))) : lane);
 	// Weight fragments requested per batch.  LN mode: 8 x 1 KiB (bf16) per wave.  Plain mode: the A fragments of the same k-steps are requested
 	// right beside them (B0 A0 B1 A1 ...), all before the first use -- fetched next to their MFMA instead, every k-step was one more
 	// dependent L2 round trip behind a full vmcnt(0) (8 in a row in mlp.c_proj: 4.7 of its 6.9 us) -- so the batch is sized to the register
@@ -250,16 +220,13 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 	FragT apre[LN ? 1 : PRE][MT];
 	const int npre = min(ks1 - ks0, PRE);
 	const int arow = lane & 15, ag = lane >> 4;
-	auto load_a_global = [&](int mt, int ks) -> FragT {
+	auto load_a_global = [&](int mt, int ks) -> FragT {   // rows in A-fragment order; rows >= M hold zeros
 		if (TTK_ABL & 16) return FragT{};
-		if (p.a_frag) return *(const FragT*)((const T*)p.a + (((int64_t)mt * KS + ks) * 64 + lane) * 8);   // rows >= M hold zeros
-		int row = mt * 16 + arow;
-		row = row < p.M ? row : p.M - 1;
-		return *(const FragT*)((const T*)p.a + (int64_t)row * p.lda + 32 * ks + 8 * ag);
+		return *(const FragT*)((const T*)p.a + (((int64_t)mt * KS + ks) * 64 + lane) * 8);
 	};
 #pragma unroll
 	for (int u = 0; u < PRE; ++u) {   // unconditional: slots beyond npre re-read the last fragment (never multiplied)
-		const int kk = max(ks0 + (u < npre ? u : npre - 1), kw0);
+		const int kk = max(ks0 + (u < npre ? u : npre - 1), 0);
 		if (TTK_ABL & 8) bpre[u] = WRaw{}; else bpre[u] = TTK_WLOAD(wp + (int64_t)kk * 64);
 		if (!LN) {
 #pragma unroll
@@ -269,11 +236,11 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 
 	if (LN) {
 		ln_finish(wave);
-		TTK_STAMP(1);
+		SK_STAMP(1);
 		for (int r0 = wave + RP * nw; r0 < 16 * MT; r0 += RP * nw) { ln_load(r0); ln_finish(r0); }
 		__syncthreads();
 	}
-	TTK_STAMP(2);
+	SK_STAMP(2);
 
 	f32x4 acc[MT];
 #pragma unroll
@@ -334,7 +301,7 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 		}
 	}
 
-	TTK_STAMPD(3, acc[0][0]);
+	SK_STAMPD(3, acc[0][0]);
 	// ---- cross-wave reduction through LDS, then epilogue by the first 256 threads
 	float vsum[MT];
 	if (TTK_ABL & 4) {
@@ -344,43 +311,12 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 #pragma unroll
 		for (int mt = 0; mt < MT; ++mt) *(f32x4*)(red + ((wave * MT + mt) * 64 + lane) * 4) = acc[mt];
 		__syncthreads();
-		TTK_STAMP(4);
+		SK_STAMP(4);
 		if (tid < 256) {
 #pragma unroll
 			for (int mt = 0; mt < MT; ++mt) {
 				float v = 0.f;
 				for (int w = 0; w < nw; ++w) v += red[((w * MT + mt) * 64 + l2) * 4 + r];
-				vsum[mt] = v;
-			}
-		}
-	}
-	if (p.ksplit > 1) {
-		// Split-K over workgroups with a deterministic in-launch combine (cdna_hip_programming.md section 5, "In-launch split-K
-		// reduction", write-through form): every slice stores its 16x16 partial with sc1 stores, drains them, and one lane
-		// takes a ticket; the workgroup that draws the last ticket reads all slices back with sc1 loads IN SLICE ORDER (bitwise
-		// reproducible, unlike float atomics) and runs the epilogue.  The ticket counter is reset by its last user.
-		float* slab = p.slab + ((int64_t)nt * p.ksplit) * 256 * MT;
-		if (tid < 256) {
-#pragma unroll
-			for (int mt = 0; mt < MT; ++mt)
-				__hip_atomic_store(slab + ((int64_t)kslice * MT + mt) * 256 + tid, vsum[mt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__syncthreads();
-		int* flag = (int*)red;                  // LDS word reused as the "I am last" broadcast
-		if (tid == 0) {
-			const int ticket = __hip_atomic_fetch_add(p.tickets + nt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			*flag = ticket == p.ksplit - 1;
-			if (ticket == p.ksplit - 1) __hip_atomic_store(p.tickets + nt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
-		__syncthreads();
-		if (!*flag) return;
-		if (tid < 256) {
-#pragma unroll
-			for (int mt = 0; mt < MT; ++mt) {
-				float v = 0.f;
-				for (int sl = 0; sl < p.ksplit; ++sl)
-					v += __hip_atomic_load(slab + ((int64_t)sl * MT + mt) * 256 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				vsum[mt] = v;
 			}
 		}
@@ -403,21 +339,20 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 		const int m = mt * 16 + 4 * (l2 >> 4) + r;
 		if (m >= p.M) continue;
 		const float v = FOLD ? (vsum[mt] - fmean[mt] * fcs) * frstd[mt] + bias : (W8 ? vsum[mt] * p.wscale : vsum[mt]) + bias;
-		if (p.mode == SK_STORE_F32) {
+		if (mode == SK_STORE_F32) {
 			p.out_f32[(int64_t)m * p.ldc + n] = v;
-			// mel head: the multinomial noise of the sampling launch that follows, one value per logit (SkinnyParams.qbuf in this mode)
-			if (p.qbuf) {
-				int mrow = p.max_ctx + m;                  // max_ctx: first row of this launch's row group
+			// mel head: the multinomial noise of the sampling launch that follows, one value per logit
+			if (p.noise) {
+				int mrow = m;
 				const int grp = (int)rng.group;            // line batch: every line draws the same rows (a handful of subtractions, not a division routine in every instantiation)
 				if (grp > 0) while (mrow >= grp) mrow -= grp;
-				p.qbuf[(int64_t)m * p.ldc + n] = torch_exponential_at(rng, draw[mt], (rng.row0 + mrow) * (int64_t)p.N + n);
+				p.noise[(int64_t)m * p.ldc + n] = torch_exponential_at(rng, draw[mt], (rng.row0 + mrow) * (int64_t)p.N + n);
 			}
-		} else if (p.mode == SK_RESIDUAL) {
+		} else if (mode == SK_RESIDUAL) {
 			p.out_f32[(int64_t)m * p.ldc + n] = res[mt] + v;
-			if (p.out_T) ((T*)p.out_T)[((((int64_t)mt * (p.N / 32) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (m & 15)) * 8 + (n & 7))] = cvt<T>(res[mt] + v);
-		} else if (p.mode == SK_ACT_T) {
-			const int64_t o = p.out_frag ? ((((int64_t)mt * (p.N / 32) + (n >> 5)) * 64 + ((n >> 3) & 3) * 16 + (m & 15)) * 8 + (n & 7)) : (int64_t)m * p.N + n;
-			((T*)p.out_T)[o] = cvt<T>(apply_act(v, p.act));
+			if (p.out_T) ((T*)p.out_T)[TTK_FRAG_INDEX(m, n, p.N / 32)] = cvt<T>(res[mt] + v);
+		} else if (mode == SK_ACT_T) {
+			((T*)p.out_T)[TTK_FRAG_INDEX(m, n, p.N / 32)] = cvt<T>(apply_act(v, p.act));
 		} else {   // SK_QKV
 			const int d = p.N / 3;
 			const int which = n / d, c = n - which * d;
@@ -431,16 +366,17 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 			}
 		}
 	}
-	TTK_STAMP(5);
+	SK_STAMP(5);
 #if defined(TTK_STAMPS) && TTK_STAMPS == 2
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // stores acknowledged
-	TTK_STAMP(6);
+	SK_STAMP(6);
 #endif
 }
 
 template <typename T, int MT, bool W8>
 static void launch_skinny_mt(const SkinnyParams& p, int waves, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-	const int grid = p.narrow ? ((p.N + 15) / 16) * p.narrow : ((p.N + 15) / 16) * p.ksplit;
+	const bool fold = p.ln_count == 0 && p.g1 && !W8;
+	const int grid = ((p.N + 15) / 16) * (p.mode == SK_RESIDUAL && p.ln_count == 0 && !fold ? 4 : 1);      // the residual projections: four workgroups per n-tile
 	const size_t red = (size_t)waves * MT * 64 * 4 * sizeof(float);
 	if (p.ln_count > 0) {
 		if (waves > 8) waves = 8;
@@ -452,7 +388,7 @@ static void launch_skinny_mt(const SkinnyParams& p, int waves, hipStream_t s, hi
 			if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_skinny<T, MT, true, 8, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 			hipExtLaunchKernelGGL((k_skinny<T, MT, true, 8, W8>), dim3(grid), dim3(64 * waves), (unsigned)lds, s, ea, eb, 0, p);
 		}
-	} else if (p.g1 && !W8) {
+	} else if (fold) {
 		const size_t lds = red + (size_t)waves * MT * 16 * 2 * sizeof(float);
 		hipExtLaunchKernelGGL((k_skinny<T, MT, false, 1, false, true>), dim3(grid), dim3(64 * waves), (unsigned)lds, s, ea, eb, 0, p);
 	} else {
@@ -471,13 +407,9 @@ static void launch_skinny_t(const SkinnyParams& p, int waves, hipStream_t s, hip
 
 void launch_skinny(int dt, const SkinnyParams& p_in, int waves, hipStream_t s) {
 	SkinnyParams p = p_in;
-	if (p.ksplit < 1 || !p.slab || !p.tickets || (p.mode == SK_STORE_F32 && p.qbuf)) p.ksplit = 1;      // (mel head: slab / tickets carry the noise arguments)
-	if (p.ln_count > 0 || p.mode == SK_QKV) p.narrow = 0;      // every workgroup of an LN kernel normalises all rows: more of them only adds work
-	if (p.ln_count == 0 && p.g1) { p.narrow = 0; p.ksplit = 1; }   // folded LayerNorm: the row statistics need all of K inside the workgroup
-	if (p.narrow) { p.ksplit = 1; p.narrow = p.narrow == 2 ? 2 : 4; }
-	if (waves < 4) waves = 4;
-	// algorithmic bytes: the weight matrix once + bias + the M activation rows in and out
+	if (waves < 4) waves = 4;                                   // the epilogue is the first 256 threads' work
 	if (dt != DT_BF16) p.w8 = 0;                                // fp8 weights exist for the bf16 arithmetic only
+	// algorithmic bytes: the weight matrix once + bias + the M activation rows in and out
 	// profiling: the event pair travels with the dispatch packet (kernel start / stop timestamps), see prof_pair
 	hipEvent_t ea = nullptr, eb = nullptr;
 	if (g_prof_on) prof_pair(PROF_SKINNY, (double)p.N * p.K * (p.w8 ? 1 : dtype_size(dt)) + 4.0 * p.N + 4.0 * p.M * p.K + 4.0 * p.M * p.N, &ea, &eb);

@@ -39,6 +39,38 @@ __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d
 	return (unsigned)w;
 }
 
+// A-fragment order of a [rows][K] operand, [m_tile][k_step][lane = k_group * 16 + row][8]: where element (row, col) sits.  A wave instruction of a decode
+// GEMV then reads 1 KiB contiguous; every kernel that writes such an operand (attention output, LayerNorm, embeddings, GEMV epilogues) indexes it here.
+// ksteps = K / 32, the k-steps of one row.  A macro, not a function: an inlined function hands the compiler the same arithmetic in another order, and
+// k_gemv / k_attn_decode then came out with other registers and another schedule -- the expression itself leaves their machine code as it was.
+#define TTK_FRAG_INDEX(row, col, ksteps) \
+	((((int64_t)((row) >> 4) * (ksteps) + ((col) >> 5)) * 64 + (((col) >> 3) & 3) * 16 + ((row) & 15)) * 8 + ((col) & 7))
+
+// Weight fragment of the decode GEMVs (skinny.hip, gemv.hip) as it sits in memory: the MFMA operand itself, or (W8, bf16 arithmetic only) 8 fp8-e4m3 bytes
+// that are widened to bf16 -- exactly, e4m3 has 3 mantissa bits -- next to their MFMA; the power-of-two tensor scale is applied to the f32 sums.
+template <typename T, bool W8> struct WFrag {
+	typedef typename Frag<T>::type raw;
+	static __device__ __forceinline__ typename Frag<T>::type dec(raw r) { return r; }
+};
+template <> struct WFrag<bf16, true> {
+	typedef unsigned raw __attribute__((ext_vector_type(2)));      // a clang vector: the non-temporal load builtin takes no HIP struct types
+	static __device__ __forceinline__ bf16x8 dec(raw r) {
+		typedef float f2 __attribute__((ext_vector_type(2)));
+		const f2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[0], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[0], true);
+		const f2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[1], false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[1], true);
+		return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)b[0], (bf16)b[1], (bf16)c[0], (bf16)c[1], (bf16)d[0], (bf16)d[1]};
+	}
+};
+// their weight-stream cache policy: non-temporal (streamed once per token) unless built with -DTTK_NT=0
+#ifndef TTK_NT
+#define TTK_NT 1
+#endif
+#if TTK_NT
+#define TTK_WLOAD(p) __builtin_nontemporal_load(p)
+#else
+#define TTK_WLOAD(p) (*(p))
+#endif
+
 template <typename T>
 __device__ __forceinline__ f32x4 mma16(typename Frag<T>::type a, typename Frag<T>::type b, f32x4 c);
 template <>

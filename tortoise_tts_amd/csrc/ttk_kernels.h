@@ -88,36 +88,33 @@ bool gemm_fuses_gn_stats(int M, int N, int C, int T);
 
 // ---------------------------------------------------------------- skinny GEMM for decode (skinny.hip)
 // out[M<=16*MT, N] = epilogue( LN?(x)[M,K] * W[N,K]^T + bias ), weights streamed once from HBM in MFMA-fragment
-// order: Wp[n_tile][k_step][lane][8].
+// order: Wp[n_tile][k_step][lane][8].  The generic decode kernel: any K % 32 == 0, any waves per workgroup.
 enum SkinnyMode { SK_STORE_F32 = 0, SK_RESIDUAL = 1, SK_ACT_T = 2, SK_QKV = 3 };
 struct SkinnyParams {
 	const void* Wp;
 	int N, K, M;
 	const float* bias;
-	// A source: LN mode (ln_count 1|2) reads f32 rows and normalises; plain mode reads T rows
+	// A source, one of three forms:
+	//   LN prologue (ln_count 1 | 2): x = f32 rows [M][ldx], normalised by every workgroup with (g1, b1) and then (g2, b2); at most 32 rows
+	//   plain (ln_count 0, g1 null): a = T-typed rows in A-fragment order [m_tile][K/32][lane][8] (ttk_common.h: TTK_FRAG_INDEX), rows >= M zero
+	//   folded LayerNorm (ln_count 0, g1 != null): a holds the UN-normalised rows, Wp = gamma o W, g1 = column sums of the T-typed Wp,
+	//     bias = b + beta W; the epilogue computes (acc - mean * g1[n]) * rstd + bias from the rows' statistics, which the waves gather
+	//     from the A fragments they multiply anyway
 	int ln_count;
 	const float* x;  int64_t ldx;
-	// LN mode: the affine parameters.  Plain mode with g1 != null = "folded LayerNorm": A holds the UN-normalised rows, Wp = gamma o W, g1 =
-	// colsum of the T-typed Wp, bias = b + beta W; the epilogue computes (acc - mean * g1[n]) * rstd + bias from the rows' statistics,
-	// which the waves gather from the A fragments they multiply anyway (needs a_frag, no narrow / ksplit)
 	const float *g1, *b1, *g2, *b2;
-	float* ln_out;              // optional f32 [M][K]: the normalised rows (block 0 writes), else null
-	const void* a;   int64_t lda;
+	const void* a;
 	int mode, act;
-	float* out_f32;  int64_t ldc;   // SK_STORE_F32 / SK_RESIDUAL (in place +=)
-	void* out_T;                    // SK_ACT_T, [M][N]; SK_RESIDUAL (optional): a T-typed copy of the updated rows in A-fragment order
-	                                // [m_tile][N/32][lane][8], the operand of the folded-LayerNorm launch that follows
-	// SK_QKV: n in [0,3d): q -> qbuf[m][n] f32 (pre-scaled), k/v -> cache[m][h][*pos][64]
-	// SK_STORE_F32 with qbuf != null (mel head): qbuf[m][n] (row stride ldc) receives the Exp(1) noise torch.multinomial would draw for logit
-	// (m, n) -- `slab` then points to a device RngArgs and `tickets` to the per-row int64 draw counters (ttk_rng.h)
-	float* qbuf; void* kcache; void* vcache; const int* d_pos; int max_ctx, H; float q_scale;
-	// optional split-K over workgroups: slab f32 [n_tiles][ksplit][MT][256], tickets int [n_tiles] (zero between launches)
-	int ksplit; float* slab; int* tickets;
-	// narrow mode (plain A only, excludes ksplit): N/4 workgroups of 4 columns each instead of N/16 of 16 -- for the N = d projections
-	int narrow;
-	// activations in MFMA-fragment order [m_tile][k_step][lane][8] (a wave reads 1 KiB contiguous instead of 16 row segments): a_frag = the
-	// plain-mode A operand is stored that way, out_frag = SK_ACT_T writes its output that way (for the next launch's a_frag)
-	int a_frag, out_frag;
+	float* out_f32;  int64_t ldc;   // SK_STORE_F32: [M][ldc]; SK_RESIDUAL: the residual stream, updated in place.  SK_RESIDUAL launches run four
+	                                // workgroups per n-tile, 4 columns each ("narrow": N = d gives too few 16-column tiles to fill the chip)
+	void* out_T;                    // T-typed output in A-fragment order [m_tile][N/32][lane][8], the operand of the launch that follows:
+	                                // SK_ACT_T act(v); SK_RESIDUAL (optional) a copy of the updated rows
+	// SK_QKV: n in [0,3d): q -> qbuf[m][n] f32 (pre-scaled), k/v -> cache[m][h][*d_pos][64]
+	float* qbuf; void* kcache; void* vcache; int max_ctx, H; float q_scale;
+	const int* d_pos;           // SK_QKV: cache row to append at; SK_STORE_F32 (optional, decode head): incremented by the launch
+	// SK_STORE_F32 (optional, mel head): noise[m][n] (row stride ldc) receives the Exp(1) value torch.multinomial would draw for logit (m, n);
+	// rng = device RngArgs, draws = per-row int64 draw counters (ttk_rng.h)
+	float* noise; const void* rng; const int64_t* draws;
 	// fp8 weights: Wp holds one byte per element in the same fragment order; the accumulated product is multiplied by wscale (a power of two)
 	int w8; float wscale;
 #ifdef TTK_STAMPS
@@ -127,9 +124,9 @@ struct SkinnyParams {
 void launch_skinny(int dt, const SkinnyParams& p, int waves, hipStream_t s);
 
 // ---------------------------------------------------------------- lean decode GEMV (gemv.hip)
-// The launches of the KV-cached decode step at the benchmarked geometry (K = 1024 / 4096, whole batch, activations in fragment order, LayerNorm
-// folded), one compile-time specialisation per role; bit-identical to k_skinny on the same operands.  launch_gemv returns false (and launches
-// nothing) for a geometry it has no instantiation for: the caller then takes launch_skinny.
+// The launches of the KV-cached decode step at the benchmarked geometry (K = 1024 / 4096, activations in fragment order, LayerNorm folded), one
+// compile-time specialisation per role; bit-identical to k_skinny on the same operands.  launch_gemv returns false (and launches nothing) for a
+// geometry it has no instantiation for: the caller (ar.hip: decode_launch) then takes launch_skinny.
 enum GemvRole { GV_QKV = 0, GV_PROJ = 1, GV_FC = 2, GV_HEAD = 3 };
 // Sixteen-row tiles a decode launch is INSTANTIATED for when the batch has M rows (k_gemv / k_skinny: MT = 1, 2, 3 or 4; round 4 added 3: three lines of
 // 16 candidates as one decode batch ran the 4-tile form, a quarter of its MFMA and operand traffic on zero rows).  A launch requests EVERY tile of
@@ -150,7 +147,7 @@ struct GemvParams {
 	int* health;                // GV_QKV / GV_FC (optional): device word that collects what the folded LayerNorm cannot represent well -- bit 0: a row
 	                            // with |mean| > 8 std (the T-typed un-normalised operand then spends > 3 of its bits on the common offset that the
 	                            // norm removes), bit 1: non-finite row statistics (an f16 operand above 65504)
-	int M, N, max_ctx, H, row0; // row0: first row of this batch inside the noise tensor's row numbering
+	int M, N, max_ctx, H, row0; // row0: first row of this batch inside the noise tensor's row numbering (always 0: the step decodes the whole batch)
 	float q_scale, wscale;
 	int K, w8;                  // host side only (dispatch): K in {1024, 4096}; w8: Wp holds fp8 bytes (GV_PROJ, bf16 arithmetic)
 #ifdef TTK_STAMPS
@@ -246,7 +243,6 @@ void launch_kv_scatter(int dt, const void* qkv, int B, int S, int H, void* kcach
 void launch_set_int(int* p, int v, hipStream_t s);
 void launch_fill_int(int* p, int v, int n, hipStream_t s);
 void launch_fill_int2(int* p, int a, int b, int n, hipStream_t s);      // n pairs {a, b}
-void launch_add_int(int* p, int v, hipStream_t s);
 // out[r][:] = A[ia[r]][:] + Bt[ib[r]][:]   (f32 tables, f32 out); ia/ib int32 device arrays; Bt may be null
 void launch_gather_add(const float* A, const int* ia, const float* Bt, const int* ib, float* out, int rows, int d, hipStream_t s);
 // decode-time embedding: out[b] = mel_emb[tok[b]] + mel_pos[*d_pos - pos_bias]
