@@ -527,6 +527,28 @@ typedef struct {
 } ttk_attn_decode_desc;
 int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ the GroupNorm32-apply kernels on caller-provided operands
+ * No reference counterpart: exposed so every launch form of csrc/norm.hip's GroupNorm-apply can be run on the same input and statistics (the forms owe the same bits).
+ * out [nb][Tout][C] = act( gn(x) * gamma + beta [ * (1 + scale[b]) + shift[b] ] ) over x f32 [nb][T][C], 32 groups; C = 128, 256, 512 or 1024.
+ *   ms: f32 [nb][32][ceil(T / (65536 / C))][3] chunk statistics (count, mean, M2); stats != 0: computed from x by this call first, else read as the caller left them.
+ *   scale / shift: null or f32 rows ss_stride apart per batch element (0: shared).  row_idx: null (Tout == T) or device int [Tout] into [0, T).
+ *   tlen: null or device int [nb], each 1..T (needs Tout == T, no row_idx): rows past tlen[b] are written as zeros, the statistics cover the rows before.
+ *   out: out_f8 ? fp8-e4m3 bytes (TTK_BF16 only) : out_f32 ? f32 : dtype.  act: 0 none, 2 SiLU.  pf: null or pf_taps blocks of pf_bytes each, touched into L2.
+ *   x, gamma, beta, scale, shift and out 16-byte aligned, ss_stride % 4 == 0, at most 64 chunks.
+ *   form: 0 = the launcher's own choice (what every product launch gets), 1 = generic, 2 = 4-row strips (C == 1024, no row_idx), 3 / 4 / 5 = rows dealt evenly over
+ *   256 / nb strips of 4 .. 9 / 12 / 18 rows (as 2, and no tlen, nb <= 64; 3 and 4: at most 24 chunks).
+ * Returns TTK_E_ARG with a message when a precondition the kernels rely on fails. */
+typedef struct {
+	const float* x; float* ms; const float* gamma; const float* beta;
+	const float* scale; const float* shift; int64_t ss_stride;
+	const int* row_idx; const int* tlen;
+	int nb, T, Tout, C, act;
+	void* out; int out_f32, out_f8;
+	const void* pf; int64_t pf_bytes; int pf_taps;
+	int stats, form;
+} ttk_gn_desc;
+int ttk_gn_apply(int dtype, const ttk_gn_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ mel front-ends of the conditioning path
  * TorchMelSpectrogram (models/arch_utils.py:361-395) and TacotronSTFT (:662-700 over STFT :560-623) as one handle type: reflect-padded
  * frames x "basis" [2 * (n_fft/2 + 1), n_fft] (windowed DFT, Re rows then Im rows) -> |.|^power -> x "mel_basis" [n_mels, n_fft/2 + 1] ->

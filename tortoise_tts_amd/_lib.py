@@ -93,6 +93,14 @@ class AttnDecodeDesc(C.Structure):
 				("shared_rows", C.c_int), ("variant", C.c_int), ("pos_line", C.c_int)]
 
 
+class GnDesc(C.Structure):
+	"""ttk_gn_desc (include/ttk.h)"""
+	_fields_ = [("x", C.c_void_p), ("ms", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+				("ss_stride", C.c_int64), ("row_idx", C.c_void_p), ("tlen", C.c_void_p), ("nb", C.c_int), ("T", C.c_int), ("Tout", C.c_int), ("C", C.c_int),
+				("act", C.c_int), ("out", C.c_void_p), ("out_f32", C.c_int), ("out_f8", C.c_int), ("pf", C.c_void_p), ("pf_bytes", C.c_int64),
+				("pf_taps", C.c_int), ("stats", C.c_int), ("form", C.c_int)]
+
+
 class ProfResult(C.Structure):
 	_fields_ = [("ms", C.c_double), ("launches", C.c_int64), ("work", C.c_double)]
 
@@ -151,6 +159,7 @@ SYMBOLS = {
 	"ttk_gemm": (_I, [_I, C.POINTER(GemmDesc), _P]),
 	"ttk_attn_fwd": (_I, [_I, C.POINTER(AttnDesc), _P]),
 	"ttk_attn_decode": (_I, [_I, C.POINTER(AttnDecodeDesc), _P]),
+	"ttk_gn_apply": (_I, [_I, C.POINTER(GnDesc), _P]),
 	"ttk_fp8_round_weights": (_I, [_P, _L, C.POINTER(C.c_float), _P]),
 	"ttk_sample_step": (_I, [_P, _L, _I, _I, _P, _L, _P, C.c_float, _L, _P, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P]),
 	"ttk_ar_decode_geometry": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),

@@ -20,15 +20,29 @@ struct DLayer { ResBlk res; AttnBlk attn; };
 // can run on a side stream beside the main body of the current one
 struct Lane {
 	WsBuf a, hf, qkv, ao, ms;
-	const void* ms_owner = nullptr;   // tensor whose GroupNorm statistics currently sit in `ms` (written by a GEMM epilogue)
+	const void* ms_owner = nullptr;   // tensor whose GroupNorm statistics a GEMM epilogue has just written (gemm() sets it, stats_of() takes it)
 };
+// the A operand of a GEMM: row-shifted / concatenated segments of K columns each
+struct Segs { int n, K, rows_per_batch; GemmSeg s[3]; };
+// what rides on a GEMM's epilogue beyond the bias.  gn_T > 0: the output is a GroupNorm input of gn_T rows per batch element, whose statistics go to `ms` (null: the
+// lane's); residual: f32 in the output's layout (may be the output); transpose: the output is [b][N][rows_per_batch]
+struct Epi { int gn_T = 0; const float* residual = nullptr; float* ms = nullptr; int act = ACT_NONE; int transpose = 0; };
+// one GroupNorm-apply launch.  next: the GEMM that consumes the output -- its weights are touched into L2 meanwhile, and fp8 weights make the output fp8;
+// mod: rows of [scale C | shift C], one per batch element `mod_stride` apart (0: shared); ms: the statistics when computed beforehand (else stats_of);
+// out: null = the lane's `a` in the kernel type; row_idx: nearest-neighbour row gather to Tout rows
+struct Gn {
+	const float *gamma, *beta; int act; const Mat* next = nullptr; const float* mod = nullptr; int64_t mod_stride = 0; const float* ms = nullptr;
+	void* out = nullptr; int out_f32 = 0; const int* row_idx = nullptr; int Tout = 0;
+};
+// one sampler step of a loop.  nb: 2b sequences with the conditioning-free evaluation, else b; emb: its row of emb_all; noise: its block (ancestral sampler) or null;
+// layout: the channels-last copy of x is not there yet, the step runs the layout launch; stage_next: its update launch also writes the next step's copy (same batch
+// layout in both; not for ragged batches, whose padding frames must read zero)
+struct StepPlan { const ttk_step* st; int nb; const float* emb; const float* noise; bool layout, stage_next; };
 }  // namespace
 
 struct ttk_diff {
 	ttk_diff_config cfg;
-	int prefetch = 1;       // GroupNorm-apply launches touch the following GEMM's weights into L2 (TTK_DIFF_PREFETCH=0: off)
 	int dt, wdt;            // kernel arithmetic type / storage type of the block GEMM weights (== dt, DT_FP8W or DT_FP8)
-	int a8 = 0;             // DT_FP8: the block GEMMs take fp8 activations too (written by GroupNorm-apply / attention) and run on the fp8 MFMA
 	size_t es;
 	Arena arena;
 	AttnBlk lat_attn[4];
@@ -46,7 +60,6 @@ struct ttk_diff {
 	WsBuf hf0, ms_hf0;      // in_layers of the FIRST integrator ResBlock applied to the staged embedding (+ the GroupNorm statistics of the result): the same in every step
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_int[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
-	int hf0_valid = 0;      // hf0 / ms_hf0 hold the staged embedding's first half-block (TTK_DIFF_HOIST=0: recomputed in every step, as before round 3)
 	int pipe = 1;           // ttk_diff_sample_ddim overlaps step i+1's integrator with step i's body (TTK_DIFF_PIPE=0: sequential)
 	int cur_b = 0, cur_T = 0, staged = 0;
 	int fuse_stats = 1;
@@ -61,87 +74,82 @@ struct ttk_diff {
 	}
 };
 
-// gn_T > 0: the output is a GroupNorm input of gn_T rows per batch element; its statistics are produced in the epilogue when the
-// shape allows (gemm_fuses_gn_stats), which saves the separate k_gn_stats launch.
-static void want_stats(ttk_diff* h, GemmParams& g, int gn_T) {
-	h->L->ms_owner = nullptr;
-	if (h->fuse_stats && gn_T > 0 && g.out_f32 && !g.transpose_out && gemm_fuses_gn_stats(g.M, g.N, h->cfg.model_channels, gn_T)) {
-		g.gn_part = (float*)h->L->ms.p; g.gn_T = gn_T; h->L->ms_owner = g.C;
-	}
+static Segs rows_of(const void* A, const Mat& m) { return {1, m.Kpad, 0, {{A, m.Kpad, 0, 0}}}; }
+// k=3 'same' conv over rows inside each batch element of Tper rows: tap j multiplies row t + j - 1
+static Segs taps3(const void* A, int64_t lda, const Mat& m, int Tper) {
+	const int64_t tap = (int64_t)m.Npad * m.Kpad;
+	return {3, m.Kpad, Tper, {{A, lda, -1, 0}, {A, lda, 0, tap}, {A, lda, 1, 2 * tap}}};
 }
 
-static void gemm1(ttk_diff* h, const void* A, int64_t lda, const Mat& m, int M, void* C, int64_t ldc, int out_f32, int act,
-				  const float* residual, hipStream_t s, int gn_T = 0) {
+// Every GEMM of the network: C [M][ldc] = epilogue(A . m^T).  With e.gn_T the statistics of the output are produced in the epilogue when the shape
+// allows (gemm_fuses_gn_stats), which saves the separate k_gn_stats launch; stats_of() finds out through ms_owner.
+static void gemm(ttk_diff* h, const Mat& m, const Segs& a, int M, void* C, int64_t ldc, int out_f32, hipStream_t s, const Epi& e = {}) {
 	GemmParams g = {};
-	g.nseg = 1; g.seg[0] = {A, lda, 0, 0};
-	g.W = m.w; g.ldw = m.Kpad; g.M = M; g.N = m.N; g.K = m.Kpad; g.bias = m.bias;
-	g.residual = residual; g.ldr = ldc; g.C = C; g.ldc = ldc; g.out_f32 = out_f32; g.act = act;
+	g.nseg = a.n;
+	for (int j = 0; j < a.n; ++j) g.seg[j] = a.s[j];
+	g.W = m.w; g.ldw = m.Kpad; g.M = M; g.N = m.N; g.K = a.K; g.rows_per_batch = a.rows_per_batch; g.bias = m.bias;
+	g.residual = e.residual; g.ldr = ldc; g.C = C; g.ldc = ldc; g.out_f32 = out_f32; g.act = e.act; g.transpose_out = e.transpose;
 	if (m.wes == 1) g.out_scale = m.wscale;      // fp8 operands (A is fp8 too: written by gn() / the attention for exactly these matrices)
-	want_stats(h, g, gn_T);
-	launch_gemm(m.wes == 1 ? DT_FP8 : h->dt, g, s);
-}
-
-// k=3 'same' conv over rows inside each batch element: tap j multiplies row t + j - 1
-static void gemm_conv3(ttk_diff* h, const void* A, int64_t lda, const Mat& m, int M, int Tper, void* C, int64_t ldc, int out_f32,
-					   const float* residual, int transpose_out, hipStream_t s, int gn_T = 0) {
-	GemmParams g = {};
-	g.nseg = 3;
-	for (int j = 0; j < 3; ++j) g.seg[j] = {A, lda, j - 1, (int64_t)j * m.Npad * m.Kpad};
-	g.W = m.w; g.ldw = m.Kpad; g.M = M; g.N = m.N; g.K = m.Kpad; g.rows_per_batch = Tper; g.bias = m.bias;
-	g.residual = residual; g.ldr = ldc; g.C = C; g.ldc = ldc; g.out_f32 = out_f32; g.transpose_out = transpose_out;
-	if (m.wes == 1) g.out_scale = m.wscale;
-	want_stats(h, g, gn_T);
-	launch_gemm(m.wes == 1 ? DT_FP8 : h->dt, g, s);
-}
-
-static void gn(ttk_diff* h, const float* x, int nb, int T, const float* gamma, const float* beta, const float* scale, const float* shift,
-			   int64_t ss_stride, int act, void* out, int out_f32, const int* row_idx, int Tout, hipStream_t s, const Mat* next = nullptr,
-			   const float* ms_pre = nullptr) {
-	const int C = h->cfg.model_channels;
-	if (!ms_pre) {
-		if (h->L->ms_owner != (const void*)x) launch_gn_stats(x, nb, T, C, (float*)h->L->ms.p, s, h->tlen);   // else: left by the producing GEMM
-		else if (h->need) launch_gn_stats(x, nb, T, C, (float*)h->L->ms.p, s, h->tlen, h->need);           // ... except for the ragged sequences of a batch
-		h->L->ms_owner = nullptr;
+	h->L->ms_owner = nullptr;
+	if (h->fuse_stats && e.gn_T > 0 && out_f32 && !e.transpose && gemm_fuses_gn_stats(M, m.N, h->cfg.model_channels, e.gn_T)) {
+		g.gn_part = e.ms ? e.ms : (float*)h->L->ms.p; g.gn_T = e.gn_T; h->L->ms_owner = C;
 	}
+	launch_gemm(m.wes == 1 ? DT_FP8 : h->dt, g, s);
+}
+
+// The GroupNorm statistics of x (nb sequences in slots of T rows) in `ms` (null: the lane's; the buffer the producing GEMM was given): left there by that
+// GEMM's epilogue -- except for the ragged sequences of a batch whose length the epilogue cannot serve, which get the separate launch -- or computed now.
+static const float* stats_of(ttk_diff* h, const float* x, int nb, int T, hipStream_t s, float* ms = nullptr) {
+	if (!ms) ms = (float*)h->L->ms.p;
+	const bool fused = h->L->ms_owner == (const void*)x;
+	h->L->ms_owner = nullptr;
+	if (!fused || h->need) launch_gn_stats(x, nb, T, h->cfg.model_channels, ms, s, h->tlen, fused ? h->need : nullptr);
+	return ms;
+}
+
+static void gn(ttk_diff* h, const float* x, int nb, int T, const Gn& d, hipStream_t s) {
+	const int C = h->cfg.model_channels;
 	GnApplyParams p = {};
-	if (h->tlen && Tout == T && !row_idx) { p.tlen = h->tlen; p.chunk_rows = gn_rows_per_chunk(C); }
-	p.x = x; p.ms = ms_pre ? ms_pre : (const float*)h->L->ms.p; p.gamma = gamma; p.beta = beta; p.scale = scale; p.shift = shift; p.ss_stride = ss_stride;
-	p.row_idx = row_idx; p.nb = nb; p.T = T; p.Tout = Tout; p.C = C; p.nchunks = gn_num_chunks(T, C); p.act = act; p.out = out; p.out_f32 = out_f32;
-	if (next && h->prefetch) { p.pf = next->w; p.pf_bytes = (int64_t)next->Npad * next->Kpad * next->wes; p.pf_taps = next->ntap; }
-	if (next && next->wes == 1) p.out_f8 = 1;    // the consumer is an fp8 GEMM
+	p.row_idx = d.row_idx; p.nb = nb; p.T = T; p.Tout = d.row_idx ? d.Tout : T; p.C = C; p.nchunks = gn_num_chunks(T, C);
+	if (h->tlen && !d.row_idx) { p.tlen = h->tlen; p.chunk_rows = gn_rows_per_chunk(C); }
+	p.x = x; p.ms = d.ms ? d.ms : stats_of(h, x, nb, T, s); p.gamma = d.gamma; p.beta = d.beta; p.act = d.act;
+	if (d.mod) { p.scale = d.mod; p.shift = d.mod + C; p.ss_stride = d.mod_stride; }
+	p.out = d.out ? d.out : h->L->a.p; p.out_f32 = d.out_f32;
+	if (d.next) { p.pf = d.next->w; p.pf_bytes = (int64_t)d.next->Npad * d.next->Kpad * d.next->wes; p.pf_taps = d.next->ntap; p.out_f8 = d.next->wes == 1; }
 	launch_gn_apply(h->dt, p, s);
 }
 
 // x (f32 stream, in place) = x + proj_out(attention(qkv(GN(x))))         arch_utils.py:183-190
 static void attn_block(ttk_diff* h, const AttnBlk& A, float* x, int nb, int T, hipStream_t s) {
 	const int C = h->cfg.model_channels, rows = nb * T;
-	gn(h, x, nb, T, A.gn_g, A.gn_b, nullptr, nullptr, 0, ACT_NONE, h->L->a.p, 0, nullptr, T, s, &A.qkv);
-	gemm1(h, h->L->a.p, C, A.qkv, rows, h->L->qkv.p, 3 * C, 0, ACT_NONE, nullptr, s);
+	gn(h, x, nb, T, {A.gn_g, A.gn_b, ACT_NONE, &A.qkv}, s);
+	gemm(h, A.qkv, rows_of(h->L->a.p, A.qkv), rows, h->L->qkv.p, 3 * C, 0, s);
 	AttnParams a = {};
 	a.qkv = h->L->qkv.p; a.ld = 3 * C; a.q_off = 0; a.k_off = 64; a.v_off = 128; a.head_stride = 192;   // head-major [H][3][64], arch_utils.py:79
 	a.out = h->L->ao.p; a.ldo = C; a.nb = nb; a.T = T; a.H = h->cfg.num_heads; a.causal = 0; a.bias = A.relbias; a.scale = 0.125f; a.tlen = h->tlen;
-	if (h->prefetch) { a.pf = A.proj.w; a.pf_bytes = (int64_t)A.proj.Npad * A.proj.Kpad * A.proj.wes; a.pf_taps = 1; }
+	a.pf = A.proj.w; a.pf_bytes = (int64_t)A.proj.Npad * A.proj.Kpad * A.proj.wes; a.pf_taps = 1;
 	a.out_f8 = A.proj.wes == 1;
 	launch_attn_fwd(h->dt, a, s);
-	gemm1(h, h->L->ao.p, C, A.proj, rows, x, C, 1, ACT_NONE, x, s, T);
+	gemm(h, A.proj, rows_of(h->L->ao.p, A.proj), rows, x, C, 1, s, {T, x});
 }
 
-// x = x + conv3(SiLU(GN(conv1(SiLU(GN(x)))) * (1 + scale) + shift))        diffusion.py:1363-1376
-// x_in (with its precomputed GroupNorm statistics ms_in): the block reads its input there and writes x -- the first integrator block of a
-// sampler step reads the staged code embedding directly instead of a per-step copy of it
-// hf_pre / ms_hf_pre: in_layers(x_in) and its statistics computed beforehand (ttk_diff_begin: the timestep enters a ResBlock only behind them, as
-// the scale / shift of the second GroupNorm) -- the block then starts at its second half
-static void res_block(ttk_diff* h, const ResBlk& R, float* x, int nb, int T, const float* emb_all, int64_t emb_stride, hipStream_t s,
-					  const float* x_in = nullptr, const float* ms_in = nullptr, const float* hf_pre = nullptr, const float* ms_hf_pre = nullptr) {
-	const int C = h->cfg.model_channels, rows = nb * T;
-	const float* src = x_in ? x_in : x;
-	if (!hf_pre) {
-		gn(h, src, nb, T, R.gn1_g, R.gn1_b, nullptr, nullptr, 0, ACT_SILU, h->L->a.p, 0, nullptr, T, s, &R.in, ms_in);
-		gemm1(h, h->L->a.p, C, R.in, rows, h->L->hf.p, C, 1, ACT_NONE, nullptr, s, T);
-	}
-	const float* sc = emb_all + (int64_t)R.emb_slot * 2 * C;
-	gn(h, hf_pre ? hf_pre : (const float*)h->L->hf.p, nb, T, R.gn2_g, R.gn2_b, sc, sc + C, emb_stride, ACT_SILU, h->L->a.p, 0, nullptr, T, s, &R.out3, ms_hf_pre);
-	gemm_conv3(h, h->L->a.p, C, R.out3, rows, T, x, C, 1, src, 0, s, T);
+// x = x + conv3(SiLU(GN(conv1(SiLU(GN(x)))) * (1 + scale) + shift))        diffusion.py:1363-1376, in its two halves: the timestep enters a ResBlock only
+// behind the first, as the scale / shift of the second GroupNorm.
+// res_in: hf = conv1(SiLU(GN(x))), hf's statistics into ms_hf (null: the lane's); ms_x: x's statistics when computed beforehand
+static void res_in(ttk_diff* h, const ResBlk& R, const float* x, int nb, int T, hipStream_t s, float* hf, const float* ms_x = nullptr, float* ms_hf = nullptr) {
+	gn(h, x, nb, T, {R.gn1_g, R.gn1_b, ACT_SILU, &R.in, nullptr, 0, ms_x}, s);
+	gemm(h, R.in, rows_of(h->L->a.p, R.in), nb * T, hf, h->cfg.model_channels, 1, s, {T, nullptr, ms_hf});
+}
+// res_out: x = res + conv3(SiLU(GN(hf) * (1 + scale) + shift)); ms_hf: hf's statistics when computed beforehand
+static void res_out(ttk_diff* h, const ResBlk& R, const float* hf, const float* ms_hf, const float* res, float* x, int nb, int T, const float* emb_all,
+					int64_t emb_stride, hipStream_t s) {
+	const int C = h->cfg.model_channels;
+	gn(h, hf, nb, T, {R.gn2_g, R.gn2_b, ACT_SILU, &R.out3, emb_all + (int64_t)R.emb_slot * 2 * C, emb_stride, ms_hf}, s);
+	gemm(h, R.out3, taps3(h->L->a.p, C, R.out3, T), nb * T, x, C, 1, s, {T, res});
+}
+static void res_block(ttk_diff* h, const ResBlk& R, float* x, int nb, int T, const float* emb_all, int64_t emb_stride, hipStream_t s) {
+	res_in(h, R, x, nb, T, s, (float*)h->L->hf.p);
+	res_out(h, R, (const float*)h->L->hf.p, nullptr, x, x, nb, T, emb_all, emb_stride, s);
 }
 
 static int reserve_lane(ttk_diff* h, Lane& L, int nb, int T) {
@@ -169,22 +177,24 @@ static int time_path(ttk_diff* h, const int64_t* t_dev, const int64_t* t_host, i
 	TTK_TRY(h->se.reserve((size_t)n * C * es)); TTK_TRY(h->emb_all.reserve((size_t)n * h->n_emb * 2 * C * 4));
 	if (t_dev) launch_timestep_embedding(h->dt, t_dev, 0, n, C, h->time_freqs, h->temb.p, s);
 	else for (int i = 0; i < n; ++i) launch_timestep_embedding(h->dt, nullptr, t_host[i], 1, C, h->time_freqs, (char*)h->temb.p + (size_t)i * C * es, s);
-	gemm1(h, h->temb.p, C, h->time0, n, h->e1.p, C, 0, ACT_SILU, nullptr, s);
-	gemm1(h, h->e1.p, C, h->time2, n, h->e2.p, C, 1, ACT_NONE, nullptr, s);
+	Epi silu; silu.act = ACT_SILU;
+	gemm(h, h->time0, rows_of(h->temb.p, h->time0), n, h->e1.p, C, 0, s, silu);
+	gemm(h, h->time2, rows_of(h->e1.p, h->time2), n, h->e2.p, C, 1, s);
 	launch_silu_cast(h->dt, (const float*)h->e2.p, h->se.p, (int64_t)n * C, s);
-	gemm1(h, h->se.p, C, h->emb_cat, n, h->emb_all.p, (int64_t)h->n_emb * 2 * C, 1, ACT_NONE, nullptr, s);
+	gemm(h, h->emb_cat, rows_of(h->se.p, h->emb_cat), n, h->emb_all.p, (int64_t)h->n_emb * 2 * C, 1, s);
 	return TTK_OK;
 }
 
 // One evaluation = integrator (the three conditioning_timestep_integrator layers on the code-embedding stream `cs`; depends on the timestep
 // only, not on x) + body (everything that sees x).  Inputs of the body: h->xcl (T-typed [nb*T][in_pad]) and cs (f32 [nb*T][C]); emb rows at
 // emb_all + b * emb_stride.  Output: out f32 [nb][out_channels][T].     diffusion.py:1549-1564
-static void integrator(ttk_diff* h, int nb, int T, const float* emb_all, int64_t emb_stride, float* cs, hipStream_t s,
-					   const float* cs_in = nullptr, const float* ms_in = nullptr) {
+// staged: the loop's form -- the first block reads the staged embedding (ttk_diff_begin: ecl, and the first half of that block on it in hf0 / ms_hf0, the same
+// in every step) and writes cs; else cs holds the embedding and is integrated in place
+static void integrator(ttk_diff* h, int nb, int T, const float* emb_all, int64_t emb_stride, float* cs, hipStream_t s, bool staged) {
 	for (int i = 0; i < 3; ++i) {
-		const bool pre = i == 0 && cs_in && h->hf0_valid;
-		res_block(h, h->integrator[i].res, cs, nb, T, emb_all, emb_stride, s, i == 0 ? cs_in : nullptr, i == 0 ? ms_in : nullptr,
-				  pre ? (const float*)h->hf0.p : nullptr, pre ? (const float*)h->ms_hf0.p : nullptr);
+		const ResBlk& R = h->integrator[i].res;
+		if (i == 0 && staged) res_out(h, R, (const float*)h->hf0.p, (const float*)h->ms_hf0.p, (const float*)h->ecl.p, cs, nb, T, emb_all, emb_stride, s);
+		else res_block(h, R, cs, nb, T, emb_all, emb_stride, s);
 		attn_block(h, h->integrator[i].attn, cs, nb, T, s);
 	}
 }
@@ -192,31 +202,19 @@ static void body(ttk_diff* h, int nb, int T, const float* emb_all, int64_t emb_s
 				 hipEvent_t cs_consumed = nullptr) {
 	const int C = h->cfg.model_channels, rows = nb * T;
 	float* x = (float*)h->xs.p;
-	gemm_conv3(h, h->xcl.p, h->in_pad, h->inp_block, rows, T, h->h0.p, C, 0, nullptr, 0, s);
+	gemm(h, h->inp_block, taps3(h->xcl.p, h->in_pad, h->inp_block, T), rows, h->h0.p, C, 0, s);
 	launch_cast(h->dt, cs, h->csT.p, (int64_t)rows * C, s);
 	if (cs_consumed) (void)hipEventRecord(cs_consumed, s);     // the last reader of `cs`: the side stream may overwrite it from here on
-	{   // integrating_conv over cat([h0, code_emb], channels): two K segments of one [C][2C] matrix
-		GemmParams g = {};
-		g.nseg = 2;
-		g.seg[0] = {h->h0.p, C, 0, 0};
-		g.seg[1] = {h->csT.p, C, 0, C};
-		g.W = h->integ.w; g.ldw = h->integ.Kpad; g.M = rows; g.N = C; g.K = C; g.bias = h->integ.bias;
-		g.C = x; g.ldc = C; g.out_f32 = 1;
-		want_stats(h, g, T);
-		launch_gemm(h->dt, g, s);
-	}
+	// integrating_conv over cat([h0, code_emb], channels): two K segments of one [C][2C] matrix
+	gemm(h, h->integ, {2, C, 0, {{h->h0.p, C, 0, 0}, {h->csT.p, C, 0, C}}}, rows, x, C, 1, s, {T});
 	for (size_t i = 0; i < h->layers.size(); ++i) {
 		res_block(h, h->layers[i].res, x, nb, T, emb_all, emb_stride, s);
 		attn_block(h, h->layers[i].attn, x, nb, T, s);
 	}
 	for (int i = 0; i < 3; ++i) res_block(h, h->tail[i], x, nb, T, emb_all, emb_stride, s);
-	gn(h, x, nb, T, h->out_g, h->out_b, nullptr, nullptr, 0, ACT_SILU, h->L->a.p, 0, nullptr, T, s);
-	gemm_conv3(h, h->L->a.p, C, h->out_conv, rows, T, out, 0, 1, nullptr, 1, s);
-}
-static void network(ttk_diff* h, int nb, int T, const float* emb_all, int64_t emb_stride, float* out, hipStream_t s,
-					const float* cs_in = nullptr, const float* ms_in = nullptr) {
-	integrator(h, nb, T, emb_all, emb_stride, (float*)h->cs.p, s, cs_in, ms_in);
-	body(h, nb, T, emb_all, emb_stride, (const float*)h->cs.p, out, s);
+	gn(h, x, nb, T, {h->out_g, h->out_b, ACT_SILU}, s);
+	Epi t; t.transpose = 1;
+	gemm(h, h->out_conv, taps3(h->L->a.p, C, h->out_conv, T), rows, out, 0, 1, s, t);
 }
 
 static int load_attn(ttk_diff* h, const WeightMap& wm, const std::string& p, AttnBlk* A) {
@@ -259,11 +257,9 @@ int ttk_diff_create(ttk_diff** out, const ttk_diff_config* cfg, const ttk_weight
 	h->cfg = *cfg;
 	h->wdt = cfg->dtype;              // ResBlock / AttentionBlock GEMM weights: rounded to fp8-e4m3 in DT_FP8W (held exactly in bf16)
 	h->dt = kernel_dtype(cfg->dtype);
-	h->a8 = cfg->dtype == TTK_FP8;
 	h->es = dtype_size(h->dt);
 	h->in_pad = round_up(cfg->in_channels, 64);
 	h->fuse_stats = getenv("TTK_NO_FUSED_GN") ? 0 : 1;
-	{ const char* e = getenv("TTK_DIFF_PREFETCH"); h->prefetch = e ? atoi(e) : 1; }
 	{ const char* e = getenv("TTK_DIFF_PIPE"); h->pipe = e ? atoi(e) : 1; }
 	const int C = cfg->model_channels;
 	WeightMap wm(w, n_w);
@@ -322,10 +318,12 @@ int ttk_diff_precompute(ttk_diff* h, const float* latents, const float* cond, co
 	TTK_TRY(h->lat_T.reserve((size_t)b * M * Cl * h->es));
 	float* x = (float*)h->xs.p;
 	launch_cast(h->dt, latents, h->lat_T.p, (int64_t)b * M * Cl, s);   // latents are already [b][M][Cl] = channels-last
-	gemm_conv3(h, h->lat_T.p, Cl, h->lat_conv, b * M, M, x, C, 1, nullptr, 0, s, M);
+	gemm(h, h->lat_conv, taps3(h->lat_T.p, Cl, h->lat_conv, M), b * M, x, C, 1, s, {M});
 	for (int i = 0; i < 4; ++i) attn_block(h, h->lat_attn[i], x, b, M, s);
 	// code_norm(x) * (1 + scale) + shift, then nearest-neighbour expansion M -> T      diffusion.py:1492,1498,1507
-	gn(h, x, b, M, h->code_g, h->code_b, cond, cond + C, 2 * C, ACT_NONE, h->ecl.p, 1, interp_idx, T, s);
+	Gn d = {h->code_g, h->code_b, ACT_NONE, nullptr, cond, 2 * C};
+	d.out = h->ecl.p; d.out_f32 = 1; d.row_idx = interp_idx; d.Tout = T;
+	gn(h, x, b, M, d, s);
 	launch_cl_to_cf((const float*)h->ecl.p, b, C, T, E_out, s);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
@@ -342,7 +340,9 @@ int ttk_diff_forward(ttk_diff* h, const float* x, const int64_t* t, const float*
 	else launch_bcast_rows(DT_F32, h->uncond, b * T, C, h->cs.p, s);            // diffusion.py:1534
 	launch_cf_to_cl(h->dt, x, b, h->cfg.in_channels, T, h->xcl.p, h->in_pad, 1, s);
 	TTK_TRY(time_path(h, t, nullptr, b, s));
-	network(h, b, T, (const float*)h->emb_all.p, (int64_t)h->n_emb * 2 * C, out, s);
+	const int64_t stride = (int64_t)h->n_emb * 2 * C;
+	integrator(h, b, T, (const float*)h->emb_all.p, stride, (float*)h->cs.p, s, false);
+	body(h, b, T, (const float*)h->emb_all.p, stride, (const float*)h->cs.p, out, s);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
@@ -362,53 +362,41 @@ int ttk_diff_begin(ttk_diff* h, const float* E, int b, int T, void* stream) {
 	h->cur_b = b; h->cur_T = T; h->staged = 1;
 	// ... and so is the first half of the first integrator ResBlock on it, conv1x1(SiLU(GN(ecl))), with the statistics its second GroupNorm needs: the
 	// same launches a step would run (so the same bits), once per utterance instead of once per step
-	static const int hoist = [] { const char* e = getenv("TTK_DIFF_HOIST"); return e ? atoi(e) : 1; }();
-	h->hf0_valid = 0;
-	if (hoist) {
-		const int nb = 2 * b, nch = gn_num_chunks(T, C);
-		const size_t ms_bytes = (size_t)nb * 32 * nch * 3 * 4;
-		TTK_TRY(h->hf0.reserve((size_t)nb * T * C * 4)); TTK_TRY(h->ms_hf0.reserve(ms_bytes));
-		const ResBlk& R = h->integrator[0].res;
-		gn(h, ecl, nb, T, R.gn1_g, R.gn1_b, nullptr, nullptr, 0, ACT_SILU, h->L->a.p, 0, nullptr, T, s, &R.in, (const float*)h->ms_ecl.p);
-		gemm1(h, h->L->a.p, C, R.in, nb * T, h->hf0.p, C, 1, ACT_NONE, nullptr, s, T);
-		if (h->L->ms_owner == (const void*)h->hf0.p) {      // statistics left by the GEMM's epilogue (gn() would take them from there) ...
-			TTK_HIP(hipMemcpyAsync(h->ms_hf0.p, h->L->ms.p, ms_bytes, hipMemcpyDeviceToDevice, s));
-			if (h->need) launch_gn_stats((const float*)h->hf0.p, nb, T, C, (float*)h->ms_hf0.p, s, h->tlen, h->need);   // ... except for the ragged sequences of a batch
-		} else {
-			launch_gn_stats((const float*)h->hf0.p, nb, T, C, (float*)h->ms_hf0.p, s, h->tlen);
-		}
-		h->L->ms_owner = nullptr;
-		h->hf0_valid = 1;
-	}
+	TTK_TRY(h->hf0.reserve((size_t)2 * b * T * C * 4)); TTK_TRY(h->ms_hf0.reserve((size_t)2 * b * 32 * gn_num_chunks(T, C) * 3 * 4));
+	res_in(h, h->integrator[0].res, ecl, 2 * b, T, s, (float*)h->hf0.p, (const float*)h->ms_ecl.p, (float*)h->ms_hf0.p);
+	stats_of(h, (const float*)h->hf0.p, 2 * b, T, s, (float*)h->ms_hf0.p);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
 
-// the part of a sampler step that sees x: layout change, network body on the integrated code stream `cs`, the DDIM / ancestral update
-// staged: the previous step of this loop has already written this step's channels-last copy of x (its update launch did); next: the step that follows in this loop, or null --
-// its copy is then written by THIS step's update launch (round 6: one layout launch per loop instead of one per step; not for ragged batches, whose padding frames must read zero)
-static int step_body(ttk_diff* h, float* x, const ttk_step* st, const float* noise, const float* emb_row, const float* cs, hipEvent_t cs_consumed, hipStream_t s,
-					 bool staged = false, const ttk_step* next = nullptr) {
-	const int b = h->cur_b, T = h->cur_T;
-	const bool cf = st->cfk >= 0.f;
-	const int nb = cf ? 2 * b : b;
-	if (!staged || h->tlen) launch_cf_to_cl(h->dt, x, b, h->cfg.in_channels, T, h->xcl.p, h->in_pad, cf ? 2 : 1, s, h->tlen);
-	float* out = (float*)h->outb.p;
-	body(h, nb, T, emb_row, 0, cs, out, s, cs_consumed);
-	StepCoefs k = {};
-	k.sqrt_recip_ac = st->sqrt_recip_ac; k.sqrt_recipm1_ac = st->sqrt_recipm1_ac; k.sqrt_ac_prev = st->sqrt_ac_prev;
-	k.sqrt_1m_ac_prev = st->sqrt_1m_ac_prev; k.cfk = st->cfk; k.coef1 = st->coef1; k.coef2 = st->coef2;
-	k.min_log = st->min_log; k.max_log = st->max_log; k.sampler = st->sampler; k.nonzero = st->nonzero;
-	const int Cin = h->cfg.in_channels;
-	if (next && !h->tlen && (next->cfk >= 0.f) == cf) launch_diffusion_step(      // (same batch layout in the next step: its padding columns are already zero)
-		out, out + (size_t)b * h->cfg.out_channels * T, x, noise, b, Cin, T, k, s, h->xcl.p, h->in_pad, next->cfk >= 0.f ? 2 : 1, elem_kind(h->dt));
-	else launch_diffusion_step(out, out + (size_t)b * h->cfg.out_channels * T, x, noise, b, Cin, T, k, s);
-	return TTK_OK;
+static StepCoefs coefs_of(const ttk_step& st) {
+	return {st.sqrt_recip_ac, st.sqrt_recipm1_ac, st.sqrt_ac_prev, st.sqrt_1m_ac_prev, st.cfk, st.coef1, st.coef2, st.min_log, st.max_log, st.sampler, st.nonzero};
 }
-static int step_impl(ttk_diff* h, float* x, const ttk_step* st, const float* noise, const float* emb_row, hipStream_t s) {
-	const int nb = st->cfk >= 0.f ? 2 * h->cur_b : h->cur_b;
-	integrator(h, nb, h->cur_T, emb_row, 0, (float*)h->cs.p, s, (const float*)h->ecl.p, (const float*)h->ms_ecl.p);
-	return step_body(h, x, st, noise, emb_row, (const float*)h->cs.p, nullptr, s);
+// The steps of a loop in the order they run: steps[n-1], ..., steps[0]; `noise` (ancestral sampler) holds one [b, in, T] draw per step in that order, null for ddim;
+// emb_all has one row per schedule index.  One layout launch per run of steps with the same batch layout: each update launch writes the next step's copy of x.
+static std::vector<StepPlan> plan_steps(ttk_diff* h, const ttk_step* steps, int n, const float* emb_all, int64_t emb_stride, const float* noise) {
+	const size_t nz = (size_t)h->cur_b * h->cfg.in_channels * h->cur_T;
+	std::vector<StepPlan> plan(n);
+	for (int j = 0; j < n; ++j) {
+		const int i = n - 1 - j;
+		const bool cf = steps[i].cfk >= 0.f;
+		StepPlan& p = plan[j];
+		p.st = &steps[i]; p.nb = cf ? 2 * h->cur_b : h->cur_b; p.emb = emb_all + i * emb_stride; p.noise = noise ? noise + j * nz : nullptr;
+		p.layout = j == 0 || !plan[j - 1].stage_next;
+		p.stage_next = i > 0 && !h->tlen && (steps[i - 1].cfk >= 0.f) == cf;
+	}
+	return plan;
+}
+
+// the part of a sampler step that sees x: layout change, network body on the integrated code stream `cs`, the DDIM / ancestral update
+static void step_body(ttk_diff* h, float* x, const StepPlan& p, const float* cs, hipEvent_t cs_consumed, hipStream_t s) {
+	const int b = h->cur_b, T = h->cur_T, Cin = h->cfg.in_channels, rep = p.nb / b;
+	if (p.layout) launch_cf_to_cl(h->dt, x, b, Cin, T, h->xcl.p, h->in_pad, rep, s, h->tlen);
+	float* out = (float*)h->outb.p;
+	body(h, p.nb, T, p.emb, 0, cs, out, s, cs_consumed);
+	const float* out_u = out + (size_t)b * h->cfg.out_channels * T;
+	if (p.stage_next) launch_diffusion_step(out, out_u, x, p.noise, b, Cin, T, coefs_of(*p.st), s, h->xcl.p, h->in_pad, rep, elem_kind(h->dt));      // (its padding columns are already zero)
+	else launch_diffusion_step(out, out_u, x, p.noise, b, Cin, T, coefs_of(*p.st), s);
 }
 
 int ttk_diff_step(ttk_diff* h, float* x, const ttk_step* st, const float* noise, void* stream) {
@@ -418,66 +406,63 @@ int ttk_diff_step(ttk_diff* h, float* x, const ttk_step* st, const float* noise,
 	TTK_REQUIRE(h->cfg.out_channels == 2 * h->cfg.in_channels, TTK_E_ARG, "ttk_diff_step: learned-range output needs out = 2 * in channels");
 	hipStream_t s = (hipStream_t)stream;
 	TTK_TRY(time_path(h, nullptr, &st->t, 1, s));
-	TTK_TRY(step_impl(h, x, st, noise, (const float*)h->emb_all.p, s));
+	const StepPlan p = plan_steps(h, st, 1, (const float*)h->emb_all.p, 0, noise)[0];
+	integrator(h, p.nb, h->cur_T, p.emb, 0, (float*)h->cs.p, s, true);
+	step_body(h, x, p, (const float*)h->cs.p, nullptr, s);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
 
-// The whole sampler loop, both samplers: steps[n-1], ..., steps[0]; `noise` (ancestral sampler) holds one [b, in, T] draw per step in the order
-// the loop consumes them (the j-th executed step reads block j), null for ddim.
+// The whole sampler loop, both samplers (see plan_steps for the order of steps and noise).
 static int sample_loop(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, int sampler, void* stream, const char* who) {
 	TTK_REQUIRE(h && x && E && steps && n_steps >= 1, TTK_E_ARG, "%s: bad argument", who);
 	TTK_REQUIRE(sampler == 0 || noise, TTK_E_ARG, "%s: the p sampler needs one noise block per step", who);
 	TTK_REQUIRE(h->cfg.out_channels == 2 * h->cfg.in_channels, TTK_E_ARG, "%s: learned-range output needs out = 2 * in channels", who);
-	const size_t nz = (size_t)b * h->cfg.in_channels * T;
 	hipStream_t s = (hipStream_t)stream;
 	TTK_TRY(ttk_diff_begin(h, E, b, T, stream));
 	// the timestep-only work of ALL steps in one pass: [n_steps] rows through time_embed + every emb_layers (weights read once)
 	std::vector<int64_t> ts(n_steps);
 	for (int i = 0; i < n_steps; ++i) { ts[i] = steps[i].t; TTK_REQUIRE(steps[i].sampler == sampler, TTK_E_ARG, "%s: step %d has sampler %d", who, i, steps[i].sampler); }
 	TTK_TRY(time_path(h, nullptr, ts.data(), n_steps, s));
-	const int64_t stride = (int64_t)h->n_emb * 2 * h->cfg.model_channels;
-	const float* emb_all = (const float*)h->emb_all.p;
-	if (!h->pipe || n_steps < 2) {
-		for (int i = n_steps - 1; i >= 0; --i) TTK_TRY(step_impl(h, x, &steps[i], noise ? noise + (size_t)(n_steps - 1 - i) * nz : nullptr, emb_all + i * stride, s));
-		TTK_HIP(hipGetLastError());
-		return TTK_OK;
-	}
+	const std::vector<StepPlan> plan = plan_steps(h, steps, n_steps, (const float*)h->emb_all.p, (int64_t)h->n_emb * 2 * h->cfg.model_channels, noise);
 	// Pipelined over two streams.  The integrator of a step depends on its timestep and the staged embedding only, never on x: the one of
 	// step j+1 runs on the side stream (own scratch lane, the other `cs` buffer) while the body of step j runs here.  Both are chains of
-	// small dependent launches that leave most of the chip idle, so they overlap; one fork and one join edge per step.
-	const int nb_max = 2 * b;
-	if (!h->side) {
-		TTK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
-		TTK_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-		for (int i = 0; i < 2; ++i) {
-			TTK_HIP(hipEventCreateWithFlags(&h->ev_int[i], hipEventDisableTiming));
-			TTK_HIP(hipEventCreateWithFlags(&h->ev_free[i], hipEventDisableTiming));
+	// small dependent launches that leave most of the chip idle, so they overlap; one fork and one join edge per step.  Sequential
+	// (TTK_DIFF_PIPE=0, or a single step): the same launches, each integrator in front of its body on the caller's stream.
+	const bool pipe = h->pipe && n_steps >= 2;
+	float* csb[2] = {(float*)h->cs.p, (float*)h->cs.p};
+	if (pipe) {
+		if (!h->side) {
+			TTK_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
+			TTK_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+			for (int i = 0; i < 2; ++i) {
+				TTK_HIP(hipEventCreateWithFlags(&h->ev_int[i], hipEventDisableTiming));
+				TTK_HIP(hipEventCreateWithFlags(&h->ev_free[i], hipEventDisableTiming));
+			}
 		}
+		TTK_TRY(reserve_lane(h, h->lane[1], 2 * b, T));
+		TTK_TRY(h->cs2.reserve((size_t)2 * b * T * h->cfg.model_channels * 4));
+		csb[1] = (float*)h->cs2.p;
+		TTK_HIP(hipEventRecord(h->ev_fork, s));
+		TTK_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
 	}
-	TTK_TRY(reserve_lane(h, h->lane[1], nb_max, T));
-	TTK_TRY(h->cs2.reserve((size_t)nb_max * T * h->cfg.model_channels * 4));
-	float* csb[2] = {(float*)h->cs.p, (float*)h->cs2.p};
-	TTK_HIP(hipEventRecord(h->ev_fork, s));
-	TTK_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-	auto enqueue_integrator = [&](int j) {      // j-th step of the loop = schedule index n_steps - 1 - j
-		const int i = n_steps - 1 - j;
-		const int nb = steps[i].cfk >= 0.f ? 2 * b : b;
-		h->L = &h->lane[1];
-		integrator(h, nb, T, emb_all + i * stride, 0, csb[j & 1], h->side, (const float*)h->ecl.p, (const float*)h->ms_ecl.p);
+	auto enqueue_integrator = [&](int j) {
+		if (pipe) h->L = &h->lane[1];
+		integrator(h, plan[j].nb, T, plan[j].emb, 0, csb[j & 1], pipe ? h->side : s, true);
 		h->L = &h->lane[0];
-		(void)hipEventRecord(h->ev_int[j & 1], h->side);
+		if (pipe) (void)hipEventRecord(h->ev_int[j & 1], h->side);
 	};
-	enqueue_integrator(0);
+	if (pipe) enqueue_integrator(0);
 	for (int j = 0; j < n_steps; ++j) {
-		if (j + 1 < n_steps) {
-			if (j >= 1) TTK_HIP(hipStreamWaitEvent(h->side, h->ev_free[(j - 1) & 1], 0));   // body j-1 has read the buffer integrator j+1 writes
-			enqueue_integrator(j + 1);
+		if (!pipe) enqueue_integrator(j);
+		else {
+			if (j + 1 < n_steps) {
+				if (j >= 1) TTK_HIP(hipStreamWaitEvent(h->side, h->ev_free[(j - 1) & 1], 0));   // body j-1 has read the buffer integrator j+1 writes
+				enqueue_integrator(j + 1);
+			}
+			TTK_HIP(hipStreamWaitEvent(s, h->ev_int[j & 1], 0));
 		}
-		TTK_HIP(hipStreamWaitEvent(s, h->ev_int[j & 1], 0));
-		const int i = n_steps - 1 - j;
-		const bool staged = j > 0 && (steps[i + 1].cfk >= 0.f) == (steps[i].cfk >= 0.f);      // the previous step's update launch wrote this step's copy (see step_body)
-		TTK_TRY(step_body(h, x, &steps[i], noise ? noise + (size_t)j * nz : nullptr, emb_all + i * stride, csb[j & 1], h->ev_free[j & 1], s, staged, i > 0 ? &steps[i - 1] : nullptr));
+		step_body(h, x, plan[j], csb[j & 1], pipe ? h->ev_free[j & 1] : nullptr, s);
 	}
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

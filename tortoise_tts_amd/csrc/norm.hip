@@ -5,7 +5,6 @@
 //                used by ResBlock diffusion.py:1338-1372 and AttentionBlock arch_utils.py:163,186
 // Internal layout is channels-last [nb][T][C], so a group is (T rows) x (C/32 contiguous channels).
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "ttk_common.h"
 #include "ttk_kernels.h"
@@ -149,9 +148,11 @@ void launch_gn_stats(const float* x, int nb, int T, int C, float* part, hipStrea
 // apply: a block owns a strip of output rows of ONE batch element.  It first merges that element's 32 groups' chunk statistics
 // (Chan et al.) into LDS, then streams its rows: thread = 4 consecutive channels (one group, since C/32 % 4 == 0).
 // GN_PASSES rows per thread: a block's fixed cost (merging 32 groups x nchunks triples, the barrier) is paid once per strip of 256 / (C/4) * GN_PASSES
-// rows; 2 = 1088 blocks of 2 rows at T = 1088, 8 = 272 blocks of 8 rows (TTK_GN_PASSES, decided by tests/diag/ddim_ab.py)
-template <typename OT, int GN_PASSES>
+// rows.  2 = 1088 blocks of 2 rows at T = 1088; 1, 4 and 8 (8 = 272 blocks of 8 rows) were tried against it with tests/diag/ddim_ab.py and lost, and with few
+// rows in all (short clips, the latent conditioner) the small strips keep the launch spread over the chip.
+template <typename OT>
 __global__ __launch_bounds__(256) void k_gn_apply(GnApplyParams p) {
+	constexpr int GN_PASSES = 2;
 	__shared__ float s_mean[32], s_rstd[32];
 	TTK_WSTAMP(p.stamps, blockIdx.x, 0);
 	const int c4n = p.C / 4;                    // threads per row
@@ -224,16 +225,20 @@ __global__ __launch_bounds__(256) void k_gn_apply(GnApplyParams p) {
 // could not be used before the touched HBM lines had come back.  Here: grid (strips, batch) -- no division at all --, the arguments pinned into SGPRs
 // by one batch of scalar loads, every request (rows, affine parameters, triples) issued up front, and the touches on a FIFTH wave that does nothing
 // else and leaves before the barrier (a terminated wave does not take part in s_barrier), so nobody waits for them but the kernel's end -- which the
-// four working waves reach later anyway.  Same arithmetic in the same order as k_gn_apply: bit-identical output.
-template <typename OT, int GN_PASSES, bool GN_TOUCH_WAVE>
-__global__ __launch_bounds__(GN_TOUCH_WAVE ? 320 : 256) void k_gn_apply_c1024(GnApplyParams p) {
-	constexpr int C = 1024;
+// four working waves reach later anyway.  Same arithmetic in the same order as k_gn_apply: bit-identical output (tests/test_gpu_gn_forms.py).
+// The fifth wave won against touches issued by the four working waves once their own loads are consumed: 122.8 - 123.0 against 123.5 - 123.7 us per layer in
+// tests/diag/ddim_chain (both far ahead of touches issued between the row requests and the triples).
+// Four rows per thread: with 2 the 1088 five-wave workgroups of a DDIM step do not fit the chip at once (two waves of each land on one SIMD: 4 per CU, 1024 slots)
+// and the last 64 start 3 us late; with 4 all 544 are resident within 0.5 us (tests/diag/ddim_chain: 4.5 / 5.1 / 5.2 -> 4.2 / 4.7 / 4.8 us per launch).
+template <typename OT>
+__global__ __launch_bounds__(320) void k_gn_apply_c1024(GnApplyParams p) {
+	constexpr int C = 1024, GN_PASSES = 4;
 	__shared__ unsigned pf_sink[64 * 4];
 	TTK_PIN_ARGS(TTK_S(p.x), TTK_S(p.ms), TTK_S(p.gamma), TTK_S(p.beta), TTK_S(p.scale), TTK_S(p.shift), TTK_S(p.ss_stride), TTK_S(p.T), TTK_S(p.nchunks),
 				 TTK_S(p.act), TTK_S(p.out), TTK_S(p.tlen), TTK_S(p.chunk_rows), TTK_S(p.pf), TTK_S(p.pf_bytes), TTK_S(p.pf_taps));
 	TTK_WSTAMP(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 0);
 	const int tid = threadIdx.x;
-	if (GN_TOUCH_WAVE && tid >= 256) {      // the touch wave: the following GEMM's weights into L2 (see GnApplyParams), then gone
+	if (tid >= 256) {      // the touch wave: the following GEMM's weights into L2 (see GnApplyParams), then gone
 		if (p.pf) l2_touch_for_next(p.pf, p.pf_bytes, p.pf_taps, __builtin_amdgcn_readfirstlane(lds_byte_addr(pf_sink)), blockIdx.y * gridDim.x + blockIdx.x,
 									gridDim.x * gridDim.y, tid - 256, 64);
 		return;
@@ -261,10 +266,6 @@ __global__ __launch_bounds__(GN_TOUCH_WAVE ? 320 : 256) void k_gn_apply_c1024(Gn
 		gn_merge_triples(part, nch, sub, [](const float* q) { return *q; }, mean, rstd);
 	}
 	TTK_WSTAMPD(p.stamps, blockIdx.y * gridDim.x + blockIdx.x, 2, rstd);
-	// (no fifth wave: the touches leave HERE -- every load this thread waits for has been consumed, nothing below waits on vmcnt, so they cost the
-	// workgroup only their issue slots and keep it alive until they land)
-	if (!GN_TOUCH_WAVE && p.pf) l2_touch_for_next(p.pf, p.pf_bytes, p.pf_taps, __builtin_amdgcn_readfirstlane(lds_byte_addr(pf_sink) + (tid >> 6) * 64), blockIdx.y * gridDim.x + blockIdx.x,
-												   gridDim.x * gridDim.y, tid, 256);
 	float a0, a1, a2, a3, d0, d1, d2, d3;
 	gn_fold_coef(mean, rstd, ga.x, be.x, sc.x, sh.x, a0, d0); gn_fold_coef(mean, rstd, ga.y, be.y, sc.y, sh.y, a1, d1);
 	gn_fold_coef(mean, rstd, ga.z, be.z, sc.z, sh.z, a2, d2); gn_fold_coef(mean, rstd, ga.w, be.w, sc.w, sh.w, a3, d3);
@@ -291,7 +292,7 @@ __global__ __launch_bounds__(GN_TOUCH_WAVE ? 320 : 256) void k_gn_apply_c1024(Gn
 // first `rem` strips (q = T / strips, rem = T % strips, both from the host: no division here) -- one workgroup per CU, 8 or 9 rows each at the DDIM step's T = 1088.
 // The fixed 4-row strips make 544 workgroups there, 2.125 per CU: the 32 CUs that hold three set the launch (4.4 us against 3.7 us for the same launch at T = 1024,
 // where 512 workgroups are two per CU; profiles/r04_ddim_chain_T1024_vs_T1088.log).  Up to GN_MAXR rows per thread, every request up front; elementwise, same
-// arithmetic: bit-identical output.
+// arithmetic: bit-identical output (tests/test_gpu_gn_forms.py).
 template <typename OT, int GN_MAXR, int NG = 8>      // NG: groups of eight statistics chunks a lane asks for (3 serves sequences up to 1536 frames: 9 dwords per lane instead of 24)
 __global__ __launch_bounds__(320) void k_gn_apply_c1024_even(GnApplyParams p, int q, int rem) {
 	constexpr int C = 1024;
@@ -353,60 +354,55 @@ __global__ __launch_bounds__(320) void k_gn_apply_c1024_even(GnApplyParams p, in
 #endif
 }
 
-template <int PASSES>
-static void launch_gn_apply_p(int dt, const GnApplyParams& p, hipStream_t s) {
-	const int strip = (256 / (p.C / 4)) * PASSES;
-	const int grid = p.nb * ((p.Tout + strip - 1) / strip);
-	if (p.out_f8) hipLaunchKernelGGL((k_gn_apply<f8, PASSES>), dim3(grid), dim3(256), 0, s, p);
-	else if (p.out_f32 || dt == DT_F32) hipLaunchKernelGGL((k_gn_apply<float, PASSES>), dim3(grid), dim3(256), 0, s, p);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_gn_apply<f16, PASSES>), dim3(grid), dim3(256), 0, s, p);
-	else hipLaunchKernelGGL((k_gn_apply<bf16, PASSES>), dim3(grid), dim3(256), 0, s, p);
-}
-void launch_gn_apply(int dt, const GnApplyParams& p, hipStream_t s) {
-	ProfScope prof(PROF_GN_APPLY, (double)p.nb * p.Tout * p.C * (4.0 + (p.out_f8 ? 1.0 : p.out_f32 ? 4.0 : dtype_size(dt))), s);
-	static const int passes = [] { const char* e = getenv("TTK_GN_PASSES"); return e ? atoi(e) : 2; }();
-	static const int fast = [] { const char* e = getenv("TTK_GN_FAST"); return e ? atoi(e) : 1; }();      // 0: the generic kernel everywhere
-	if (fast && p.C == 1024 && !p.row_idx && p.Tout == p.T && passes == 2 && p.nb <= 65535) {      // the DDIM loop's launches: k_gn_apply_c1024
-		// rows per thread: with 2 the 1088 five-wave workgroups of a DDIM step do not fit the chip at once (two waves of each land on one SIMD: 4 per CU, 1024 slots) and
-		// the last 64 start 3 us late; with 4 all 544 are resident within 0.5 us (tests/diag/ddim_chain: 4.5 / 5.1 / 5.2 -> 4.2 / 4.7 / 4.8 us per launch)
-		// rows dealt evenly, one workgroup per CU (k_gn_apply_c1024_even), when a sequence's rows split into <= 256 / nb strips of 4 .. 18 rows and the batch is not ragged
-		static const int even = [] { const char* e = getenv("TTK_GN_EVEN"); return e ? atoi(e) : 1; }();
-		if (even && !p.tlen && p.nb >= 1 && p.nb <= 64) {
-			const int strips = 256 / p.nb, q = p.T / strips, rem = p.T % strips;
-			if (q >= 4 && q + (rem ? 1 : 0) <= 18) {
-				const dim3 grid(strips, p.nb);
-#define GN_EVEN(OT) do { const int mr = q + (rem ? 1 : 0); \
-						if (p.nchunks <= 24 && mr <= 9) hipLaunchKernelGGL((k_gn_apply_c1024_even<OT, 9, 3>), grid, dim3(320), 0, s, p, q, rem); \
-						else if (p.nchunks <= 24 && mr <= 12) hipLaunchKernelGGL((k_gn_apply_c1024_even<OT, 12, 3>), grid, dim3(320), 0, s, p, q, rem); \
-						else hipLaunchKernelGGL((k_gn_apply_c1024_even<OT, 18, 8>), grid, dim3(320), 0, s, p, q, rem); } while (0)
-				if (p.out_f8) GN_EVEN(f8);
-				else if (p.out_f32 || dt == DT_F32) GN_EVEN(float);
-				else if (dt == DT_F16) GN_EVEN(f16);
-				else GN_EVEN(bf16);
-#undef GN_EVEN
-				return;
-			}
-		}
-		static const int cp = [] { const char* e = getenv("TTK_GN_C1024_PASSES"); return e && atoi(e) == 2 ? 2 : 4; }();
-		const dim3 grid((p.T + cp - 1) / cp, p.nb);
-		// the weight touches on a fifth wave (default) or, TTK_GN_TOUCH_WAVE=0, issued by the four working waves once their own loads are consumed:
-		// 122.8 - 123.0 against 123.5 - 123.7 us per layer in tests/diag/ddim_chain (both far ahead of touches issued between the row requests and the triples)
-		static const int tw = [] { const char* e = getenv("TTK_GN_TOUCH_WAVE"); return e ? atoi(e) : 1; }();
-#define GN_GO(OT) do { if (cp == 4) { if (tw) hipLaunchKernelGGL((k_gn_apply_c1024<OT, 4, true>), grid, dim3(320), 0, s, p); else hipLaunchKernelGGL((k_gn_apply_c1024<OT, 4, false>), grid, dim3(256), 0, s, p); } \
-	else if (tw) hipLaunchKernelGGL((k_gn_apply_c1024<OT, 2, true>), grid, dim3(320), 0, s, p); else hipLaunchKernelGGL((k_gn_apply_c1024<OT, 2, false>), grid, dim3(256), 0, s, p); } while (0)
-		if (p.out_f8) GN_GO(f8);
-		else if (p.out_f32 || dt == DT_F32) GN_GO(float);
-		else if (dt == DT_F16) GN_GO(f16);
-		else GN_GO(bf16);
-#undef GN_GO
-		return;
+// The form a launch gets (host only).  Generic: k_gn_apply, everything.  Strips: k_gn_apply_c1024, the DDIM loop's launches (C = 1024, no row gather).  Even:
+// k_gn_apply_c1024_even<rows, NG>, one workgroup per CU, when a sequence's rows split into 256 / nb strips of 4 .. 18 rows and the batch is not ragged.
+enum GnApplyForm { GN_GENERIC = 1, GN_STRIPS = 2, GN_EVEN_9 = 3, GN_EVEN_12 = 4, GN_EVEN_18 = 5 };
+static int gn_apply_form(const GnApplyParams& p) {
+	if (!(p.C == 1024 && !p.row_idx && p.Tout == p.T && p.nb <= 65535)) return GN_GENERIC;
+	if (!p.tlen && p.nb >= 1 && p.nb <= 64) {
+		const int strips = 256 / p.nb, q = p.T / strips, mr = q + (p.T % strips ? 1 : 0);
+		if (q >= 4 && mr <= 18) return p.nchunks <= 24 && mr <= 9 ? GN_EVEN_9 : (p.nchunks <= 24 && mr <= 12 ? GN_EVEN_12 : GN_EVEN_18);
 	}
-	// few rows in all (short clips, the latent conditioner): keep the strips small so the launch still spreads over the chip
-	const int rows = p.nb * p.Tout * (p.C / 4) / 256;
-	if (passes >= 8 && rows >= 8 * 256) launch_gn_apply_p<8>(dt, p, s);
-	else if (passes >= 4 && rows >= 4 * 256) launch_gn_apply_p<4>(dt, p, s);
-	else if (passes == 1) launch_gn_apply_p<1>(dt, p, s);
-	else launch_gn_apply_p<2>(dt, p, s);
+	return GN_STRIPS;
+}
+const char* gn_apply_form_refusal(const GnApplyParams& p, int form) {
+	if (form < 0 || form > GN_EVEN_18) return "form must be 0 (the launcher's choice), 1 (generic), 2 (4-row strips), 3, 4 or 5 (even: 9, 12 or 18 rows)";
+	if (form <= GN_GENERIC) return nullptr;
+	if (p.C != 1024 || p.row_idx || p.Tout != p.T || p.nb > 65535) return "forms 2 to 5 need C == 1024, no row_idx, Tout == T and nb <= 65535";
+	if (form == GN_STRIPS) return nullptr;
+	if (p.tlen || p.nb < 1 || p.nb > 64) return "the even forms need no tlen and nb <= 64";
+	const int strips = 256 / p.nb, q = p.T / strips, mr = q + (p.T % strips ? 1 : 0);
+	if (q < 4 || mr > (form == GN_EVEN_9 ? 9 : (form == GN_EVEN_12 ? 12 : 18))) return "the even forms need strips (T over 256 / nb) of at least 4 rows and at most 9 / 12 / 18";
+	if (form != GN_EVEN_18 && p.nchunks > 24) return "forms 3 and 4 read at most 24 statistics chunks";
+	return nullptr;
+}
+
+// the one output-type dispatch: go(OT{}) with the element type of `out`
+template <typename F>
+static void gn_out_type(int dt, const GnApplyParams& p, F&& go) {
+	if (p.out_f8) go(f8{});
+	else if (p.out_f32 || dt == DT_F32) go(float{});
+	else if (dt == DT_F16) go(f16{});
+	else go(bf16{});
+}
+void launch_gn_apply(int dt, const GnApplyParams& p, hipStream_t s, int form) {
+	ProfScope prof(PROF_GN_APPLY, (double)p.nb * p.Tout * p.C * (4.0 + (p.out_f8 ? 1.0 : p.out_f32 ? 4.0 : dtype_size(dt))), s);
+	if (!form) form = gn_apply_form(p);
+	gn_out_type(dt, p, [&](auto ot) {
+		using OT = decltype(ot);
+		if (form == GN_GENERIC) {
+			const int strip = (256 / (p.C / 4)) * 2;
+			hipLaunchKernelGGL((k_gn_apply<OT>), dim3(p.nb * ((p.Tout + strip - 1) / strip)), dim3(256), 0, s, p);
+		} else if (form == GN_STRIPS) {
+			hipLaunchKernelGGL((k_gn_apply_c1024<OT>), dim3((p.T + 3) / 4, p.nb), dim3(320), 0, s, p);
+		} else {
+			const int strips = 256 / p.nb, q = p.T / strips, rem = p.T % strips;
+			const dim3 grid(strips, p.nb);
+			if (form == GN_EVEN_9) hipLaunchKernelGGL((k_gn_apply_c1024_even<OT, 9, 3>), grid, dim3(320), 0, s, p, q, rem);
+			else if (form == GN_EVEN_12) hipLaunchKernelGGL((k_gn_apply_c1024_even<OT, 12, 3>), grid, dim3(320), 0, s, p, q, rem);
+			else hipLaunchKernelGGL((k_gn_apply_c1024_even<OT, 18, 8>), grid, dim3(320), 0, s, p, q, rem);
+		}
+	});
 }
 
 }  // namespace ttk

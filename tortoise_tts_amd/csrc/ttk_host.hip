@@ -273,6 +273,39 @@ extern "C" int ttk_attn_fwd(int dtype, const ttk_attn_desc* d, void* stream) {
 	return TTK_OK;
 }
 
+// Every launch form of GroupNorm-apply on caller-provided operands (include/ttk.h): the descriptor is GnApplyParams plus the host-only form, and `stats` for the
+// statistics launch in front.  With form = 0 the launcher chooses exactly as for the handles' launches.
+static_assert(sizeof(ttk_gn_desc) == 144, "ttk_gn_desc layout (tortoise_tts_amd/_lib.py mirrors it)");
+extern "C" int ttk_gn_apply(int dtype, const ttk_gn_desc* d, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_gn_apply: null descriptor");
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16 || dtype == TTK_F16, TTK_E_ARG, "ttk_gn_apply: dtype must be TTK_F32, TTK_BF16 or TTK_F16, got %d", dtype);
+	TTK_REQUIRE(d->x && d->ms && d->gamma && d->beta && d->out, TTK_E_ARG, "ttk_gn_apply: null x, ms, gamma, beta or out");
+	TTK_REQUIRE(d->C == 128 || d->C == 256 || d->C == 512 || d->C == 1024, TTK_E_ARG, "ttk_gn_apply: C must be 128, 256, 512 or 1024 (C %% 128 == 0, C <= 1024), got %d", d->C);
+	TTK_REQUIRE(d->nb >= 1 && d->T >= 1 && d->Tout >= 1, TTK_E_ARG, "ttk_gn_apply: need nb >= 1, T >= 1, Tout >= 1 (got nb=%d T=%d Tout=%d)", d->nb, d->T, d->Tout);
+	TTK_REQUIRE(d->row_idx || d->Tout == d->T, TTK_E_ARG, "ttk_gn_apply: Tout != T needs row_idx");
+	TTK_REQUIRE(!d->tlen || (!d->row_idx && d->Tout == d->T), TTK_E_ARG, "ttk_gn_apply: tlen needs Tout == T and no row_idx");
+	TTK_REQUIRE(gn_num_chunks(d->T, d->C) <= 64, TTK_E_ARG, "ttk_gn_apply: %d rows are more than 64 statistics chunks", d->T);
+	TTK_REQUIRE(!d->scale == !d->shift && d->ss_stride >= 0 && d->ss_stride % 4 == 0, TTK_E_ARG, "ttk_gn_apply: scale and shift come together, ss_stride >= 0 and %% 4 == 0");
+	for (const void* q : {(const void*)d->x, (const void*)d->gamma, (const void*)d->beta, (const void*)d->scale, (const void*)d->shift, (const void*)d->out})
+		TTK_REQUIRE(((uintptr_t)q & 15) == 0, TTK_E_ARG, "ttk_gn_apply: x, gamma, beta, scale, shift and out must be 16-byte aligned");
+	TTK_REQUIRE(d->act == 0 || d->act == 2, TTK_E_ARG, "ttk_gn_apply: act must be 0 (none) or 2 (SiLU), got %d", d->act);
+	TTK_REQUIRE(!d->out_f8 || dtype == TTK_BF16, TTK_E_ARG, "ttk_gn_apply: out_f8 only with TTK_BF16");
+	TTK_REQUIRE(!d->pf || (d->pf_bytes >= 0 && d->pf_taps >= 1), TTK_E_ARG, "ttk_gn_apply: pf needs pf_bytes >= 0 and pf_taps >= 1");
+	GnApplyParams p = {};
+	p.x = d->x; p.ms = d->ms; p.gamma = d->gamma; p.beta = d->beta; p.scale = d->scale; p.shift = d->shift; p.ss_stride = d->ss_stride;
+	p.row_idx = d->row_idx; p.nb = d->nb; p.T = d->T; p.Tout = d->Tout; p.C = d->C; p.nchunks = gn_num_chunks(d->T, d->C); p.act = d->act;
+	p.out = d->out; p.out_f32 = d->out_f32 ? 1 : 0; p.out_f8 = d->out_f8 ? 1 : 0;
+	if (d->tlen) { p.tlen = d->tlen; p.chunk_rows = gn_rows_per_chunk(d->C); }
+	if (d->pf) { p.pf = d->pf; p.pf_bytes = d->pf_bytes; p.pf_taps = d->pf_taps; }
+	const char* why = gn_apply_form_refusal(p, d->form);
+	TTK_REQUIRE(!why, TTK_E_ARG, "ttk_gn_apply: %s (form=%d C=%d nb=%d T=%d Tout=%d tlen=%s row_idx=%s)", why, d->form, p.C, p.nb, p.T, p.Tout, p.tlen ? "set" : "null", p.row_idx ? "set" : "null");
+	if (d->stats) launch_gn_stats(d->x, d->nb, d->T, d->C, d->ms, (hipStream_t)stream, d->tlen);
+	launch_gn_apply(dtype, p, (hipStream_t)stream, d->form);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
 extern "C" int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream) {
 	using namespace ttk;
 	TTK_REQUIRE(d, TTK_E_ARG, "ttk_attn_decode: null descriptor");

@@ -186,7 +186,10 @@ struct GnApplyParams {
 	unsigned long long* stamps;   // diagnostic build only
 #endif
 };
-void launch_gn_apply(int dt, const GnApplyParams& p, hipStream_t s);
+// form (host only, never a kernel argument): 0 = the launcher's choice; 1 = generic (k_gn_apply), 2 = 4-row strips (k_gn_apply_c1024), 3 / 4 / 5 = rows dealt evenly
+// (k_gn_apply_c1024_even with 9 / 12 / 18 rows per thread) -- an explicit form is legal only where gn_apply_form_refusal returns null
+void launch_gn_apply(int dt, const GnApplyParams& p, hipStream_t s, int form = 0);
+const char* gn_apply_form_refusal(const GnApplyParams& p, int form);
 
 // ---------------------------------------------------------------- attention (attn.hip)
 struct AttnParams {
