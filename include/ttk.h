@@ -262,6 +262,28 @@ int ttk_fp8_round_weights(float* x, int64_t n, float* scale_out, void* stream);
 int ttk_ar_latents(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B,
 				   float* latents_out, void* stream);
 
+/* UnifiedVoice.forward(..., return_latent=False, text_first=True) on inputs that are clipped and padded already (unified_voice.py:576-612,
+ * get_logits :508-531): the teacher-forced dense pass, ln_f + final_norm on the text rows 1 .. Tt+2 and the mel rows Tt+3 .. Tt+M+4 of every
+ * sequence, text_head / mel_head, and F.cross_entropy against the targets of build_aligned_inputs_and_targets (:489-492), built on the device:
+ *   text [t_0 .. t_{Tt-1}, stop_text, stop_text], mel [c_0 .. c_{M-1}, stop_mel, stop_mel].
+ *   cond [B, D] f32, text [B, Tt] int64, codes [B, M] int64.  Every output is optional (null = not wanted), all f32:
+ *   loss_out[2] = {text mean, mel mean} (means in the order of ttk_xent_rows); nll_text_out [B, Tt+2], nll_mel_out [B, M+2] = the
+ *   reduction="none" rows; text_logits_out [B, number_text_tokens + 1, Tt+2], mel_logits_out [B, number_mel_codes, M+2] = the reference's
+ *   permute(0, 2, 1), contiguous.
+ * Needs a handle created with `text_head.weight` / `text_head.bias` among its weights (else TTK_E_STATE).  B is not bound by max_batch; the
+ * KV cache and the state of a running generation are not touched.                                                                     */
+int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, float* loss_out,
+				 float* nll_text_out, float* nll_mel_out, float* text_logits_out, float* mel_logits_out, void* stream);
+
+/* Row cross-entropy on its own (csrc/xent.hip), F.cross_entropy(reduction="none") of f32 logits [rows][ld] whose first C columns are valid
+ * (columns [C, ld) are never read) against int64 target [rows]:  nll_out[r] = logsumexp(x_r) - x_r[target[r]], the maximum subtracted before
+ * the exponential, one pass over the row.  A target outside [0, C) gives NaN for that row and reads nothing.
+ *   mean_out (optional, 1 float): part[i] = nll[i] + nll[i + 256] + ... added in that order from 0.f for i in 0..255, then part[i] += part[i + o]
+ *     for o = 128, 64, .. 1 (i < o), mean = part[0] / rows.  One workgroup, no atomics: the same bits on every run.
+ *   logits_t_out (optional): the same logits, f32 [rows / T][C][T] contiguous (row r = b * T + t  ->  [b][c][t]); rows % T == 0.          */
+int ttk_xent_rows(const float* logits, int64_t ld, int rows, int C, const int64_t* target, float* nll_out, float* mean_out,
+				  float* logits_t_out, int T, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Diffusion decoder: DiffusionTTS + the DDIM / ancestral step (tortoise_tts/models/diffusion.py:1389-1574, 325-431,
  * 646-694, 510-554) and AttentionBlock / GroupNorm32 / RelativePositionBias (arch_utils.py:24-190, xtransformers.py:148). */

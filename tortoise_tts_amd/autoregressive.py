@@ -1,10 +1,12 @@
 """Drop-in for the reference's autoregressive module object: same method names, arguments and return values as
 `UnifiedVoice` (/root/reference/tortoise_tts/models/unified_voice.py:334-679) for the calls `TTS.inference` makes
-(tortoise_tts/inference.py:266-285, 334-346, 371-379), backed by libttk (HIP, gfx950).  No torch fallback exists:
+(tortoise_tts/inference.py:266-285, 334-346, 371-379) and for `forward`'s teacher-forced losses (:544-612), backed by libttk (HIP, gfx950).  No torch fallback exists:
 every forward goes through the C ABI or raises.
 
 What runs where
   * GPT-2 stack, embeddings, final norms, mel head, KV cache ........ libttk  (csrc/ar.hip and kernels)
+  * forward's losses: both heads, the row cross-entropy, the [B, C, T] logits  libttk  (ttk_ar_score; csrc/xent.hip); the clipping and padding of its
+    integer inputs is `score_inputs`, index work on the host side
   * logits processors / warpers, softmax, multinomial(1) given its noise, stop/pad bookkeeping, the next step's input
     embedding ......................................................... libttk  (csrc/sample.hip, one launch per token)
   * the Exp(1) noise of torch.multinomial ............................ libttk, inside the mel-head launch: torch's own Philox
@@ -40,9 +42,52 @@ import torch
 
 from . import _lib
 from .sampling import LogitsPipeline, multinomial1, setup_seed
-from .weights import ARConfig, ar_shapes
+from .weights import ARConfig, ar_score_shapes, ar_shapes
 
 LAG = 2      # steps the host runs ahead of the device-side end-of-generation word it polls
+
+
+def check_ids(ids: torch.Tensor, n: int, what: str):
+	"""token ids index embedding rows on the device: an id outside the table must be the IndexError nn.Embedding raises in the
+	reference, not an out-of-bounds read"""
+	if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+		raise IndexError(f"{what} ids must lie in [0, {n}); got [{int(ids.min())}, {int(ids.max())}]")
+
+
+def score_inputs(cfg: ARConfig, text_inputs, text_lengths, mel_codes, wav_lengths, types=None, clip_inputs=True):
+	"""What `UnifiedVoice.forward` does to its integer inputs before the embeddings (unified_voice.py:561-583), as plain index work on the tensors'
+	own device: the `types` product, the clip to the longest text / clip of the batch, `set_mel_padding` (:494-506: codes past
+	wav_lengths // mel_length_compression + 1 become the stop token), and the targets of `build_aligned_inputs_and_targets` on the padded rows.
+	Returns (text [B, Tt'], codes [B, M'], text_targets [B, Tt' + 2], mel_targets [B, M' + 2]), all int64; the inputs are left as they are."""
+	text = torch.as_tensor(text_inputs).to(torch.int64)
+	codes = torch.as_tensor(mel_codes).to(torch.int64)
+	if text.dim() != 2 or codes.dim() != 2:
+		raise ValueError("text_inputs and mel_codes are [B, T] id tensors")
+	B, M = codes.shape
+	if types is not None:
+		text = text * (1 + torch.as_tensor(types).to(text.device, torch.int64)).unsqueeze(-1)
+	wav_lengths = torch.as_tensor(wav_lengths).view(-1).to("cpu")
+	mel_lengths = torch.div(wav_lengths, cfg.mel_length_compression, rounding_mode="trunc")
+	if mel_lengths.numel() not in (1, B):
+		raise ValueError("wav_lengths must have 1 or B entries")
+	if clip_inputs:
+		max_text_len, max_mel_len = int(torch.as_tensor(text_lengths).max()), int(mel_lengths.max())
+		if max_mel_len < 1:
+			raise ValueError(f"wav_lengths clip the mel codes to {max_mel_len} (the longest clip has fewer than mel_length_compression = {cfg.mel_length_compression} samples)")
+		if max_text_len < 1:
+			raise ValueError(f"text_lengths clip the text to {max_text_len} tokens")
+		text, codes = text[:, :max_text_len], codes[:, :max_mel_len]
+		M = codes.shape[1]
+	check_ids(text, cfg.number_text_tokens + 1, "text token")
+	check_ids(codes, cfg.number_mel_codes, "mel code")
+	if int(mel_lengths.min()) + 1 < M:
+		codes = codes.clone()
+		for b in range(B):
+			end = int(mel_lengths[b if mel_lengths.numel() == B else 0]) + 1
+			if end < M:
+				codes[b, end:] = cfg.stop_mel_token
+	pad = torch.nn.functional.pad
+	return text, codes, pad(text, (0, 2), value=cfg.stop_text_token), pad(codes, (0, 2), value=cfg.stop_mel_token)
 
 
 class UnifiedVoice(_lib.Handle):
@@ -68,7 +113,9 @@ class UnifiedVoice(_lib.Handle):
 		self.model_dim, self.layers, self.heads = cfg.model_dim, cfg.layers, cfg.heads
 		self.number_mel_codes = cfg.number_mel_codes
 
-		names = list(ar_shapes(cfg).keys())
+		# the text head is read by the teacher-forced losses only (forward(return_latent=False)): uploaded when the state dict holds it
+		self.scoring = "text_head.weight" in state_dict and "text_head.bias" in state_dict
+		names = list((ar_score_shapes if self.scoring else ar_shapes)(cfg).keys())
 		missing = [n for n in names if n not in state_dict]
 		if missing:
 			raise _lib.TTKError(f"state_dict lacks {len(missing)} hot-path tensors, e.g. {missing[:3]}")
@@ -85,10 +132,7 @@ class UnifiedVoice(_lib.Handle):
 
 	# ------------------------------------------------------------------ C-ABI calls
 	def _check_ids(self, ids: torch.Tensor, n: int, what: str):
-		"""token ids index embedding rows on the device: an id outside the table must be the IndexError nn.Embedding raises in the
-		reference, not an out-of-bounds read"""
-		if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
-			raise IndexError(f"{what} ids must lie in [0, {n}); got [{int(ids.min())}, {int(ids.max())}]")
+		check_ids(ids, n, what)
 
 	def _prefill(self, cond: torch.Tensor, text: torch.Tensor, B: int, prompt: Optional[torch.Tensor] = None) -> torch.Tensor:
 		"""prompt [1 or B, n] int64: the mel tokens of a prompted continuation, cached behind start_mel (include/ttk.h: ttk_ar_prefill_prompted)"""
@@ -149,11 +193,16 @@ class UnifiedVoice(_lib.Handle):
 	# ------------------------------------------------------------------ reference surface
 	def forward(self, speech_conditioning_latent, text_inputs, text_lengths, mel_codes, wav_lengths, types=None,
 				text_first=True, raw_mels=None, return_attentions=False, return_latent=False, clip_inputs=True):
-		"""unified_voice.py:544-599 in the one mode inference uses: return_latent=True, clip_inputs=False
-		(inference.py:371-379).  Returns f32 [B, M, model_dim]."""
-		if not return_latent or clip_inputs or types is not None or raw_mels is not None or not text_first or return_attentions:
-			raise NotImplementedError("only forward(..., return_latent=True, clip_inputs=False) is on the inference hot path")
-		B, M = mel_codes.shape
+		"""unified_voice.py:544-612, text first.  return_latent=True (what inference uses, with clip_inputs=False: inference.py:371-379): f32
+		[B, M', model_dim].  return_latent=False, the reference's default: (loss_text, loss_mel, mel_logits) -- the mean teacher-forced
+		cross-entropies as 0-dim f32 device tensors and the mel logits [B, number_mel_codes, M' + 2] f32; `self.loss` holds the two losses as in the
+		reference and `self.last_nll` the per-token rows {"text": [B, Tt' + 2], "mel": [B, M' + 2]} (F.cross_entropy(reduction="none"))."""
+		if raw_mels is not None or not text_first or return_attentions:
+			raise NotImplementedError("forward is implemented text first on mel codes: text_first=False, raw_mels and return_attentions are not")
+		if not return_latent and not self.scoring:
+			raise NotImplementedError("this model was built without text_head.weight / text_head.bias, which the losses need: pass the full state dict "
+									  "(weights.ar_score_shapes), or scoring=True to checkpoint.load_autoregressive")
+		B = mel_codes.shape[0]
 		cond = speech_conditioning_latent.to(self.device, torch.float32)
 		if cond.shape[0] != B:
 			cond = cond.expand(B, -1)
@@ -161,24 +210,30 @@ class UnifiedVoice(_lib.Handle):
 		text = text_inputs.to(self.device, torch.int64)
 		if text.shape[0] != B:
 			text = text.expand(B, -1)
-		text = text.contiguous()
-		codes = mel_codes.to(self.device, torch.int64).contiguous()
-		self._check_ids(text, self.cfg.number_text_tokens + 1, "text token")
-		self._check_ids(codes, self.cfg.number_mel_codes, "mel code")
-		# set_mel_padding (:494-506) rewrites codes past wav_lengths // compression + 1 with the stop token
-		mel_lengths = torch.div(torch.as_tensor(wav_lengths).view(-1).to("cpu"), self.mel_length_compression, rounding_mode="trunc")
-		if mel_lengths.numel() not in (1, B):
-			raise ValueError("wav_lengths must have 1 or B entries")
-		if int(mel_lengths.min()) + 1 < M:
-			codes = codes.clone()
-			for b in range(B):
-				end = int(mel_lengths[b if mel_lengths.numel() == B else 0]) + 1
-				if end < M:
-					codes[b, end:] = self.stop_mel_token
+		text, codes, _, _ = score_inputs(self.cfg, text, text_lengths, mel_codes.to(self.device, torch.int64), wav_lengths, types, clip_inputs)
+		text, codes = text.contiguous(), codes.contiguous()
+		if not return_latent:
+			r = self._score(cond, text, codes)
+			self.loss = dict(text=r["loss"][0], mel=r["loss"][1])
+			self.last_nll = dict(text=r["nll_text"], mel=r["nll_mel"])
+			return r["loss"][0], r["loss"][1], r["mel_logits"]
+		M = codes.shape[1]
 		out = torch.empty((B, M, self.cfg.model_dim), device=self.device, dtype=torch.float32)
 		_lib.check(self.lib.ttk_ar_latents(self._h, cond.data_ptr(), text.data_ptr(), text.shape[1], codes.data_ptr(), M, B,
 										   out.data_ptr(), _lib.stream_ptr()), "ttk_ar_latents")
 		return out
+
+	def _score(self, cond: torch.Tensor, text: torch.Tensor, codes: torch.Tensor, text_logits: bool = False) -> Dict[str, torch.Tensor]:
+		"""include/ttk.h: ttk_ar_score on clipped and padded device inputs (cond [B, D] f32, text [B, Tt], codes [B, M] int64, contiguous)"""
+		_lib.require_cuda(cond, text, codes)
+		c, B, Tt, M = self.cfg, codes.shape[0], text.shape[1], codes.shape[1]
+		new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)
+		r = dict(loss=new(2), nll_text=new(B, Tt + 2), nll_mel=new(B, M + 2), mel_logits=new(B, c.number_mel_codes, M + 2))
+		if text_logits:
+			r["text_logits"] = new(B, c.number_text_tokens + 1, Tt + 2)
+		_lib.check(self.lib.ttk_ar_score(self._h, cond.data_ptr(), text.data_ptr(), Tt, codes.data_ptr(), M, B, r["loss"].data_ptr(), r["nll_text"].data_ptr(),
+										 r["nll_mel"].data_ptr(), _lib.ptr(r.get("text_logits")), r["mel_logits"].data_ptr(), _lib.stream_ptr()), "ttk_ar_score")
+		return r
 
 	__call__ = forward
 

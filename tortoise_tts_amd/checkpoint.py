@@ -29,7 +29,7 @@ from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
-from .weights import ARConfig, DiffusionConfig, ar_shapes, diffusion_shapes
+from .weights import ARConfig, DiffusionConfig, ar_score_shapes, ar_shapes, diffusion_shapes
 
 SAFETENSORS_EXT = (".safetensor", ".safetensors", ".sft")
 _PARAM_ORIG = ".parametrizations.weight.original"
@@ -216,8 +216,9 @@ def select_hot_path(sd: Mapping[str, torch.Tensor], shapes: Mapping[str, Tuple[i
 
 
 def load_autoregressive_state(path, lora_path=None, *, cfg: Optional[ARConfig] = None, lora_scaling: Optional[float] = None,
-							  state_dict_key: Optional[str] = None) -> Tuple[Dict[str, torch.Tensor], ARConfig]:
-	"""`autoregressive.pth` (+ optional LoRA file) -> (hot-path state_dict with adapters folded in, config)."""
+							  state_dict_key: Optional[str] = None, scoring: bool = False) -> Tuple[Dict[str, torch.Tensor], ARConfig]:
+	"""`autoregressive.pth` (+ optional LoRA file) -> (hot-path state_dict with adapters folded in, config).  scoring: keep `text_head.*` as well,
+	which `UnifiedVoice.forward(return_latent=False)` (the teacher-forced losses) reads."""
 	sd = unwrap_state_dict(read_checkpoint(path), state_dict_key)
 	lora = None
 	if lora_path is not None:
@@ -225,7 +226,7 @@ def load_autoregressive_state(path, lora_path=None, *, cfg: Optional[ARConfig] =
 		lora_scaling = lora_scaling if lora_scaling is not None else file_scaling
 	sd = materialize_lora(sd, lora, scaling=lora_scaling)
 	cfg = cfg or infer_ar_config(sd)
-	return select_hot_path(sd, ar_shapes(cfg), "autoregressive"), cfg
+	return select_hot_path(sd, (ar_score_shapes if scoring else ar_shapes)(cfg), "autoregressive"), cfg
 
 
 def load_diffusion_state(path, *, cfg: Optional[DiffusionConfig] = None, state_dict_key: Optional[str] = None
@@ -236,11 +237,12 @@ def load_diffusion_state(path, *, cfg: Optional[DiffusionConfig] = None, state_d
 	return select_hot_path(sd, diffusion_shapes(cfg), "diffusion"), cfg
 
 
-def load_autoregressive(path, lora_path=None, *, dtype="bf16", device="cuda", max_batch=16, max_ctx=None, **kw):
+def load_autoregressive(path, lora_path=None, *, dtype="bf16", device="cuda", max_batch=16, max_ctx=None, scoring=False, **kw):
 	"""The counterpart of `load_model("autoregressive")` + the LoRA block of `TTS.__init__` (models/__init__.py:104-110,163-167;
-	inference.py:204-216) returning the libttk-backed `UnifiedVoice`."""
+	inference.py:204-216) returning the libttk-backed `UnifiedVoice`.  `scoring=True` keeps the text head: the model then also computes the
+	teacher-forced losses (`forward(..., return_latent=False)`)."""
 	from .autoregressive import UnifiedVoice
-	sd, cfg = load_autoregressive_state(path, lora_path, **kw)
+	sd, cfg = load_autoregressive_state(path, lora_path, scoring=scoring, **kw)
 	extra = {} if max_ctx is None else {"max_ctx": max_ctx}
 	return UnifiedVoice(sd, cfg, dtype=dtype, device=device, max_batch=max_batch, **extra)
 

@@ -74,6 +74,20 @@ __global__ void k_build_latent_emb(const float* cond, const int64_t* text, int T
 	*(float4*)(out + row * d + c) = v;
 }
 
+// targets of the scoring pass: build_aligned_inputs_and_targets (unified_voice.py:489-492) on the padded inputs of :577-578 -- [ids.., stop, stop] per sequence
+__global__ void k_build_score_targets(const int64_t* text, int Tt, int stop_text, const int64_t* codes, int M, int stop_mel, int B, int64_t* tgt_text, int64_t* tgt_mel) {
+	const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const int64_t nt = (int64_t)B * (Tt + 2), nm = (int64_t)B * (M + 2);
+	if (idx < nt) {
+		const int b = (int)(idx / (Tt + 2)), j = (int)(idx - (int64_t)b * (Tt + 2));
+		tgt_text[idx] = j < Tt ? text[(int64_t)b * Tt + j] : stop_text;
+	} else if (idx < nt + nm) {
+		const int64_t i = idx - nt;
+		const int b = (int)(i / (M + 2)), j = (int)(i - (int64_t)b * (M + 2));
+		tgt_mel[i] = j < M ? codes[(int64_t)b * M + j] : stop_mel;
+	}
+}
+
 }  // namespace
 
 struct ttk_ar {
@@ -85,6 +99,8 @@ struct ttk_ar {
 	std::vector<ARLayer> L;
 	float *lnf_g, *lnf_b, *fn_g, *fn_b;
 	Mat head;
+	Mat text_head;          // ttk_ar_score only: uploaded when `text_head.weight` is among the weights (scoring); the mel head's dense copy is head.w
+	bool scoring = false;
 	float *text_emb, *mel_emb, *mel_pos, *text_pos;
 	void *kc, *vc;          // [layers][max_batch][H][max_ctx][64]
 	size_t kv_layer_stride; // elements
@@ -106,6 +122,7 @@ struct ttk_ar {
 	int lnfold = 1;         // ln_1 + c_attn and ln_2 + c_fc of the decode step with the LayerNorm folded into the matrix (TTK_AR_LNFOLD=0: LN prologue, normalises in f32 first)
 	int lean = 1;           // decode launches on the compile-time-specialised kernels of gemv.hip where one exists (TTK_AR_LEAN=0: k_skinny everywhere)
 	WsBuf ws_x, ws_a, ws_qkv, ws_ao, ws_h;
+	WsBuf ws_score;         // ttk_ar_score: row-major logits of both heads, targets, nll rows
 	int B = 0, P = 0, k = 0, ready = 0;
 	int Pmax = 0;           // longest prefix of the batch (capacity checks); == P for one line
 	~ttk_ar() { attn_pos_slot_release(pos_slot); }      // also the failure path of ttk_ar_create; the workspaces and the arena free themselves after this
@@ -115,7 +132,7 @@ struct ttk_ar {
 // NaN patterns from here on (tests/test_gpu_reuse.py runs the reuse scenarios under the flag).
 static int poison_scratch(ttk_ar* h, hipStream_t s) {
 	if (!h->poison) return TTK_OK;
-	for (WsBuf* w : {&h->ws_x, &h->ws_a, &h->ws_qkv, &h->ws_ao, &h->ws_h})
+	for (WsBuf* w : {&h->ws_x, &h->ws_a, &h->ws_qkv, &h->ws_ao, &h->ws_h, &h->ws_score})
 		if (w->p) TTK_HIP(hipMemsetAsync(w->p, 0xFF, w->cap, s));
 	return TTK_OK;
 }
@@ -301,6 +318,10 @@ int ttk_ar_create(ttk_ar** out, const ttk_ar_config* cfg, const ttk_weight_view*
 	TTK_TRY(upload_f32(h->arena, wm, "final_norm.weight", d, &h->fn_g));
 	TTK_TRY(upload_f32(h->arena, wm, "final_norm.bias", d, &h->fn_b));
 	TTK_TRY(upload_mat(h->arena, wm, h->dt, "mel_head.weight", "mel_head.bias", PK_NK, cfg->number_mel_codes, d, true, &h->head));
+	if (wm.find("text_head.weight")) {      // the scoring weights (ttk_ar_score); a handle without them is what it was before that entry existed
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, "text_head.weight", "text_head.bias", PK_NK, cfg->number_text_tokens_p1, d, false, &h->text_head));
+		h->scoring = true;
+	}
 	TTK_TRY(upload_f32(h->arena, wm, "text_embedding.weight", (int64_t)cfg->number_text_tokens_p1 * d, &h->text_emb));
 	TTK_TRY(upload_f32(h->arena, wm, "mel_embedding.weight", (int64_t)cfg->number_mel_codes * d, &h->mel_emb));
 	TTK_TRY(upload_f32(h->arena, wm, "mel_pos_embedding.emb.weight", (int64_t)cfg->max_mel_seq_len * d, &h->mel_pos));
@@ -563,6 +584,59 @@ int ttk_ar_latents(ttk_ar* h, const float* cond, const int64_t* text, int Tt, co
 	for (int b = 0; b < B; ++b)
 		launch_layernorm(h->dt, x + ((size_t)b * S + Tt + 3) * d, d, M, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b,
 						 latents_out + (size_t)b * M * d, d, 1, s);
+	TTK_TRY(poison_scratch(h, s));
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, float* loss_out, float* nll_text_out, float* nll_mel_out,
+				 float* text_logits_out, float* mel_logits_out, void* stream) {
+	TTK_REQUIRE(h && cond && text && codes, TTK_E_ARG, "ttk_ar_score: null argument");
+	TTK_REQUIRE(h->scoring, TTK_E_STATE, "ttk_ar_score: this handle was created without text_head.weight / text_head.bias: pass the full state dict to ttk_ar_create");
+	const ttk_ar_config& c = h->cfg;
+	TTK_REQUIRE(B >= 1 && Tt >= 1 && M >= 1, TTK_E_ARG, "ttk_ar_score: empty input (B=%d Tt=%d M=%d)", B, Tt, M);
+	TTK_REQUIRE(Tt + 2 <= c.max_text_seq_len, TTK_E_ARG, "ttk_ar_score: %d text tokens exceed the position table", Tt);
+	TTK_REQUIRE(M + 2 <= c.max_mel_seq_len, TTK_E_ARG, "ttk_ar_score: %d mel codes exceed the position table (%d)", M, c.max_mel_seq_len - 2);
+	const int S = Tt + M + 5, d = c.model_dim, Rt = Tt + 2, Rm = M + 2;
+	const int Ct = c.number_text_tokens_p1, Cm = c.number_mel_codes, ldt = round_up(Ct, 4), ldm = round_up(Cm, 4);      // rows of the logits start on 16 bytes
+	const int64_t rows_t = (int64_t)B * Rt, rows_m = (int64_t)B * Rm;
+	TTK_REQUIRE((int64_t)B * S * 4 * d * (int64_t)h->es < (1ll << 31) && rows_m * ldm * 4 < (1ll << 31) && rows_t * ldt * 4 < (1ll << 31), TTK_E_ARG,
+				"ttk_ar_score: B=%d x (Tt=%d + M=%d) makes a GEMM operand of 2 GiB or more (32-bit buffer offsets): score the batch in parts", B, Tt, M);
+	hipStream_t s = (hipStream_t)stream;
+	TTK_TRY(h->ws_x.reserve((size_t)B * S * d * sizeof(float)));
+	// [logits text | logits mel | nll text | nll mel | targets text | targets mel]: every part starts on 16 bytes
+	const size_t o_lm = (size_t)rows_t * ldt * 4, o_nt = o_lm + (size_t)rows_m * ldm * 4, o_nm = o_nt + (size_t)round_up((int)rows_t, 4) * 4;
+	const size_t o_tt = o_nm + (size_t)round_up((int)rows_m, 4) * 4, o_tm = o_tt + (size_t)round_up((int)rows_t, 2) * 8;
+	TTK_TRY(h->ws_score.reserve(o_tm + (size_t)rows_m * 8));
+	char* ws = (char*)h->ws_score.p;
+	float *lg_t = (float*)ws, *lg_m = (float*)(ws + o_lm);
+	float *nll_t = nll_text_out ? nll_text_out : (float*)(ws + o_nt), *nll_m = nll_mel_out ? nll_mel_out : (float*)(ws + o_nm);
+	int64_t *tg_t = (int64_t*)(ws + o_tt), *tg_m = (int64_t*)(ws + o_tm);
+	float* x = (float*)h->ws_x.p;
+	const int64_t total = (int64_t)B * S * (d / 4);
+	hipLaunchKernelGGL(k_build_latent_emb, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cond, text, Tt, codes, M, B, d,
+					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, c.stop_mel_token, x);
+	hipLaunchKernelGGL(k_build_score_targets, dim3((unsigned)((rows_t + rows_m + 255) / 256)), dim3(256), 0, s, text, Tt, c.stop_text_token, codes, M, c.stop_mel_token, B, tg_t, tg_m);
+	TTK_TRY(dense_forward(h, x, B, S, false, s));
+	// enc = final_norm(ln_f(h))[:, 1:]; the text head reads its first Tt + 2 rows, the mel head its last M + 2   (unified_voice.py:518-530).  ws_a holds
+	// B * S rows (dense_forward): the B * (S - 1) normalised rows of both heads fit, T-typed, text rows first
+	char* a_t = (char*)h->ws_a.p;
+	char* a_m = a_t + (size_t)rows_t * d * h->es;
+	for (int b = 0; b < B; ++b) {
+		launch_layernorm(h->dt, x + ((size_t)b * S + 1) * d, d, Rt, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, a_t + (size_t)b * Rt * d * h->es, d, 0, s);
+		launch_layernorm(h->dt, x + ((size_t)b * S + Tt + 3) * d, d, Rm, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, a_m + (size_t)b * Rm * d * h->es, d, 0, s);
+	}
+	struct Head { const Mat* W; const void* a; int rows, C, ld, T; float* lg; const int64_t* tg; float* nll; float* out_t; };
+	const Head heads[2] = {{&h->text_head, a_t, (int)rows_t, Ct, ldt, Rt, lg_t, tg_t, nll_t, text_logits_out}, {&h->head, a_m, (int)rows_m, Cm, ldm, Rm, lg_m, tg_m, nll_m, mel_logits_out}};
+	for (int i = 0; i < 2; ++i) {
+		const Head& q = heads[i];
+		GemmParams g = {};
+		g.nseg = 1; g.seg[0] = {q.a, d, 0, 0};
+		g.W = q.W->w; g.ldw = q.W->Kpad; g.M = q.rows; g.N = q.C; g.K = d; g.bias = q.W->bias;
+		g.C = q.lg; g.ldc = q.ld; g.out_f32 = 1;
+		launch_gemm(h->dt, g, s);
+		launch_xent_rows(q.lg, q.ld, q.rows, q.C, q.tg, q.nll, loss_out ? loss_out + i : nullptr, q.out_t, q.T, s);
+	}
 	TTK_TRY(poison_scratch(h, s));
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

@@ -242,6 +242,11 @@ void attn_pos_slot_release(int slot);
 // copy k/v of a dense qkv buffer [B*S][3d] (GPT-2 order q|k|v, head h at h*64) into the cache rows [0,S)
 void launch_kv_scatter(int dt, const void* qkv, int B, int S, int H, void* kcache, void* vcache, int max_ctx, hipStream_t s, int t0 = 0);
 
+// ---------------------------------------------------------------- row cross-entropy (xent.hip)
+// nll[r] = logsumexp(logits[r][0..C)) - logits[r][target[r]], one pass per row; mean (optional) = the rows summed in the fixed order include/ttk.h
+// documents, / rows; logits_t (optional) = the same logits as f32 [rows / T][C][T].  Columns [C, ld) are never read.
+void launch_xent_rows(const float* logits, int64_t ld, int rows, int C, const int64_t* target, float* nll, float* mean, float* logits_t, int T, hipStream_t s);
+
 // ---------------------------------------------------------------- elementwise (elementwise.hip)
 void launch_set_int(int* p, int v, hipStream_t s);
 void launch_fill_int(int* p, int v, int n, hipStream_t s);

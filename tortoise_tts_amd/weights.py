@@ -208,7 +208,7 @@ DIFF_FULL = DiffusionConfig()
 
 
 def ar_shapes(c: ARConfig) -> Dict[str, Tuple[int, ...]]:
-	"""Hot-path subset of `UnifiedVoice.state_dict()` (conditioning_encoder / text_head are off-path)."""
+	"""Hot-path subset of `UnifiedVoice.state_dict()` (conditioning_encoder is off-path; text_head is read by scoring only: `ar_score_shapes`)."""
 	d = c.model_dim
 	s: Dict[str, Tuple[int, ...]] = {
 		"text_embedding.weight": (c.number_text_tokens + 1, d),
@@ -229,6 +229,14 @@ def ar_shapes(c: ARConfig) -> Dict[str, Tuple[int, ...]]:
 			p + "mlp.c_fc.weight": (d, 4 * d), p + "mlp.c_fc.bias": (4 * d,),
 			p + "mlp.c_proj.weight": (4 * d, d), p + "mlp.c_proj.bias": (d,),
 		})
+	return s
+
+
+def ar_score_shapes(c: ARConfig) -> Dict[str, Tuple[int, ...]]:
+	"""`ar_shapes` plus the text head (unified_voice.py:416): what `UnifiedVoice.forward(return_latent=False)` reads -- the teacher-forced
+	losses.  `synth_tensor` seeds by name, so every `ar_shapes` tensor of a synthetic state dict stays what it is."""
+	s = ar_shapes(c)
+	s.update({"text_head.weight": (c.number_text_tokens + 1, c.model_dim), "text_head.bias": (c.number_text_tokens + 1,)})
 	return s
 
 
