@@ -441,6 +441,35 @@ int ttk_dvae_quantize(ttk_dvae* h, const float* z, int M, int64_t* codes_out, vo
  * nothing is launched. */
 int ttk_dvae_decode(ttk_dvae* h, const int64_t* codes, int B, int n, float* mel_out, float* hidden_out, void* stream);
 
+/* ------------------------------------------------------------------ random voices: RandomLatentConverter
+ * models/random_latent_generator.py:10-52: a Gaussian row through five EqualLinear layers and one nn.Linear is a conditioning latent
+ * (`rlg_auto.pth`: 1024 channels, `rlg_diffuser.pth`: 2048).  f32 throughout (csrc/rlg.hip).
+ *
+ * The layer on its own:  out[r, n] = gain * act(sum_k x[r, k] * W[n, k] + bias[n]),  x f32 [rows][ldx], W f32 row-major [N][K], bias f32 [N] or
+ * null, out f32 [rows][ldo]; act 0 = identity, 1 = leaky-ReLU with `slope` (y > 0 ? y : y * slope).
+ *   1 <= rows <= 16;  K a multiple of 4, 4 <= K <= 8192;  N >= 1;  ldx >= K and a multiple of 4;  ldo >= N;  x and W 16-byte aligned, x != out.
+ *   Anything else returns TTK_E_ARG and launches nothing.
+ *   Order of one sum: lane l of a 64-lane wave adds the products of elements 4 (l + 64 i) .. 4 (l + 64 i) + 3, i = 0, 1, .., in rising k with
+ *   fmaf from 0.f; the 64 partial sums are folded by a + b over lane distances 32, 16, .. 1.  It does not depend on `rows`: row r of a 16-row call
+ *   has the bits of the 1-row call on that row.  No atomics: the same bits on every run.                                                   */
+int ttk_linear_rows(const float* x, int64_t ldx, const float* W, const float* bias, int rows, int K, int N, int act, float slope, float gain,
+					float* out, int64_t ldo, void* stream);
+
+typedef struct ttk_rlg ttk_rlg;
+typedef struct {
+	int channels;                             /* 1024 / 2048; a multiple of 4, <= 8192 */
+	int n_layers;                             /* 6: layers 0 .. n_layers-2 are act 1 with slope and gain, the last is act 0 with gain 1 */
+	int max_rows;                             /* latents drawn by one call, 1..16 */
+	float slope;                              /* 0.2 (fused_leaky_relu) */
+	float gain;                               /* 2 ** 0.5 */
+} ttk_rlg_config;
+/* weights: "layers.{i}.weight" [channels, channels] and "layers.{i}.bias" [channels], the EFFECTIVE operands: the caller has folded EqualLinear's
+ * `weight * scale` and `bias * lr_mul` (tortoise_tts_amd/random_latent.py does, with the reference's own expressions); they are uploaded as given. */
+int ttk_rlg_create(ttk_rlg** out, const ttk_rlg_config* cfg, const ttk_weight_view* weights, int n_weights);
+int ttk_rlg_destroy(ttk_rlg* h);
+/* RandomLatentConverter.forward :49-52 behind its torch.randn: noise f32 [rows, channels] -> out f32 [rows, channels]; one launch per layer. */
+int ttk_rlg_forward(ttk_rlg* h, const float* noise, int rows, float* out, void* stream);
+
 /* ------------------------------------------------------------------ CLVP candidate scoring
  * models/clvp.py:21-136 (x-transformers branch): weights = CLVP.state_dict() with each attention's to_q / to_k / to_v stacked into
  * "<attn>.__qkv.weight" [3 * dim, dim] and "__rotary_inv_freq" [16] (RotaryEmbedding(32).inv_freq), as tortoise_tts_amd/clvp.py packs. */

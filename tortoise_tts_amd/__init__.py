@@ -4,7 +4,7 @@ exposed under the reference's own method names.  See DESIGN.md and INTEGRATION.m
 from .weights import ARConfig, CLVPConfig, DiffusionConfig, DVAEConfig, HiFiGANConfig, UnivNetConfig, VocoderConfig  # noqa: F401
 
 __all__ = ["ARConfig", "DiffusionConfig", "UnifiedVoice", "DiffusionTTS", "get_diffuser", "denormalize_tacotron_mel",
-		   "load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder", "BigVGAN", "UnivNet", "HiFiGAN", "DiscreteVAE", "CLVP",
+		   "load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_random_latent_generator", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder", "BigVGAN", "UnivNet", "HiFiGAN", "DiscreteVAE", "RandomLatentConverter", "CLVP",
 		   "VocoderConfig", "UnivNetConfig", "HiFiGANConfig", "DVAEConfig", "CLVPConfig", "ConditioningEncoder", "ContextualEmbedder", "TorchMelSpectrogram", "TacotronSTFT", "VoiceBpeTokenizer", "TTS"]
 
 
@@ -42,10 +42,13 @@ def __getattr__(name):   # lazy: importing the package must not need the built l
 	if name == "DiscreteVAE":
 		from .dvae import DiscreteVAE
 		return DiscreteVAE
+	if name == "RandomLatentConverter":
+		from .random_latent import RandomLatentConverter
+		return RandomLatentConverter
 	if name == "mel":
 		import importlib
 		return importlib.import_module(".mel", __name__)
-	if name in ("load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_dvae_state", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder"):
+	if name in ("load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_dvae_state", "load_random_latent_generator", "load_rlg_state", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder"):
 		from . import checkpoint
 		return getattr(checkpoint, name)
 	raise AttributeError(name)

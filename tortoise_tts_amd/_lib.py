@@ -147,6 +147,10 @@ SYMBOLS = {
 	"ttk_dvae_encode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
 	"ttk_dvae_quantize": (_I, [_P, _P, _I, _P, _P]),
 	"ttk_dvae_decode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+	"ttk_linear_rows": (_I, [_P, _L, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _P, _L, _P]),
+	"ttk_rlg_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
+	"ttk_rlg_destroy": (_I, [_P]),
+	"ttk_rlg_forward": (_I, [_P, _P, _I, _P, _P]),
 	"ttk_clvp_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_clvp_destroy": (_I, [_P]),
 	"ttk_clvp_score": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),

@@ -327,6 +327,26 @@ def load_dvae(path, *, cfg=None, dtype="f32", device="cuda", state_dict_key: Opt
 	return DiscreteVAE(sd, cfg, dtype=dtype, device=device)
 
 
+def load_rlg_state(path, *, state_dict_key: Optional[str] = None) -> Tuple[Dict[str, torch.Tensor], int]:
+	"""`rlg_auto.pth` / `rlg_diffuser.pth` -> (the twelve `layers.{0..5}.weight|bias` tensors as stored, channels): the width is read off
+	`layers.0.weight`, every layer is shape-checked against it."""
+	from .weights import rlg_shapes
+	sd = unwrap_state_dict(read_checkpoint(path), state_dict_key)
+	w = sd.get("layers.0.weight")
+	if w is None or w.dim() != 2:
+		raise CheckpointError("not a RandomLatentConverter state_dict: missing layers.0.weight [channels, channels]")
+	channels = int(w.shape[0])
+	return select_hot_path(sd, rlg_shapes(channels), "random latent generator"), channels
+
+
+def load_random_latent_generator(path, *, device="cuda", state_dict_key: Optional[str] = None):
+	"""`load_model("rlg_autoregressive")` / `load_model("rlg_diffusion")` (models/__init__.py:97-103): a plain state_dict of `RandomLatentConverter(channels)`;
+	the width (1024 for the autoregressive latent, 2048 for the diffusion one) comes from the file.  f32, the only mode."""
+	from .random_latent import RandomLatentConverter
+	sd, channels = load_rlg_state(path, state_dict_key=state_dict_key)
+	return RandomLatentConverter(sd, channels, device=device)
+
+
 def load_clvp(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = None):
 	"""`load_model("clvp")` (models/__init__.py:111-113): `clvp2.pth` is a plain state_dict of the x-transformers CLVP."""
 	from .clvp import CLVP

@@ -27,11 +27,13 @@ def set_seed(seed=None) -> int:
 
 class TTS:
 	def __init__(self, autoregressive, diffusion, tokenizer, *, vocoder=None, clvp=None, conditioning_encoder=None, contextual_embedder=None,
-				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None, hifigan=None, dvae=None):
+				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None, hifigan=None, dvae=None,
+				 rlg_auto=None, rlg_diffuser=None):
 		self.hot = TTSHotPath(autoregressive, diffusion, vocoder=vocoder, clvp=clvp)
 		self.univnet = univnet          # tortoise_tts_amd.UnivNet: the vocoder of vocoder_type="vocoder"
 		self.hifigan = hifigan          # tortoise_tts_amd.HiFiGAN: the vocoder of vocoder_type="hifigan" (AR latents -> audio, no diffusion)
 		self.dvae = dvae                # tortoise_tts_amd.DiscreteVAE: `encode_audio` then returns the clip's mel codes as well (emb/mel.py:95)
+		self.rlg_auto, self.rlg_diffuser = rlg_auto, rlg_diffuser      # tortoise_tts_amd.RandomLatentConverter pair: the voice of `references=None`
 		self.tokenizer = tokenizer
 		self.conditioning_encoder, self.contextual_embedder, self.tms, self.stft = conditioning_encoder, contextual_embedder, tms, stft
 		self.device = autoregressive.device
@@ -67,8 +69,18 @@ class TTS:
 			out = {"codes": codes, **out}
 		return out
 
+	def random_voice(self, rows: int = 1) -> dict:
+		"""TorToiSe's random voices (the reference's `rlg` pair, models/__init__.py:97-103): {"latent": (ar_latent [rows, C_ar], diff_latent
+		[rows, C_diff])} drawn from the default device generator, the autoregressive latent first, then the diffusion one -- the original order.
+		`encode_audio` passes the dict through, so it can be kept and given as `references` again."""
+		if self.rlg_auto is None or self.rlg_diffuser is None:
+			raise ValueError("TTS was built without the random latent converters (rlg_auto=, rlg_diffuser=)")
+		ref = torch.empty((int(rows), 0))
+		ar_latent = self.rlg_auto(ref)
+		return {"latent": (ar_latent, self.rlg_diffuser(ref))}
+
 	@torch.inference_mode()
-	def inference(self, text: str, references, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
+	def inference(self, text: str, references=None, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
 				  seed=None, candidates=1, references_sr: int = 22050) -> Tuple[torch.Tensor, int]:
 		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
@@ -76,7 +88,10 @@ class TTS:
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
 		diffusion model (see `_hifigan_wav`; the reference returns [1, samples] on that branch, here the shape is that of the other two).
 		beam_width > 1 (inference.py:342: num_beams) samples every line by beam search -- `candidates` <= beam_width finished beams come back, ranked
-		with `length_penalty` -- on the "bigvgan" and "vocoder" branches, line by line; the streaming "hifigan" branch takes no beams."""
+		with `length_penalty` -- on the "bigvgan" and "vocoder" branches, line by line; the streaming "hifigan" branch takes no beams.
+		references=None speaks in a random voice (`random_voice`; needs `rlg_auto=` and `rlg_diffuser=`): `set_seed(seed)` then runs BEFORE the voice
+		is drawn, so `seed` fixes the voice, and once more behind it, so the line is sampled as `inference(text, that_voice, seed=seed)` samples it.
+		With references given the order is the reference's: the clip is encoded first, then the seed is set."""
 		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
 			raise NotImplementedError(f"vocoder_type {vocoder_type!r} is unknown ('bigvgan', 'vocoder', 'hifigan')")
 		if vocoder_type == "hifigan" and self.hifigan is None:
@@ -91,6 +106,9 @@ class TTS:
 				raise ValueError("TTS was built without a UnivNet vocoder (univnet=)")
 		elif self.hot.vocoder is None:
 			raise ValueError("TTS was built without a vocoder")
+		if references is None:
+			seed = set_seed(seed)
+			references = self.random_voice()
 		ar_latent, diff_latent = self.encode_audio(references, references_sr)["latent"]
 		set_seed(seed)
 		lines = []

@@ -409,6 +409,38 @@ def dvae_codebook(mean: torch.Tensor, std: torch.Tensor, num_tokens: int, seed: 
 	return mean[:, None] + std[:, None] * torch.randn((mean.shape[0], num_tokens), generator=g, dtype=torch.float32)
 
 
+RLG_LAYERS = 6          # RandomLatentConverter: five EqualLinear layers and one nn.Linear (models/random_latent_generator.py:45-46)
+RLG_LR_MUL = .1
+
+
+def rlg_shapes(channels: int) -> Dict[str, Tuple[int, ...]]:
+	"""`RandomLatentConverter(channels).state_dict()` (models/random_latent_generator.py:42-47)."""
+	s: Dict[str, Tuple[int, ...]] = {}
+	for i in range(RLG_LAYERS):
+		s[f"layers.{i}.weight"] = (channels, channels); s[f"layers.{i}.bias"] = (channels,)
+	return s
+
+
+def rlg_state_dict(channels: int, seed: int) -> Dict[str, torch.Tensor]:
+	"""Seeded synthetic `RandomLatentConverter` weights, per key like `synth_tensor` but at the reference's own scales: an EqualLinear weight is
+	`randn / lr_mul` (std 10, random_latent_generator.py:28) and its forward multiplies by lr_mul / sqrt(channels), so the effective matrix is
+	fan-in scaled.  With `_gain_for`'s fan-in gains the folded matrices would be ~0.1 / channels: every layer would output its bias and a broken
+	GEMV would pass.  EqualLinear biases have std 1 (trained ones are not the zero they start as; the forward multiplies them by lr_mul), the last
+	layer is an nn.Linear: weight std 1 / sqrt(channels), bias std 0.05."""
+	out = {}
+	for name, shape in rlg_shapes(channels).items():
+		g = torch.Generator(device="cpu")
+		g.manual_seed((seed * 1000003 + zlib.crc32(name.encode())) % (2 ** 63 - 1))
+		last = name.startswith(f"layers.{RLG_LAYERS - 1}.")
+		t = torch.randn(shape, generator=g, dtype=torch.float32)
+		if name.endswith(".weight"):
+			t = t * (1.0 / math.sqrt(channels)) if last else t.div_(RLG_LR_MUL)
+		elif last:
+			t = t * 0.05
+		out[name] = t
+	return out
+
+
 def weight_norm_names(shapes: Dict[str, Tuple[int, ...]]) -> Dict[str, Tuple[int, ...]]:
 	"""The same keys as a checkpoint of `nn.utils.weight_norm` modules spells them: every conv `weight` becomes `weight_g` [out, 1, 1]
 	and `weight_v` (the norm is over every dimension but the first)."""
