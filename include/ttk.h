@@ -306,6 +306,19 @@ int ttk_diff_destroy(ttk_diff* h);
 int ttk_diff_precompute(ttk_diff* h, const float* latents, const float* cond, const int32_t* interp_idx, int b, int M,
 						int T, float* E_out, void* stream);
 
+/* DiffusionTTS.timestep_independent(codes, cond, T, return_code_pred) for integer mel codes (diffusion.py:1487-1515, the `else` of :1493):
+ *   codes [b, M] int64 device -> code_embedding rows -> code_converter (three AttentionBlocks) -> the same code_norm / modulation / expansion as
+ *   ttk_diff_precompute -> E_out [b, C, T] f32; mel_pred_out (NULL, or [b, in_channels, T] f32) = mel_head(E), the k = 3 convolution of :1512.
+ * Needs a handle whose create call was given "code_embedding.weight" [in_tokens, C] (in_tokens is read off that view), "code_converter.{0,1,2}.*"
+ * (+ "__relbias", as every attention block) and "mel_head.weight" / "mel_head.bias" (weights.py: diffusion_code_shapes); else TTK_E_STATE.  The
+ * caller validates the ids (0 <= id < in_tokens; tortoise_tts_amd/diffusion.py raises IndexError); the gather clamps, so no id reads outside
+ * the table.  Nothing is synchronised.                                                                                                     */
+int ttk_diff_precompute_codes(ttk_diff* h, const int64_t* codes, const float* cond, const int32_t* interp_idx, int b, int M, int T,
+							  float* E_out, float* mel_pred_out, void* stream);
+/* mel_head over embeddings that already exist: E [b, C, T] f32 (from either precompute entry) -> mel_pred_out [b, in_channels, T] f32, bit for
+ * bit what ttk_diff_precompute_codes writes beside the same E.  The reference's `return_code_pred=True` on LATENT conditioning (:1509-1515). */
+int ttk_diff_mel_head(ttk_diff* h, const float* E, int b, int T, float* mel_pred_out, void* stream);
+
 /* DiffusionTTS.forward(x, t, precomputed_aligned_embeddings=E[, conditioning_free=True]) (diffusion.py:1517-1574):
  *   x [b, in, T] f32, t [b] int64 device, E [b, C, T] f32 or NULL (=> conditioning_free) -> out [b, out_channels, T].  */
 int ttk_diff_forward(ttk_diff* h, const float* x, const int64_t* t, const float* E, int b, int T, float* out, void* stream);

@@ -172,6 +172,8 @@ SYMBOLS = {
 	"ttk_diff_create": (_I, [C.POINTER(_P), C.POINTER(DiffConfigC), C.POINTER(WeightView), _I]),
 	"ttk_diff_destroy": (_I, [_P]),
 	"ttk_diff_precompute": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+	"ttk_diff_precompute_codes": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+	"ttk_diff_mel_head": (_I, [_P, _P, _I, _I, _P, _P]),
 	"ttk_diff_forward": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
 	"ttk_diff_begin": (_I, [_P, _P, _I, _I, _P]),
 	"ttk_diff_step": (_I, [_P, _P, C.POINTER(StepC), _P, _P]),

@@ -29,7 +29,7 @@ from typing import Dict, Mapping, Optional, Tuple
 
 import torch
 
-from .weights import ARConfig, DiffusionConfig, ar_score_shapes, ar_shapes, diffusion_shapes
+from .weights import ARConfig, DiffusionConfig, ar_score_shapes, ar_shapes, diffusion_code_shapes, diffusion_shapes
 
 SAFETENSORS_EXT = (".safetensor", ".safetensors", ".sft")
 _PARAM_ORIG = ".parametrizations.weight.original"
@@ -229,12 +229,19 @@ def load_autoregressive_state(path, lora_path=None, *, cfg: Optional[ARConfig] =
 	return select_hot_path(sd, (ar_score_shapes if scoring else ar_shapes)(cfg), "autoregressive"), cfg
 
 
-def load_diffusion_state(path, *, cfg: Optional[DiffusionConfig] = None, state_dict_key: Optional[str] = None
+def load_diffusion_state(path, *, cfg: Optional[DiffusionConfig] = None, state_dict_key: Optional[str] = None, codes: Optional[bool] = None
 						 ) -> Tuple[Dict[str, torch.Tensor], DiffusionConfig]:
+	"""codes: the token-conditioning tensors (`weights.diffusion_code_shapes`; `in_tokens` is read off `code_embedding.weight`) -- None: kept when the
+	file has all of them, True: required, False: dropped.  Shape-checked like the rest when kept."""
 	sd = unwrap_state_dict(read_checkpoint(path), state_dict_key)
 	sd = materialize_lora(sd)          # the reference only adapts modules under `gpt`; this just normalises parametrised keys
 	cfg = cfg or infer_diffusion_config(sd)
-	return select_hot_path(sd, diffusion_shapes(cfg), "diffusion"), cfg
+	out = select_hot_path(sd, diffusion_shapes(cfg), "diffusion")
+	table = sd.get("code_embedding.weight")
+	code_shapes = diffusion_code_shapes(cfg, int(table.shape[0]) if table is not None and table.dim() == 2 else 1)
+	if codes or (codes is None and all(k in sd for k in code_shapes)):
+		out.update(select_hot_path(sd, code_shapes, "diffusion (token conditioning)"))
+	return out, cfg
 
 
 def load_autoregressive(path, lora_path=None, *, dtype="bf16", device="cuda", max_batch=16, max_ctx=None, scoring=False, **kw):
@@ -247,10 +254,10 @@ def load_autoregressive(path, lora_path=None, *, dtype="bf16", device="cuda", ma
 	return UnifiedVoice(sd, cfg, dtype=dtype, device=device, max_batch=max_batch, **extra)
 
 
-def load_diffusion(path, *, dtype="bf16", device="cuda", **kw):
+def load_diffusion(path, *, dtype="bf16", device="cuda", codes: Optional[bool] = None, **kw):
 	from .diffusion import DiffusionTTS
-	sd, cfg = load_diffusion_state(path, **kw)
-	return DiffusionTTS(sd, cfg, dtype=dtype, device=device)
+	sd, cfg = load_diffusion_state(path, codes=codes, **kw)
+	return DiffusionTTS(sd, cfg, dtype=dtype, device=device, codes=codes)
 
 
 def load_conditioning_encoder(path, lora_path=None, *, dtype="bf16", device="cuda", cfg: Optional[ARConfig] = None, state_dict_key: Optional[str] = None):

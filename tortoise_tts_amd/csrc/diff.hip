@@ -48,6 +48,10 @@ struct ttk_diff {
 	AttnBlk lat_attn[4];
 	Mat lat_conv, inp_block, integ, out_conv, time0, time2, emb_cat;
 	float *code_g, *code_b, *out_g, *out_b, *uncond, *time_freqs;
+	// token conditioning (optional: present when the create call was given `code_embedding.weight`): the table in the kernel type, code_converter, mel_head
+	void* code_table = nullptr; int in_tokens = 0;
+	AttnBlk code_attn[3];
+	Mat mel_head;
 	DLayer integrator[3];
 	std::vector<DLayer> layers;
 	ResBlk tail[3];
@@ -241,6 +245,24 @@ static int load_res(ttk_diff* h, const WeightMap& wm, const std::string& p, ResB
 	return TTK_OK;
 }
 
+// The tail both kinds of aligned conditioning share: code_norm(x) * (1 + scale) + shift, nearest-neighbour expansion M -> T into ecl (f32 channels-last), and the
+// channels-first copy the caller gets      diffusion.py:1492,1498,1507
+static void precompute_tail(ttk_diff* h, const float* x, const float* cond, const int32_t* interp_idx, int b, int M, int T, float* E_out, hipStream_t s) {
+	const int C = h->cfg.model_channels;
+	Gn d = {h->code_g, h->code_b, ACT_NONE, nullptr, cond, 2 * C};
+	d.out = h->ecl.p; d.out_f32 = 1; d.row_idx = interp_idx; d.Tout = T;
+	gn(h, x, b, M, d, s);
+	launch_cl_to_cf((const float*)h->ecl.p, b, C, T, E_out, s);
+}
+// mel_pred [b][in_channels][T] f32 = mel_head(E), a k = 3 convolution over the expanded embedding (diffusion.py:1512): the GEMM form of `out`, its 100 output
+// channels padded to the tile the same way.  from_ecl: the operand copy in the kernel type is made from ecl; else the caller has put it into csT.
+static void mel_head_of(ttk_diff* h, int b, int T, float* out, hipStream_t s, bool from_ecl) {
+	const int C = h->cfg.model_channels;
+	if (from_ecl) launch_cast(h->dt, (const float*)h->ecl.p, h->csT.p, (int64_t)b * T * C, s);
+	Epi t; t.transpose = 1;
+	gemm(h, h->mel_head, taps3(h->csT.p, C, h->mel_head, T), b * T, out, 0, 1, s, t);
+}
+
 extern "C" {
 
 int ttk_diff_create(ttk_diff** out, const ttk_diff_config* cfg, const ttk_weight_view* w, int n_w) {
@@ -290,6 +312,24 @@ int ttk_diff_create(ttk_diff** out, const ttk_diff_config* cfg, const ttk_weight
 	}
 	for (int i = 0; i < 3; ++i) TTK_TRY(load_res(h.get(), wm, "layers." + std::to_string(cfg->num_layers + i) + ".", &h->tail[i], slot++));
 	h->n_emb = slot;
+	if (const ttk_weight_view* tv = wm.find("code_embedding.weight")) {
+		// in_tokens is the table's own row count: ttk_diff_config stays as it is
+		TTK_REQUIRE(tv->ndim == 2 && tv->shape[0] >= 1 && tv->shape[0] < (1LL << 31) && tv->shape[1] == C, TTK_E_WEIGHT,
+					"ttk_diff_create: code_embedding.weight must be [in_tokens][%d]", C);
+		h->in_tokens = (int)tv->shape[0];
+		const int64_t n = (int64_t)h->in_tokens * C;
+		if (h->dt == DT_F32) { float* t = nullptr; TTK_TRY(upload_f32(h->arena, wm, "code_embedding.weight", n, &t)); h->code_table = t; }
+		else {
+			WsBuf tmp;
+			TTK_TRY(tmp.reserve((size_t)n * 4));
+			TTK_HIP(hipMemcpy(tmp.p, tv->data, (size_t)n * 4, hipMemcpyDefault));
+			TTK_TRY(h->arena.alloc(&h->code_table, (size_t)n * h->es));
+			launch_cast(h->dt, (const float*)tmp.p, h->code_table, n, 0);
+			TTK_HIP(hipDeviceSynchronize());
+		}
+		for (int i = 0; i < 3; ++i) TTK_TRY(load_attn(h.get(), wm, "code_converter." + std::to_string(i) + ".", &h->code_attn[i]));
+		TTK_TRY(upload_mat(h->arena, wm, h->dt, "mel_head.weight", "mel_head.bias", PK_CONV3, cfg->in_channels, C, false, &h->mel_head));
+	}
 	TTK_TRY(h->arena.alloc((void**)&h->d_tlen, 128 * sizeof(int)));
 	TTK_TRY(h->arena.alloc((void**)&h->d_need, 128 * sizeof(int)));
 	// all emb_layers.1 linears stacked into one [n_emb * 2C][C] matrix ("__emb_cat.*", built by the Python packer)
@@ -320,11 +360,38 @@ int ttk_diff_precompute(ttk_diff* h, const float* latents, const float* cond, co
 	launch_cast(h->dt, latents, h->lat_T.p, (int64_t)b * M * Cl, s);   // latents are already [b][M][Cl] = channels-last
 	gemm(h, h->lat_conv, taps3(h->lat_T.p, Cl, h->lat_conv, M), b * M, x, C, 1, s, {M});
 	for (int i = 0; i < 4; ++i) attn_block(h, h->lat_attn[i], x, b, M, s);
-	// code_norm(x) * (1 + scale) + shift, then nearest-neighbour expansion M -> T      diffusion.py:1492,1498,1507
-	Gn d = {h->code_g, h->code_b, ACT_NONE, nullptr, cond, 2 * C};
-	d.out = h->ecl.p; d.out_f32 = 1; d.row_idx = interp_idx; d.Tout = T;
-	gn(h, x, b, M, d, s);
-	launch_cl_to_cf((const float*)h->ecl.p, b, C, T, E_out, s);
+	precompute_tail(h, x, cond, interp_idx, b, M, T, E_out, s);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_diff_precompute_codes(ttk_diff* h, const int64_t* codes, const float* cond, const int32_t* interp_idx, int b, int M, int T,
+							  float* E_out, float* mel_pred_out, void* stream) {
+	TTK_REQUIRE(h && codes && cond && interp_idx && E_out, TTK_E_ARG, "ttk_diff_precompute_codes: null argument");
+	TTK_REQUIRE(h->code_table, TTK_E_STATE, "ttk_diff_precompute_codes: the handle was created without code_embedding / code_converter / mel_head");
+	TTK_REQUIRE(b >= 1 && M >= 1 && T >= 1, TTK_E_ARG, "ttk_diff_precompute_codes: empty input (b=%d M=%d T=%d)", b, M, T);
+	hipStream_t s = (hipStream_t)stream;
+	TTK_TRY(reserve_ws(h, b, M > T ? M : T));
+	h->staged = 0;   // ecl is reused below
+	float* x = (float*)h->xs.p;
+	launch_embed_rows(h->dt, h->code_table, codes, b * M, h->cfg.model_channels, h->in_tokens, x, s);      // diffusion.py:1496
+	h->L->ms_owner = nullptr;      // x's statistics come from the separate launch, as for any tensor no GEMM wrote
+	for (int i = 0; i < 3; ++i) attn_block(h, h->code_attn[i], x, b, M, s);
+	precompute_tail(h, x, cond, interp_idx, b, M, T, E_out, s);
+	if (mel_pred_out) mel_head_of(h, b, T, mel_pred_out, s, true);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_diff_mel_head(ttk_diff* h, const float* E, int b, int T, float* mel_pred_out, void* stream) {
+	TTK_REQUIRE(h && E && mel_pred_out, TTK_E_ARG, "ttk_diff_mel_head: null argument");
+	TTK_REQUIRE(h->code_table, TTK_E_STATE, "ttk_diff_mel_head: the handle was created without code_embedding / code_converter / mel_head");
+	TTK_REQUIRE(b >= 1 && T >= 1, TTK_E_ARG, "ttk_diff_mel_head: empty input");
+	hipStream_t s = (hipStream_t)stream;
+	TTK_TRY(reserve_ws(h, b, T));
+	h->staged = 0;   // the workspaces may have moved
+	launch_cf_to_cl(h->dt, E, b, h->cfg.model_channels, T, h->csT.p, h->cfg.model_channels, 1, s);
+	mel_head_of(h, b, T, mel_pred_out, s, false);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

@@ -27,6 +27,30 @@ void launch_gather_add(const float* A, const int* ia, const float* Bt, const int
 	hipLaunchKernelGGL(k_gather_add, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, A, ia, Bt, ib, out, rows, d);
 }
 
+// out[r][:] = f32(table[ids[r]][:]): the token branch of the diffusion model's aligned conditioning (diffusion.py:1496), the table in the handle's element type,
+// the rows the f32 channels-last residual stream the attention blocks update in place.  Eight channels per thread -- one 16-byte load of a 16-bit table (two of an
+// f32 one), two 16-byte stores -- and C / 8 consecutive threads per row: a row of 1024 channels is two waves, one of 128 a quarter wave.  The host validates
+// the ids before the launch; the clamp keeps a bad one inside the table all the same.
+template <typename T>
+__global__ void k_embed_rows(const T* table, const int64_t* ids, int rows, int C, int n_tok, float* out) {
+	const int tpr = C >> 3;                                   // threads per row; 256 % tpr == 0 (C in {128, 256, 512, 1024})
+	const int r = blockIdx.x * (256 / tpr) + (int)threadIdx.x / tpr, c = ((int)threadIdx.x % tpr) * 8;
+	if (r >= rows) return;
+	int64_t id = ids[r];
+	id = id < 0 ? 0 : (id >= n_tok ? n_tok - 1 : id);
+	const typename Frag<T>::type v = *(const typename Frag<T>::type*)(table + id * C + c);
+	float* o = out + (int64_t)r * C + c;
+	*(float4*)o = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+	*(float4*)(o + 4) = make_float4((float)v[4], (float)v[5], (float)v[6], (float)v[7]);
+}
+void launch_embed_rows(int dt, const void* table, const int64_t* ids, int rows, int C, int n_tok, float* out, hipStream_t s) {
+	const int rpb = 256 / (C / 8);
+	const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
+	if (dt == DT_BF16) hipLaunchKernelGGL((k_embed_rows<bf16>), grid, dim3(256), 0, s, (const bf16*)table, ids, rows, C, n_tok, out);
+	else if (dt == DT_F16) hipLaunchKernelGGL((k_embed_rows<f16>), grid, dim3(256), 0, s, (const f16*)table, ids, rows, C, n_tok, out);
+	else hipLaunchKernelGGL((k_embed_rows<float>), grid, dim3(256), 0, s, (const float*)table, ids, rows, C, n_tok, out);
+}
+
 // decode: x[b] = mel_embedding[tok[b]] + mel_pos_embedding[*d_pos + pos_off]
 // (unified_voice.py:213-214; with d_pos = cache length before this step = P + k, pos_off = 1 - P gives the k + 1 quirk)
 // frag (optional): the same rows, T-typed, in A-fragment order [m_tile][d/32][lane][8] for a folded-LayerNorm launch (skinny.hip)

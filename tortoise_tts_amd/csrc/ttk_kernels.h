@@ -253,6 +253,8 @@ void launch_fill_int(int* p, int v, int n, hipStream_t s);
 void launch_fill_int2(int* p, int a, int b, int n, hipStream_t s);      // n pairs {a, b}
 // out[r][:] = A[ia[r]][:] + Bt[ib[r]][:]   (f32 tables, f32 out); ia/ib int32 device arrays; Bt may be null
 void launch_gather_add(const float* A, const int* ia, const float* Bt, const int* ib, float* out, int rows, int d, hipStream_t s);
+// out[r][:] = f32(table[clamp(ids[r], 0, n_tok - 1)][:]); table T-typed [n_tok][C], ids int64 device [rows], C in {128, 256, 512, 1024}
+void launch_embed_rows(int dt, const void* table, const int64_t* ids, int rows, int C, int n_tok, float* out, hipStream_t s);
 // decode-time embedding: out[b] = mel_emb[tok[b]] + mel_pos[*d_pos - pos_bias]
 void launch_decode_embed(const float* emb, const int64_t* tok, const float* pos, const int* d_pos, int pos_off, int pos_rows,
 						 float* out, int B, int d, hipStream_t s, void* frag = nullptr, int frag_f32 = 0);

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import DiffusionConfig, diffusion_shapes
+from .weights import DiffusionConfig, diffusion_code_shapes, diffusion_shapes
 
 TACOTRON_MEL_MAX = 2.3143386840820312
 TACOTRON_MEL_MIN = -11.512925148010254
@@ -64,9 +64,11 @@ def nearest_index(M: int, T: int) -> torch.Tensor:
 	return torch.from_numpy(np.minimum(idx, M - 1).astype(np.int32))
 
 
-def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: DiffusionConfig) -> Dict[str, torch.Tensor]:
-	"""Reference-layout tensors + the derived host tables ttk_diff_create expects (include/ttk.h)."""
+def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: DiffusionConfig, codes: bool = False) -> Dict[str, torch.Tensor]:
+	"""Reference-layout tensors + the derived host tables ttk_diff_create expects (include/ttk.h).  codes: the token-conditioning tensors as well."""
 	out = {k: sd[k] for k in diffusion_shapes(cfg)}
+	if codes:
+		out.update({k: sd[k] for k in diffusion_code_shapes(cfg)})
 	out["__time_freqs"] = time_freqs(cfg.model_channels)
 	res_prefixes = [f"conditioning_timestep_integrator.{i}.resblk." for i in range(3)]
 	res_prefixes += [f"layers.{i}.resblk." for i in range(cfg.num_layers)]
@@ -81,17 +83,55 @@ def pack_state_dict(sd: Dict[str, torch.Tensor], cfg: DiffusionConfig) -> Dict[s
 
 
 # ------------------------------------------------------------------------------------------------ the network
+def _resolve_codes(state_dict, cfg: DiffusionConfig, codes: Optional[bool]) -> int:
+	"""`DiffusionTTS(codes=...)`: in_tokens when the token-conditioning tensors are to be built, else 0."""
+	names = list(diffusion_code_shapes(cfg))
+	missing = [n for n in names if n not in state_dict]
+	if codes is False or (codes is None and missing):
+		return 0
+	if missing:
+		raise _lib.TTKError(f"codes=True, but the state_dict lacks {len(missing)} token-conditioning tensors, e.g. {missing[:3]}")
+	table = state_dict["code_embedding.weight"]
+	if table.dim() != 2 or table.shape[1] != cfg.model_channels:
+		raise _lib.TTKError(f"code_embedding.weight is {tuple(table.shape)}, expected [in_tokens, {cfg.model_channels}]")
+	return int(table.shape[0])
+
+
+def check_aligned_conditioning(aligned_conditioning, in_tokens: int, return_code_pred: bool = False) -> bool:
+	"""Host-side argument checks of `timestep_independent`, before any launch.  Returns True for mel codes, False for latents (`is_latent`,
+	diffusion.py:1269: float tensors are latents).  Codes outside [0, in_tokens) raise IndexError, as `nn.Embedding` does."""
+	tokens = not aligned_conditioning.dtype.is_floating_point
+	if (tokens or return_code_pred) and in_tokens <= 0:
+		what = "token conditioning (code_embedding / code_converter)" if tokens else "return_code_pred (mel_head)"
+		raise NotImplementedError(f"{what} needs the token-conditioning tensors: build the model with DiffusionTTS(..., codes=True) from a state "
+								  f"dict that holds code_embedding, code_converter and mel_head")
+	if tokens:
+		if aligned_conditioning.dim() != 2 or aligned_conditioning.numel() == 0:
+			raise ValueError(f"mel codes must be [b, M], got {tuple(aligned_conditioning.shape)}")
+		if aligned_conditioning.dtype == torch.bool:
+			raise TypeError("mel codes must be an integer tensor")
+		lo, hi = int(aligned_conditioning.min()), int(aligned_conditioning.max())
+		if lo < 0 or hi >= in_tokens:
+			raise IndexError(f"mel code {lo if lo < 0 else hi} is outside the code embedding's [0, {in_tokens})")
+	elif aligned_conditioning.dim() != 3:
+		raise ValueError(f"latents must be [b, M, C], got {tuple(aligned_conditioning.shape)}")
+	return tokens
+
+
 class DiffusionTTS(_lib.Handle):
 	def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: DiffusionConfig = DiffusionConfig(), dtype: str = "bf16",
-				 device: str = "cuda:0"):
+				 device: str = "cuda:0", codes: Optional[bool] = None):
+		"""codes: token conditioning (`code_embedding`, `code_converter`, `mel_head`; diffusion.py:1427-1432, 1456) -- None: built when the state dict
+		holds all of those tensors, True: required, False: left out."""
 		self.cfg = cfg
+		self.in_tokens = _resolve_codes(state_dict, cfg, codes)
 		super().__init__(device)
 		self.dtype = _lib.DTYPES[dtype]
 		self.in_channels, self.out_channels, self.model_channels = cfg.in_channels, cfg.out_channels, cfg.model_channels
 		missing = [n for n in diffusion_shapes(cfg) if n not in state_dict]
 		if missing:
 			raise _lib.TTKError(f"state_dict lacks {len(missing)} hot-path tensors, e.g. {missing[:3]}")
-		packed = pack_state_dict(state_dict, cfg)
+		packed = pack_state_dict(state_dict, cfg, codes=self.in_tokens > 0)
 		c = _lib.DiffConfigC(cfg.model_channels, cfg.num_layers, cfg.in_channels, cfg.in_latent_channels, cfg.out_channels,
 							 cfg.num_heads, self.dtype)
 		self._create("diff", c, packed, list(packed.keys()))
@@ -101,47 +141,64 @@ class DiffusionTTS(_lib.Handle):
 		"""`next(model.parameters()).device` is queried by the sampler (diffusion.py:788)."""
 		yield torch.empty(0, device=self.device)
 
-	def timestep_independent(self, aligned_conditioning, conditioning_latent, expected_seq_len, return_code_pred=False):
-		"""diffusion.py:1487-1510, latent conditioning: [b, M, C_latent] f32, [b, 2C] -> [b, C, T] f32."""
-		if return_code_pred:
-			raise NotImplementedError("return_code_pred is a training-only branch")
-		if aligned_conditioning.dtype != torch.float32:
-			raise NotImplementedError("token conditioning (code_embedding/code_converter) is off the inference path")
-		lat = aligned_conditioning.to(self.device, torch.float32).contiguous()
-		cond = conditioning_latent.to(self.device, torch.float32).contiguous()
-		b, M, _ = lat.shape
-		if cond.shape[0] != b:
-			cond = cond.expand(b, -1).contiguous()
-		T = int(expected_seq_len)
+	def _index(self, M: int, T: int) -> torch.Tensor:
 		key = (M, T)
 		if key not in self._idx_cache:
 			self._idx_cache[key] = nearest_index(M, T).to(self.device)
-		E = torch.empty((b, self.cfg.model_channels, T), device=self.device, dtype=torch.float32)
-		_lib.check(self.lib.ttk_diff_precompute(self._h, lat.data_ptr(), cond.data_ptr(), self._idx_cache[key].data_ptr(), b, M, T,
-												E.data_ptr(), _lib.stream_ptr()), "ttk_diff_precompute")
-		return E
+		return self._idx_cache[key]
+
+	def timestep_independent(self, aligned_conditioning, conditioning_latent, expected_seq_len, return_code_pred=False):
+		"""diffusion.py:1487-1515.  aligned_conditioning: AR latents [b, M, C_latent] f32, or mel codes [b, M] of an integer type (`is_latent`, :1269);
+		conditioning_latent [b, 2C] -> E [b, C, T] f32, with return_code_pred (E, mel_pred [b, in_channels, T] f32)."""
+		tokens = check_aligned_conditioning(aligned_conditioning, self.in_tokens, return_code_pred)
+		cond = conditioning_latent.to(self.device, torch.float32).contiguous()
+		b, M = aligned_conditioning.shape[:2]
+		if cond.shape[0] != b:
+			cond = cond.expand(b, -1).contiguous()
+		T = int(expected_seq_len)
+		idx = self._index(M, T)
+		with torch.cuda.device(self.device):
+			E = torch.empty((b, self.cfg.model_channels, T), device=self.device, dtype=torch.float32)
+			mel_pred = torch.empty((b, self.cfg.in_channels, T), device=self.device, dtype=torch.float32) if return_code_pred else None
+			if tokens:
+				codes = aligned_conditioning.to(self.device, torch.int64).contiguous()
+				_lib.check(self.lib.ttk_diff_precompute_codes(self._h, codes.data_ptr(), cond.data_ptr(), idx.data_ptr(), b, M, T, E.data_ptr(),
+															  _lib.ptr(mel_pred), _lib.stream_ptr()), "ttk_diff_precompute_codes")
+			else:
+				lat = aligned_conditioning.to(self.device, torch.float32).contiguous()
+				_lib.check(self.lib.ttk_diff_precompute(self._h, lat.data_ptr(), cond.data_ptr(), idx.data_ptr(), b, M, T,
+														E.data_ptr(), _lib.stream_ptr()), "ttk_diff_precompute")
+				if return_code_pred:
+					_lib.check(self.lib.ttk_diff_mel_head(self._h, E.data_ptr(), b, T, mel_pred.data_ptr(), _lib.stream_ptr()), "ttk_diff_mel_head")
+		return (E, mel_pred) if return_code_pred else E
 
 	def forward(self, x, timesteps, aligned_conditioning=None, conditioning_latent=None, precomputed_aligned_embeddings=None,
 				conditioning_free=False, return_code_pred=False):
-		"""diffusion.py:1517-1574 with precomputed embeddings: [b, 100, T], [b] -> [b, 200, T] f32."""
-		if return_code_pred:
-			raise NotImplementedError("return_code_pred is a training-only branch")
+		"""diffusion.py:1517-1574: [b, 100, T], [b] -> [b, 200, T] f32; with return_code_pred (out, mel_pred).  The reference runs `mel_head` whenever it is
+		given aligned conditioning and drops the result unless asked; here it runs when asked."""
+		assert not (return_code_pred and precomputed_aligned_embeddings is not None)  # mutually exclusive (diffusion.py:1530)
+		if not conditioning_free and precomputed_aligned_embeddings is None and (aligned_conditioning is None or conditioning_latent is None):
+			raise ValueError("need precomputed_aligned_embeddings or (aligned_conditioning, conditioning_latent)")
+		if return_code_pred and conditioning_free:
+			raise NotImplementedError("return_code_pred with conditioning_free: the reference has no mel_pred to return there (diffusion.py:1533-1573)")
+		if not conditioning_free and precomputed_aligned_embeddings is None:      # argument checks first: they need no device
+			check_aligned_conditioning(aligned_conditioning, self.in_tokens, return_code_pred)
 		x = x.to(self.device, torch.float32).contiguous()
 		b, _, T = x.shape
 		t = timesteps.to(self.device, torch.int64).contiguous()
-		E = None
+		E = mel_pred = None
 		if not conditioning_free:
 			if precomputed_aligned_embeddings is None:
-				if aligned_conditioning is None or conditioning_latent is None:
-					raise ValueError("need precomputed_aligned_embeddings or (aligned_conditioning, conditioning_latent)")
-				precomputed_aligned_embeddings = self.timestep_independent(aligned_conditioning, conditioning_latent, T)
+				precomputed_aligned_embeddings = self.timestep_independent(aligned_conditioning, conditioning_latent, T, return_code_pred)
+				if return_code_pred:
+					precomputed_aligned_embeddings, mel_pred = precomputed_aligned_embeddings
 			E = precomputed_aligned_embeddings.to(self.device, torch.float32).contiguous()
 			if E.shape[0] != b:
 				E = E.expand(b, -1, -1).contiguous()
 		out = torch.empty((b, self.cfg.out_channels, T), device=self.device, dtype=torch.float32)
 		_lib.check(self.lib.ttk_diff_forward(self._h, x.data_ptr(), t.data_ptr(), _lib.ptr(E), b, T, out.data_ptr(),
 											 _lib.stream_ptr()), "ttk_diff_forward")
-		return out
+		return (out, mel_pred) if return_code_pred else out
 
 	__call__ = forward
 

@@ -46,13 +46,27 @@ def trim_calm_tokens(codes: torch.Tensor, latents: torch.Tensor) -> torch.Tensor
 	return latents
 
 
+def check_diffusion_conditioning(diffusion_conditioning: str, diffusion: DiffusionTTS) -> bool:
+	"""True for "codes" (the diffusion model reads the sampled mel codes, diffusion.py:1493-1497), False for "latents"; refuses what cannot run -- before
+	anything is sampled."""
+	if diffusion_conditioning not in ("latents", "codes"):
+		raise ValueError(f"diffusion_conditioning: 'latents' or 'codes', got {diffusion_conditioning!r}")
+	if diffusion_conditioning == "codes" and not getattr(diffusion, "in_tokens", 0):
+		raise NotImplementedError("diffusion_conditioning='codes' needs a diffusion model with token conditioning: DiffusionTTS(..., codes=True) from a state dict "
+								  "that holds code_embedding, code_converter and mel_head")
+	return diffusion_conditioning == "codes"
+
+
 class HotPathStages:
 	"""`dist.ShardStages` on the libttk-backed modules: what one rank of a candidate-sharded utterance runs (dist.sharded_candidates)."""
 
 	def __init__(self, tts: "TTSHotPath", text_tokens, autoregressive_latents, diffusion_latents, *, max_ar_steps=500,
 				 max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0,
-				 diffusion_sampler="ddim", cond_free=True, suppress_tokens=None, phase_marks=None):
+				 diffusion_sampler="ddim", cond_free=True, suppress_tokens=None, phase_marks=None, diffusion_conditioning="latents"):
 		self.tts, self.ar, self.diff = tts, tts.autoregressive, tts.diffusion
+		if check_diffusion_conditioning(diffusion_conditioning, self.diff):
+			raise NotImplementedError("diffusion_conditioning='codes' is not available on the candidate-sharded path: its ranks exchange every candidate's latents "
+									  "(dist.sharded_candidates); use TTSHotPath.inference or inference_lines")
 		self.phase_marks = phase_marks      # measurement only: receives (name, event) at the phase boundaries, as TTSHotPath.inference does
 		self.text = text_tokens.to(self.ar.device)
 		self.al, self.dl = autoregressive_latents, diffusion_latents
@@ -187,7 +201,7 @@ class TTSHotPath:
 	def inference(self, text_tokens: torch.Tensor, autoregressive_latents: torch.Tensor, diffusion_latents: torch.Tensor, *,
 				  max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, diffusion_sampler="ddim", cond_free=True, candidates=1,
-				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1):
+				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1, diffusion_conditioning="latents"):
 		"""text_tokens [1, Tt] int64; latents from the reference's conditioning encoders ([1,1024], [1,2048]).
 		latents_for: "all" = the latent pass over every candidate, as the reference runs it before scoring (inference.py:370-379; the benchmarked
 		workload); "winner" = the k = 1 variant: the candidate is chosen first and only its row goes through the dense
@@ -196,9 +210,13 @@ class TTSHotPath:
 		phase_marks (measurement only): a list that receives (name, torch.cuda.Event) at the phase boundaries -- start, after the AR
 		sampling, after the latent pass, after the diffusion -- for bench.py's per-phase roofline.
 		beam_width: `num_beams=max(1, beam_width)` of the reference's call (inference.py:342); above 1 the `candidates` best finished beams come back
-		(candidates <= beam_width) and `length_penalty` ranks them."""
+		(candidates <= beam_width) and `length_penalty` ranks them.
+		diffusion_conditioning: "latents" = the reference's call (inference.py:370-402); "codes" = the diffusion model reads the sampled, stop-token-fixed
+		mel codes of the chosen candidate themselves (its token branch, diffusion.py:1493-1497) and the dense latent pass is skipped: the calm-token cut
+		applies to the code row as it does to the latent rows, `T` follows from the row's length the same way.  Needs `DiffusionTTS(..., codes=True)`."""
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
+		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
 
 		def mark(name):
 			if phase_marks is not None:
@@ -221,7 +239,10 @@ class TTSHotPath:
 		if latents_for not in ("all", "winner"):
 			raise ValueError("latents_for: 'all' or 'winner'")
 		pre_best, pre_scores = 0, None
-		if latents_for == "winner":
+		latents = None
+		if from_codes:              # no dense pass: the candidate is chosen below and its code row is the aligned conditioning
+			pass
+		elif latents_for == "winner":
 			if self.clvp is not None and B > 1:
 				pre_scores = self.clvp(text_tokens, codes, return_loss=False)
 				pre_best = int(torch.argmax(pre_scores))
@@ -237,12 +258,15 @@ class TTSHotPath:
 		# (`TTSHotPath(..., clvp=)`) it does what the to-do asks for: the best-scoring candidate's latents, trimmed by its own codes.
 		mark("latent_pass")
 		best, scores = pre_best, pre_scores
-		if latents_for == "all" and self.clvp is not None and B > 1:
+		if (latents_for == "all" or from_codes) and self.clvp is not None and B > 1:
 			scores = self.clvp(text_tokens, codes, return_loss=False)
 			best = int(torch.argmax(scores))
-		latents = trim_calm_tokens(codes[best:best + 1], latents[best:best + 1] if latents_for == "all" else latents)
-		T = latents.shape[1] * 4 * 24000 // 22050
-		E = diff.timestep_independent(latents, diffusion_latents, T, False)
+		if from_codes:
+			aligned = trim_calm_tokens(codes[best:best + 1], codes[best:best + 1])
+		else:
+			aligned = latents = trim_calm_tokens(codes[best:best + 1], latents[best:best + 1] if latents_for == "all" else latents)
+		T = aligned.shape[1] * 4 * 24000 // 22050
+		E = diff.timestep_independent(aligned, diffusion_latents, T, False)
 		noise = torch.randn((1, 100, T), device=dev) * diffusion_temp
 		mel = diffuser.sample_loop(diff, (1, 100, T), sampler=diffusion_sampler, noise=noise,
 								   model_kwargs={"precomputed_aligned_embeddings": E}, progress=False)
@@ -250,13 +274,16 @@ class TTSHotPath:
 		mels = denormalize_tacotron_mel(mel)[:, :, :T]
 		seconds = T * HOP / SAMPLE_RATE
 		if return_all:
-			return mels, seconds, dict(codes=codes, latents=latents, E=E, noise=noise, mel=mel, scores=scores, best=best)
+			aux = dict(codes=codes, latents=latents, E=E, noise=noise, mel=mel, scores=scores, best=best)
+			if from_codes:
+				aux["aligned"] = aligned      # the code row the diffusion model read (`latents` is None: no dense pass ran)
+			return mels, seconds, aux
 		return mels, seconds
 
 	@torch.inference_mode()
 	def inference_lines(self, lines, autoregressive_latents, diffusion_latents, *, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8,
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
-						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None):
+						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents"):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -274,10 +301,12 @@ class TTSHotPath:
 		line's AR phase starts; the worker draws nothing.
 		Batched lines keep that property: each row decodes with its own line's cache length, every line draws the same noise, and before a line's
 		own draws the generators are put where its `generate` alone would have left them (UnifiedVoice.position_rng_after_line).
+		diffusion_conditioning="codes": as in `inference` -- each line's chosen code row is its aligned conditioning, no dense latent pass.
 		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
+		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		extra = {"suppress_tokens": suppress_tokens} if suppress_tokens else {}
 		main = torch.cuda.current_stream(dev)
@@ -324,9 +353,12 @@ class TTSHotPath:
 					if self.clvp is not None and B > 1:
 						best = int(torch.argmax(self.clvp(text_tokens, codes, return_loss=False)))
 					# the dense latent pass on the chosen row only (rows are independent: the bits `inference` gets from the all-candidates pass)
-					al_row = autoregressive_latents if autoregressive_latents.shape[0] == 1 else autoregressive_latents[best:best + 1]
-					latents = ar.forward(al_row, text_tokens, torch.tensor([text_tokens.shape[1]], dtype=torch.int32), codes[best:best + 1],
-										 torch.tensor([M * ar.mel_length_compression]), return_latent=True, clip_inputs=False)
+					if from_codes:
+						latents = codes[best:best + 1]                          # the code row itself is the aligned conditioning
+					else:
+						al_row = autoregressive_latents if autoregressive_latents.shape[0] == 1 else autoregressive_latents[best:best + 1]
+						latents = ar.forward(al_row, text_tokens, torch.tensor([text_tokens.shape[1]], dtype=torch.int32), codes[best:best + 1],
+											 torch.tensor([M * ar.mel_length_compression]), return_latent=True, clip_inputs=False)
 					latents = trim_calm_tokens(codes[best:best + 1], latents)     # host copy of the codes: the AR phase of this line is complete
 					T = latents.shape[1] * 4 * 24000 // 22050
 					noise = torch.randn((1, 100, T), device=dev) * diffusion_temp

@@ -134,6 +134,71 @@ class TTS:
 			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)[0]) for tokens in lines]
 		return torch.concat(wavs, dim=-1), SAMPLE_RATE
 
+	@torch.inference_mode()
+	def decode_codes(self, codes, references=None, *, max_diffusion_steps=80, diffusion_temp=1.0, diffusion_sampler="ddim", cond_free=True,
+					 vocoder_type="bigvgan", seed=None, references_sr: int = 22050) -> Tuple[torch.Tensor, int]:
+		"""Mel codes -> waveform without the autoregressive model: the diffusion model's token branch (diffusion.py:1493-1497) on `codes`, the sampler and
+		the vocoder as in `inference`.  codes: [1, M] integers (what `encode_audio(...)["codes"]` or the AR sampling give), or a list of such rows --
+		the rows' waveforms come back concatenated in time, each what its own call with the same `seed` gives; with the DDIM sampler and conditioning-free guidance several
+		rows are diffused as one ragged batch (SpacedDiffusion.sample_loop_lines).  The voice is the diffusion latent of `references` (clip tensor(s) or an
+		`encode_audio` dict), or a random voice when None, seeded as in `inference`.  T = M * 4 * 24000 // 22050 frames per row (inference.py:400).
+		Returns (wav [1, 1, samples], 24000).  vocoder_type "bigvgan" or "vocoder"; "hifigan" is refused: it reads AR latents, which codes alone do not give."""
+		from .diffusion import denormalize_tacotron_mel, get_diffuser
+		from .inference import check_diffusion_conditioning
+		if vocoder_type == "hifigan":
+			raise NotImplementedError("decode_codes cannot use vocoder_type='hifigan': HiFiGAN turns the autoregressive model's latents into audio (inference.py:250-329), "
+									  "and mel codes alone do not give those; use 'bigvgan' or 'vocoder'")
+		if vocoder_type not in ("bigvgan", "vocoder"):
+			raise NotImplementedError(f"vocoder_type {vocoder_type!r} is unknown ('bigvgan', 'vocoder')")
+		if vocoder_type == "vocoder":
+			if self.univnet is None:
+				raise ValueError("TTS was built without a UnivNet vocoder (univnet=)")
+		elif self.hot.vocoder is None:
+			raise ValueError("TTS was built without a vocoder")
+		diff = self.hot.diffusion
+		check_diffusion_conditioning("codes", diff)
+		rows = [codes] if isinstance(codes, torch.Tensor) else list(codes)
+		rows = [r[None] if r.dim() == 1 else r for r in rows]
+		if not rows or any(r.dim() != 2 or r.shape[0] != 1 or r.shape[1] == 0 or r.dtype.is_floating_point for r in rows):
+			raise ValueError("codes: an integer tensor [1, M], or a list of such rows")
+		if references is None:
+			seed = set_seed(seed)
+			references = self.random_voice()
+		diff_latent = self.encode_audio(references, references_sr)["latent"][1]
+		seed = set_seed(seed)
+		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
+		prepared = []
+		for r in rows:
+			# every row draws from the generators as `seed` leaves them -- the start noise, then DDIM's ignored per-step draws (diffusion.py:685) -- so a row of a
+			# list is what its own call gives (`inference` has the same property: the reference reseeds per line, stream_generator.py:296)
+			set_seed(seed)
+			T = r.shape[1] * 4 * 24000 // 22050
+			E = diff.timestep_independent(r.to(self.device), diff_latent, T, False)
+			noise = torch.randn((1, 100, T), device=self.device) * diffusion_temp
+			if diffusion_sampler == "ddim":
+				for _ in range(diffuser.num_timesteps):
+					torch.randn_like(noise)
+			prepared.append((E, noise, T))
+		if len(prepared) > 1 and diffusion_sampler == "ddim" and cond_free:
+			mels = diffuser.sample_loop_lines(diff, [n for _, n, _ in prepared], [E for E, _, _ in prepared])
+		else:
+			mels = [diffuser.sample_loop(diff, (1, 100, T), sampler=diffusion_sampler, noise=n, model_kwargs={"precomputed_aligned_embeddings": E},
+										 progress=False, consume_rng=diffusion_sampler != "ddim") for E, n, T in prepared]
+		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference
+		return torch.concat([to_wav(denormalize_tacotron_mel(m)) for m in mels], dim=-1), SAMPLE_RATE
+
+	def resynthesize(self, wav, sr: int = 22050, references=None, **kw) -> Tuple[torch.Tensor, int]:
+		"""A clip -> its mel codes (`encode_audio`, needs `dvae=`) -> waveform (`decode_codes`): the round trip through the 8192-way code stream.
+		references=None speaks in the source clip's own voice; else in that of `references`.  `kw` goes to `decode_codes`."""
+		if self.dvae is None:
+			raise ValueError("TTS was built without a DiscreteVAE (dvae=): resynthesize needs the clip's mel codes")
+		enc = self.encode_audio(wav, sr)
+		if "codes" not in enc:
+			raise ValueError("the voice dict holds no mel codes: pass the clip, or a dict that `encode_audio` made with dvae=")
+		if references is None:
+			references = enc
+		return self.decode_codes(enc["codes"], references, **kw)
+
 	def _univnet_wav(self, mels: torch.Tensor) -> torch.Tensor:
 		"""UnivNet on one line's mel [1, 100, T] with the noise the reference draws for that line: `generate` reseeds every generator to 0 per
 		line (`setup_seed(0)`, stream_generator.py:36-45, 296), nothing after it draws from the CPU generator (AR sampling and the diffusion noise

@@ -288,6 +288,21 @@ def diffusion_shapes(c: DiffusionConfig) -> Dict[str, Tuple[int, ...]]:
 	return s
 
 
+DIFF_CODE_TOKENS = 8193          # `DiffusionTTS(in_tokens=8193)`, diffusion.py:1396: the DVAE's 8192 mel codes and one more
+
+
+def diffusion_code_shapes(c: DiffusionConfig, in_tokens: int = DIFF_CODE_TOKENS) -> Dict[str, Tuple[int, ...]]:
+	"""The token-conditioning tensors of `DiffusionTTS.state_dict()` (diffusion.py:1427-1432, 1456): `code_embedding`, the three `code_converter`
+	AttentionBlocks and `mel_head`.  Optional for the handle (`DiffusionTTS(codes=...)`); kept apart from `diffusion_shapes`, whose synthetic tensors are
+	drawn per name (`synth_tensor`), so a state dict with and without these holds the same bits everywhere else."""
+	ch = c.model_channels
+	s: Dict[str, Tuple[int, ...]] = {"code_embedding.weight": (in_tokens, ch)}
+	for i in range(3):
+		s.update(_attn_shapes(f"code_converter.{i}.", ch, c.num_heads))
+	s.update({"mel_head.weight": (c.in_channels, ch, 3), "mel_head.bias": (c.in_channels,)})
+	return s
+
+
 def ar_conditioning_shapes(c: ARConfig, spec_dim: int = 80, attn_blocks: int = 6) -> Dict[str, Tuple[int, ...]]:
 	"""`UnifiedVoice.conditioning_encoder` (ConditioningEncoder, models/unified_voice.py:269-293, built at :397 with
 	`num_attn_heads=heads`): 1x1 conv spec_dim -> model_dim, then AttentionBlocks without relative position bias."""
