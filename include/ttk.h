@@ -613,6 +613,47 @@ typedef struct {
 } ttk_gn_desc;
 int ttk_gn_apply(int dtype, const ttk_gn_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ the weight-streaming decode launches on caller-provided operands
+ * No reference counterpart: exposed so every launch form of csrc/skinny.hip (k_skinny) and csrc/gemv.hip (k_gemv) can be tested against a float64
+ * LN(x) W^T + b of the same operands, element by element (tests/test_gpu_skinny_forms.py).
+ * ttk_gemv_mat: ONE decode matrix, uploaded and packed by the very functions ttk_ar_create uses (fragment order, fp8 rounding, and -- when "gamma" and "beta"
+ *   are among the weights -- the folded-LayerNorm operands gamma o W, its column sums and b + beta W).  Weights by name: "weight" f32 [N][K] (layout 0,
+ *   nn.Linear as mel_head has it) or [K][N] (layout 1, HF Conv1D), "bias" [N], optional "gamma" / "beta" [K].  K % 64 == 0.  dtype as ttk_ar_config
+ *   (TTK_FP8W: fp8 weights under bf16 arithmetic, the fold kept in bf16).
+ * ttk_gemv_launch: one launch over M rows.
+ *   role: 0 qkv (q pre-scaled to qbuf f32 [M][K], k / v appended to the caches [M][H][max_ctx][64] at row d_pos[0] when that is < max_ctx; N == 3K, K == 64 H),
+ *         1 proj (out_f32 [M][N] += the product, in place; out_T optional: the updated rows in fragment order), 2 fc (out_T = gelu_new, fragment order),
+ *         3 head (out_f32 [M][N]; noise / rng / draws as ttk_ar_set_noise; bump != 0: d_pos[0] += 1).
+ *   form: 0 plain (a = rows of `dtype` in A-fragment order [ceil16(M) / 16][K / 32][64][8], proj and head only), 1 folded LayerNorm over the UN-normalised rows
+ *         `a` (qkv and fc, a matrix created with gamma / beta; health optional: the word ttk_ar_health reads), 2 LayerNorm prologue over f32 rows x [M][K] with
+ *         (g1, b1) and then optionally (g2, b2) (qkv, fc, head; at most 32 rows outside the head).
+ *   `a` and `out_T` hold every row of the 1, 2, 3 or 4 sixteen-row tiles the launch is instantiated for (ttk_ar_decode_geometry); rows >= M of `a` are never
+ *   allowed to reach a live output, rows >= M of out_T are never written.
+ *   family: 0 = what the decode step chooses (the same code decides), 1 = k_skinny, 2 = k_gemv (refused where it has no instantiation).
+ *   waves: 0 = the decode step's choice, else 4..16 waves per k_skinny workgroup (at most 8 in form 2).
+ *   model_dim: the width of the model the matrix belongs to, which the decode step's waves choice depends on; 0 = N for proj, K otherwise -- right for every
+ *   matrix but mlp.c_proj (N x 4N: pass N) and test matrices whose N is not the model's width.  With it, family 0 / waves 0 is what the decode step runs.
+ *   launched (optional, HOST int): receives the family that ran, 1 or 2.
+ * Returns TTK_E_ARG with a message, and launches nothing, when a precondition the kernels rely on fails -- including a launch whose LDS exceeds a compute unit's. */
+typedef struct ttk_gemv_mat ttk_gemv_mat;
+typedef struct { int dtype, layout, N, K; } ttk_gemv_mat_config;
+int ttk_gemv_mat_create(ttk_gemv_mat** out, const ttk_gemv_mat_config* cfg, const ttk_weight_view* weights, int n_weights);
+int ttk_gemv_mat_destroy(ttk_gemv_mat* h);
+typedef struct {
+	int dtype, role, form, M;                 /* dtype: the arithmetic type of a / out_T / the caches: what the matrix was created for (TTK_BF16 for TTK_FP8W) */
+	const void* a; const float* x;
+	const float *g1, *b1, *g2, *b2;
+	float* out_f32; void* out_T;
+	float* qbuf; void* kcache; void* vcache;
+	int max_ctx, H; float q_scale; int bump;  /* q_scale: must be 0.125 (head dim 64), the one value the decode step uses */
+	int* d_pos;
+	float* noise; const int64_t* rng; const int64_t* draws;
+	int* health;
+	int* launched;
+	int family, waves, model_dim;
+} ttk_gemv_desc;
+int ttk_gemv_launch(const ttk_gemv_mat* W, const ttk_gemv_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ mel front-ends of the conditioning path
  * TorchMelSpectrogram (models/arch_utils.py:361-395) and TacotronSTFT (:662-700 over STFT :560-623) as one handle type: reflect-padded
  * frames x "basis" [2 * (n_fft/2 + 1), n_fft] (windowed DFT, Re rows then Im rows) -> |.|^power -> x "mel_basis" [n_mels, n_fft/2 + 1] ->

@@ -74,7 +74,7 @@ int main(int argc, char** argv) {
 		GemvParams gq = {};
 		gq.Wp = p.Wp; gq.a = xfrag; gq.bias = bias; gq.csum = bias; gq.qbuf = qbuf; gq.kcache = L[i].kc; gq.vcache = L[i].vc; gq.d_pos = dpos;
 		gq.M = B; gq.N = 3 * d; gq.K = d; gq.max_ctx = max_ctx; gq.H = H; gq.q_scale = 0.125f; gq.stamps = p.stamps;
-		if (!(lean && launch_gemv(DT_BF16, GV_QKV, gq, s))) launch_skinny(DT_BF16, p, wv_qkv, s);
+		if (!(lean && launch_gemv(DT_BF16, GV_QKV, gq, s)) && launch_skinny(DT_BF16, p, wv_qkv, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 		AttnDecodeParams a = {};
 		a.qbuf = qbuf; a.kcache = L[i].kc; a.vcache = L[i].vc; a.d_pos = dpos; a.pos_slot_p1 = pos_slot + 1; a.B = B; a.H = H; a.max_ctx = max_ctx; a.ctx_hint = ctx; a.out = ao; a.out_frag = 1; a.shared_rows = 1;
 		a.stamps = st ? st + 1 * SLOTS : nullptr;
@@ -83,17 +83,17 @@ int main(int argc, char** argv) {
 		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = xfrag; p.stamps = st ? st + 2 * SLOTS : nullptr;
 		GemvParams gp = {};
 		gp.Wp = p.Wp; gp.a = ao; gp.bias = bias; gp.out_f32 = x; gp.out_T = xfrag; gp.M = B; gp.N = d; gp.K = d; gp.stamps = p.stamps;
-		if (!(lean && launch_gemv(DT_BF16, GV_PROJ, gp, s))) launch_skinny(DT_BF16, p, wv_proj, s);
+		if (!(lean && launch_gemv(DT_BF16, GV_PROJ, gp, s)) && launch_skinny(DT_BF16, p, wv_proj, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 		p = {}; p.Wp = L[i].wfc; p.N = 4 * d; p.K = d; p.M = B; p.bias = bias; p.g1 = bias; p.a = xfrag;
 		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hb; p.stamps = st ? st + 3 * SLOTS : nullptr;
 		GemvParams gf = {};
 		gf.Wp = p.Wp; gf.a = xfrag; gf.bias = bias; gf.csum = bias; gf.out_T = hb; gf.M = B; gf.N = 4 * d; gf.K = d; gf.stamps = p.stamps;
-		if (!(lean && launch_gemv(DT_BF16, GV_FC, gf, s))) launch_skinny(DT_BF16, p, wv_fc, s);
+		if (!(lean && launch_gemv(DT_BF16, GV_FC, gf, s)) && launch_skinny(DT_BF16, p, wv_fc, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 		p = {}; p.Wp = L[i].wproj2; p.N = d; p.K = 4 * d; p.M = B; p.bias = bias; p.a = hb;
 		p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = xfrag; p.stamps = st ? st + 4 * SLOTS : nullptr;
 		GemvParams g2 = {};
 		g2.Wp = p.Wp; g2.a = hb; g2.bias = bias; g2.out_f32 = x; g2.out_T = xfrag; g2.M = B; g2.N = d; g2.K = 4 * d; g2.stamps = p.stamps;
-		if (!(lean && launch_gemv(DT_BF16, GV_PROJ, g2, s))) launch_skinny(DT_BF16, p, wv_proj2, s);
+		if (!(lean && launch_gemv(DT_BF16, GV_PROJ, g2, s)) && launch_skinny(DT_BF16, p, wv_proj2, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 	};
 	for (int i = 0; i < NL; ++i) layer(i, nullptr);      // warm (code objects, first-touch)
 	CK(hipStreamSynchronize(s));

@@ -38,17 +38,17 @@ int main(int argc, char** argv) {
 		if (fold) { p.g1 = bias; p.a = ao; } else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = g; p.b1 = b; }
 		p.mode = SK_QKV; p.qbuf = qbuf; p.kcache = kc; p.vcache = vc; p.d_pos = dpos; p.max_ctx = max_ctx; p.H = H; p.q_scale = 0.125f;
 		p.stamps = which == 0 ? st : nullptr;
-		launch_skinny(DT_BF16, p, 8, s);
+		if (launch_skinny(DT_BF16, p, 8, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 		p = {}; p.Wp = sets[i].wproj; p.N = d; p.K = d; p.M = B; p.bias = bias; p.a = ao; p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d; p.out_T = fold ? ao : nullptr;
 		p.stamps = which == 1 ? st : nullptr;
-		launch_skinny(DT_BF16, p, 8, s);
+		if (launch_skinny(DT_BF16, p, 8, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 		p = {}; p.Wp = sets[i].wfc; p.N = 4 * d; p.K = d; p.M = B; p.bias = bias;
 		if (fold) { p.g1 = bias; p.a = ao; } else { p.ln_count = 1; p.x = x; p.ldx = d; p.g1 = g; p.b1 = b; }
 		p.mode = SK_ACT_T; p.act = ACT_GELU_NEW; p.out_T = hb; p.stamps = which == 2 ? st : nullptr;
-		launch_skinny(DT_BF16, p, 8, s);
+		if (launch_skinny(DT_BF16, p, 8, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 		p = {}; p.Wp = sets[i].wproj2; p.N = d; p.K = 4 * d; p.M = B; p.bias = bias; p.a = hb; p.mode = SK_RESIDUAL; p.out_f32 = x; p.ldc = d;
 		p.stamps = which == 3 ? st : nullptr;
-		launch_skinny(DT_BF16, p, 16, s);
+		if (launch_skinny(DT_BF16, p, 16, s) != hipSuccess) { printf("launch_skinny refused the launch\n"); exit(1); }
 	};
 	const char* names[4] = {"ln1+qkv (192 WG x 8 waves)", "c_proj (64x4 WG x 8)", "ln2+fc+gelu (256 WG x 8)", "mlp.c_proj (64x4 WG x 16)"};
 	const int grids[4] = {192, 256, 256, 256};

@@ -166,6 +166,25 @@ def test_folded_layernorm_on_outlier_channels_and_on_a_common_offset(ar_sd, dtyp
 		assert m.last_health & 1
 
 
+@pytest.mark.parametrize("which", ["full-size, TTK_AR_LEAN=0", "model_dim 192"])
+def test_common_offset_is_reported_by_the_generic_kernel_too(ar_sd, which):
+	"""the fold runs on k_skinny for every model_dim != 1024 and for every handle under TTK_AR_LEAN=0: the same common offset of 40 std, the same warning
+	(until k_skinny's folded form carried the health word these streams drifted silently)"""
+	from tortoise_tts_amd.autoregressive import UnifiedVoice
+	full = which.startswith("full")
+	cfg = W.AR_FULL if full else W.ARConfig(layers=2, model_dim=192, heads=3)
+	sd = dict(ar_sd) if full else W.synth_state_dict(W.ar_shapes(cfg), 3)
+	sd["mel_embedding.weight"] = sd["mel_embedding.weight"] + 40 * sd["mel_embedding.weight"].std().item()
+	g = torch.Generator().manual_seed(92)
+	text = torch.randint(1, 255, (1, 12), generator=g)
+	cond = torch.randn(1, cfg.model_dim, generator=g)
+	with torch.inference_mode():
+		m = _with_env("TTK_AR_LEAN", "0" if full else "1", lambda: UnifiedVoice(sd, cfg, dtype="bf16", device=DEV, max_batch=16, max_ctx=12 + 4 + 16))
+		with pytest.warns(RuntimeWarning, match="TTK_AR_LNFOLD=0"):
+			m.inference_speech(cond.to(DEV), text.to(DEV), do_sample=True, temperature=0.8, top_k=0, num_return_sequences=16, max_generate_length=4)
+		assert m.last_health & 1
+
+
 # ---- k_skinny where no fixture model reaches it: a projection whose N / 16 is no multiple of 8
 ODD = W.ARConfig(layers=2, model_dim=192, heads=3)      # 12 column tiles in c_proj / mlp.c_proj; K = 192 and 768: 6 and 24 k-steps over 4 waves
 

@@ -34,6 +34,7 @@ def test_struct_layouts_match_header_sizes():
 	assert ctypes.sizeof(_lib.GemmSeg) == 32 and ctypes.sizeof(_lib.GemmDesc) == 496   # ttk_gemm_seg / ttk_gemm_desc (static_assert'ed in csrc/ttk_host.hip)
 	assert ctypes.sizeof(_lib.AttnDesc) == 96 and ctypes.sizeof(_lib.AttnDecodeDesc) == 80   # ttk_attn_desc / ttk_attn_decode_desc (static_assert'ed in csrc/ttk_host.hip)
 	assert ctypes.sizeof(_lib.GnDesc) == 144                        # ttk_gn_desc (static_assert'ed in csrc/ttk_host.hip)
+	assert ctypes.sizeof(_lib.GemvMatConfigC) == 16 and ctypes.sizeof(_lib.GemvDesc) == 184   # ttk_gemv_mat_config / ttk_gemv_desc (static_assert'ed in csrc/ttk_host.hip)
 	from tortoise_tts_amd.vocoder import VocConfigC
 	assert ctypes.sizeof(VocConfigC) == (2 + 8 + 8 + 2 + 4 + 12 + 2) * 4          # ttk_voc_config: 38 ints
 
@@ -362,6 +363,27 @@ def test_every_batch_a_handle_accepts_requests_no_more_fragment_rows_than_create
 		assert lib.ttk_ar_decode_geometry(dtype, cap + 1, 1, out) != 0 and lib.ttk_ar_decode_geometry(dtype, 8, 9, out) != 0
 	assert (True, 4) in seen and lib.ttk_ar_decode_geometry(_lib.DTYPES["bf16"], 48, 48, out) == 0 and out[0] == 48 and out[2] == 48      # round 3's faulting case (now a 3-tile form)
 	assert lib.ttk_ar_decode_geometry(_lib.DTYPES["bf16"], 64, 40, out) == 0 and out[0] == 64 and out[1] == 3 and out[2] == 48
+
+
+def test_ar_create_refuses_a_config_whose_layernorm_launches_exceed_a_compute_units_lds():
+	"""The prefill's head (and the TTK_AR_LNFOLD=0 step) keeps every candidate's normalised row in LDS: 16 MT (K sizeof(T) + 16) bytes plus the reduce area, against the
+	160 KiB of a gfx950 compute unit.  ttk_ar_create checks it with the other config checks, before a weight is looked up or the GPU is touched -- such a handle
+	used to be created and then fail in its first prefill with a raw launch error.  An accepted config goes on to the weights (none are given here)."""
+	lib = _lib.load()
+	views, keep = _lib.weight_views({"none": torch.zeros(1)}, ["none"])
+
+	def create(model_dim, dtype, max_batch):
+		cfg = _lib.ARConfigC(2, model_dim, model_dim // 64, 32, 32, 256, 8194, 255, 0, 8192, 8193, _lib.DTYPES[dtype], max_batch, 64)
+		h = ctypes.c_void_p()
+		return lib.ttk_ar_create(ctypes.byref(h), ctypes.byref(cfg), views, 1), lib.ttk_last_error().decode()
+	rc, msg = create(2048, "f32", 32)
+	assert rc == -1 and "2048" in msg and "32" in msg and "LDS" in msg and str(160 * 1024) in msg, (rc, msg)
+	assert str(32 * (2048 * 4 + 16) + 4 * 2 * 64 * 16) in msg      # the prefill's head over 17 rows (two m-tiles, four waves): the first batch that does not fit
+	rc, msg = create(1536, "bf16", 64)
+	assert rc == -1 and "LDS" in msg, (rc, msg)
+	for model_dim, dtype, max_batch in ((2048, "f32", 16), (1024, "bf16", 64), (2048, "bf16", 32), (1024, "f32", 32)):
+		rc, msg = create(model_dim, dtype, max_batch)
+		assert rc == -3 and "missing weight" in msg, (model_dim, dtype, max_batch, rc, msg)      # TTK_E_WEIGHT: the config itself was accepted
 
 
 def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):

@@ -101,6 +101,20 @@ class GnDesc(C.Structure):
 				("pf_taps", C.c_int), ("stats", C.c_int), ("form", C.c_int)]
 
 
+class GemvMatConfigC(C.Structure):
+	"""ttk_gemv_mat_config (include/ttk.h)"""
+	_fields_ = [(n, C.c_int) for n in ("dtype", "layout", "N", "K")]
+
+
+class GemvDesc(C.Structure):
+	"""ttk_gemv_desc (include/ttk.h)"""
+	_fields_ = [("dtype", C.c_int), ("role", C.c_int), ("form", C.c_int), ("M", C.c_int), ("a", C.c_void_p), ("x", C.c_void_p),
+				("g1", C.c_void_p), ("b1", C.c_void_p), ("g2", C.c_void_p), ("b2", C.c_void_p), ("out_f32", C.c_void_p), ("out_T", C.c_void_p),
+				("qbuf", C.c_void_p), ("kcache", C.c_void_p), ("vcache", C.c_void_p), ("max_ctx", C.c_int), ("H", C.c_int), ("q_scale", C.c_float),
+				("bump", C.c_int), ("d_pos", C.c_void_p), ("noise", C.c_void_p), ("rng", C.c_void_p), ("draws", C.c_void_p), ("health", C.c_void_p),
+				("launched", C.POINTER(C.c_int)), ("family", C.c_int), ("waves", C.c_int), ("model_dim", C.c_int)]
+
+
 class ProfResult(C.Structure):
 	_fields_ = [("ms", C.c_double), ("launches", C.c_int64), ("work", C.c_double)]
 
@@ -166,6 +180,9 @@ SYMBOLS = {
 	"ttk_attn_fwd": (_I, [_I, C.POINTER(AttnDesc), _P]),
 	"ttk_attn_decode": (_I, [_I, C.POINTER(AttnDecodeDesc), _P]),
 	"ttk_gn_apply": (_I, [_I, C.POINTER(GnDesc), _P]),
+	"ttk_gemv_mat_create": (_I, [C.POINTER(_P), C.POINTER(GemvMatConfigC), C.POINTER(WeightView), _I]),
+	"ttk_gemv_mat_destroy": (_I, [_P]),
+	"ttk_gemv_launch": (_I, [_P, C.POINTER(GemvDesc), _P]),
 	"ttk_fp8_round_weights": (_I, [_P, _L, C.POINTER(C.c_float), _P]),
 	"ttk_sample_step": (_I, [_P, _L, _I, _I, _P, _L, _P, C.c_float, _L, _P, _P, _P, _L, _L, _P, _P, _L, _L, _P, _P, _P]),
 	"ttk_ar_decode_geometry": (_I, [_I, _I, _I, C.POINTER(C.c_int32)]),

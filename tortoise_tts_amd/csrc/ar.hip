@@ -182,19 +182,7 @@ static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipSt
 	return TTK_OK;
 }
 
-// ---- the weight-streaming launches of the decode step, each described once
-enum DecodeRole { DR_QKV = 0, DR_PROJ, DR_FC, DR_PROJ2, DR_HEAD };      // ln_1 + c_attn, c_proj + residual, ln_2 + c_fc + gelu_new, mlp.c_proj + residual, mel_head
-struct DecodeLaunch {
-	int role;
-	const Mat* W; int N, K;
-	const void* a;                   // rows, T-typed in A-fragment order: x_frag (DR_QKV / DR_FC: un-normalised, the LayerNorm is folded into W), attn_out, hbuf
-	const float *ln_g, *ln_b;        // the LayerNorm in front: DR_QKV / DR_FC (used as such only with TTK_AR_LNFOLD=0), the prefill's head (ln_f)
-	const float *ln2_g, *ln2_b;      // the prefill's head: final_norm behind ln_f
-	float* out_f32;                  // DR_PROJ / DR_PROJ2: the residual stream, updated in place; DR_HEAD: logits
-	void* out_T;                     // DR_FC: activations; DR_PROJ / DR_PROJ2 (optional): T copy of the updated rows; both in A-fragment order
-	void *kc, *vc;                   // DR_QKV: this layer's caches
-	bool bump;                       // DR_HEAD: the launch advances the cache length
-};
+namespace ttk {
 
 // Waves per workgroup of the k_skinny launches (k_gemv's are template parameters that repeat them).  A wave requests its operands in batches of 8 k-steps
 // (4 in f32), so K / 32 / waves should be a multiple of that: with 8 waves on K = 1024 every bf16 wave owned 4 k-steps and half of its 16 load
@@ -202,81 +190,98 @@ struct DecodeLaunch {
 // 4 (K = 1024) / 8 (K = 4096) measured best in the 250-token loop (bf16, B = 16).  f32: batches of 4 k-steps, 32 / 4 = 8 waves; K = 4096: 4 batches each.
 // LN prologue: 8 waves x 2 rows normalise 16 candidates in one pass.  The head has 513 n-tiles: two 8-wave workgroups fit a CU (512 slots), so tile 513
 // ran as a second round on an empty chip; five 4-wave ones fit and the tiles run as one round.  Small models: 4 everywhere.
-static int skinny_waves(int role, bool ln_prologue, int dt, int d) {
+int skinny_waves(int role, bool ln_prologue, int dt, int d) {
 	if (d < 1024 || role == DR_HEAD) return 4;
 	if (ln_prologue || dt == DT_F32) return 8;
 	return role == DR_PROJ2 ? 8 : 4;
 }
 
-// One launch on M rows: k_gemv where the lean kernels are allowed and have an instantiation for the geometry, else k_skinny on the same operands.
-static void decode_launch(ttk_ar* h, const DecodeLaunch& L, int M, hipStream_t s) {
-	const ttk_ar_config& c = h->cfg;
+int decode_launch(const DecodeCtx& c, const DecodeLaunch& L, int M, hipStream_t s) {
 	const Mat& W = *L.W;
-	const bool fold = h->lnfold && (L.role == DR_QKV || L.role == DR_FC);      // x_frag times gamma o W, the norm finished in the epilogue
-	const bool prologue = L.ln_g && !fold;                                     // f32 rows of h->x normalised inside the launch
+	const bool fold = c.lnfold && (L.role == DR_QKV || L.role == DR_FC);      // x_frag times gamma o W, the norm finished in the epilogue
+	const bool prologue = L.ln_g && !fold;                                     // f32 rows of L.x normalised inside the launch
 	const bool residual = L.role == DR_PROJ || L.role == DR_PROJ2;
 	GemvParams g = {};
 	g.Wp = fold ? W.wfrag_fold : W.wfrag; g.bias = fold ? W.bias_fold : W.bias; g.csum = fold ? W.csum : nullptr;
 	g.w8 = fold ? 0 : W.w8; g.wscale = W.wscale;       // (fp8 weights: the fold is kept in bf16)
 	g.a = L.a; g.out_f32 = L.out_f32; g.out_T = L.out_T; g.M = M; g.N = L.N; g.K = L.K; g.row0 = 0;
-	if (fold) g.health = h->d_health;
-	if (L.role == DR_QKV) { g.qbuf = h->qbuf; g.kcache = L.kc; g.vcache = L.vc; g.d_pos = h->d_pos; g.max_ctx = c.max_ctx; g.H = c.heads; g.q_scale = 0.125f; }
-	if (L.role == DR_HEAD) { g.d_pos = L.bump ? h->d_pos : nullptr; g.noise = h->rng_q; g.rng = h->rng_args; g.draws = h->rng_draws; }
+	if (fold) g.health = c.health;
+	if (L.role == DR_QKV) { g.qbuf = L.qbuf; g.kcache = L.kc; g.vcache = L.vc; g.d_pos = L.d_pos; g.max_ctx = L.max_ctx; g.H = L.H; g.q_scale = 0.125f; }
+	if (L.role == DR_HEAD) { g.d_pos = L.bump ? L.d_pos : nullptr; g.noise = c.rng_q; g.rng = c.rng_args; g.draws = c.rng_draws; }
 	const int gv = L.role == DR_QKV ? GV_QKV : (L.role == DR_FC ? GV_FC : (L.role == DR_HEAD ? GV_HEAD : GV_PROJ));
 	// the ONE place that decides between the kernel families: launch_gemv declines (gemv_supported) what it has no instantiation for
-	if (h->lean && h->lnfold && !prologue && launch_gemv(h->dt, gv, g, s)) return;
+	if (c.family == 2 || (c.family == 0 && c.lean && c.lnfold && !prologue)) {
+		if (!prologue && launch_gemv(c.dt, gv, g, s)) { if (c.launched) *c.launched = 2; return TTK_OK; }
+		TTK_REQUIRE(c.family != 2, TTK_E_ARG, "decode_launch: k_gemv has no instantiation for this launch");
+	}
 	SkinnyParams p = {};
 	p.Wp = g.Wp; p.w8 = g.w8; p.wscale = g.wscale; p.N = L.N; p.K = L.K; p.M = M; p.bias = g.bias;
-	if (prologue) { p.ln_count = L.ln2_g ? 2 : 1; p.x = h->x; p.ldx = c.model_dim; p.g1 = L.ln_g; p.b1 = L.ln_b; p.g2 = L.ln2_g; p.b2 = L.ln2_b; }
-	else { p.a = L.a; p.g1 = g.csum; }
+	if (prologue) { p.ln_count = L.ln2_g ? 2 : 1; p.x = L.x; p.ldx = L.ldx; p.g1 = L.ln_g; p.b1 = L.ln_b; p.g2 = L.ln2_g; p.b2 = L.ln2_b; }
+	else { p.a = L.a; p.g1 = g.csum; p.health = g.health; }
 	p.mode = L.role == DR_QKV ? SK_QKV : (L.role == DR_FC ? SK_ACT_T : (residual ? SK_RESIDUAL : SK_STORE_F32));
 	p.act = L.role == DR_FC ? ACT_GELU_NEW : ACT_NONE;
 	p.out_f32 = L.out_f32; p.ldc = L.N; p.out_T = L.out_T;
 	p.qbuf = g.qbuf; p.kcache = g.kcache; p.vcache = g.vcache; p.max_ctx = g.max_ctx; p.H = g.H; p.q_scale = g.q_scale; p.d_pos = g.d_pos;
 	p.noise = g.noise; p.rng = g.rng; p.draws = g.draws;
-	launch_skinny(h->dt, p, skinny_waves(L.role, prologue, h->dt, c.model_dim), s);
+	const int waves = c.waves ? c.waves : skinny_waves(L.role, prologue, c.dt, c.model_dim);
+	const hipError_t e = launch_skinny(c.dt, p, waves, s);
+	if (e != hipSuccess) {
+		const size_t lds = skinny_lds_bytes(c.dt, decode_row_tiles(M), L.K, skinny_launch_waves(waves, prologue), prologue ? SKF_PROLOGUE : (fold ? SKF_FOLD : SKF_PLAIN));
+		set_error("decode launch over M=%d rows, K=%d (%zu bytes of LDS; a compute unit has %zu) was not launched: %s", M, L.K, lds, CU_LDS_BYTES, hipGetErrorString(e));
+		return lds > CU_LDS_BYTES ? TTK_E_ARG : TTK_E_HIP;
+	}
+	if (c.launched) *c.launched = 1;
+	return TTK_OK;
+}
+
+}  // namespace ttk
+
+static DecodeCtx decode_ctx(const ttk_ar* h) {
+	return DecodeCtx{h->dt, h->lnfold, h->lean, h->cfg.model_dim, h->d_health, h->rng_args, h->rng_draws, h->rng_q, 0, 0, nullptr};
 }
 
 // the prefill's head: ln_f + final_norm + mel_head on the f32 rows h->x [B][d], the norms inside the launch (once per utterance; the decode step splits them off)
-static void head_launch(ttk_ar* h, int B, float* logits, hipStream_t s) {
+static int head_launch(ttk_ar* h, int B, float* logits, hipStream_t s) {
 	DecodeLaunch L = {DR_HEAD, &h->head, h->cfg.number_mel_codes, h->cfg.model_dim};
 	L.ln_g = h->lnf_g; L.ln_b = h->lnf_b; L.ln2_g = h->fn_g; L.ln2_b = h->fn_b; L.out_f32 = logits;
-	decode_launch(h, L, B, s);
+	L.x = h->x; L.ldx = h->cfg.model_dim;
+	return decode_launch(decode_ctx(h), L, B, s);
 }
 
 // one decode step of the whole batch on stream s: layers x {ln_1+c_attn+KV append, attention, c_proj+res, ln_2+c_fc+gelu, mlp.c_proj+res} + ln_f/final_norm + mel_head
-static void decode_rows(ttk_ar* h, float* logits_out, float* hidden_out, hipStream_t s) {
+static int decode_rows(ttk_ar* h, float* logits_out, float* hidden_out, hipStream_t s) {
 	const ttk_ar_config& c = h->cfg;
 	const int d = c.model_dim, B = h->B, dt = h->dt;
+	const DecodeCtx ctx = decode_ctx(h);
 	void* xf = h->lnfold ? h->x_frag : nullptr;      // T copy of the residual rows: written by the projections, operand of the folded launches
 	for (int l = 0; l < c.layers; ++l) {
 		const ARLayer& L = h->L[l];
 		char* kc = (char*)h->kc + (size_t)l * h->kv_layer_stride * h->es;
 		char* vc = (char*)h->vc + (size_t)l * h->kv_layer_stride * h->es;
 		DecodeLaunch qkv = {DR_QKV, &L.attn, 3 * d, d, h->x_frag, L.ln1_g, L.ln1_b};
-		qkv.kc = kc; qkv.vc = vc;
-		decode_launch(h, qkv, B, s);
+		qkv.kc = kc; qkv.vc = vc; qkv.x = h->x; qkv.ldx = d; qkv.qbuf = h->qbuf; qkv.d_pos = h->d_pos; qkv.max_ctx = c.max_ctx; qkv.H = c.heads;
+		TTK_TRY(decode_launch(ctx, qkv, B, s));
 		AttnDecodeParams a = {};
 		a.qbuf = h->qbuf; a.kcache = kc; a.vcache = vc; a.d_pos = h->d_pos; a.pos_slot_p1 = h->pos_slot + 1; a.B = B; a.H = c.heads; a.max_ctx = c.max_ctx; a.ctx_hint = h->P + 2 + h->k;
 		a.out = h->attn_out; a.out_frag = 1; a.shared_rows = 1; a.row_info = h->lines_mode ? h->d_rowinfo : nullptr;
 		launch_attn_decode(dt, a, s);
 		DecodeLaunch proj = {DR_PROJ, &L.proj, d, d, h->attn_out};
 		proj.out_f32 = h->x; proj.out_T = xf;
-		decode_launch(h, proj, B, s);
+		TTK_TRY(decode_launch(ctx, proj, B, s));
 		DecodeLaunch fc = {DR_FC, &L.fc, 4 * d, d, h->x_frag, L.ln2_g, L.ln2_b};
-		fc.out_T = h->hbuf;
-		decode_launch(h, fc, B, s);
+		fc.out_T = h->hbuf; fc.x = h->x; fc.ldx = d;
+		TTK_TRY(decode_launch(ctx, fc, B, s));
 		DecodeLaunch proj2 = {DR_PROJ2, &L.proj2, d, 4 * d, h->hbuf};
 		proj2.out_f32 = h->x; proj2.out_T = xf;
-		decode_launch(h, proj2, B, s);
+		TTK_TRY(decode_launch(ctx, proj2, B, s));
 	}
 	// ln_f + final_norm ONCE (4 workgroups), the mel head as a plain 513-tile GEMV over the normalised rows in fragment order: with the norms inside the
 	// GEMV every one of the 513 workgroups normalised all 16 rows, two passes each -- 17 us for 16.8 MB of weights
 	if (h->ring_base && !hidden_out) launch_layernorm(dt, h->x, d, B, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, h->attn_out, d, 0, s, 1, nullptr, h->ring_idx, h->ring_stride, h->d_ring);
 	else launch_layernorm(dt, h->x, d, B, d, h->lnf_g, h->lnf_b, h->fn_g, h->fn_b, h->attn_out, d, 0, s, 1, hidden_out);
 	DecodeLaunch head = {DR_HEAD, &h->head, c.number_mel_codes, d, h->attn_out};
-	head.out_f32 = logits_out; head.bump = true;      // the last launch of the step advances the cache length
-	decode_launch(h, head, B, s);
+	head.out_f32 = logits_out; head.bump = true; head.d_pos = h->d_pos;      // the last launch of the step advances the cache length
+	return decode_launch(ctx, head, B, s);
 }
 
 extern "C" {
@@ -290,6 +295,19 @@ int ttk_ar_create(ttk_ar** out, const ttk_ar_config* cfg, const ttk_weight_view*
 	TTK_REQUIRE(cfg->max_batch >= 1 && cfg->max_batch <= (cfg->dtype == TTK_F32 ? 32 : 64), TTK_E_ARG,
 				"ttk_ar_create: max_batch %d out of range", cfg->max_batch);
 	TTK_REQUIRE(cfg->max_ctx >= 8, TTK_E_ARG, "ttk_ar_create: max_ctx %d too small", cfg->max_ctx);
+	{   // The launches that hold every candidate's normalised row in LDS must fit a compute unit for every batch this handle accepts: the prefill's head
+		// (two norms inside the launch, all B rows) and the step launches of TTK_AR_LNFOLD=0 (at most 32 rows: decode_impl).  Checked here, not at the first prefill.
+		const int kdt = kernel_dtype(cfg->dtype), d = cfg->model_dim;
+		for (int B = 1; B <= cfg->max_batch; ++B) {
+			const int mt = decode_row_tiles(B);
+			const size_t head = skinny_lds_bytes(kdt, mt, d, skinny_launch_waves(skinny_waves(DR_HEAD, true, kdt, d), true), SKF_PROLOGUE);
+			TTK_REQUIRE(head <= CU_LDS_BYTES, TTK_E_ARG, "ttk_ar_create: model_dim %d with max_batch %d: the prefill's head over %d rows needs %zu bytes of LDS, a compute unit has %zu", d,
+						cfg->max_batch, B, head, CU_LDS_BYTES);
+			const size_t step = skinny_lds_bytes(kdt, mt, d, skinny_launch_waves(skinny_waves(DR_QKV, true, kdt, d), true), SKF_PROLOGUE);
+			TTK_REQUIRE(B > 32 || step <= CU_LDS_BYTES, TTK_E_ARG, "ttk_ar_create: model_dim %d with max_batch %d: the TTK_AR_LNFOLD=0 step over %d rows needs %zu bytes of LDS, a compute unit has %zu", d,
+						cfg->max_batch, B, step, CU_LDS_BYTES);
+		}
+	}
 	std::unique_ptr<ttk_ar> h(new ttk_ar());
 	h->cfg = *cfg;
 	h->wdt = cfg->dtype;
@@ -404,7 +422,7 @@ static int prefill_impl(ttk_ar* h, const float* cond_latent, int Bc, const int64
 					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, x, prompt, prompt_rows, n_in);
 	TTK_TRY(dense_forward(h, x, Bp, S, true, s));
 	launch_copy_rows(x + (size_t)(S - 1) * d, shared ? 0 : (int64_t)S * d, h->x, d, B, d, s);      // source stride 0: one row to all candidates
-	head_launch(h, B, logits_out, s);
+	TTK_TRY(head_launch(h, B, logits_out, s));
 	launch_set_int(h->d_pos, S, s);
 	launch_set_int(h->d_pos + 1, shared ? S : 0, s);      // rows of the shared prefix (AttnDecodeParams.shared_rows): device-resident, like the cache length
 	TTK_TRY(poison_scratch(h, s));
@@ -459,7 +477,7 @@ int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* te
 		launch_fill_int2((int*)(h->d_rowinfo + r0), start, r0, rows_per_line, s);
 		toff += Tt;
 	}
-	head_launch(h, B, logits_out, s);
+	TTK_TRY(head_launch(h, B, logits_out, s));
 	launch_set_int(h->d_pos, Smax, s);
 	launch_set_int(h->d_pos + 1, Smax, s);
 	TTK_TRY(poison_scratch(h, s));
@@ -483,7 +501,7 @@ static int decode_impl(ttk_ar* h, const int64_t* tok, float* logits_out, float* 
 	// x[b] = mel_embedding[tok] + mel_pos[k + 1]; *d_pos = P + k rows are cached  =>  offset 1 - P   (unified_voice.py:213-214)
 	// (tok == null: ttk_ar_sample_next has written the rows already)
 	if (tok) launch_decode_embed(h->mel_emb, tok, h->mel_pos, h->d_pos, 1 - h->P, c.max_mel_seq_len, h->x, B, d, s, h->lnfold ? h->x_frag : nullptr, elem_kind(h->dt));
-	decode_rows(h, logits_out, hidden_out, s);
+	TTK_TRY(decode_rows(h, logits_out, hidden_out, s));
 	h->k += 1;
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 			}
 		}
 	}
-	float fmean[MT], frstd[MT];
+	float fmean[MT], frstd[MT], fvar[MT], fsq[MT];
 	if (FOLD && tid < 256) {
 #pragma unroll
 		for (int mt = 0; mt < MT; ++mt) {
@@ -329,7 +329,9 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 			for (int w = 0; w < nw; ++w) { const float2 t = *(const float2*)(rstat + ((w * MT + mt) * 16 + 4 * (l2 >> 4) + r) * 2); a1 += t.x; a2 += t.y; }
 			const float mean = a1 / (float)p.K;
 			fmean[mt] = mean;
-			frstd[mt] = rsqrtf(fmaxf(a2 / (float)p.K - mean * mean, 0.f) + 1e-5f);      // E[x^2] - mean^2 in f32, as the LN prologue does
+			fvar[mt] = fmaxf(a2 / (float)p.K - mean * mean, 0.f);      // E[x^2] - mean^2 in f32, as the LN prologue does
+			fsq[mt] = a2;
+			frstd[mt] = rsqrtf(fvar[mt] + 1e-5f);
 		}
 	}
 	if (!mine) return;
@@ -339,6 +341,11 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 		const int m = mt * 16 + 4 * (l2 >> 4) + r;
 		if (m >= p.M) continue;
 		const float v = FOLD ? (vsum[mt] - fmean[mt] * fcs) * frstd[mt] + bias : (W8 ? vsum[mt] * p.wscale : vsum[mt]) + bias;
+		// what the fold cannot represent well is reported, not hidden: k_gemv's two conditions (one workgroup looks; never taken on a healthy stream)
+		if (FOLD && p.health && blockIdx.x == 0 && (l2 & 15) == 0) {
+			const int bad = (fmean[mt] * fmean[mt] > 64.f * (fvar[mt] + 1e-5f) ? 1 : 0) | (fsq[mt] - fsq[mt] != 0.f ? 2 : 0);
+			if (bad) atomicOr(p.health, bad);
+		}
 		if (mode == SK_STORE_F32) {
 			p.out_f32[(int64_t)m * p.ldc + n] = v;
 			// mel head: the multinomial noise of the sampling launch that follows, one value per logit
@@ -373,49 +380,48 @@ __global__ __launch_bounds__(LN ? 512 : 1024) void k_skinny(SkinnyParams p) {
 #endif
 }
 
+// one launch of an instantiation: the LDS it needs is checked against the CU and, past the default limit, granted by the runtime BEFORE the launch
+static hipError_t skinny_go(void (*kern)(SkinnyParams), const SkinnyParams& p, int grid, int waves, size_t lds, hipStream_t s, double work) {
+	if (lds > CU_LDS_BYTES) return hipErrorInvalidValue;
+	if (lds > LDS_DEFAULT_LIMIT) {
+		const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e == hipErrorInvalidValue ? hipErrorUnknown : e;      // (hipErrorInvalidValue is kept for "more than a compute unit has")
+	}
+	// profiling: the event pair travels with the dispatch packet (kernel start / stop timestamps), see prof_pair; taken only now that the launch is certain
+	hipEvent_t ea = nullptr, eb = nullptr;
+	if (g_prof_on) prof_pair(PROF_SKINNY, work, &ea, &eb);
+	hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), (unsigned)lds, s, ea, eb, 0, p);
+	return hipSuccess;
+}
+
 template <typename T, int MT, bool W8>
-static void launch_skinny_mt(const SkinnyParams& p, int waves, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+static hipError_t launch_skinny_mt(int dt, const SkinnyParams& p, int waves, hipStream_t s, double work) {
 	const bool fold = p.ln_count == 0 && p.g1 && !W8;
 	const int grid = ((p.N + 15) / 16) * (p.mode == SK_RESIDUAL && p.ln_count == 0 && !fold ? 4 : 1);      // the residual projections: four workgroups per n-tile
-	const size_t red = (size_t)waves * MT * 64 * 4 * sizeof(float);
-	if (p.ln_count > 0) {
-		if (waves > 8) waves = 8;
-		const size_t lds = (size_t)16 * MT * (p.K * sizeof(T) + 16) + (size_t)waves * MT * 64 * 4 * sizeof(float);
-		if (p.K <= 1024) {
-			if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_skinny<T, MT, true, 4, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			hipExtLaunchKernelGGL((k_skinny<T, MT, true, 4, W8>), dim3(grid), dim3(64 * waves), (unsigned)lds, s, ea, eb, 0, p);
-		} else {
-			if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k_skinny<T, MT, true, 8, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-			hipExtLaunchKernelGGL((k_skinny<T, MT, true, 8, W8>), dim3(grid), dim3(64 * waves), (unsigned)lds, s, ea, eb, 0, p);
-		}
-	} else if (fold) {
-		const size_t lds = red + (size_t)waves * MT * 16 * 2 * sizeof(float);
-		hipExtLaunchKernelGGL((k_skinny<T, MT, false, 1, false, true>), dim3(grid), dim3(64 * waves), (unsigned)lds, s, ea, eb, 0, p);
-	} else {
-		hipExtLaunchKernelGGL((k_skinny<T, MT, false, 1, W8>), dim3(grid), dim3(64 * waves), (unsigned)red, s, ea, eb, 0, p);
-	}
+	waves = skinny_launch_waves(waves, p.ln_count > 0);
+	const size_t lds = skinny_lds_bytes(dt, MT, p.K, waves, p.ln_count > 0 ? SKF_PROLOGUE : (fold ? SKF_FOLD : SKF_PLAIN));
+	if (p.ln_count > 0) return skinny_go(p.K <= 1024 ? k_skinny<T, MT, true, 4, W8> : k_skinny<T, MT, true, 8, W8>, p, grid, waves, lds, s, work);
+	if (fold) return skinny_go(k_skinny<T, MT, false, 1, false, true>, p, grid, waves, lds, s, work);
+	return skinny_go(k_skinny<T, MT, false, 1, W8>, p, grid, waves, lds, s, work);
 }
 
 template <typename T, bool W8>
-static void launch_skinny_t(const SkinnyParams& p, int waves, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+static hipError_t launch_skinny_t(int dt, const SkinnyParams& p, int waves, hipStream_t s, double work) {
 	const int mt = decode_row_tiles(p.M);
-	if (mt == 1) launch_skinny_mt<T, 1, W8>(p, waves, s, ea, eb);
-	else if (mt == 2) launch_skinny_mt<T, 2, W8>(p, waves, s, ea, eb);
-	else if (mt == 3) launch_skinny_mt<T, 3, W8>(p, waves, s, ea, eb);
-	else launch_skinny_mt<T, 4, W8>(p, waves, s, ea, eb);
+	if (mt == 1) return launch_skinny_mt<T, 1, W8>(dt, p, waves, s, work);
+	if (mt == 2) return launch_skinny_mt<T, 2, W8>(dt, p, waves, s, work);
+	if (mt == 3) return launch_skinny_mt<T, 3, W8>(dt, p, waves, s, work);
+	return launch_skinny_mt<T, 4, W8>(dt, p, waves, s, work);
 }
 
-void launch_skinny(int dt, const SkinnyParams& p_in, int waves, hipStream_t s) {
+hipError_t launch_skinny(int dt, const SkinnyParams& p_in, int waves, hipStream_t s) {
 	SkinnyParams p = p_in;
-	if (waves < 4) waves = 4;                                   // the epilogue is the first 256 threads' work
 	if (dt != DT_BF16) p.w8 = 0;                                // fp8 weights exist for the bf16 arithmetic only
 	// algorithmic bytes: the weight matrix once + bias + the M activation rows in and out
-	// profiling: the event pair travels with the dispatch packet (kernel start / stop timestamps), see prof_pair
-	hipEvent_t ea = nullptr, eb = nullptr;
-	if (g_prof_on) prof_pair(PROF_SKINNY, (double)p.N * p.K * (p.w8 ? 1 : dtype_size(dt)) + 4.0 * p.N + 4.0 * p.M * p.K + 4.0 * p.M * p.N, &ea, &eb);
-	if (dt == DT_BF16) { if (p.w8) launch_skinny_t<bf16, true>(p, waves, s, ea, eb); else launch_skinny_t<bf16, false>(p, waves, s, ea, eb); }
-	else if (dt == DT_F16) launch_skinny_t<f16, false>(p, waves, s, ea, eb);
-	else launch_skinny_t<float, false>(p, waves, s, ea, eb);
+	const double work = (double)p.N * p.K * (p.w8 ? 1 : dtype_size(dt)) + 4.0 * p.N + 4.0 * p.M * p.K + 4.0 * p.M * p.N;
+	if (dt == DT_BF16) return p.w8 ? launch_skinny_t<bf16, true>(dt, p, waves, s, work) : launch_skinny_t<bf16, false>(dt, p, waves, s, work);
+	if (dt == DT_F16) return launch_skinny_t<f16, false>(dt, p, waves, s, work);
+	return launch_skinny_t<float, false>(dt, p, waves, s, work);
 }
 
 }  // namespace ttk

@@ -111,6 +111,35 @@ int upload_mat(Arena& ar, const WeightMap& wm, int dt, const std::string& wname,
 int fold_layernorm(Arena& ar, const WeightMap& wm, int dt, const std::string& wname, const std::string& bname, const std::string& gname,
 				   const std::string& betaname, Mat* m);
 
+// ---- the weight-streaming launches of the decode step, each described once (ar.hip).  The handle's token step and ttk_gemv_launch (kernel tests on
+// caller-provided operands) both go through decode_launch: ONE place chooses the kernel family and the waves per workgroup.
+enum DecodeRole { DR_QKV = 0, DR_PROJ, DR_FC, DR_PROJ2, DR_HEAD };      // ln_1 + c_attn, c_proj + residual, ln_2 + c_fc + gelu_new, mlp.c_proj + residual, mel_head
+struct DecodeLaunch {
+	int role;
+	const Mat* W; int N, K;
+	const void* a;                   // rows, T-typed in A-fragment order: x_frag (DR_QKV / DR_FC: un-normalised, the LayerNorm is folded into W), attn_out, hbuf
+	const float *ln_g, *ln_b;        // the LayerNorm in front: DR_QKV / DR_FC (used as such only without the fold), the prefill's head (ln_f)
+	const float *ln2_g, *ln2_b;      // the prefill's head: final_norm behind ln_f
+	float* out_f32;                  // DR_PROJ / DR_PROJ2: the residual stream, updated in place; DR_HEAD: logits
+	void* out_T;                     // DR_FC: activations; DR_PROJ / DR_PROJ2 (optional): T copy of the updated rows; both in A-fragment order
+	void *kc, *vc;                   // DR_QKV: this layer's caches
+	bool bump;                       // DR_HEAD: the launch advances the cache length
+	const float* x; int64_t ldx;     // f32 rows the LayerNorm-prologue form normalises
+	float* qbuf; int* d_pos; int max_ctx, H;      // DR_QKV: scaled queries, cache row to append at, cache geometry; d_pos also DR_HEAD with bump
+};
+struct DecodeCtx {
+	int dt;                          // arithmetic type of the kernels (DT_F32 / DT_BF16 / DT_F16)
+	int lnfold, lean, model_dim;     // TTK_AR_LNFOLD, TTK_AR_LEAN, the model's width
+	int* health;                     // device word of the folded launches (ttk_ar_health)
+	const int64_t* rng_args; const int64_t* rng_draws; float* rng_q;      // DR_HEAD: multinomial noise (ttk_ar_set_noise)
+	// kernel tests only (ttk_gemv_launch; a handle leaves both 0): family 1 = k_skinny, 2 = k_gemv instead of the choice below; waves per k_skinny workgroup
+	int family, waves;
+	int* launched;                   // (optional, host) receives the family that was launched: 1 = k_skinny, 2 = k_gemv
+};
+int skinny_waves(int role, bool ln_prologue, int dt, int d);
+// One launch on M rows: k_gemv where the lean kernels are allowed and have an instantiation for the geometry, else k_skinny on the same operands.
+int decode_launch(const DecodeCtx& c, const DecodeLaunch& L, int M, hipStream_t s);
+
 // sample.hip: the fused per-token sampling launch; emb / pos / x_out non-null = also write the next decode step's input rows
 int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 					   hipStream_t stream, const char* who);

@@ -336,3 +336,113 @@ extern "C" int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* s
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
+
+// One decode matrix and one weight-streaming launch on caller-provided operands (include/ttk.h).  The matrix goes through upload_mat / fold_layernorm, the launch through
+// decode_launch (ar.hip): what the token step of a ttk_ar handle runs.  What is checked here is what the kernels take for granted and cannot check themselves.
+struct ttk_gemv_mat {
+	ttk::Arena arena;
+	ttk::Mat m;
+	int dtype = 0, dt = 0;      // as created / the arithmetic type of the kernels
+	bool folded = false;
+};
+static_assert(sizeof(ttk_gemv_mat_config) == 16 && sizeof(ttk_gemv_desc) == 184, "ttk_gemv_mat_config / ttk_gemv_desc layout (tortoise_tts_amd/_lib.py mirrors it)");
+extern "C" int ttk_gemv_mat_create(ttk_gemv_mat** out, const ttk_gemv_mat_config* cfg, const ttk_weight_view* w, int n_w) {
+	using namespace ttk;
+	TTK_REQUIRE(out && cfg && w, TTK_E_ARG, "ttk_gemv_mat_create: null argument");
+	TTK_REQUIRE(cfg->dtype == TTK_F32 || cfg->dtype == TTK_BF16 || cfg->dtype == TTK_F16 || cfg->dtype == TTK_FP8W, TTK_E_ARG, "ttk_gemv_mat_create: bad dtype %d", cfg->dtype);
+	TTK_REQUIRE(cfg->layout == PK_NK || cfg->layout == PK_KN, TTK_E_ARG, "ttk_gemv_mat_create: layout must be 0 ([N][K]) or 1 ([K][N]), got %d", cfg->layout);
+	// the packers pad K to 64 while the kernels index fragments by K / 32: any other K and the two disagree
+	TTK_REQUIRE(cfg->N >= 1 && cfg->K >= 64 && cfg->K % 64 == 0, TTK_E_ARG, "ttk_gemv_mat_create: need N >= 1 and K %% 64 == 0 (got N=%d K=%d)", cfg->N, cfg->K);
+	std::unique_ptr<ttk_gemv_mat> h(new ttk_gemv_mat());
+	h->dtype = cfg->dtype; h->dt = kernel_dtype(cfg->dtype);
+	WeightMap wm(w, n_w);
+	TTK_TRY(upload_mat(h->arena, wm, cfg->dtype, "weight", "bias", cfg->layout, cfg->N, cfg->K, true, &h->m));
+	const bool g = wm.find("gamma") != nullptr, b = wm.find("beta") != nullptr;
+	TTK_REQUIRE(g == b, TTK_E_ARG, "ttk_gemv_mat_create: gamma and beta come together");
+	if (g) {
+		TTK_REQUIRE(cfg->layout == PK_KN, TTK_E_ARG, "ttk_gemv_mat_create: the LayerNorm fold is defined on HF Conv1D matrices (layout 1)");
+		TTK_TRY(fold_layernorm(h->arena, wm, h->dt, "weight", "bias", "gamma", "beta", &h->m));
+		h->folded = true;
+	}
+	*out = h.release();
+	return TTK_OK;
+}
+extern "C" int ttk_gemv_mat_destroy(ttk_gemv_mat* h) {
+	if (!h) return TTK_OK;
+	(void)hipDeviceSynchronize();
+	delete h;
+	return TTK_OK;
+}
+extern "C" int ttk_gemv_launch(const ttk_gemv_mat* W, const ttk_gemv_desc* d, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(W && d, TTK_E_ARG, "ttk_gemv_launch: null matrix or descriptor");
+	const int N = W->m.N, K = W->m.K, dt = W->dt;
+	TTK_REQUIRE(d->dtype == TTK_F32 || d->dtype == TTK_BF16 || d->dtype == TTK_F16, TTK_E_ARG, "ttk_gemv_launch: dtype must be TTK_F32, TTK_BF16 or TTK_F16, got %d", d->dtype);
+	TTK_REQUIRE(!(W->m.w8 && d->dtype != TTK_BF16), TTK_E_ARG, "ttk_gemv_launch: an fp8 matrix runs under bf16 arithmetic only (dtype %d)", d->dtype);
+	TTK_REQUIRE(d->dtype == dt, TTK_E_ARG, "ttk_gemv_launch: dtype %d is not the arithmetic type the matrix was packed for (%d)", d->dtype, dt);
+	TTK_REQUIRE(d->role >= 0 && d->role <= 3, TTK_E_ARG, "ttk_gemv_launch: role must be 0 (qkv), 1 (proj), 2 (fc) or 3 (head), got %d", d->role);
+	TTK_REQUIRE(d->form >= 0 && d->form <= 2, TTK_E_ARG, "ttk_gemv_launch: form must be 0 (plain), 1 (folded LayerNorm) or 2 (LayerNorm prologue), got %d", d->form);
+	const bool qkv = d->role == 0, proj = d->role == 1, fc = d->role == 2, head = d->role == 3;
+	const bool fold = d->form == 1, prologue = d->form == 2;
+	const int cap = dt == DT_F32 ? 32 : 64;
+	TTK_REQUIRE(d->M >= 1 && d->M <= cap, TTK_E_ARG, "ttk_gemv_launch: M=%d outside 1..%d", d->M, cap);
+	TTK_REQUIRE(!(prologue && !head && d->M > 32), TTK_E_ARG, "ttk_gemv_launch: the LayerNorm-prologue form outside the head holds at most 32 rows in LDS; M=%d", d->M);
+	TTK_REQUIRE(!fold || qkv || fc, TTK_E_ARG, "ttk_gemv_launch: a folded LayerNorm sits in front of qkv and fc only (role %d)", d->role);
+	TTK_REQUIRE(!fold || W->folded, TTK_E_ARG, "ttk_gemv_launch: the folded form needs a matrix created with gamma and beta");
+	TTK_REQUIRE(d->form != 0 || proj || head, TTK_E_ARG, "ttk_gemv_launch: qkv and fc take the folded or the prologue form (no decode launch multiplies them plainly)");
+	TTK_REQUIRE(!(prologue && proj), TTK_E_ARG, "ttk_gemv_launch: the residual projections have no LayerNorm in front");
+	auto al = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; };
+	if (prologue) {
+		TTK_REQUIRE(d->x && d->g1 && d->b1 && (!d->g2 == !d->b2), TTK_E_ARG, "ttk_gemv_launch: the prologue form needs x, g1 and b1 (null), and g2 with b2 or neither");
+		TTK_REQUIRE(al(d->x, 16) && al(d->g1, 16) && al(d->b1, 16) && al(d->g2, 16) && al(d->b2, 16), TTK_E_ARG, "ttk_gemv_launch: x, g1, b1, g2 and b2 must be 16-byte aligned");
+	} else {
+		TTK_REQUIRE(d->a, TTK_E_ARG, "ttk_gemv_launch: null a");
+		TTK_REQUIRE(al(d->a, 16), TTK_E_ARG, "ttk_gemv_launch: a must be 16-byte aligned");
+	}
+	TTK_REQUIRE(al(d->out_T, 16) && al(d->out_f32, 4), TTK_E_ARG, "ttk_gemv_launch: out_T must be 16-byte aligned, out_f32 4-byte aligned");
+	TTK_REQUIRE(!d->out_T || N % 32 == 0, TTK_E_ARG, "ttk_gemv_launch: out_T is in fragment order: needs N %% 32 == 0 (N=%d)", N);
+	if (qkv) {
+		TTK_REQUIRE(d->qbuf && d->kcache && d->vcache && d->d_pos, TTK_E_ARG, "ttk_gemv_launch: qkv: null qbuf, kcache, vcache or d_pos");
+		TTK_REQUIRE(al(d->qbuf, 16) && al(d->kcache, 16) && al(d->vcache, 16) && al(d->d_pos, 4), TTK_E_ARG, "ttk_gemv_launch: qbuf, kcache and vcache must be 16-byte aligned, d_pos 4-byte aligned");
+		TTK_REQUIRE(N == 3 * K && d->H >= 1 && K == 64 * d->H, TTK_E_ARG, "ttk_gemv_launch: qkv needs N == 3 K and K == 64 H (N=%d K=%d H=%d)", N, K, d->H);
+		TTK_REQUIRE(d->max_ctx >= 1, TTK_E_ARG, "ttk_gemv_launch: qkv needs max_ctx >= 1");
+		TTK_REQUIRE(d->q_scale == 0.125f, TTK_E_ARG, "ttk_gemv_launch: q_scale must be 0.125 (head dim 64), got %g", (double)d->q_scale);
+	} else if (fc) {
+		TTK_REQUIRE(d->out_T, TTK_E_ARG, "ttk_gemv_launch: fc: null out_T");
+	} else {
+		TTK_REQUIRE(d->out_f32, TTK_E_ARG, "ttk_gemv_launch: %s: null out_f32", proj ? "proj" : "head");
+	}
+	if (head) {
+		TTK_REQUIRE((d->noise && d->rng && d->draws) || (!d->noise && !d->rng && !d->draws), TTK_E_ARG, "ttk_gemv_launch: head: pass noise, rng and draws or none of them");
+		TTK_REQUIRE(al(d->noise, 4) && al(d->rng, 8) && al(d->draws, 8), TTK_E_ARG, "ttk_gemv_launch: noise must be 4-byte aligned, rng and draws 8-byte aligned");
+		TTK_REQUIRE(!d->bump || (d->d_pos && al(d->d_pos, 4)), TTK_E_ARG, "ttk_gemv_launch: bump needs a 4-byte aligned d_pos");
+	}
+	TTK_REQUIRE(al(d->health, 4), TTK_E_ARG, "ttk_gemv_launch: health must be 4-byte aligned");
+	TTK_REQUIRE(d->family >= 0 && d->family <= 2, TTK_E_ARG, "ttk_gemv_launch: family must be 0 (the decode step's choice), 1 (k_skinny) or 2 (k_gemv), got %d", d->family);
+	TTK_REQUIRE(d->waves == 0 || (d->waves >= 4 && d->waves <= (prologue ? 8 : 16)), TTK_E_ARG, "ttk_gemv_launch: waves must be 0 or 4..%d, got %d", prologue ? 8 : 16, d->waves);
+	const int drole = qkv ? DR_QKV : (fc ? DR_FC : (head ? DR_HEAD : (K == N ? DR_PROJ : DR_PROJ2)));
+	DecodeCtx c = {};
+	TTK_REQUIRE(d->model_dim >= 0 && d->model_dim % 64 == 0, TTK_E_ARG, "ttk_gemv_launch: model_dim must be 0 or a multiple of 64, got %d", d->model_dim);
+	c.dt = dt; c.lean = 1; c.lnfold = !(prologue && !head); c.model_dim = d->model_dim ? d->model_dim : (proj ? N : K); c.health = d->health; c.launched = d->launched;
+	c.rng_args = d->rng; c.rng_draws = d->draws; c.rng_q = d->noise; c.family = d->family; c.waves = d->waves;
+	if (d->family == 2) {
+		TTK_REQUIRE(!prologue, TTK_E_ARG, "ttk_gemv_launch: family 2: k_gemv has no LayerNorm-prologue form");
+		GemvParams g = {};
+		g.M = d->M; g.N = N; g.K = K; g.w8 = fold ? 0 : W->m.w8;
+		TTK_REQUIRE(gemv_supported(dt, qkv ? GV_QKV : (fc ? GV_FC : (head ? GV_HEAD : GV_PROJ)), g), TTK_E_ARG,
+					"ttk_gemv_launch: family 2: k_gemv has no instantiation for role %d at N=%d K=%d M=%d%s", d->role, N, K, d->M, g.w8 ? " with fp8 weights" : "");
+	}
+	{   // k_skinny, if this launch falls to it: its LDS against the compute unit's
+		const int waves = skinny_launch_waves(d->waves ? d->waves : skinny_waves(drole, prologue, dt, c.model_dim), prologue);
+		const size_t lds = skinny_lds_bytes(dt, decode_row_tiles(d->M), K, waves, prologue ? SKF_PROLOGUE : (fold ? SKF_FOLD : SKF_PLAIN));
+		TTK_REQUIRE(d->family == 2 || lds <= CU_LDS_BYTES, TTK_E_ARG, "ttk_gemv_launch: M=%d K=%d with %d waves needs %zu bytes of LDS, a compute unit has %zu", d->M, K, waves, lds, CU_LDS_BYTES);
+	}
+	DecodeLaunch L = {};
+	L.role = drole; L.W = &W->m; L.N = N; L.K = K; L.a = d->a;
+	if (prologue) { L.ln_g = d->g1; L.ln_b = d->b1; L.ln2_g = d->g2; L.ln2_b = d->b2; L.x = d->x; L.ldx = K; }
+	L.out_f32 = d->out_f32; L.out_T = d->out_T; L.kc = d->kcache; L.vc = d->vcache; L.bump = head && d->bump != 0;
+	L.qbuf = d->qbuf; L.d_pos = d->d_pos; L.max_ctx = d->max_ctx; L.H = d->H;
+	TTK_TRY(decode_launch(c, L, d->M, (hipStream_t)stream));
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}

@@ -102,7 +102,12 @@ struct SkinnyParams {
 	//     from the A fragments they multiply anyway
 	int ln_count;
 	const float* x;  int64_t ldx;
-	const float *g1, *b1, *g2, *b2;
+	const float* g1;
+	union {
+		const float* b1;
+		int* health;   // folded LayerNorm (optional): the device word of GemvParams.health, same two bits under the same two conditions.  It takes the slot of b1, which only
+	};                 // the prologue form reads: the argument block, and with it the code of every instantiation without the fold, stays what it was before the word existed
+	const float *g2, *b2;
 	const void* a;
 	int mode, act;
 	float* out_f32;  int64_t ldc;   // SK_STORE_F32: [M][ldc]; SK_RESIDUAL: the residual stream, updated in place.  SK_RESIDUAL launches run four
@@ -121,7 +126,22 @@ struct SkinnyParams {
 	unsigned long long* stamps;   // diagnostic build only
 #endif
 };
-void launch_skinny(int dt, const SkinnyParams& p, int waves, hipStream_t s);
+// Dynamic LDS of a k_skinny launch -- the ONE definition: launch_skinny sizes the launch with it, ttk_ar_create and ttk_gemv_launch hold it against what a
+// gfx950 CU has before anything is launched.  Prologue: the 16 * MT normalised rows as T (padded by 16 bytes each) in front of the cross-wave reduce area
+// [wave][m_tile][lane][4]; fold: the reduce area plus the row statistics [wave][m_tile][16][2].
+enum SkinnyForm { SKF_PLAIN = 0, SKF_FOLD = 1, SKF_PROLOGUE = 2 };
+constexpr size_t CU_LDS_BYTES = 160 * 1024;      // LDS of one gfx950 compute unit: no workgroup can ask for more
+constexpr size_t LDS_DEFAULT_LIMIT = 64 * 1024;  // above this a kernel needs hipFuncAttributeMaxDynamicSharedMemorySize raised first
+// waves per workgroup a k_skinny launch really runs: at least 4 (the epilogue is the first 256 threads' work), at most 8 with the LayerNorm prologue (512-thread launch bounds)
+inline int skinny_launch_waves(int waves, bool prologue) { return waves < 4 ? 4 : (prologue && waves > 8 ? 8 : waves); }
+inline size_t skinny_lds_bytes(int dt, int MT, int K, int waves, int form) {
+	const size_t red = (size_t)waves * MT * 64 * 4 * sizeof(float);
+	if (form == SKF_PROLOGUE) return (size_t)16 * MT * ((size_t)K * dtype_size(dt) + 16) + red;
+	return form == SKF_FOLD ? red + (size_t)waves * MT * 16 * 2 * sizeof(float) : red;
+}
+// anything but hipSuccess: NOTHING was launched (and nothing recorded for the profile) -- hipErrorInvalidValue: more LDS than a CU has, and only then; else what
+// the runtime answered when asked for the size
+hipError_t launch_skinny(int dt, const SkinnyParams& p, int waves, hipStream_t s);
 
 // ---------------------------------------------------------------- lean decode GEMV (gemv.hip)
 // The launches of the KV-cached decode step at the benchmarked geometry (K = 1024 / 4096, activations in fragment order, LayerNorm folded), one
@@ -155,6 +175,7 @@ struct GemvParams {
 #endif
 };
 bool launch_gemv(int dt, int role, const GemvParams& p, hipStream_t s);
+bool gemv_supported(int dt, int role, const GemvParams& p);      // what launch_gemv has an instantiation for
 
 // ---------------------------------------------------------------- norms (norm.hip)
 // y = LN2?(LN1(x)) per row; out is T or f32; frag: out in the skinny GEMV's A-fragment order instead of row-major; out2 (optional): also f32 [rows][d]
