@@ -483,6 +483,48 @@ int ttk_rlg_destroy(ttk_rlg* h);
 /* RandomLatentConverter.forward :49-52 behind its torch.randn: noise f32 [rows, channels] -> out f32 [rows, channels]; one launch per layer. */
 int ttk_rlg_forward(ttk_rlg* h, const float* noise, int rows, float* out, void* stream);
 
+/* ------------------------------------------------------------------ the TorToiSe detector: AudioMiniEncoderWithClassifierHead
+ * models/classifier.py:79-149 (what upstream's `classify_audio_clip` runs from classifier.pth): Conv1d(1, 32, k = 3) on raw 24 kHz audio, `depth`
+ * stages of `resnet_blocks` ResBlocks (GroupNorm, SiLU, k = 5 conv, twice, + x) and a k = 5 stride-4 Downsample that doubles the channels,
+ * GroupNorm + SiLU + 1x1 conv to embedding_dim, `attn_blocks` AttentionBlocks, position 0, Linear(embedding_dim, classes).  Weights: the module's
+ * state_dict ("enc.init.0.*", "enc.res.N.*", "enc.final.{0,2}.*", "enc.attn.N.{norm,qkv,proj_out}.*", "head.*").  The residual stream and every
+ * GroupNorm are f32; `dtype` rounds only GEMM / MFMA operands (csrc/classifier.hip). */
+typedef struct ttk_cls ttk_cls;
+typedef struct {
+	int classes;                              /* 2; 1..16 */
+	int spec_dim;                             /* 1 */
+	int embedding_dim;                        /* 512; a multiple of 128 */
+	int depth;                                /* 5; 1..6 */
+	int downsample_factor;                    /* 4 */
+	int resnet_blocks;                        /* 2 */
+	int attn_blocks;                          /* 4 */
+	int num_attn_heads;                       /* 4; embedding_dim / num_attn_heads is 64 or 128 */
+	int base_channels;                        /* 32 */
+	int kernel_size;                          /* 5 */
+	int dtype;                                /* TTK_F32 | TTK_BF16 */
+} ttk_cls_config;
+int ttk_cls_create(ttk_cls** out, const ttk_cls_config* cfg, const ttk_weight_view* weights, int n_weights);
+int ttk_cls_destroy(ttk_cls* h);
+/* audio f32 [B, T] (one channel, 24 kHz) -> emb_out f32 [B, embedding_dim] and logits_out f32 [B, classes] (either may be null).  A clip whose last
+ * stage has more than 3584 positions at head width 128 is refused (the row-wave attention's limit). */
+int ttk_cls_forward(ttk_cls* h, const float* audio, int B, int T, float* emb_out, float* logits_out, void* stream);
+/* The same, and copies of the f32 channels-last rows along the way: taps[0] the stem [B, T, 32], taps[1 + l] stage l after its Downsample
+ * [B, ceil(L_l / 4), 64 * 2^l], taps[depth + 1] enc.final [B, L_depth, embedding_dim]; n_taps = depth + 2, a null entry is skipped. */
+int ttk_cls_forward_taps(ttk_cls* h, const float* audio, int B, int T, float* emb_out, float* logits_out, float* const* taps, int n_taps, void* stream);
+/* The fused ResBlock convolution of the 32- and 64-channel stages on its own:
+ *   out[b, t, n] = bias[n] + sum_{j < 5} sum_k w[n, k, j] * a[b, t + j - 2, k] (+ residual[b, t, n]),   a = silu(groupnorm(x)) or, with stats null, x;
+ * rows outside [0, L) of the SAME batch element are zero.  x, residual, out f32 [B, L, C] (out may be residual, not x), C = 32 | 64; stats f32
+ * [B, groups, 2] = (mean, rstd) per group as ttk_cls_gn_stats writes them; gamma, beta f32 [C]; w f32 [C, C, 5] (Conv1d's layout); bias f32 [C].
+ * dtype TTK_F32 | TTK_BF16: a and w are rounded to it once, products accumulate in f32, taps ascending, then k ascending in steps of 32. */
+int ttk_cls_conv5_rows(int dtype, const float* x, int B, int L, int C, const float* stats, int groups, const float* gamma, const float* beta, const float* w,
+					   const float* bias, const float* residual, float* out, void* stream);
+/* GroupNorm statistics split over row chunks: x f32 [B, L, C] -> stats_out f32 [B, groups, 2] = (mean, 1 / sqrt(biased variance + 1e-5)).  One
+ * workgroup per (batch element, chunk of ttk_cls_stats_rows(C) rows) writes a two-pass (count, mean, M2) per group to `part` (scratch of at least
+ * B * ceil(L / ttk_cls_stats_rows(C)) * groups * 3 floats); a second launch merges the chunks in ascending order (Chan et al.).  No atomics: the
+ * same bits on every run.  C and groups are powers of two. */
+int ttk_cls_stats_rows(int C);
+int ttk_cls_gn_stats(const float* x, int B, int L, int C, int groups, float* part, int64_t part_floats, float* stats_out, void* stream);
+
 /* ------------------------------------------------------------------ CLVP candidate scoring
  * models/clvp.py:21-136 (x-transformers branch): weights = CLVP.state_dict() with each attention's to_q / to_k / to_v stacked into
  * "<attn>.__qkv.weight" [3 * dim, dim] and "__rotary_inv_freq" [16] (RotaryEmbedding(32).inv_freq), as tortoise_tts_amd/clvp.py packs. */

@@ -1,11 +1,11 @@
 """tortoise_tts_amd: MI355X-native (gfx950) inference hot path of e-c-k-e-r/tortoise-tts -- the UnifiedVoice KV-cached
 mel-token decode and the DiffusionTTS DDIM mel decoder -- as hand-written HIP kernels behind a C ABI (include/ttk.h),
 exposed under the reference's own method names.  See DESIGN.md and INTEGRATION.md."""
-from .weights import ARConfig, CLVPConfig, DiffusionConfig, DVAEConfig, HiFiGANConfig, UnivNetConfig, VocoderConfig  # noqa: F401
+from .weights import ARConfig, ClassifierConfig, CLVPConfig, DiffusionConfig, DVAEConfig, HiFiGANConfig, UnivNetConfig, VocoderConfig  # noqa: F401
 
 __all__ = ["ARConfig", "DiffusionConfig", "UnifiedVoice", "DiffusionTTS", "get_diffuser", "denormalize_tacotron_mel",
-		   "load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_random_latent_generator", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder", "BigVGAN", "UnivNet", "HiFiGAN", "DiscreteVAE", "RandomLatentConverter", "CLVP",
-		   "VocoderConfig", "UnivNetConfig", "HiFiGANConfig", "DVAEConfig", "CLVPConfig", "ConditioningEncoder", "ContextualEmbedder", "TorchMelSpectrogram", "TacotronSTFT", "VoiceBpeTokenizer", "TTS"]
+		   "load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_random_latent_generator", "load_classifier", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder", "BigVGAN", "UnivNet", "HiFiGAN", "DiscreteVAE", "RandomLatentConverter", "AudioMiniEncoderWithClassifierHead", "CLVP",
+		   "VocoderConfig", "UnivNetConfig", "HiFiGANConfig", "DVAEConfig", "ClassifierConfig", "CLVPConfig", "ConditioningEncoder", "ContextualEmbedder", "TorchMelSpectrogram", "TacotronSTFT", "VoiceBpeTokenizer", "TTS"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need the built library (CPU-side tools, oracle, weights)
@@ -45,10 +45,13 @@ def __getattr__(name):   # lazy: importing the package must not need the built l
 	if name == "RandomLatentConverter":
 		from .random_latent import RandomLatentConverter
 		return RandomLatentConverter
+	if name == "AudioMiniEncoderWithClassifierHead":
+		from .classifier import AudioMiniEncoderWithClassifierHead
+		return AudioMiniEncoderWithClassifierHead
 	if name == "mel":
 		import importlib
 		return importlib.import_module(".mel", __name__)
-	if name in ("load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_dvae_state", "load_random_latent_generator", "load_rlg_state", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder"):
+	if name in ("load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_dvae_state", "load_random_latent_generator", "load_rlg_state", "load_classifier", "load_classifier_state", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder"):
 		from . import checkpoint
 		return getattr(checkpoint, name)
 	raise AttributeError(name)

@@ -165,6 +165,13 @@ SYMBOLS = {
 	"ttk_rlg_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_rlg_destroy": (_I, [_P]),
 	"ttk_rlg_forward": (_I, [_P, _P, _I, _P, _P]),
+	"ttk_cls_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
+	"ttk_cls_destroy": (_I, [_P]),
+	"ttk_cls_forward": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+	"ttk_cls_forward_taps": (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(_P), _I, _P]),
+	"ttk_cls_conv5_rows": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+	"ttk_cls_stats_rows": (_I, [_I]),
+	"ttk_cls_gn_stats": (_I, [_P, _I, _I, _I, _I, _P, _L, _P, _P]),
 	"ttk_clvp_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_clvp_destroy": (_I, [_P]),
 	"ttk_clvp_score": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P]),

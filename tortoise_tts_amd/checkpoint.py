@@ -354,6 +354,21 @@ def load_random_latent_generator(path, *, device="cuda", state_dict_key: Optiona
 	return RandomLatentConverter(sd, channels, device=device)
 
 
+def load_classifier_state(path, *, cfg=None, state_dict_key: Optional[str] = None):
+	"""`classifier.pth` -> (the tensors the handle reads, config): a plain state_dict of `AudioMiniEncoderWithClassifierHead`, shape-checked."""
+	from .weights import CLASSIFIER_FULL, classifier_shapes
+	cfg = cfg or CLASSIFIER_FULL
+	sd = unwrap_state_dict(read_checkpoint(path), state_dict_key)
+	return select_hot_path(sd, classifier_shapes(cfg), "classifier"), cfg
+
+
+def load_classifier(path, *, cfg=None, dtype="f32", device="cuda", state_dict_key: Optional[str] = None):
+	"""Upstream's `classify_audio_clip` loads `classifier.pth` into the configuration weights.CLASSIFIER_FULL; so does this."""
+	from .classifier import AudioMiniEncoderWithClassifierHead
+	sd, cfg = load_classifier_state(path, cfg=cfg, state_dict_key=state_dict_key)
+	return AudioMiniEncoderWithClassifierHead(sd, cfg, dtype=dtype, device=device)
+
+
 def load_clvp(path, *, cfg=None, dtype="bf16", device="cuda", state_dict_key: Optional[str] = None):
 	"""`load_model("clvp")` (models/__init__.py:111-113): `clvp2.pth` is a plain state_dict of the x-transformers CLVP."""
 	from .clvp import CLVP

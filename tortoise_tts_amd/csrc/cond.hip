@@ -6,9 +6,10 @@
 // One-off per voice (a few hundred mel frames), so this file reuses the dense GEMM and, for head width 64, the MFMA attention of
 // the hot path, and adds plain kernels for what those do not cover: the strided stem (im2col), GroupNorm for any channels-per-group,
 // attention for head width 128 (one wave per query row), and the pooling.  Layout: channels-last [b*T rows][C], f32 residual stream.
-#include <float.h>
+// The AttentionBlock (its GroupNorm, the row-wave attention, the block loop) lives in ttk_attn_block.h, shared with classifier.hip.
 #include <stdlib.h>
 
+#include "ttk_attn_block.h"
 #include "ttk_common.h"
 #include "ttk_host.h"
 
@@ -35,83 +36,6 @@ __global__ __launch_bounds__(256) void k_cond_im2col(const float* __restrict__ s
 	out[i] = cvt<T>(v);
 }
 
-__device__ __forceinline__ float block_sum256(float v, float* red) {
-	v = wave_sum(v);
-	__syncthreads();
-	if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// GroupNorm of one (batch element, group) per workgroup: two-pass mean / biased variance in f32 (F.group_norm, eps 1e-5), any C / groups
-template <typename OT>
-__global__ __launch_bounds__(256) void k_cond_gn(const float* __restrict__ x, int T, int C, int groups, const float* __restrict__ gamma,
-												 const float* __restrict__ beta, OT* __restrict__ out) {
-	__shared__ float red[4];
-	const int g = blockIdx.x, cpg = C / groups, n = T * cpg;
-	const int64_t off = (int64_t)blockIdx.y * T * C + g * cpg;
-	float s = 0.f;
-	for (int e = threadIdx.x; e < n; e += 256) { const int t = e / cpg, c = e - t * cpg; s += x[off + (int64_t)t * C + c]; }
-	const float mean = block_sum256(s, red) / (float)n;
-	float q = 0.f;
-	for (int e = threadIdx.x; e < n; e += 256) { const int t = e / cpg, c = e - t * cpg; const float d = x[off + (int64_t)t * C + c] - mean; q += d * d; }
-	const float rstd = rsqrtf(block_sum256(q, red) / (float)n + 1e-5f);
-	for (int e = threadIdx.x; e < n; e += 256) {
-		const int t = e / cpg, c = e - t * cpg;
-		const int64_t i = off + (int64_t)t * C + c;
-		out[i] = cvt<OT>((x[i] - mean) * rstd * gamma[g * cpg + c] + beta[g * cpg + c]);
-	}
-}
-
-// Attention for head widths the MFMA kernel does not cover.  One wave per query row: lanes split the keys for q.k (+ bias) and the
-// softmax statistics, scores live in the wave's LDS strip, then lanes split the head dims for P.V.  f32 throughout.
-template <typename T, int HD>
-__global__ __launch_bounds__(256) void k_attn_rowwave(AttnParams p) {
-	typedef typename Frag<T>::type FragT;
-	extern __shared__ float smem[];
-	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const int q = blockIdx.x * 4 + wave, h = blockIdx.y, b = blockIdx.z;
-	if (q >= p.T) return;                               // no workgroup barrier below: a wave may leave alone
-	float* sc = smem + (int64_t)wave * p.T;
-	float* qs = smem + (int64_t)4 * p.T + wave * HD;
-	const T* base = (const T*)p.qkv + (int64_t)b * p.T * p.ld + h * p.head_stride;
-	for (int d = lane; d < HD; d += 64) qs[d] = (float)base[(int64_t)q * p.ld + p.q_off + d] * p.scale;
-	__builtin_amdgcn_wave_barrier();
-	float m = -FLT_MAX;
-	for (int j = lane; j < p.T; j += 64) {
-		const T* kp = base + (int64_t)j * p.ld + p.k_off;
-		float s = 0.f;
-#pragma unroll 4
-		for (int d = 0; d < HD; d += 8) {
-			const FragT kf = *(const FragT*)(kp + d);
-#pragma unroll
-			for (int e = 0; e < 8; ++e) s += qs[d + e] * (float)kf[e];
-		}
-		if (p.bias) { int rel = j - q; rel = rel < -64 ? -64 : (rel > 64 ? 64 : rel); s += p.bias[h * 129 + rel + 64]; }
-		sc[j] = s;
-		m = fmaxf(m, s);
-	}
-	m = wave_max(m);
-	float l = 0.f;
-	for (int j = lane; j < p.T; j += 64) { const float e = __expf(sc[j] - m); sc[j] = e; l += e; }
-	l = wave_sum(l);
-	__builtin_amdgcn_wave_barrier();
-	constexpr int DPL = HD / 64;
-	float o[DPL];
-#pragma unroll
-	for (int e = 0; e < DPL; ++e) o[e] = 0.f;
-	const T* vp = base + p.v_off + lane * DPL;
-	for (int j = 0; j < p.T; ++j) {
-		const float pj = sc[j];
-#pragma unroll
-		for (int e = 0; e < DPL; ++e) o[e] += pj * (float)vp[(int64_t)j * p.ld + e];
-	}
-	T* op = (T*)p.out + ((int64_t)b * p.T + q) * p.ldo + h * HD + lane * DPL;
-	const float inv = 1.f / l;
-#pragma unroll
-	for (int e = 0; e < DPL; ++e) op[e] = cvt<T>(o[e] * inv);
-}
-
 // out[b][c] = mean over the T rows (mode 1) or row 0 (mode 0) of x f32 [b][T][C]
 __global__ __launch_bounds__(256) void k_cond_pool(const float* __restrict__ x, int T, int C, int mode, float* __restrict__ out) {
 	const int c = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
@@ -124,8 +48,6 @@ __global__ __launch_bounds__(256) void k_cond_pool(const float* __restrict__ x, 
 	}
 	out[(int64_t)b * C + c] = s;
 }
-
-struct Block { float *gn_g = nullptr, *gn_b = nullptr, *relbias = nullptr; Mat qkv, proj; };
 
 }  // namespace
 
@@ -141,23 +63,6 @@ struct ttk_cond {
 
 namespace {
 
-int gn_groups(int channels) {    // arch_utils.py:27-44
-	int g = 32;
-	if (channels <= 16) g = 8;
-	else if (channels <= 64) g = 16;
-	while (channels % g != 0) g /= 2;
-	return g;
-}
-
-void gemm_plain(int dt, const void* A, int64_t lda, const Mat& w, int M, const float* residual, void* C, int out_f32, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = 1;
-	g.seg[0] = {A, lda, 0, 0};
-	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.bias = w.bias;
-	g.residual = residual; g.ldr = w.N; g.C = C; g.ldc = w.N; g.out_f32 = out_f32;
-	launch_gemm(dt, g, s);
-}
-
 template <typename T>
 int encode_t(ttk_cond* h, const float* mel, int b, int Tf, float* out, hipStream_t s) {
 	const ttk_cond_config& c = h->cfg;
@@ -165,7 +70,7 @@ int encode_t(ttk_cond* h, const float* mel, int b, int Tf, float* out, hipStream
 	const int T1 = c.stem == TTK_COND_STEM_DOWN4 ? (Tf - 1) / 2 + 1 : Tf;
 	const int T2 = c.stem == TTK_COND_STEM_DOWN4 ? (T1 - 1) / 2 + 1 : Tf;
 	const int64_t rows = (int64_t)b * T2;
-	TTK_REQUIRE(h->hd == 64 || T2 <= 3584, TTK_E_ARG, "ttk_cond_encode: %d positions exceed the row-wave attention's LDS strip (3584)", T2);
+	TTK_REQUIRE(h->hd == 64 || T2 <= kRowWaveMaxT, TTK_E_ARG, "ttk_cond_encode: %d positions exceed the row-wave attention's LDS strip (%d)", T2, kRowWaveMaxT);
 	// workspace: x f32 [rows][C] | a T [rows][C] | qkv T [rows][3C] | ao T [rows][C]; the stem's operands alias a/qkv/ao (free until block 0)
 	const size_t im0 = (size_t)b * T1 * h->stem0.Kpad * h->es, mid = c.stem == TTK_COND_STEM_DOWN4 ? (size_t)b * T1 * (C / 2) * 4 : 0;
 	const size_t im1 = c.stem == TTK_COND_STEM_DOWN4 ? (size_t)rows * h->stem1.Kpad * h->es : 0;
@@ -197,17 +102,7 @@ int encode_t(ttk_cond* h, const float* mel, int b, int Tf, float* out, hipStream
 	T* a = (T*)sp;
 	T* qkv = a + rows * C;
 	T* ao = qkv + rows * 3 * C;
-	for (const Block& B : h->blocks) {
-		hipLaunchKernelGGL((k_cond_gn<T>), dim3(h->groups, b), dim3(256), 0, s, x, T2, C, h->groups, B.gn_g, B.gn_b, a);
-		gemm_plain(dt, a, C, B.qkv, (int)rows, nullptr, qkv, 0, s);
-		AttnParams ap = {};
-		ap.qkv = qkv; ap.ld = 3 * C; ap.q_off = 0; ap.k_off = h->hd; ap.v_off = 2 * h->hd; ap.head_stride = 3 * h->hd;   // head-major [H][3][hd], arch_utils.py:79
-		ap.out = ao; ap.ldo = C; ap.nb = b; ap.T = T2; ap.H = c.num_heads; ap.causal = 0; ap.bias = B.relbias;
-		ap.scale = 1.f / sqrtf((float)h->hd);                                      // (q * hd^-1/4) . (k * hd^-1/4)
-		if (h->hd == 64) launch_attn_fwd(dt, ap, s);
-		else hipLaunchKernelGGL((k_attn_rowwave<T, 128>), dim3((T2 + 3) / 4, c.num_heads, b), dim3(256), (size_t)(4 * T2 + 4 * 128) * 4, s, ap);
-		gemm_plain(dt, ao, C, B.proj, (int)rows, x, x, 1, s);
-	}
+	attn_blocks<T>(dt, h->blocks, x, b, T2, C, h->groups, c.num_heads, a, qkv, ao, s);
 	hipLaunchKernelGGL(k_cond_pool, dim3((C + 255) / 256, b), dim3(256), 0, s, x, T2, C, c.pool, out);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
@@ -239,16 +134,7 @@ int ttk_cond_create(ttk_cond** out, const ttk_cond_config* cfg, const ttk_weight
 	} else {
 		TTK_TRY(upload_mat(h->arena, wm, h->dt, "stem.0.weight", "stem.0.bias", PK_NK, C, cfg->in_channels, false, &h->stem0));
 	}
-	h->blocks.resize(cfg->num_blocks);
-	for (int i = 0; i < cfg->num_blocks; ++i) {
-		Block& B = h->blocks[i];
-		const std::string p = "blocks." + std::to_string(i) + ".";
-		TTK_TRY(upload_f32(h->arena, wm, p + "norm.weight", C, &B.gn_g));
-		TTK_TRY(upload_f32(h->arena, wm, p + "norm.bias", C, &B.gn_b));
-		TTK_TRY(upload_mat(h->arena, wm, h->dt, p + "qkv.weight", p + "qkv.bias", PK_NK, 3 * C, C, false, &B.qkv));
-		TTK_TRY(upload_mat(h->arena, wm, h->dt, p + "proj_out.weight", p + "proj_out.bias", PK_NK, C, C, false, &B.proj));
-		if (cfg->relpos) TTK_TRY(upload_f32(h->arena, wm, p + "__relbias", (int64_t)cfg->num_heads * 129, &B.relbias));
-	}
+	TTK_TRY(upload_attn_blocks(h->arena, wm, h->dt, "blocks.", cfg->num_blocks, C, cfg->num_heads, cfg->relpos != 0, &h->blocks));
 	hipError_t e = hipDeviceSynchronize();
 	if (e != hipSuccess) { set_error("ttk_cond_create: %s", hipGetErrorString(e)); return TTK_E_HIP; }
 	*out = h.release();

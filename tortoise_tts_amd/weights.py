@@ -188,6 +188,31 @@ class CLVPConfig:
 		return self.dim * self.ff_mult
 
 
+@dataclasses.dataclass(frozen=True)
+class ClassifierConfig:
+	"""`AudioMiniEncoderWithClassifierHead(classes, **kwargs)` (models/classifier.py:79-149) as upstream's `classify_audio_clip` builds it for
+	`classifier.pth`.  tortoise_tts_amd/classifier.py refuses what the kernels do not cover, with the reason."""
+	classes: int = 2
+	spec_dim: int = 1
+	embedding_dim: int = 512
+	depth: int = 5
+	downsample_factor: int = 4
+	resnet_blocks: int = 2
+	attn_blocks: int = 4
+	num_attn_heads: int = 4
+	base_channels: int = 32
+	dropout: float = 0
+	kernel_size: int = 5
+	distribute_zero_label: bool = False
+
+	def stage_lengths(self, T: int):
+		"""[T, ceil(T / 4), ...]: the rows in front of every stage and behind the last (Conv1d k = 5, stride 4, padding 2)"""
+		out = [int(T)]
+		for _ in range(self.depth):
+			out.append((out[-1] + self.downsample_factor - 1) // self.downsample_factor)
+		return out
+
+
 AR_SMALL = ARConfig(layers=2, model_dim=128, heads=2)
 CLVP_SMALL = CLVPConfig(dim=128, depth=2, heads=2)
 CLVP_FULL = CLVPConfig()
@@ -203,6 +228,9 @@ HIFIGAN_SMALL = HiFiGANConfig(in_channels=128, cond_channels=128, upsample_initi
 DVAE_FULL = DVAEConfig()
 # 200 codes: no multiple of the quantizer's 16-code tile or 64-code workgroup range, and within AR_SMALL's mel-code count
 DVAE_SMALL = DVAEConfig(channels=80, hidden_dim=32, codebook_dim=32, num_tokens=200, num_resnet_blocks=1)
+CLASSIFIER_FULL = ClassifierConfig()
+# stages of 32, 64 and 128 channels: both widths of the fused k = 5 convolution and one GEMM stage; one head of width 128
+CLASSIFIER_SMALL = ClassifierConfig(embedding_dim=128, depth=3, resnet_blocks=1, attn_blocks=2, num_attn_heads=1)
 DIFF_SMALL = DiffusionConfig(model_channels=128, num_layers=2, in_latent_channels=128, num_heads=2)
 DIFF_FULL = DiffusionConfig()
 
@@ -422,6 +450,35 @@ def dvae_codebook(mean: torch.Tensor, std: torch.Tensor, num_tokens: int, seed: 
 	g.manual_seed((seed * 1000003 + zlib.crc32(b"codebook.embed")) % (2 ** 63 - 1))
 	mean, std = torch.as_tensor(mean, dtype=torch.float32), torch.as_tensor(std, dtype=torch.float32)
 	return mean[:, None] + std[:, None] * torch.randn((mean.shape[0], num_tokens), generator=g, dtype=torch.float32)
+
+
+def classifier_shapes(c: ClassifierConfig) -> Dict[str, Tuple[int, ...]]:
+	"""`AudioMiniEncoderWithClassifierHead.state_dict()` (models/classifier.py:92-112, 127-128): `enc.res` numbers ResBlocks and Downsamples in one
+	sequence; the AttentionBlocks have no relative position embeddings."""
+	k, ch = c.kernel_size, c.base_channels
+	s: Dict[str, Tuple[int, ...]] = {"enc.init.0.weight": (ch, c.spec_dim, 3), "enc.init.0.bias": (ch,)}
+	n = 0
+	for _ in range(c.depth):
+		for _ in range(c.resnet_blocks):
+			p = f"enc.res.{n}."
+			s[p + "in_layers.0.weight"] = (ch,); s[p + "in_layers.0.bias"] = (ch,)
+			s[p + "in_layers.2.weight"] = (ch, ch, k); s[p + "in_layers.2.bias"] = (ch,)
+			s[p + "out_layers.0.weight"] = (ch,); s[p + "out_layers.0.bias"] = (ch,)
+			s[p + "out_layers.3.weight"] = (ch, ch, k); s[p + "out_layers.3.bias"] = (ch,)
+			n += 1
+		s[f"enc.res.{n}.op.weight"] = (2 * ch, ch, 5); s[f"enc.res.{n}.op.bias"] = (2 * ch,)
+		n += 1
+		ch *= 2
+	E = c.embedding_dim
+	s["enc.final.0.weight"] = (ch,); s["enc.final.0.bias"] = (ch,)
+	s["enc.final.2.weight"] = (E, ch, 1); s["enc.final.2.bias"] = (E,)
+	for i in range(c.attn_blocks):
+		p = f"enc.attn.{i}."
+		s[p + "norm.weight"] = (E,); s[p + "norm.bias"] = (E,)
+		s[p + "qkv.weight"] = (3 * E, E, 1); s[p + "qkv.bias"] = (3 * E,)
+		s[p + "proj_out.weight"] = (E, E, 1); s[p + "proj_out.bias"] = (E,)
+	s["head.weight"] = (c.classes, E); s["head.bias"] = (c.classes,)
+	return s
 
 
 RLG_LAYERS = 6          # RandomLatentConverter: five EqualLinear layers and one nn.Linear (models/random_latent_generator.py:45-46)
