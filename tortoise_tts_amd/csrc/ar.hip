@@ -5,7 +5,7 @@
 // Reference: /root/reference/tortoise_tts/models/unified_voice.py:98-254 (GPT2InferenceModel), :334-668 (UnifiedVoice),
 //            HF:models/gpt2/modeling_gpt2.py:144-310,514-634 (GPT-2 block math).
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 
 using namespace ttk;
 
@@ -147,11 +147,7 @@ static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipSt
 	for (int l = 0; l < h->cfg.layers; ++l) {
 		const ARLayer& L = h->L[l];
 		launch_layernorm(dt, x, d, rows, d, L.ln1_g, L.ln1_b, nullptr, nullptr, h->ws_a.p, d, 0, s);
-		GemmParams g = {};
-		g.nseg = 1; g.seg[0] = {h->ws_a.p, d, 0, 0};
-		g.W = L.attn.w; g.ldw = L.attn.Kpad; g.M = rows; g.N = 3 * d; g.K = d; g.bias = L.attn.bias;
-		g.C = h->ws_qkv.p; g.ldc = 3 * d;
-		launch_gemm(dt, g, s);
+		launch_gemm(dt, dense_gemm(h->ws_a.p, d, L.attn, rows, h->ws_qkv.p, 0), s);
 		if (write_kv) {
 			const size_t row0 = (size_t)kv_row0 * H * h->cfg.max_ctx * 64;      // first candidate slice written
 			char* kc = (char*)h->kc + ((size_t)l * h->kv_layer_stride + row0) * h->es;
@@ -162,22 +158,12 @@ static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipSt
 		a.qkv = h->ws_qkv.p; a.ld = 3 * d; a.q_off = 0; a.k_off = d; a.v_off = 2 * d; a.head_stride = 64;
 		a.out = h->ws_ao.p; a.ldo = d; a.nb = B; a.T = S; a.H = H; a.causal = 1; a.bias = nullptr; a.scale = 0.125f;
 		launch_attn_fwd(dt, a, s);
-		g = {};
-		g.nseg = 1; g.seg[0] = {h->ws_ao.p, d, 0, 0};
-		g.W = L.proj.w; g.ldw = L.proj.Kpad; g.M = rows; g.N = d; g.K = d; g.bias = L.proj.bias;
-		g.residual = x; g.ldr = d; g.C = x; g.ldc = d; g.out_f32 = 1;
-		launch_gemm(dt, g, s);
+		gemm_plain(dt, h->ws_ao.p, d, L.proj, rows, x, x, 1, s);
 		launch_layernorm(dt, x, d, rows, d, L.ln2_g, L.ln2_b, nullptr, nullptr, h->ws_a.p, d, 0, s);
-		g = {};
-		g.nseg = 1; g.seg[0] = {h->ws_a.p, d, 0, 0};
-		g.W = L.fc.w; g.ldw = L.fc.Kpad; g.M = rows; g.N = 4 * d; g.K = d; g.bias = L.fc.bias; g.act = ACT_GELU_NEW;
-		g.C = h->ws_h.p; g.ldc = 4 * d;
-		launch_gemm(dt, g, s);
-		g = {};
-		g.nseg = 1; g.seg[0] = {h->ws_h.p, 4 * d, 0, 0};
-		g.W = L.proj2.w; g.ldw = L.proj2.Kpad; g.M = rows; g.N = d; g.K = 4 * d; g.bias = L.proj2.bias;
-		g.residual = x; g.ldr = d; g.C = x; g.ldc = d; g.out_f32 = 1;
-		launch_gemm(dt, g, s);
+		GemmParams fc = dense_gemm(h->ws_a.p, d, L.fc, rows, h->ws_h.p, 0);
+		fc.act = ACT_GELU_NEW;
+		launch_gemm(dt, fc, s);
+		gemm_plain(dt, h->ws_h.p, 4 * d, L.proj2, rows, x, x, 1, s);
 	}
 	return TTK_OK;
 }
@@ -418,7 +404,7 @@ static int prefill_impl(ttk_ar* h, const float* cond_latent, int Bc, const int64
 	TTK_TRY(h->ws_x.reserve((size_t)Bp * S * d * sizeof(float)));
 	float* x = (float*)h->ws_x.p;
 	const int64_t total = (int64_t)Bp * S * (d / 4);
-	hipLaunchKernelGGL(k_build_prefill_emb, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cond_latent, Bc, text, Tt, Bp, d,
+	hipLaunchKernelGGL(k_build_prefill_emb, dim3(grid_for(total)), dim3(256), 0, s, cond_latent, Bc, text, Tt, Bp, d,
 					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, x, prompt, prompt_rows, n_in);
 	TTK_TRY(dense_forward(h, x, Bp, S, true, s));
 	launch_copy_rows(x + (size_t)(S - 1) * d, shared ? 0 : (int64_t)S * d, h->x, d, B, d, s);      // source stride 0: one row to all candidates
@@ -470,7 +456,7 @@ int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* te
 		// *d_pos, as for one line) and only the attention needs to know where a candidate's rows begin
 		const int Tt = text_len[g], S = Tt + 4, r0 = g * rows_per_line, start = Smax - S;
 		const int64_t total = (int64_t)S * (d / 4);
-		hipLaunchKernelGGL(k_build_prefill_emb, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cond_latents + (size_t)g * d, 1, text + toff, Tt, 1, d,
+		hipLaunchKernelGGL(k_build_prefill_emb, dim3(grid_for(total)), dim3(256), 0, s, cond_latents + (size_t)g * d, 1, text + toff, Tt, 1, d,
 						   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, x);
 		TTK_TRY(dense_forward(h, x, 1, S, true, s, r0, start));
 		launch_copy_rows(x + (size_t)(S - 1) * d, 0, h->x + (size_t)r0 * d, d, rows_per_line, d, s);      // the line's last prefix row to all its candidates
@@ -595,7 +581,7 @@ int ttk_ar_latents(ttk_ar* h, const float* cond, const int64_t* text, int Tt, co
 	TTK_TRY(h->ws_x.reserve((size_t)B * S * d * sizeof(float)));
 	float* x = (float*)h->ws_x.p;
 	const int64_t total = (int64_t)B * S * (d / 4);
-	hipLaunchKernelGGL(k_build_latent_emb, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cond, text, Tt, codes, M, B, d,
+	hipLaunchKernelGGL(k_build_latent_emb, dim3(grid_for(total)), dim3(256), 0, s, cond, text, Tt, codes, M, B, d,
 					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, c.stop_mel_token, x);
 	TTK_TRY(dense_forward(h, x, B, S, false, s));
 	// enc = final_norm(ln_f(h)); mel rows start at 1 + (Tt + 2); keep the first M of the M + 2   (unified_voice.py:518-522,595)
@@ -632,9 +618,9 @@ int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, cons
 	int64_t *tg_t = (int64_t*)(ws + o_tt), *tg_m = (int64_t*)(ws + o_tm);
 	float* x = (float*)h->ws_x.p;
 	const int64_t total = (int64_t)B * S * (d / 4);
-	hipLaunchKernelGGL(k_build_latent_emb, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cond, text, Tt, codes, M, B, d,
+	hipLaunchKernelGGL(k_build_latent_emb, dim3(grid_for(total)), dim3(256), 0, s, cond, text, Tt, codes, M, B, d,
 					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, c.stop_mel_token, x);
-	hipLaunchKernelGGL(k_build_score_targets, dim3((unsigned)((rows_t + rows_m + 255) / 256)), dim3(256), 0, s, text, Tt, c.stop_text_token, codes, M, c.stop_mel_token, B, tg_t, tg_m);
+	hipLaunchKernelGGL(k_build_score_targets, dim3(grid_for(rows_t + rows_m)), dim3(256), 0, s, text, Tt, c.stop_text_token, codes, M, c.stop_mel_token, B, tg_t, tg_m);
 	TTK_TRY(dense_forward(h, x, B, S, false, s));
 	// enc = final_norm(ln_f(h))[:, 1:]; the text head reads its first Tt + 2 rows, the mel head its last M + 2   (unified_voice.py:518-530).  ws_a holds
 	// B * S rows (dense_forward): the B * (S - 1) normalised rows of both heads fit, T-typed, text rows first
@@ -648,10 +634,8 @@ int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, cons
 	const Head heads[2] = {{&h->text_head, a_t, (int)rows_t, Ct, ldt, Rt, lg_t, tg_t, nll_t, text_logits_out}, {&h->head, a_m, (int)rows_m, Cm, ldm, Rm, lg_m, tg_m, nll_m, mel_logits_out}};
 	for (int i = 0; i < 2; ++i) {
 		const Head& q = heads[i];
-		GemmParams g = {};
-		g.nseg = 1; g.seg[0] = {q.a, d, 0, 0};
-		g.W = q.W->w; g.ldw = q.W->Kpad; g.M = q.rows; g.N = q.C; g.K = d; g.bias = q.W->bias;
-		g.C = q.lg; g.ldc = q.ld; g.out_f32 = 1;
+		GemmParams g = dense_gemm(q.a, d, *q.W, q.rows, q.lg, 1);
+		g.ldc = q.ld;
 		launch_gemm(h->dt, g, s);
 		launch_xent_rows(q.lg, q.ld, q.rows, q.C, q.tg, q.nll, loss_out ? loss_out + i : nullptr, q.out_t, q.T, s);
 	}

@@ -12,8 +12,6 @@
 //   4 waves x 32 queries per workgroup, 64-key K/V tiles staged through LDS, f32 softmax/accumulators.
 //
 // k_attn_decode: single-query KV-cached attention for the AR decode step (HBM-bound: streams the K/V cache once).
-#include <stdlib.h>
-
 #include <hip/hip_ext.h>
 
 #include <mutex>
@@ -408,69 +406,53 @@ __global__ __launch_bounds__(64 * NWV, NWV == 4 ? 2 : 1) void k_attn_fwd(AttnPar
 #endif
 }
 
-template <typename T>
-static void launch_attn_fwd_t(const AttnParams& p, hipStream_t s, int form) {
-	auto launch_w8 = [&] {
-		dim3 grid((p.T + 127) / 128, p.H, p.nb);
-		if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1, 8>), grid, dim3(512), 0, s, p);
-		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1, 8>), grid, dim3(512), 0, s, p);
-	};
-	auto launch_bal = [&](int G) {
-		dim3 grid(G, p.H, p.nb);
-		if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1, 9>), grid, dim3(576), 0, s, p);
-		else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1, 9>), grid, dim3(576), 0, s, p);
-	};
-	auto launch_blocks = [&](bool big) {
-		if (big) {
-			dim3 grid((p.T + 127) / 128, p.H, p.nb);
-			if (p.causal) hipLaunchKernelGGL((k_attn_fwd<T, true, false, 2>), grid, dim3(256), 0, s, p);
-			else if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 2>), grid, dim3(256), 0, s, p);
-			else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 2>), grid, dim3(256), 0, s, p);
-		} else {
-			dim3 grid((p.T + 63) / 64, p.H, p.nb);
-			if (p.causal) hipLaunchKernelGGL((k_attn_fwd<T, true, false, 1>), grid, dim3(256), 0, s, p);
-			else if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, 1>), grid, dim3(256), 0, s, p);
-			else hipLaunchKernelGGL((k_attn_fwd<T, false, false, 1>), grid, dim3(256), 0, s, p);
-		}
-	};
-	// an explicit form (ttk_attn_fwd: kernel-level tests) overrides the knobs below; the caller has asked attn_fwd_form_refusal first
-	if (form == 1 || form == 2) return launch_blocks(form == 2);
-	if (form == 3) return launch_w8();
-	if (form == 4) return launch_bal(256 / (p.nb * p.H));
-	static const int force_qt = [] { const char* e = getenv("TTK_ATTN_QT"); return e ? atoi(e) : 0; }();   // tuning knob
-	const bool big = force_qt ? force_qt == 2 : (int64_t)((p.T + 127) / 128) * p.H * p.nb >= 512;   // enough 128-query blocks for 2 waves per SIMD
-	// 128-query blocks as 8 waves x 16 queries once they cover most of the chip (TTK_ATTN_W8=0: off); non-causal only: a causal block of 8 waves
-	// would idle its upper waves on the diagonal tiles
-	// (measured at T = 1088: 141.3 vs 139.9 ms per DDIM loop -- 288 such blocks on 256 CUs leave 32 CUs with two, the same quantisation that
-	// costs the 64-query form 544 blocks on 768 slots; kept as a knob, off by default)
-	static const int w8 = [] { const char* e = getenv("TTK_ATTN_W8"); return e ? atoi(e) : 0; }();
-	if (w8 && !big && !force_qt && !p.causal && (int64_t)((p.T + 127) / 128) * p.H * p.nb >= 192) return launch_w8();
-	// balanced form: batch x heads x G workgroups == 256 (the CUs), each with 8..9 tiles
-	static const int bal = [] { const char* e = getenv("TTK_ATTN_BAL"); return e ? atoi(e) : 1; }();
-	if (bal && !force_qt && !p.causal && !p.tlen && p.nb * p.H <= 256 && 256 % (p.nb * p.H) == 0) {
-		const int G = 256 / (p.nb * p.H), tiles = (p.T + 15) / 16;
-		if ((tiles + G - 1) / G <= 9 && tiles / G >= 6) return launch_bal(G);
-	}
-	launch_blocks(big);
+// Form 4, balanced: batch x heads x G workgroups == 256 (the CUs), each with at most 9 16-query tiles, one per wave.  Its geometry and what stands against it
+// (null: nothing) -- read by the explicit form's check and by the launcher's own choice alike.
+struct AttnBalanced { int G, tiles; const char* refusal; };
+static AttnBalanced attn_balanced(const AttnParams& p) {
+	const int tiles = (p.T + 15) / 16;
+	if (p.causal || p.tlen) return {0, tiles, "form 4 (balanced) is non-causal and takes no tlen (a workgroup's tile share is computed from T)"};
+	if ((int64_t)p.nb * p.H > 256 || 256 % (p.nb * p.H) != 0) return {0, tiles, "form 4 (balanced) needs 256 % (nb * H) == 0"};
+	const int G = 256 / (p.nb * p.H);
+	if ((tiles + G - 1) / G > 9) return {G, tiles, "form 4 (balanced) has 9 waves: at most 9 16-query tiles per workgroup, ceil(ceil(T / 16) / (256 / (nb * H))) <= 9"};
+	return {G, tiles, nullptr};
 }
-// what an explicit form needs for its result to be right (null: nothing stands against it).  The launcher's own choice (form 0) tests the same conditions
-// itself, plus those that only decide which form is faster.
+// what an explicit form needs for its result to be right (null: nothing stands against it)
 const char* attn_fwd_form_refusal(const AttnParams& p, int form) {
 	if (form < 0 || form > 4) return "form must be 0 (the launcher's choice), 1 (64-query blocks), 2 (128-query blocks), 3 (8 waves x 16 queries) or 4 (balanced)";
 	if (form == 3 && p.causal) return "form 3 (8 waves x 16 queries) has no causal kernel";
-	if (form == 4) {
-		if (p.causal || p.tlen) return "form 4 (balanced) is non-causal and takes no tlen (a workgroup's tile share is computed from T)";
-		if ((int64_t)p.nb * p.H > 256 || 256 % (p.nb * p.H) != 0) return "form 4 (balanced) needs 256 % (nb * H) == 0";
-		const int G = 256 / (p.nb * p.H), tiles = (p.T + 15) / 16;
-		if ((tiles + G - 1) / G > 9) return "form 4 (balanced) has 9 waves: at most 9 16-query tiles per workgroup, ceil(ceil(T / 16) / (256 / (nb * H))) <= 9";
-	}
-	return nullptr;
+	return form == 4 ? attn_balanced(p).refusal : nullptr;
 }
+// Form 0, the launcher's choice: balanced where it is legal and every workgroup gets at least 6 tiles; else 128-query blocks once there are enough of them
+// for 2 waves per SIMD, else 64-query blocks.  Form 3 (128-query blocks as 8 waves x 16 queries; non-causal only: a causal block of 8 waves would idle its upper
+// waves on the diagonal tiles) is never chosen: measured at T = 1088, 141.3 vs 139.9 ms per DDIM loop -- 288 such blocks on 256 CUs leave 32 CUs with two, the same
+// quantisation that costs the 64-query form 544 blocks on 768 slots.
+static int attn_fwd_choice(const AttnParams& p) {
+	const AttnBalanced b = attn_balanced(p);
+	if (!b.refusal && b.tiles / b.G >= 6) return 4;
+	return (int64_t)((p.T + 127) / 128) * p.H * p.nb >= 512 ? 2 : 1;
+}
+// grid (gx, H, nb), NWV waves; the 8- and 9-wave forms have no causal kernel
+template <typename T, int QT, int NWV>
+static void attn_fwd_go(const AttnParams& p, int gx, hipStream_t s) {
+	const dim3 grid(gx, p.H, p.nb), block(64 * NWV);
+	if constexpr (NWV == 4) {
+		if (p.causal) { hipLaunchKernelGGL((k_attn_fwd<T, true, false, QT, NWV>), grid, block, 0, s, p); return; }
+	}
+	if (p.bias) hipLaunchKernelGGL((k_attn_fwd<T, false, true, QT, NWV>), grid, block, 0, s, p);
+	else hipLaunchKernelGGL((k_attn_fwd<T, false, false, QT, NWV>), grid, block, 0, s, p);
+}
+// an explicit form (ttk_attn_fwd: kernel-level tests) has passed attn_fwd_form_refusal at the caller
 void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s, int form) {
 	ProfScope prof(PROF_ATTN_FWD, 4.0 * p.nb * p.H * (double)p.T * p.T * HD * (p.causal ? 0.5 : 1.0), s);
-	if (dt == DT_BF16) launch_attn_fwd_t<bf16>(p, s, form);
-	else if (dt == DT_F16) launch_attn_fwd_t<f16>(p, s, form);
-	else launch_attn_fwd_t<float>(p, s, form);
+	if (form == 0) form = attn_fwd_choice(p);
+	by_dtype(dt, [&](auto t) {
+		using T = decltype(t);
+		if (form == 1) attn_fwd_go<T, 1, 4>(p, (p.T + 63) / 64, s);
+		else if (form == 2) attn_fwd_go<T, 2, 4>(p, (p.T + 127) / 128, s);
+		else if (form == 3) attn_fwd_go<T, 1, 8>(p, (p.T + 127) / 128, s);
+		else attn_fwd_go<T, 1, 9>(p, 256 / (p.nb * p.H), s);
+	});
 }
 
 // ------------------------------------------------------------------------------------------------ decode
@@ -633,20 +615,20 @@ __global__ __launch_bounds__(64 * NW) void k_attn_decode(AttnDecodeParams p) {
 #endif
 }
 
+// ROWS: the batch holds several text lines (row_info); SLOT: the position words come through the position line
+template <typename T, int NW, int UN, bool ROWS, bool SLOT>
+static void attn_decode_go(const AttnDecodeParams& p, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+	hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN, ROWS, SLOT>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p);
+}
 template <typename T, int NW, int UN>
 static void launch_attn_decode_t(const AttnDecodeParams& p, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-	static const bool no_line = [] { const char* e = getenv("TTK_ATTN_POS_LINE"); return e && atoi(e) == 0; }();      // A/B knob: 0 = always through d_pos
-	const bool slot = p.pos_slot_p1 > 0 && !no_line;
-	if (p.row_info) { if (slot) hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN, true, true>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p);
-					  else hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN, true>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p); }
-	else if (slot) hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN, false, true>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p);
-	else hipExtLaunchKernelGGL((k_attn_decode<T, NW, UN>), dim3(p.H, p.B), dim3(64 * NW), 0, s, ea, eb, 0, p);
+	static void (*const go[2][2])(const AttnDecodeParams&, hipStream_t, hipEvent_t, hipEvent_t) = {
+		{attn_decode_go<T, NW, UN, false, false>, attn_decode_go<T, NW, UN, false, true>}, {attn_decode_go<T, NW, UN, true, false>, attn_decode_go<T, NW, UN, true, true>}};
+	go[p.row_info != nullptr][p.pos_slot_p1 > 0](p, s, ea, eb);
 }
-void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s, int force_variant) {
+void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s, int variant) {
 	hipEvent_t ea = nullptr, eb = nullptr;      // kernel start / stop timestamps when profiling (prof_pair)
 	if (g_prof_on) prof_pair(PROF_ATTN_DECODE, 2.0 * p.B * p.H * (double)p.ctx_hint * HD * dtype_size(dt), &ea, &eb);
-	static const int env_variant = [] { const char* e = getenv("TTK_ATTN_DECODE"); return e ? atoi(e) : 0; }();   // tuning knob: 0 = default
-	const int variant = force_variant ? force_variant : env_variant;      // an explicit variant (ttk_attn_decode: kernel-level tests) overrides the knob
 	if (dt == DT_BF16) {
 		// 250-token AR loop, B=16, one box: 4 waves x 4 groups (first version, 128 keys per round trip) 261.9 ms; 8 x 6 257.5 ms;
 		// 16 x 3 256.8 ms
@@ -678,11 +660,8 @@ __global__ void k_kv_scatter(const T* qkv, int B, int S, int H, T* kc, T* vc, in
 	*(FragT*)(vc + dst) = *(const FragT*)(src + 2 * d + c);
 }
 void launch_kv_scatter(int dt, const void* qkv, int B, int S, int H, void* kcache, void* vcache, int max_ctx, hipStream_t s, int t0) {
-	const int64_t total = (int64_t)B * S * (H * HD / 8);
-	const int grid = (int)((total + 255) / 256);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_kv_scatter<bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)qkv, B, S, H, (bf16*)kcache, (bf16*)vcache, max_ctx, t0);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_kv_scatter<f16>), dim3(grid), dim3(256), 0, s, (const f16*)qkv, B, S, H, (f16*)kcache, (f16*)vcache, max_ctx, t0);
-	else hipLaunchKernelGGL((k_kv_scatter<float>), dim3(grid), dim3(256), 0, s, (const float*)qkv, B, S, H, (float*)kcache, (float*)vcache, max_ctx, t0);
+	const dim3 grid(grid_for((int64_t)B * S * (H * HD / 8)));
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_kv_scatter<T>), grid, dim3(256), 0, s, (const T*)qkv, B, S, H, (T*)kcache, (T*)vcache, max_ctx, t0); });
 }
 
 }  // namespace ttk

@@ -40,7 +40,6 @@ constexpr int kMaxGroups = 32;
 // rows of one statistics chunk: 2048 at 32 channels .. 64 at 1024 and above (64 Ki elements per workgroup)
 inline int stats_rows(int C) { return std::min(2048, std::max(64, 65536 / C)); }
 inline int stats_chunks(int L, int C) { const int R = stats_rows(C); return (L + R - 1) / R; }
-unsigned grid_for(int64_t total) { return (unsigned)((total + 255) / 256); }
 
 // audio f32 [B][T] -> rows f32 [B][T][32]: out[t][c] = bias[c] + sum_j w[c][j] * x[t + j - 1], taps ascending, zero outside the clip
 __global__ __launch_bounds__(256) void k_cls_stem(const float* __restrict__ x, int Tn, const float* __restrict__ w, const float* __restrict__ bias,
@@ -260,18 +259,18 @@ int launch_conv5(int dt, const float* x, int B, int L, int C, const float* ms, c
 				 const float* residual, float* out, hipStream_t s) {
 	const int ntiles = (L + kTile - 1) / kTile, gx = std::min(ntiles, kMaxConvGrid), tpw = (ntiles + gx - 1) / gx;
 	const dim3 grid((unsigned)((ntiles + tpw - 1) / tpw), (unsigned)B);
-#define TTK_CLS_CONV5(TT, CC) hipLaunchKernelGGL((k_cls_conv5<TT, CC>), grid, dim3(256), 0, s, x, L, ms, gamma, beta, G, w, bias, residual, out, tpw)
-	if (dt == DT_BF16) { if (C == 32) TTK_CLS_CONV5(bf16, 32); else TTK_CLS_CONV5(bf16, 64); }
-	else { if (C == 32) TTK_CLS_CONV5(float, 32); else TTK_CLS_CONV5(float, 64); }
-#undef TTK_CLS_CONV5
+	by_f32_bf16(dt, [&](auto t) {
+		using T = decltype(t);
+		if (C == 32) hipLaunchKernelGGL((k_cls_conv5<T, 32>), grid, dim3(256), 0, s, x, L, ms, gamma, beta, G, w, bias, residual, out, tpw);
+		else hipLaunchKernelGGL((k_cls_conv5<T, 64>), grid, dim3(256), 0, s, x, L, ms, gamma, beta, G, w, bias, residual, out, tpw);
+	});
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
 
 void launch_pack(int dt, const float* src, int C, int B, int L, int Lp, const float* ms, const float* gamma, const float* beta, int G, void* dst, int ld, hipStream_t s) {
 	const int64_t total = (int64_t)B * Lp * ld;
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_cls_pack<bf16>), dim3(grid_for(total)), dim3(256), 0, s, src, C, L, Lp, ms, gamma, beta, G, (bf16*)dst, ld, total);
-	else hipLaunchKernelGGL((k_cls_pack<float>), dim3(grid_for(total)), dim3(256), 0, s, src, C, L, Lp, ms, gamma, beta, G, (float*)dst, ld, total);
+	by_f32_bf16(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_cls_pack<T>), dim3(grid_for(total)), dim3(256), 0, s, src, C, L, Lp, ms, gamma, beta, G, (T*)dst, ld, total); });
 }
 
 // Conv1d(k = 5, stride 4, padding 2) over operand rows x T [B][Lp][ld] (Lp % 4 == 0, rows >= L zero): f32 y [B * Lp / 4][N]
@@ -493,13 +492,10 @@ int ttk_cls_forward_taps(ttk_cls* h, const float* audio, int B, int T, float* em
 		TTK_TRY(tap_out(depth + 1, x, (int64_t)B * Lf * E));
 	}
 	const int64_t rows = (int64_t)B * Lf;
-	if (dt == DT_BF16) {
-		bf16* at = (bf16*)a;
-		attn_blocks<bf16>(dt, h->blocks, x, B, Lf, E, h->groups_emb, c.num_attn_heads, at, at + rows * E, at + rows * E * 4, s);
-	} else {
-		float* at = (float*)a;
-		attn_blocks<float>(dt, h->blocks, x, B, Lf, E, h->groups_emb, c.num_attn_heads, at, at + rows * E, at + rows * E * 4, s);
-	}
+	by_f32_bf16(dt, [&](auto t) {
+		decltype(t)* at = (decltype(t)*)a;
+		attn_blocks(dt, h->blocks, x, B, Lf, E, h->groups_emb, c.num_attn_heads, at, at + rows * E, at + rows * E * 4, s);
+	});
 	hipLaunchKernelGGL(k_cls_head, dim3((unsigned)B), dim3(256), 0, s, x, Lf, E, h->head_w, h->head_b, c.classes, emb_out, logits_out);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 #include "ttk_kernels.h"
 
 using namespace ttk;
@@ -119,35 +119,39 @@ struct ttk_clvp {
 
 namespace {
 
-void gemm_plain(int dt, const void* A, int lda, const Mat& w, int M, const float* residual, void* C, int out_f32, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = 1;
-	g.seg[0] = {A, lda, 0, 0};
-	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.bias = w.bias;
-	g.residual = residual; g.ldr = w.N; g.C = C; g.ldc = w.N; g.out_f32 = out_f32;
-	launch_gemm(dt, g, s);
-}
+// h->ws of a score call: the buffers of one encoder pass over at most `rows` rows (the two passes run one after the other), then both latents f32 [B][d]
+struct Ws {
+	size_t x, xn, qkv, ao, tl, sl, total;
+	Ws(const ttk_clvp* h, size_t rows, size_t B) {
+		const size_t d = h->cfg.dim, inner = h->cfg.inner;
+		WsPlan p;
+		x = p.take(rows * d * 4);                                     // [rows][d] f32 residual stream
+		xn = p.take(rows * d * h->es);                                // [rows][d]
+		qkv = p.take(rows * std::max(3 * d, 2 * inner) * h->es);      // [rows][3d]  (also the GLU projection [rows][2 * inner])
+		ao = p.take(rows * std::max(d, inner) * h->es);               // [rows][max(d, inner)]
+		tl = p.take(B * d * 4); sl = p.take(B * d * 4);
+		total = p.total;
+	}
+};
 
 template <typename T>
-void encode_t(ttk_clvp* h, const Encoder& e, const int64_t* ids, int B, int S, int ids_stride, float* latent /* [B][d] f32 */, hipStream_t s) {
+void encode_t(ttk_clvp* h, const Ws& w, const Encoder& e, const int64_t* ids, int B, int S, int ids_stride, float* latent /* [B][d] f32 */, hipStream_t s) {
 	const ttk_clvp_config& c = h->cfg;
 	const int d = c.dim, H = c.heads, inner = c.inner, dt = h->dt;
 	const int64_t rows = (int64_t)B * S;
 	char* base = (char*)h->ws.p;
-	float* x = (float*)base;                                        // [rows][d] f32 residual stream
-	T* xn = (T*)(base + (size_t)rows * d * 4);                      // [rows][d]
-	T* qkv = xn + rows * d;                                         // [rows][3d]  (also the GLU projection [rows][2 * inner])
-	T* ao = qkv + rows * (size_t)std::max(3 * d, 2 * inner);        // [rows][max(d, inner)]
+	float* x = (float*)(base + w.x);
+	T *xn = (T*)(base + w.xn), *qkv = (T*)(base + w.qkv), *ao = (T*)(base + w.ao);
 	{
 		const int64_t total = rows * (d / 4);
-		hipLaunchKernelGGL(k_embed_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, e.emb, ids, (int64_t)S, ids_stride, x, rows, d, e.vocab);
+		hipLaunchKernelGGL(k_embed_rows, dim3(grid_for(total)), dim3(256), 0, s, e.emb, ids, (int64_t)S, ids_stride, x, rows, d, e.vocab);
 	}
 	for (const EncLayer& L : e.L) {
 		hipLaunchKernelGGL((k_rmsnorm<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, L.g_attn, xn);
 		gemm_plain(dt, xn, d, L.qkv, (int)rows, nullptr, qkv, 0, s);
 		{
 			const int64_t total = rows * 3 * H * 16;
-			hipLaunchKernelGGL((k_rotary<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, rows, S, H, h->inv_freq);
+			hipLaunchKernelGGL((k_rotary<T>), dim3(grid_for(total)), dim3(256), 0, s, qkv, rows, S, H, h->inv_freq);
 		}
 		AttnParams a = {};
 		a.qkv = qkv; a.ld = 3 * d; a.q_off = 0; a.k_off = d; a.v_off = 2 * d; a.head_stride = 64; a.out = ao; a.ldo = d;
@@ -158,13 +162,13 @@ void encode_t(ttk_clvp* h, const Encoder& e, const int64_t* ids, int B, int S, i
 		gemm_plain(dt, xn, d, L.ff1, (int)rows, nullptr, qkv, 0, s);
 		{
 			const int64_t total = rows * inner;
-			hipLaunchKernelGGL((k_geglu<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, rows, inner, ao);
+			hipLaunchKernelGGL((k_geglu<T>), dim3(grid_for(total)), dim3(256), 0, s, qkv, rows, inner, ao);
 		}
 		gemm_plain(dt, ao, inner, L.ff2, (int)rows, x, x, 1, s);
 	}
 	float* xf = (float*)qkv;                                         // final LayerNorm output, f32 [rows][d] (the qkv buffer is free now)
 	launch_layernorm(dt, x, d, (int)rows, d, e.norm_g, e.norm_b, nullptr, nullptr, xf, d, 1, s);
-	hipLaunchKernelGGL((k_mean_rows<T>), dim3((unsigned)((B * d + 255) / 256)), dim3(256), 0, s, xf, B, S, d, xn);
+	hipLaunchKernelGGL((k_mean_rows<T>), dim3(grid_for(B * d)), dim3(256), 0, s, xf, B, S, d, xn);
 	gemm_plain(dt, xn, d, e.to_latent, B, nullptr, latent, 1, s);
 }
 
@@ -225,19 +229,14 @@ int ttk_clvp_score(ttk_clvp* h, const int64_t* text, int Bt, int Tt, const int64
 	const ttk_clvp_config& c = h->cfg;
 	hipStream_t s = (hipStream_t)stream;
 	const int d = c.dim;
-	const int64_t rows = std::max((int64_t)Bt * Tt, (int64_t)B * M);
-	const size_t per_row = (size_t)d * 4 + (size_t)(d + std::max(3 * d, 2 * c.inner) + std::max(d, c.inner)) * h->es;
-	const size_t lat_off = (rows * per_row + 255) / 256 * 256;
-	TTK_TRY(h->ws.reserve(lat_off + (size_t)2 * B * d * 4 + 256));
-	float* tl = (float*)((char*)h->ws.p + lat_off);
-	float* sl = tl + (size_t)B * d;
-	if (h->dt == DT_BF16) {
-		encode_t<bf16>(h, h->text, text, Bt, Tt, Tt, tl, s);
-		encode_t<bf16>(h, h->speech, codes, B, M, M, sl, s);
-	} else {
-		encode_t<float>(h, h->text, text, Bt, Tt, Tt, tl, s);
-		encode_t<float>(h, h->speech, codes, B, M, M, sl, s);
-	}
+	const Ws w(h, std::max((size_t)Bt * Tt, (size_t)B * M), B);
+	TTK_TRY(h->ws.reserve(w.total));
+	float *tl = (float*)((char*)h->ws.p + w.tl), *sl = (float*)((char*)h->ws.p + w.sl);
+	by_f32_bf16(h->dt, [&](auto t) {
+		using T = decltype(t);
+		encode_t<T>(h, w, h->text, text, Bt, Tt, Tt, tl, s);
+		encode_t<T>(h, w, h->speech, codes, B, M, M, sl, s);
+	});
 	hipLaunchKernelGGL(k_clvp_score, dim3(B), dim3(64), 0, s, tl, Bt, sl, d, h->temperature, scores);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

@@ -72,38 +72,36 @@ int encode_t(ttk_cond* h, const float* mel, int b, int Tf, float* out, hipStream
 	const int64_t rows = (int64_t)b * T2;
 	TTK_REQUIRE(h->hd == 64 || T2 <= kRowWaveMaxT, TTK_E_ARG, "ttk_cond_encode: %d positions exceed the row-wave attention's LDS strip (%d)", T2, kRowWaveMaxT);
 	// workspace: x f32 [rows][C] | a T [rows][C] | qkv T [rows][3C] | ao T [rows][C]; the stem's operands alias a/qkv/ao (free until block 0)
-	const size_t im0 = (size_t)b * T1 * h->stem0.Kpad * h->es, mid = c.stem == TTK_COND_STEM_DOWN4 ? (size_t)b * T1 * (C / 2) * 4 : 0;
-	const size_t im1 = c.stem == TTK_COND_STEM_DOWN4 ? (size_t)rows * h->stem1.Kpad * h->es : 0;
-	const size_t xbytes = (size_t)rows * C * 4, blk = (size_t)rows * C * 5 * h->es;
-	const size_t scratch = std::max(blk, ((im0 + 255) / 256 + (mid + 255) / 256 + (im1 + 255) / 256) * 256);
-	TTK_TRY(h->ws.reserve(xbytes + scratch + 1024));
-	char* base = (char*)h->ws.p;
-	float* x = (float*)base;
-	char* sp = base + (xbytes + 255) / 256 * 256;
+	const bool down4 = c.stem == TTK_COND_STEM_DOWN4;
+	WsPlan stem, blk, ws;
+	const size_t o_a0 = stem.take((size_t)b * T1 * h->stem0.Kpad * h->es), o_y = stem.take(down4 ? (size_t)b * T1 * (C / 2) * 4 : 0),
+				 o_a1 = stem.take(down4 ? (size_t)rows * h->stem1.Kpad * h->es : 0);
+	const size_t o_a = blk.take((size_t)rows * C * h->es), o_qkv = blk.take((size_t)rows * 3 * C * h->es), o_ao = blk.take((size_t)rows * C * h->es);
+	const size_t o_x = ws.take((size_t)rows * C * 4), o_sp = ws.take(std::max(blk.total, stem.total));
+	TTK_TRY(h->ws.reserve(ws.total));
+	float* x = (float*)((char*)h->ws.p + o_x);
+	char* sp = (char*)h->ws.p + o_sp;
 	{
-		T* a0 = (T*)sp;
+		T* a0 = (T*)(sp + o_a0);
 		const int64_t total = (int64_t)b * T1 * h->stem0.Kpad;
-		if (c.stem == TTK_COND_STEM_DOWN4) {
-			float* y = (float*)(sp + (im0 + 255) / 256 * 256);
-			T* a1 = (T*)((char*)y + (mid + 255) / 256 * 256);
-			hipLaunchKernelGGL((k_cond_im2col<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1,
+		if (down4) {
+			float* y = (float*)(sp + o_y);
+			T* a1 = (T*)(sp + o_a1);
+			hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total)), dim3(256), 0, s, mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1,
 							   c.in_channels, Tf, T1, 3, 2, 1, h->stem0.Kpad, total, a0);
 			gemm_plain(dt, a0, h->stem0.Kpad, h->stem0, b * T1, nullptr, y, 1, s);
 			const int64_t total1 = rows * h->stem1.Kpad;
-			hipLaunchKernelGGL((k_cond_im2col<T>), dim3((unsigned)((total1 + 255) / 256)), dim3(256), 0, s, y, (int64_t)T1 * (C / 2), (int64_t)1, (int64_t)(C / 2),
+			hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total1)), dim3(256), 0, s, y, (int64_t)T1 * (C / 2), (int64_t)1, (int64_t)(C / 2),
 							   C / 2, T1, T2, 3, 2, 1, h->stem1.Kpad, total1, a1);
 			gemm_plain(dt, a1, h->stem1.Kpad, h->stem1, (int)rows, nullptr, x, 1, s);
 		} else {
-			hipLaunchKernelGGL((k_cond_im2col<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1,
+			hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total)), dim3(256), 0, s, mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1,
 							   c.in_channels, Tf, Tf, 1, 1, 0, h->stem0.Kpad, total, a0);
 			gemm_plain(dt, a0, h->stem0.Kpad, h->stem0, (int)rows, nullptr, x, 1, s);
 		}
 	}
-	T* a = (T*)sp;
-	T* qkv = a + rows * C;
-	T* ao = qkv + rows * 3 * C;
-	attn_blocks<T>(dt, h->blocks, x, b, T2, C, h->groups, c.num_heads, a, qkv, ao, s);
-	hipLaunchKernelGGL(k_cond_pool, dim3((C + 255) / 256, b), dim3(256), 0, s, x, T2, C, c.pool, out);
+	attn_blocks<T>(dt, h->blocks, x, b, T2, C, h->groups, c.num_heads, (T*)(sp + o_a), (T*)(sp + o_qkv), (T*)(sp + o_ao), s);
+	hipLaunchKernelGGL(k_cond_pool, dim3(grid_for(C), b), dim3(256), 0, s, x, T2, C, c.pool, out);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
@@ -152,7 +150,7 @@ int ttk_cond_encode(ttk_cond* h, const float* mel, int b, int T, float* out, voi
 	TTK_REQUIRE(h && mel && out, TTK_E_ARG, "ttk_cond_encode: null argument");
 	TTK_REQUIRE(b >= 1 && T >= 1, TTK_E_ARG, "ttk_cond_encode: empty input (b=%d T=%d)", b, T);
 	TTK_REQUIRE(T <= 8192, TTK_E_ARG, "ttk_cond_encode: %d frames exceed the 8192-frame limit of a conditioning clip", T);
-	return h->dt == DT_BF16 ? encode_t<bf16>(h, mel, b, T, out, (hipStream_t)stream) : encode_t<float>(h, mel, b, T, out, (hipStream_t)stream);
+	return by_f32_bf16(h->dt, [&](auto t) { return encode_t<decltype(t)>(h, mel, b, T, out, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -193,20 +193,9 @@ struct ttk_dvae {
 
 namespace {
 
-template <typename F>
-void by_dtype(int dt, F f) {
-	if (dt == DT_BF16) f(bf16());
-	else if (dt == DT_F16) f(f16());
-	else f(float());
-}
-unsigned grid_for(int64_t total) { return (unsigned)((total + 255) / 256); }
-
 void launch_pack(int dt, const float* src, int C, int B, int L, int Lp, int relu, float* keep, void* dst, int ld, hipStream_t s) {
 	const int64_t total = (int64_t)B * Lp * ld;
-	by_dtype(dt, [&](auto t) {
-		typedef decltype(t) T;
-		hipLaunchKernelGGL((k_dvae_pack<T>), dim3(grid_for(total)), dim3(256), 0, s, src, C, L, Lp, relu, keep, (T*)dst, ld, total);
-	});
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_dvae_pack<T>), dim3(grid_for(total)), dim3(256), 0, s, src, C, L, Lp, relu, keep, (T*)dst, ld, total); });
 }
 
 // k = 3, stride 2, padding 1 over operand rows x T [B][Lp][ld] (Lp even, rows >= L zero): f32 y [B * Lp / 2][N]
@@ -284,7 +273,7 @@ int launch_quant(ttk_dvae* h, const float* z, int M, float* pmin, int* pidx, int
 #undef TTK_DVAE_QUANT
 		default: TTK_REQUIRE(false, TTK_E_ARG, "ttk_dvae: codebook_dim %d has no quantizer instantiation", D);
 	}
-	hipLaunchKernelGGL(k_dvae_qcombine, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, pmin, pidx, nw, M, codes);
+	hipLaunchKernelGGL(k_dvae_qcombine, dim3(grid_for(M)), dim3(256), 0, s, pmin, pidx, nw, M, codes);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
@@ -333,7 +322,7 @@ int ttk_dvae_create(ttk_dvae** out, const ttk_dvae_config* cfg, const ttk_weight
 		TTK_TRY(upload_f32(tmp, wm, "codebook.embed", (int64_t)D * V, &embed));
 		TTK_TRY(h->arena.alloc((void**)&h->cb, (size_t)V * D * 4));
 		TTK_TRY(h->arena.alloc((void**)&h->e2, (size_t)V * 4));
-		hipLaunchKernelGGL(k_dvae_codebook, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, 0, embed, D, V, h->cb, h->e2);
+		hipLaunchKernelGGL(k_dvae_codebook, dim3(grid_for(V)), dim3(256), 0, 0, embed, D, V, h->cb, h->e2);
 		TTK_HIP(hipDeviceSynchronize());
 	}
 	*out = h.release();
@@ -386,10 +375,7 @@ int ttk_dvae_encode(ttk_dvae* h, const float* mel, int B, int T, int64_t* codes_
 
 	{
 		const int64_t total = (int64_t)B * L0p * ld0;
-		by_dtype(dt, [&](auto t) {
-			typedef decltype(t) TT;
-			hipLaunchKernelGGL((k_dvae_in<TT>), dim3(grid_for(total)), dim3(256), 0, s, mel, c.channels, L0, L0p, (TT*)x0, ld0, total);
-		});
+		by_dtype(dt, [&](auto t) { using TT = decltype(t); hipLaunchKernelGGL((k_dvae_in<TT>), dim3(grid_for(total)), dim3(256), 0, s, mel, c.channels, L0, L0p, (TT*)x0, ld0, total); });
 	}
 	conv_stride2(dt, x0, ld0, es, h->enc0, B, L0p, y, s);                  // f32 [B * L1][H]
 	launch_pack(dt, y, H, B, L1, L1p, 1, nullptr, x1, ld1, s);
@@ -434,10 +420,7 @@ int ttk_dvae_decode(ttk_dvae* h, const int64_t* codes, int B, int n, float* mel_
 
 	{
 		const int64_t total = (int64_t)M * ldD;
-		by_dtype(dt, [&](auto t) {
-			typedef decltype(t) TT;
-			hipLaunchKernelGGL((k_dvae_gather<TT>), dim3(grid_for(total)), dim3(256), 0, s, codes, h->cb, c.num_tokens, D, (TT*)gt, ldD, total);
-		});
+		by_dtype(dt, [&](auto t) { using TT = decltype(t); hipLaunchKernelGGL((k_dvae_gather<TT>), dim3(grid_for(total)), dim3(256), 0, s, codes, h->cb, c.num_tokens, D, (TT*)gt, ldD, total); });
 	}
 	conv_same(dt, gt, ldD, h->dec_in, 1, 1, M, n, nullptr, x, 1, s);                 // f32 [M][2 H]
 	for (int i = 0; i < c.num_resnet_blocks; ++i) resblock(dt, h->dec_res[i], x, C2, ld2, B, n, a, a2, hb, s);

@@ -8,9 +8,9 @@ namespace ttk {
 __global__ void k_set_int(int* p, int v) { *p = v; }
 void launch_set_int(int* p, int v, hipStream_t s) { hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, s, p, v); }
 __global__ void k_fill_int(int* p, int v, int n) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) p[i] = v; }
-void launch_fill_int(int* p, int v, int n, hipStream_t s) { if (n > 0) hipLaunchKernelGGL(k_fill_int, dim3((n + 255) / 256), dim3(256), 0, s, p, v, n); }
+void launch_fill_int(int* p, int v, int n, hipStream_t s) { if (n > 0) hipLaunchKernelGGL(k_fill_int, dim3(grid_for(n)), dim3(256), 0, s, p, v, n); }
 __global__ void k_fill_int2(int* p, int a, int b, int n) { const int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) { p[2 * i] = a; p[2 * i + 1] = b; } }
-void launch_fill_int2(int* p, int a, int b, int n, hipStream_t s) { if (n > 0) hipLaunchKernelGGL(k_fill_int2, dim3((n + 255) / 256), dim3(256), 0, s, p, a, b, n); }
+void launch_fill_int2(int* p, int a, int b, int n, hipStream_t s) { if (n > 0) hipLaunchKernelGGL(k_fill_int2, dim3(grid_for(n)), dim3(256), 0, s, p, a, b, n); }
 
 // out[r] = A[ia[r]] + Bt[ib[r]]      (unified_voice.py:582,590,641: embedding + learned position embedding)
 __global__ void k_gather_add(const float* A, const int* ia, const float* Bt, const int* ib, float* out, int rows, int d) {
@@ -24,7 +24,7 @@ __global__ void k_gather_add(const float* A, const int* ia, const float* Bt, con
 }
 void launch_gather_add(const float* A, const int* ia, const float* Bt, const int* ib, float* out, int rows, int d, hipStream_t s) {
 	const int64_t total = (int64_t)rows * (d / 4);
-	hipLaunchKernelGGL(k_gather_add, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, A, ia, Bt, ib, out, rows, d);
+	hipLaunchKernelGGL(k_gather_add, dim3(grid_for(total)), dim3(256), 0, s, A, ia, Bt, ib, out, rows, d);
 }
 
 // out[r][:] = f32(table[ids[r]][:]): the token branch of the diffusion model's aligned conditioning (diffusion.py:1496), the table in the handle's element type,
@@ -46,9 +46,7 @@ __global__ void k_embed_rows(const T* table, const int64_t* ids, int rows, int C
 void launch_embed_rows(int dt, const void* table, const int64_t* ids, int rows, int C, int n_tok, float* out, hipStream_t s) {
 	const int rpb = 256 / (C / 8);
 	const dim3 grid((unsigned)((rows + rpb - 1) / rpb));
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_embed_rows<bf16>), grid, dim3(256), 0, s, (const bf16*)table, ids, rows, C, n_tok, out);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_embed_rows<f16>), grid, dim3(256), 0, s, (const f16*)table, ids, rows, C, n_tok, out);
-	else hipLaunchKernelGGL((k_embed_rows<float>), grid, dim3(256), 0, s, (const float*)table, ids, rows, C, n_tok, out);
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_embed_rows<T>), grid, dim3(256), 0, s, (const T*)table, ids, rows, C, n_tok, out); });
 }
 
 // decode: x[b] = mel_embedding[tok[b]] + mel_pos_embedding[*d_pos + pos_off]
@@ -72,7 +70,7 @@ __global__ void k_decode_embed(const float* emb, const int64_t* tok, const float
 }
 void launch_decode_embed(const float* emb, const int64_t* tok, const float* pos, const int* d_pos, int pos_off, int pos_rows, float* out, int B, int d, hipStream_t s,
 						 void* frag, int frag_f32) {
-	hipLaunchKernelGGL(k_decode_embed, dim3((B * (d / 4) + 255) / 256), dim3(256), 0, s, emb, tok, pos, d_pos, pos_off, pos_rows, out, B, d, frag, frag_f32);
+	hipLaunchKernelGGL(k_decode_embed, dim3(grid_for(B * (d / 4))), dim3(256), 0, s, emb, tok, pos, d_pos, pos_off, pos_rows, out, B, d, frag, frag_f32);
 }
 
 __global__ void k_copy_rows(const float* src, int64_t lds_, float* dst, int64_t ldd, int rows, int d) {
@@ -84,7 +82,7 @@ __global__ void k_copy_rows(const float* src, int64_t lds_, float* dst, int64_t 
 }
 void launch_copy_rows(const float* src, int64_t lds_, float* dst, int64_t ldd, int rows, int d, hipStream_t s) {
 	const int64_t total = (int64_t)rows * (d / 4);
-	hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, lds_, dst, ldd, rows, d);
+	hipLaunchKernelGGL(k_copy_rows, dim3(grid_for(total)), dim3(256), 0, s, src, lds_, dst, ldd, rows, d);
 }
 
 template <typename T>
@@ -99,9 +97,7 @@ __global__ void k_cast(const float* src, T* dst, int64_t n) {
 }
 void launch_cast(int dt, const float* src, void* dst, int64_t n, hipStream_t s) {
 	const unsigned grid = (unsigned)((n / 4 + 256) / 256);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_cast<bf16>), dim3(grid), dim3(256), 0, s, src, (bf16*)dst, n);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_cast<f16>), dim3(grid), dim3(256), 0, s, src, (f16*)dst, n);
-	else hipLaunchKernelGGL((k_cast<float>), dim3(grid), dim3(256), 0, s, src, (float*)dst, n);
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_cast<T>), dim3(grid), dim3(256), 0, s, src, (T*)dst, n); });
 }
 
 // channel-first f32 [nb][C][T] -> channels-last T-typed [rep*nb*T][ldo], zero padded columns C..ldo (LDS tile transpose)
@@ -124,9 +120,7 @@ __global__ void k_cf_to_cl(const float* src, int nb, int C, int Tn, T* dst, int6
 }
 void launch_cf_to_cl(int dt, const float* src, int nb, int C, int T, void* dst, int64_t ldo, int rep, hipStream_t s, const int* tlen) {
 	dim3 grid((T + 31) / 32, (unsigned)((ldo + 31) / 32), nb);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_cf_to_cl<bf16>), grid, dim3(256), 0, s, src, nb, C, T, (bf16*)dst, ldo, rep, tlen);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_cf_to_cl<f16>), grid, dim3(256), 0, s, src, nb, C, T, (f16*)dst, ldo, rep, tlen);
-	else hipLaunchKernelGGL((k_cf_to_cl<float>), grid, dim3(256), 0, s, src, nb, C, T, (float*)dst, ldo, rep, tlen);
+	by_dtype(dt, [&](auto t) { using E = decltype(t); hipLaunchKernelGGL((k_cf_to_cl<E>), grid, dim3(256), 0, s, src, nb, C, T, (E*)dst, ldo, rep, tlen); });
 }
 
 __global__ void k_cl_to_cf(const float* src, int nb, int C, int Tn, float* dst) {
@@ -155,11 +149,8 @@ __global__ void k_bcast_rows(const float* vec, int rows, int C, T* dst) {
 	dst[idx] = cvt<T>(vec[idx % C]);
 }
 void launch_bcast_rows(int dt, const float* vec, int rows, int C, void* dst, hipStream_t s) {
-	const int64_t total = (int64_t)rows * C;
-	const unsigned grid = (unsigned)((total + 255) / 256);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_bcast_rows<bf16>), dim3(grid), dim3(256), 0, s, vec, rows, C, (bf16*)dst);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_bcast_rows<f16>), dim3(grid), dim3(256), 0, s, vec, rows, C, (f16*)dst);
-	else hipLaunchKernelGGL((k_bcast_rows<float>), dim3(grid), dim3(256), 0, s, vec, rows, C, (float*)dst);
+	const dim3 grid(grid_for((int64_t)rows * C));
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_bcast_rows<T>), grid, dim3(256), 0, s, vec, rows, C, (T*)dst); });
 }
 
 // diffusion.py:1277-1295: emb[i] = cat(cos(t*f), sin(t*f)); f_j = exp(-ln(1e4) * j / half) is a host-computed f32 table
@@ -177,10 +168,8 @@ __global__ void k_timestep_embedding(const int64_t* t, int64_t t_host, int n, in
 	out[(int64_t)i * C + half + j] = cvt<T>(sinf(a));
 }
 void launch_timestep_embedding(int dt, const int64_t* t, int64_t t_host, int n, int C, const float* freqs, void* out, hipStream_t s) {
-	const unsigned grid = (n * (C / 2) + 255) / 256;
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_timestep_embedding<bf16>), dim3(grid), dim3(256), 0, s, t, t_host, n, C, freqs, (bf16*)out);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_timestep_embedding<f16>), dim3(grid), dim3(256), 0, s, t, t_host, n, C, freqs, (f16*)out);
-	else hipLaunchKernelGGL((k_timestep_embedding<float>), dim3(grid), dim3(256), 0, s, t, t_host, n, C, freqs, (float*)out);
+	const dim3 grid(grid_for(n * (C / 2)));
+	by_dtype(dt, [&](auto e) { using T = decltype(e); hipLaunchKernelGGL((k_timestep_embedding<T>), grid, dim3(256), 0, s, t, t_host, n, C, freqs, (T*)out); });
 }
 
 template <typename T>
@@ -189,10 +178,7 @@ __global__ void k_silu_cast(const float* x, T* y, int64_t n) {
 	if (i < n) y[i] = cvt<T>(silu_precise(x[i]));
 }
 void launch_silu_cast(int dt, const float* x, void* y, int64_t n, hipStream_t s) {
-	const unsigned grid = (unsigned)((n + 255) / 256);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_silu_cast<bf16>), dim3(grid), dim3(256), 0, s, x, (bf16*)y, n);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_silu_cast<f16>), dim3(grid), dim3(256), 0, s, x, (f16*)y, n);
-	else hipLaunchKernelGGL((k_silu_cast<float>), dim3(grid), dim3(256), 0, s, x, (float*)y, n);
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_silu_cast<T>), dim3(grid_for(n)), dim3(256), 0, s, x, (T*)y, n); });
 }
 
 // Per-step sampler epilogue on channel-first buffers.  out_c / out_u: network outputs [nb][2C][T] (eps | var) of the
@@ -241,7 +227,7 @@ __global__ void k_diffusion_step(const float* out_c, const float* out_u, float* 
 }
 void launch_diffusion_step(const float* out_c, const float* out_u, float* x, const float* noise, int nb, int C, int T, StepCoefs c, hipStream_t s, void* xcl, int ldo, int rep, int ekind) {
 	const int64_t total = (int64_t)nb * C * T;
-	hipLaunchKernelGGL(k_diffusion_step, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, out_c, out_u, x, noise, nb, C, T, c, xcl, ldo, rep, ekind);
+	hipLaunchKernelGGL(k_diffusion_step, dim3(grid_for(total)), dim3(256), 0, s, out_c, out_u, x, noise, nb, C, T, c, xcl, ldo, rep, ekind);
 }
 
 }  // namespace ttk

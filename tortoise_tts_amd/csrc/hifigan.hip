@@ -251,19 +251,12 @@ struct ttk_hifigan {
 
 namespace {
 
-template <typename T>
-void launch_act_t(const float* x, int C, float slope, void* out, int ldo, int64_t rows, hipStream_t s) {
-	const int64_t total = rows * ldo;
-	hipLaunchKernelGGL((k_hifi_act<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, C, slope, (T*)out, ldo, rows);
-}
 void launch_act(int dt, const float* x, int C, void* out, int ldo, int64_t rows, hipStream_t s) {
-	if (dt == DT_BF16) launch_act_t<bf16>(x, C, kSlope, out, ldo, rows, s);
-	else launch_act_t<float>(x, C, kSlope, out, ldo, rows, s);
+	by_f32_bf16(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_hifi_act<T>), dim3(grid_for(rows * ldo)), dim3(256), 0, s, x, C, kSlope, (T*)out, ldo, rows); });
 }
 template <typename T>
 void launch_mean_t(float* const* y, int n, float div, int C, float* out, void* out_t, int ldo, int64_t rows, hipStream_t s) {
-	const int64_t total = rows * ldo;
-	hipLaunchKernelGGL((k_hifi_mean<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, y[0], y[1], y[2], y[3], n, div, C, out, (T*)out_t, ldo, kSlope, rows);
+	hipLaunchKernelGGL((k_hifi_mean<T>), dim3(grid_for(rows * ldo)), dim3(256), 0, s, y[0], y[1], y[2], y[3], n, div, C, out, (T*)out_t, ldo, kSlope, rows);
 }
 
 void launch_narrow(int C, const void* a, int lda, const bf16* wfrag, const float* bias, int L, int k, int dil, int mode, const float* xres, float* xout,
@@ -282,7 +275,7 @@ void launch_narrow(int C, const void* a, int lda, const bf16* wfrag, const float
 int pack_frag(Arena& ar, const Mat& m, int C, int k, bf16** out) {
 	TTK_TRY(ar.alloc((void**)out, (size_t)k * C * C * 2));
 	const int total = k * C * C;
-	hipLaunchKernelGGL(k_hifi_pack_frag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, (const bf16*)m.w, m.Npad, m.Kpad, C, k, *out);
+	hipLaunchKernelGGL(k_hifi_pack_frag, dim3(grid_for(total)), dim3(256), 0, 0, (const bf16*)m.w, m.Npad, m.Kpad, C, k, *out);
 	TTK_HIP(hipDeviceSynchronize());
 	return TTK_OK;
 }
@@ -419,9 +412,7 @@ int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* au
 	{
 		const int64_t total = (int64_t)F * in_ld;
 		const float rs2 = (float)(1.0 / (24000.0 / 22050.0));
-		const unsigned grid = (unsigned)((total + 255) / 256);
-		if (dt == DT_BF16) hipLaunchKernelGGL((k_hifi_interp<bf16>), dim3(grid), dim3(256), 0, s, latents, n, c.in_channels, F, rs2, (bf16*)in_t, in_ld);
-		else hipLaunchKernelGGL((k_hifi_interp<float>), dim3(grid), dim3(256), 0, s, latents, n, c.in_channels, F, rs2, (float*)in_t, in_ld);
+		by_f32_bf16(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_hifi_interp<T>), dim3(grid_for(total)), dim3(256), 0, s, latents, n, c.in_channels, F, rs2, (T*)in_t, in_ld); });
 	}
 	conv_taps(dt, in_t, in_ld, h->conv_pre, h->pre_bias, 7, -3, 1, F, F, nullptr, hb, 1, s);         // conv_pre + cond_layer(g), f32 [F][ch0]
 	int L = F, ch = ch0;
@@ -456,11 +447,10 @@ int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* au
 					cur = xb[j];
 				}
 			}
-			if (dt == DT_BF16) launch_mean_t<bf16>(xb, c.n_kernels, (float)c.n_kernels, ch, y, last ? nullptr : xt, ld, L, s);
-			else launch_mean_t<float>(xb, c.n_kernels, (float)c.n_kernels, ch, y, last ? nullptr : xt, ld, L, s);
+			by_f32_bf16(dt, [&](auto t) { launch_mean_t<decltype(t)>(xb, c.n_kernels, (float)c.n_kernels, ch, y, last ? nullptr : xt, ld, L, s); });
 		}
 	}
-	hipLaunchKernelGGL(k_hifi_post, dim3((unsigned)((L + 255) / 256)), dim3(256), (size_t)7 * ch * 4, s, y, L, ch, h->post_w, h->post_b, audio);
+	hipLaunchKernelGGL(k_hifi_post, dim3(grid_for(L)), dim3(256), (size_t)7 * ch * 4, s, y, L, ch, h->post_w, h->post_b, audio);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

@@ -7,7 +7,7 @@
 #include <stdlib.h>
 
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 
 using namespace ttk;
 
@@ -126,32 +126,25 @@ int ttk_mel_forward(ttk_mel* h, const float* wav, int b, int n, float* mel, void
 	const int64_t rows = (int64_t)b * F;
 	TTK_REQUIRE(rows * c.n_fft < ((int64_t)1 << 31), TTK_E_ARG, "ttk_mel_forward: %lld frames exceed one launch (split the batch)", (long long)rows);
 	hipStream_t s = (hipStream_t)stream;
-	const size_t fr = (size_t)rows * c.n_fft * 4, sp = (size_t)rows * 2 * h->nb * 4, mg = (size_t)rows * h->melb.Kpad * 4, mm = (size_t)rows * c.n_mels * 4;
-	auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-	TTK_TRY(h->ws.reserve(al(fr) + al(sp) + al(mg) + al(mm)));
-	float* frames = (float*)h->ws.p;
-	float* spec = (float*)((char*)frames + al(fr));
-	float* mag = (float*)((char*)spec + al(sp));
-	float* mraw = (float*)((char*)mag + al(mg));
+	WsPlan ws;
+	const size_t o_fr = ws.take((size_t)rows * c.n_fft * 4), o_sp = ws.take((size_t)rows * 2 * h->nb * 4), o_mg = ws.take((size_t)rows * h->melb.Kpad * 4),
+				 o_mm = ws.take((size_t)rows * c.n_mels * 4);
+	TTK_TRY(h->ws.reserve(ws.total));
+	char* base = (char*)h->ws.p;
+	float *frames = (float*)(base + o_fr), *spec = (float*)(base + o_sp), *mag = (float*)(base + o_mg), *mraw = (float*)(base + o_mm);
 	{
 		const int64_t total = rows * c.n_fft;
-		hipLaunchKernelGGL(k_mel_frames, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wav, n, F, c.n_fft, c.hop, c.clip, total, frames);
+		hipLaunchKernelGGL(k_mel_frames, dim3(grid_for(total)), dim3(256), 0, s, wav, n, F, c.n_fft, c.hop, c.clip, total, frames);
 	}
-	GemmParams g = {};
-	g.nseg = 1; g.seg[0] = {frames, c.n_fft, 0, 0};
-	g.W = h->basis.w; g.ldw = h->basis.Kpad; g.M = (int)rows; g.N = h->basis.N; g.K = h->basis.Kpad; g.C = spec; g.ldc = h->basis.N; g.out_f32 = 1;
-	launch_gemm(DT_F32, g, s);
+	launch_gemm(DT_F32, dense_gemm(frames, c.n_fft, h->basis, (int)rows, spec, 1), s);
 	{
 		const int64_t total = rows * h->melb.Kpad;
-		hipLaunchKernelGGL(k_mel_mag, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, spec, h->nb, h->melb.Kpad, c.power, total, mag);
+		hipLaunchKernelGGL(k_mel_mag, dim3(grid_for(total)), dim3(256), 0, s, spec, h->nb, h->melb.Kpad, c.power, total, mag);
 	}
-	GemmParams g2 = {};
-	g2.nseg = 1; g2.seg[0] = {mag, h->melb.Kpad, 0, 0};
-	g2.W = h->melb.w; g2.ldw = h->melb.Kpad; g2.M = (int)rows; g2.N = c.n_mels; g2.K = h->melb.Kpad; g2.C = mraw; g2.ldc = c.n_mels; g2.out_f32 = 1;
-	launch_gemm(DT_F32, g2, s);
+	launch_gemm(DT_F32, dense_gemm(mag, h->melb.Kpad, h->melb, (int)rows, mraw, 1), s);
 	{
 		const int64_t total = (int64_t)b * c.n_mels * F;
-		hipLaunchKernelGGL(k_mel_log, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mraw, F, c.n_mels, h->norms, total, mel);
+		hipLaunchKernelGGL(k_mel_log, dim3(grid_for(total)), dim3(256), 0, s, mraw, F, c.n_mels, h->norms, total, mel);
 	}
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
@@ -164,7 +157,7 @@ int ttk_resample_fir(const float* wav, int b, int n, const float* kernels, int g
 	TTK_REQUIRE((int64_t)n_out <= ((int64_t)n / gorig + 1) * gnew, TTK_E_ARG, "ttk_resample_fir: n_out %d exceeds the %lld samples the clip yields", n_out,
 				(long long)(((int64_t)n / gorig + 1) * gnew));
 	const int64_t total = (int64_t)b * n_out;
-	hipLaunchKernelGGL(k_resample_fir, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, wav, n, kernels, gorig, gnew, width,
+	hipLaunchKernelGGL(k_resample_fir, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, wav, n, kernels, gorig, gnew, width,
 					   2 * width + gorig, n_out, total, out);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

@@ -34,10 +34,7 @@ __global__ void k_pack_nk(const float* src, int layout, int N, int K, int Npad, 
 void launch_pack_nk(int dt, const float* src, int layout, int N, int K, int Npad, int Kpad, void* dst, hipStream_t s, int ntap) {
 	if (ntap <= 0) ntap = layout == PK_CONV3 ? 3 : 1;
 	const int64_t total = (int64_t)ntap * Npad * Kpad;
-	const unsigned grid = (unsigned)((total + 255) / 256);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_pack_nk<bf16>), dim3(grid), dim3(256), 0, s, src, layout, N, K, Npad, Kpad, ntap, (bf16*)dst);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_pack_nk<f16>), dim3(grid), dim3(256), 0, s, src, layout, N, K, Npad, Kpad, ntap, (f16*)dst);
-	else hipLaunchKernelGGL((k_pack_nk<float>), dim3(grid), dim3(256), 0, s, src, layout, N, K, Npad, Kpad, ntap, (float*)dst);
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_pack_nk<T>), dim3(grid_for(total)), dim3(256), 0, s, src, layout, N, K, Npad, Kpad, ntap, (T*)dst); });
 }
 
 // [Npad][K] -> Wp[n_tile][k_step][lane][8]: lane l holds W[16nt + (l&15)][32ks + 8(l>>4) + j]
@@ -52,11 +49,8 @@ __global__ void k_pack_frag(const T* src, int Npad, int K, T* dst) {
 	dst[idx] = src[(int64_t)(16 * nt + (lane & 15)) * K + 32 * ks + 8 * (lane >> 4) + j];
 }
 void launch_pack_frag(int dt, const void* src, int Npad, int K, void* dst, hipStream_t s) {
-	const int64_t total = (int64_t)Npad * K;
-	const unsigned grid = (unsigned)((total + 255) / 256);
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_pack_frag<bf16>), dim3(grid), dim3(256), 0, s, (const bf16*)src, Npad, K, (bf16*)dst);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_pack_frag<f16>), dim3(grid), dim3(256), 0, s, (const f16*)src, Npad, K, (f16*)dst);
-	else hipLaunchKernelGGL((k_pack_frag<float>), dim3(grid), dim3(256), 0, s, (const float*)src, Npad, K, (float*)dst);
+	const dim3 grid(grid_for((int64_t)Npad * K));
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_pack_frag<T>), grid, dim3(256), 0, s, (const T*)src, Npad, K, (T*)dst); });
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm folded into a decode GEMV
@@ -68,7 +62,7 @@ __global__ void k_scale_kn(float* w, const float* gamma, int K, int N) {
 	if (i < (int64_t)K * N) w[i] *= gamma[i / N];
 }
 void launch_scale_kn(float* w, const float* gamma, int K, int N, hipStream_t s) {
-	hipLaunchKernelGGL(k_scale_kn, dim3((unsigned)(((int64_t)K * N + 255) / 256)), dim3(256), 0, s, w, gamma, K, N);
+	hipLaunchKernelGGL(k_scale_kn, dim3(grid_for((int64_t)K * N)), dim3(256), 0, s, w, gamma, K, N);
 }
 // csum[n] = sum_k W'[n][k] over the ROUNDED (T-typed) values the kernel multiplies with, so that mean * csum cancels exactly what the
 // MFMAs summed; one wave per row, f32 partial sums over 16 elements per lane, f64 across lanes
@@ -83,9 +77,7 @@ __global__ void k_rowsum(const T* w, int64_t ld, int N, int K, float* out) {
 	if (lane == 0) out[n] = (float)acc;
 }
 void launch_rowsum(int dt, const void* w, int64_t ld, int N, int K, float* out, hipStream_t s) {
-	if (dt == DT_BF16) hipLaunchKernelGGL((k_rowsum<bf16>), dim3((N + 3) / 4), dim3(256), 0, s, (const bf16*)w, ld, N, K, out);
-	else if (dt == DT_F16) hipLaunchKernelGGL((k_rowsum<f16>), dim3((N + 3) / 4), dim3(256), 0, s, (const f16*)w, ld, N, K, out);
-	else hipLaunchKernelGGL((k_rowsum<float>), dim3((N + 3) / 4), dim3(256), 0, s, (const float*)w, ld, N, K, out);
+	by_dtype(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_rowsum<T>), dim3((N + 3) / 4), dim3(256), 0, s, (const T*)w, ld, N, K, out); });
 }
 // bias'[n] = b[n] + sum_k beta[k] * W[k][n]   (f32 weights as given, f64 accumulation)
 __global__ void k_bias_fold(const float* w, const float* beta, const float* b, int K, int N, float* out) {
@@ -96,7 +88,7 @@ __global__ void k_bias_fold(const float* w, const float* beta, const float* b, i
 	out[n] = (float)acc;
 }
 void launch_bias_fold(const float* w, const float* beta, const float* b, int K, int N, float* out, hipStream_t s) {
-	hipLaunchKernelGGL(k_bias_fold, dim3((N + 255) / 256), dim3(256), 0, s, w, beta, b, K, N, out);
+	hipLaunchKernelGGL(k_bias_fold, dim3(grid_for(N)), dim3(256), 0, s, w, beta, b, K, N, out);
 }
 
 // ------------------------------------------------------------------------------------------------ fp8-e4m3 weights
@@ -139,7 +131,7 @@ __global__ void k_fp8_roundtrip(float* x, int64_t n, float scale, float inv) {
 	if (i < n) x[i] = fp8_round(x[i] * inv) * scale;
 }
 void launch_fp8_roundtrip(float* x, int64_t n, float scale, hipStream_t s) {
-	hipLaunchKernelGGL(k_fp8_roundtrip, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, scale, 1.0f / scale);
+	hipLaunchKernelGGL(k_fp8_roundtrip, dim3(grid_for(n)), dim3(256), 0, s, x, n, scale, 1.0f / scale);
 }
 // the dense fp8 GEMM's weight operand: same index mapping as k_pack_nk, one fp8-e4m3 byte per element (value / scale, exact: the source was
 // rounded to scale * fp8 grid by k_fp8_roundtrip)
@@ -162,7 +154,7 @@ __global__ void k_pack_nk_f8(const float* src, int layout, int N, int K, int Npa
 void launch_pack_nk_f8(const float* src, int layout, int N, int K, int Npad, int Kpad, float scale, void* dst, hipStream_t s, int ntap) {
 	if (ntap <= 0) ntap = layout == PK_CONV3 ? 3 : 1;
 	const int64_t total = (int64_t)ntap * Npad * Kpad;
-	hipLaunchKernelGGL(k_pack_nk_f8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, layout, N, K, Npad, Kpad, ntap, 1.0f / scale, (unsigned char*)dst);
+	hipLaunchKernelGGL(k_pack_nk_f8, dim3(grid_for(total)), dim3(256), 0, s, src, layout, N, K, Npad, Kpad, ntap, 1.0f / scale, (unsigned char*)dst);
 }
 // [Npad][K] bf16 (values = fp8 grid * scale) -> Wp8[n_tile][k_step][lane][8 bytes], same element order as k_pack_frag
 __global__ void k_pack_frag_fp8(const bf16* src, int Npad, int K, float inv, unsigned char* dst) {
@@ -178,7 +170,7 @@ __global__ void k_pack_frag_fp8(const bf16* src, int Npad, int K, float inv, uns
 }
 void launch_pack_frag_fp8(const void* src, int Npad, int K, float scale, void* dst, hipStream_t s) {
 	const int64_t total = (int64_t)Npad * K / 2;
-	hipLaunchKernelGGL(k_pack_frag_fp8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const bf16*)src, Npad, K, 1.0f / scale, (unsigned char*)dst);
+	hipLaunchKernelGGL(k_pack_frag_fp8, dim3(grid_for(total)), dim3(256), 0, s, (const bf16*)src, Npad, K, 1.0f / scale, (unsigned char*)dst);
 }
 
 }  // namespace ttk

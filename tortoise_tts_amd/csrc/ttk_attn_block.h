@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "ttk_common.h"
-#include "ttk_host.h"
+#include "ttk_conv.h"
 
 namespace ttk {
 namespace {
@@ -99,15 +99,6 @@ inline int gn_groups(int channels) {    // arch_utils.py:27-44
 	else if (channels <= 64) g = 16;
 	while (channels % g != 0) g /= 2;
 	return g;
-}
-
-inline void gemm_plain(int dt, const void* A, int64_t lda, const Mat& w, int M, const float* residual, void* C, int out_f32, hipStream_t s) {
-	GemmParams g = {};
-	g.nseg = 1;
-	g.seg[0] = {A, lda, 0, 0};
-	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.bias = w.bias;
-	g.residual = residual; g.ldr = w.N; g.C = C; g.ldc = w.N; g.out_f32 = out_f32;
-	launch_gemm(dt, g, s);
 }
 
 // blocks "<prefix><i>.{norm,qkv,proj_out}.*" (+ "__relbias" [heads][129] when relpos) of C channels

@@ -1,5 +1,5 @@
-// Host layer shared by the three vocoders (voc.hip, univnet.hip, hifigan.hip): Conv1d and ConvTranspose1d over channels-last rows as
-// launches of the segment GEMM (gemm.hip), the workspace planner, the ResBlock weight upload and the tanh + clamp + trim output kernel.
+// Host layer over the segment GEMM (gemm.hip), shared by every handle that launches it on a Mat: the dense layer, Conv1d and ConvTranspose1d over
+// channels-last rows, the workspace planner, and for the vocoders the ResBlock weight upload and the tanh + clamp + trim output kernel.
 #pragma once
 #include "ttk_host.h"
 
@@ -11,6 +11,22 @@ inline GemmParams conv_gemm(const Mat& w, const float* bias, int M, int L, void*
 	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.rows_per_batch = L; g.bias = bias;
 	g.C = C; g.ldc = ldc; g.out_f32 = out_f32;
 	return g;
+}
+
+// the plain-matrix sibling, a dense layer: C = A W^T + bias over the M rows of A (T-typed [M][lda]), one segment, rows without batch structure (rows_per_batch
+// stays 0), f32 or T-typed output at row stride N.  The caller adds what its layer has besides: act, residual / ldr, out_scale, another ldc.
+inline GemmParams dense_gemm(const void* A, int64_t lda, const Mat& w, int M, void* C, int out_f32) {
+	GemmParams g = {};
+	g.nseg = 1; g.seg[0] = {A, lda, 0, 0};
+	g.W = w.w; g.ldw = w.Kpad; g.M = M; g.N = w.N; g.K = w.Kpad; g.bias = w.bias;
+	g.C = C; g.ldc = w.N; g.out_f32 = out_f32;
+	return g;
+}
+// ... launched, with an optional f32 residual [M][N] (may alias an f32 C)
+inline void gemm_plain(int dt, const void* A, int64_t lda, const Mat& w, int M, const float* residual, void* C, int out_f32, hipStream_t s) {
+	GemmParams g = dense_gemm(A, lda, w, M, C, out_f32);
+	g.residual = residual; g.ldr = w.N;
+	launch_gemm(dt, g, s);
 }
 
 // Conv1d of k taps, one GEMM segment per tap: out[m] = bias + sum_j A[m + shift0 + j * step] * W_j^T (+ residual), rows outside m's batch
@@ -78,6 +94,6 @@ __global__ void k_tanh_out(const float* y, int B, int L, int keep, float* audio)
 
 }  // namespace
 
-inline dim3 tanh_out_grid(int B, int keep) { return dim3((unsigned)(((int64_t)B * keep + 255) / 256)); }
+inline dim3 tanh_out_grid(int B, int keep) { return dim3(grid_for((int64_t)B * keep)); }
 
 }  // namespace ttk

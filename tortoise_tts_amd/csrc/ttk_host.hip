@@ -1,4 +1,4 @@
-#include "ttk_host.h"
+#include "ttk_conv.h"
 
 #include <stdarg.h>
 
@@ -180,9 +180,10 @@ extern "C" int ttk_gemm_nt(int dtype, const void* A, const void* W, int M, int N
 	const int kmul = dtype == TTK_FP8 ? 128 : (dtype == TTK_F32 ? 32 : 64);
 	TTK_REQUIRE(M >= 1 && N >= 128 && N % 128 == 0 && K >= kmul && K % kmul == 0, TTK_E_ARG,
 				"ttk_gemm_nt: need M >= 1, N %% 128 == 0, K %% %d == 0 (got M=%d N=%d K=%d)", kmul, M, N, K);
-	GemmParams g = {};
-	g.nseg = 1; g.seg[0] = {A, K, 0, 0};
-	g.W = W; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = bias; g.C = C; g.ldc = N; g.out_f32 = 1; g.out_scale = out_scale;
+	Mat m;
+	m.w = const_cast<void*>(W); m.N = N; m.Kpad = K; m.bias = const_cast<float*>(bias);
+	GemmParams g = dense_gemm(A, K, m, M, C, 1);
+	g.out_scale = out_scale;
 	launch_gemm(dtype, g, (hipStream_t)stream);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;

@@ -16,6 +16,18 @@ enum DType { DT_F32 = 0, DT_BF16 = 1, DT_FP8W = 2, DT_FP8 = 3, DT_F16 = 4 };
 inline int elem_kind(int dt) { return dt == DT_F32 ? 1 : (dt == DT_F16 ? 2 : 0); }      // ttk::ElemKind of a "T-typed" buffer
 inline size_t dtype_size(int dt) { return dt == DT_F32 ? 4 : 2; }
 inline int kernel_dtype(int dt) { return (dt == DT_FP8W || dt == DT_FP8) ? DT_BF16 : dt; }
+// The host code's one dtype ladder: f(T()) with the element type T of a kernel dtype, `using T = decltype(t)` inside f.  by_f32_bf16 is for the handles
+// that take f32 and bf16 only: it instantiates no f16 kernel.
+template <typename F>
+auto by_dtype(int dt, F f) {
+	if (dt == DT_BF16) return f(__bf16());
+	if (dt == DT_F16) return f(_Float16());
+	return f(float());
+}
+template <typename F>
+auto by_f32_bf16(int dt, F f) { return dt == DT_BF16 ? f(__bf16()) : f(float()); }
+// workgroups of a 256-thread launch with one thread per element
+inline unsigned grid_for(int64_t total) { return (unsigned)((total + 255) / 256); }
 
 // ---------------------------------------------------------------- per-kernel timing (ttk_host.hip)
 // When enabled (ttk_prof_begin) every launcher brackets its launch with two HIP events on the launch stream and adds its
@@ -228,8 +240,8 @@ struct AttnParams {
 	unsigned long long* stamps;   // diagnostic build only
 #endif
 };
-// form (host only, never a kernel argument): 0 = the launcher's choice from nb x H x T and the TTK_ATTN_* knobs; 1 = 64-query blocks, 2 = 128-query blocks,
-// 3 = 8 waves x 16 queries, 4 = balanced -- an explicit form overrides the knobs and is legal only where attn_fwd_form_refusal returns null
+// form (host only, never a kernel argument): 0 = the launcher's choice, a function of nb x H x T alone (attn.hip: attn_fwd_choice); 1 = 64-query blocks, 2 = 128-query blocks,
+// 3 = 8 waves x 16 queries, 4 = balanced -- an explicit form is legal only where attn_fwd_form_refusal returns null
 void launch_attn_fwd(int dt, const AttnParams& p, hipStream_t s, int form = 0);
 const char* attn_fwd_form_refusal(const AttnParams& p, int form);
 
@@ -253,7 +265,7 @@ struct AttnDecodeParams {
 	unsigned long long* stamps;   // diagnostic build only
 #endif
 };
-// variant (host only): 0 = the default (waves, unroll) shape or what TTK_ATTN_DECODE asks for; 1 = 4 x 4, 2 = 8 x 6 (both bf16 only)
+// variant (host only): 0 = the default (waves, unroll) shape of the dtype; 1 = 4 x 4, 2 = 8 x 6 (both bf16 only)
 void launch_attn_decode(int dt, const AttnDecodeParams& p, hipStream_t s, int variant = 0);
 // the position line (csrc/attn.hip): up to 8 decode handles keep {valid cache rows, shared-prefix rows} in one 64-byte line of the code object.  acquire returns the slot
 // (and the device address of its two words), or -1 when all are taken -- the handle then keeps the words in its own allocation and the kernel reads them through d_pos

@@ -204,14 +204,9 @@ struct ttk_univnet {
 
 namespace {
 
-template <typename T>
-void launch_act_t(const ActRows& p, hipStream_t s) {
-	const int64_t total = (int64_t)p.B * (p.L + 2 * p.pad) * p.ldo;
-	hipLaunchKernelGGL((k_act_rows<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
-}
 void launch_act(int dt, const ActRows& p, hipStream_t s) {
-	if (dt == DT_BF16) launch_act_t<bf16>(p, s);
-	else launch_act_t<float>(p, s);
+	const dim3 grid(grid_for((int64_t)p.B * (p.L + 2 * p.pad) * p.ldo));
+	by_f32_bf16(dt, [&](auto t) { hipLaunchKernelGGL((k_act_rows<decltype(t)>), grid, dim3(256), 0, s, p); });
 }
 // channels-last f32 [B * L][C] rows (row stride st, batch stride sb) -> T operand
 ActRows act_cl(const float* src, int64_t sb, int64_t st, int B, int L, int C, int act, int pad, void* outT, int ldo) {
@@ -372,8 +367,7 @@ int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int 
 		launch_act(dt, act_cl(x, (int64_t)L * C, C, B, L, C, 1, 0, at, lda), s);                     // lrelu(x), first layer's operand
 		for (int n = 0; n < c.n_layers; ++n) {
 			conv_same(dt, at, lda, blk.conv[n], 3, c.dilations[n], M, L, nullptr, y, 1, s);                    // y = conv_d(lrelu(x)), f32
-			if (dt == DT_BF16) launch_lvc_t<bf16>(C, y, kern, kb, x, at, B, L, cond_hop, T1, n, kst, bst, lda, s);
-			else launch_lvc_t<float>(C, y, kern, kb, x, at, B, L, cond_hop, T1, n, kst, bst, lda, s);
+			by_f32_bf16(dt, [&](auto t) { launch_lvc_t<decltype(t)>(C, y, kern, kb, x, at, B, L, cond_hop, T1, n, kst, bst, lda, s); });
 		}
 		// `at` now holds lrelu(x): the next block's convt_pre operand
 	}

@@ -134,14 +134,9 @@ struct ttk_voc {
 
 namespace {
 
-template <typename T>
-void launch_snake_t(const float* x, int L, int C, const Snake& sn, const float* g, void* y, int64_t rows, hipStream_t s) {
-	const int64_t total = rows * (C / 4);
-	hipLaunchKernelGGL((k_snake_aa<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, L, C, sn.a, sn.invb, g, (T*)y, rows);
-}
 void launch_snake(int dt, const float* x, int L, int C, const Snake& sn, const float* g, void* y, int64_t rows, hipStream_t s) {
-	if (dt == DT_BF16) launch_snake_t<bf16>(x, L, C, sn, g, y, rows, s);
-	else launch_snake_t<float>(x, L, C, sn, g, y, rows, s);
+	const dim3 grid(grid_for(rows * (C / 4)));
+	by_f32_bf16(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_snake_aa<T>), grid, dim3(256), 0, s, x, L, C, sn.a, sn.invb, g, (T*)y, rows); });
 }
 
 int upload_snake(Arena& ar, const WeightMap& wm, const std::string& prefix, int C, bool logscale, Snake* out) {
@@ -254,8 +249,7 @@ int ttk_voc_inference(ttk_voc* h, const float* mel, int B, int Tm, float* audio,
 
 	{
 		const int64_t total = (int64_t)B * L0 * mel_ld;
-		if (dt == DT_BF16) hipLaunchKernelGGL((k_voc_mel_in<bf16>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mel, B, c.num_mels, Tm, PAD, -11.5129f, (bf16*)mel_t, mel_ld);
-		else hipLaunchKernelGGL((k_voc_mel_in<float>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, mel, B, c.num_mels, Tm, PAD, -11.5129f, (float*)mel_t, mel_ld);
+		by_f32_bf16(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_voc_mel_in<T>), dim3(grid_for(total)), dim3(256), 0, s, mel, B, c.num_mels, Tm, PAD, -11.5129f, (T*)mel_t, mel_ld); });
 	}
 	conv_same(dt, mel_t, mel_ld, h->conv_pre, 7, 1, B * L0, L0, nullptr, xt, 0, s);      // conv_pre -> T [B*L0][ch0]
 	int L = L0, ch = c.ch0;
@@ -277,9 +271,7 @@ int ttk_voc_inference(ttk_voc* h, const float* mel, int B, int Tm, float* audio,
 		}
 		{
 			const int64_t total = (int64_t)M * ch;
-			const unsigned grid = (unsigned)((total + 255) / 256);
-			if (dt == DT_BF16) hipLaunchKernelGGL((k_voc_mean<bf16>), dim3(grid), dim3(256), 0, s, xb[0], xb[1], xb[2], xb[3], c.n_kernels, y, (bf16*)xt, total);
-			else hipLaunchKernelGGL((k_voc_mean<float>), dim3(grid), dim3(256), 0, s, xb[0], xb[1], xb[2], xb[3], c.n_kernels, y, (float*)xt, total);
+			by_f32_bf16(dt, [&](auto t) { using T = decltype(t); hipLaunchKernelGGL((k_voc_mean<T>), dim3(grid_for(total)), dim3(256), 0, s, xb[0], xb[1], xb[2], xb[3], c.n_kernels, y, (T*)xt, total); });
 		}
 	}
 	const int M = B * L;
