@@ -275,6 +275,26 @@ int ttk_ar_latents(ttk_ar* h, const float* cond, const int64_t* text, int Tt, co
 int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, float* loss_out,
 				 float* nll_text_out, float* nll_mel_out, float* text_logits_out, float* mel_logits_out, void* stream);
 
+/* Run-time LoRA adapters on a live handle (the reference: TTS.enable_lora / disable_lora, inference.py:99-104, and the weight parametrization
+ * W + (lora_B lora_A) * alpha / rank of models/lora.py:120-123, 136-145).  The adapted matrices are the 4 x layers HF Conv1D weights
+ * gpt.h.<l>.{attn.c_attn, attn.c_proj, mlp.c_fc, mlp.c_proj}.weight, [K_in][N_out]; lora_B is [K_in][rank], lora_A [rank][N_out].
+ *
+ * The init call (once, after create; `weights` as given to create, host or device) keeps f32 masters of those matrices plus scratch for one of them
+ *   in the handle: 12 d^2 layers 4 bytes (1.51 GB at d = 1024, 30 layers).  TTK_FP8W handles are refused (TTK_E_ARG): their per-matrix scale follows
+ *   the adapted matrix.  A handle that never makes this call is what it was before the call existed.
+ * The set call makes the handle compute with W0 + (lora_B lora_A) * scaling for every module whose pair is among `adapters`, and with W0 for every
+ *   other one; n == 0 detaches everything.  adapters[i].name is "<module>.lora_A" / "<module>.lora_B" (module as above, without ".weight"),
+ *   .data an f32 DEVICE pointer that stays valid until the work enqueued here has run, .shape the two sizes; rank 1..256.
+ *   Arithmetic, per element: acc = 0; for r rising: acc = acc + lora_B[k][r] * lora_A[r][n], product and sum each rounded to f32 (no fused multiply-add);
+ *   W' = W0 + acc * scaling, again two roundings.  A plain f32 loop on the host reproduces the bits, and the packed operands are written by the launches
+ *   create uses: a switched handle computes bit for bit what a handle created from the host-folded weights computes.
+ *   Only enqueues on `stream`: no allocation, no synchronisation, operands rewritten in place (a captured token step stays valid) and only for matrices
+ *   that are or become adapted.  The caller must not switch while a generation is between its prefill and its last step.
+ *   Every view is checked before the first launch; TTK_E_ARG / TTK_E_WEIGHT name the tensor: no init call before, half a pair, a module outside the
+ *   4 x layers, a shape that does not fit, rank > 256.  After a refusal the handle is unchanged.                                              */
+int ttk_ar_lora_init(ttk_ar* h, const ttk_weight_view* weights, int n_w);
+int ttk_ar_lora_set(ttk_ar* h, const ttk_weight_view* adapters, int n, float scaling, void* stream);
+
 /* Row cross-entropy on its own (csrc/xent.hip), F.cross_entropy(reduction="none") of f32 logits [rows][ld] whose first C columns are valid
  * (columns [C, ld) are never read) against int64 target [rows]:  nll_out[r] = logsumexp(x_r) - x_r[target[r]], the maximum subtracted before
  * the exponential, one pass over the row.  A target outside [0, C) gives NaN for that row and reads nothing.

@@ -5,7 +5,7 @@ from .weights import ARConfig, ClassifierConfig, CLVPConfig, DiffusionConfig, DV
 
 __all__ = ["ARConfig", "DiffusionConfig", "UnifiedVoice", "DiffusionTTS", "get_diffuser", "denormalize_tacotron_mel",
 		   "load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_random_latent_generator", "load_classifier", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder", "BigVGAN", "UnivNet", "HiFiGAN", "DiscreteVAE", "RandomLatentConverter", "AudioMiniEncoderWithClassifierHead", "CLVP",
-		   "VocoderConfig", "UnivNetConfig", "HiFiGANConfig", "DVAEConfig", "ClassifierConfig", "CLVPConfig", "ConditioningEncoder", "ContextualEmbedder", "TorchMelSpectrogram", "TacotronSTFT", "VoiceBpeTokenizer", "TTS"]
+		   "VocoderConfig", "UnivNetConfig", "HiFiGANConfig", "DVAEConfig", "ClassifierConfig", "CLVPConfig", "ConditioningEncoder", "ContextualEmbedder", "TorchMelSpectrogram", "TacotronSTFT", "VoiceBpeTokenizer", "TTS", "read_lora", "normalize_lora"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need the built library (CPU-side tools, oracle, weights)
@@ -51,7 +51,7 @@ def __getattr__(name):   # lazy: importing the package must not need the built l
 	if name == "mel":
 		import importlib
 		return importlib.import_module(".mel", __name__)
-	if name in ("load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_dvae_state", "load_random_latent_generator", "load_rlg_state", "load_classifier", "load_classifier_state", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder"):
+	if name in ("load_autoregressive", "load_diffusion", "load_bigvgan", "load_univnet", "load_hifigan", "load_dvae", "load_dvae_state", "load_random_latent_generator", "load_rlg_state", "load_classifier", "load_classifier_state", "load_clvp", "load_conditioning_encoder", "load_contextual_embedder", "read_lora", "normalize_lora"):
 		from . import checkpoint
 		return getattr(checkpoint, name)
 	raise AttributeError(name)

@@ -145,6 +145,8 @@ SYMBOLS = {
 	"ttk_sample_step_warped": (_I, [C.POINTER(SampleArgs), _P]),
 	"ttk_ar_latents": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
 	"ttk_ar_score": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+	"ttk_ar_lora_init": (_I, [_P, C.POINTER(WeightView), _I]),
+	"ttk_ar_lora_set": (_I, [_P, C.POINTER(WeightView), _I, C.c_float, _P]),
 	"ttk_xent_rows": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _P]),
 	"ttk_voc_create": (_I, [C.POINTER(_P), _P, C.POINTER(WeightView), _I]),
 	"ttk_voc_destroy": (_I, [_P]),

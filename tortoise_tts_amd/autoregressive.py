@@ -90,11 +90,22 @@ def score_inputs(cfg: ARConfig, text_inputs, text_lengths, mel_codes, wav_length
 	return text, codes, pad(text, (0, 2), value=cfg.stop_text_token), pad(codes, (0, 2), value=cfg.stop_mel_token)
 
 
+LORA_MAX_RANK = 256      # csrc/ar.hip: ttk_ar_lora_set
+
+
+def lora_modules(cfg: ARConfig) -> Tuple[str, ...]:
+	"""the 4 x layers HF Conv1D modules run-time adapters attach to (include/ttk.h: ttk_ar_lora_init)"""
+	return tuple(f"gpt.h.{l}.{m}" for l in range(cfg.layers) for m in ("attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj"))
+
+
 class UnifiedVoice(_lib.Handle):
 	def __init__(self, state_dict: Dict[str, torch.Tensor], cfg: ARConfig = ARConfig(), dtype: str = "bf16",
 				 device: str = "cuda:0", max_batch: int = 16, max_ctx: Optional[int] = None, use_graph: bool = True,
-				 hf_exact_top_p: bool = False):
-		"""hf_exact_top_p: run HF's TopPLogitsWarper as torch ops in front of the sampling kernel when top_p < 1 (its f32 cumsum rounding, bit for
+				 hf_exact_top_p: bool = False, adapters: bool = False):
+		"""adapters: keep f32 masters of the GPT-2 block matrices on the device (12 * model_dim^2 * layers * 4 bytes) so that LoRA adapters can be attached,
+		swapped and detached on the live handle (`load_lora` / `enable_lora` / `disable_lora`); not available with fp8 weights.  Off: the handle is what it
+		always was, and an adapter is folded into the weights before they get here (checkpoint.materialize_lora).
+		hf_exact_top_p: run HF's TopPLogitsWarper as torch ops in front of the sampling kernel when top_p < 1 (its f32 cumsum rounding, bit for
 		bit) instead of the kernel's exact fixed-point cut -- the two differ only on rows whose cumulative mass ties with 1 - top_p within f32
 		rounding (csrc/sample.hip; tests/test_gpu_parity.py::test_top_p_boundary_stress); costs the per-token torch launches the kernel removed."""
 		self.hf_exact_top_p = hf_exact_top_p
@@ -123,6 +134,13 @@ class UnifiedVoice(_lib.Handle):
 						   cfg.number_text_tokens + 1, cfg.number_mel_codes, cfg.start_text_token, cfg.stop_text_token,
 						   cfg.start_mel_token, cfg.stop_mel_token, self.dtype, max_batch, self.max_ctx)
 		self._create("ar", c, state_dict, names)
+		self._adapters, self._loras, self.active_lora = bool(adapters), {}, None
+		if adapters:
+			mats = lora_modules(cfg)
+			views, keep = _lib.weight_views(state_dict, [m + ".weight" for m in mats])
+			with torch.cuda.device(self.device):
+				_lib.check(self.lib.ttk_ar_lora_init(self._h, views, len(mats)), "ttk_ar_lora_init")
+			del keep
 		self._states: Dict[tuple, "_GenState"] = {}
 		self._prefix = None
 		self._streaming = False          # a streamed generation is open on this handle (its KV cache, noise and latent ring belong to it)
@@ -433,6 +451,78 @@ class UnifiedVoice(_lib.Handle):
 		reference's module is re-entrant because HF keeps all of that per call); starting another one would corrupt both silently, so it is refused"""
 		if self._streaming:
 			raise _lib.TTKError("a streamed generation is still open on this model: exhaust or close() its generator before starting another generation")
+
+	# ------------------------------------------------------------------ run-time LoRA adapters (inference.py:99-104, 204-216; models/lora.py:120-145)
+	def _require_adapters(self):
+		if not getattr(self, "_adapters", False):
+			raise _lib.TTKError("this model was built without adapters=True: it keeps no f32 masters to attach an adapter to (build it with "
+								"UnifiedVoice(..., adapters=True) or load_autoregressive(..., adapters=True); without it a LoRA file is folded in at load time)")
+
+	def load_lora(self, name: str, tensors_or_path, scaling: Optional[float] = None):
+		"""Read an adapter (a LoRA file as `TTS` reads it, or a dict of its tensors), check it against this model and keep it on the device under `name`;
+		`enable_lora(name)` attaches it.  Keys as in `checkpoint.normalize_lora`; scaling: the argument, else the file's alpha / rank, else 1.0 (the
+		reference's default adapter has alpha == rank).  Loading under the name of the enabled adapter re-attaches the new tensors."""
+		from .checkpoint import CheckpointError, normalize_lora, read_lora
+		self._require_adapters()
+		file_scaling = None
+		if isinstance(tensors_or_path, (str, os.PathLike)):
+			tensors, file_scaling = read_lora(tensors_or_path)
+		else:
+			tensors = dict(tensors_or_path)
+		shapes = ar_shapes(self.cfg)
+		known = lora_modules(self.cfg)
+		flat = {}
+		for mod, (A, Bm) in normalize_lora(tensors).items():
+			if mod not in known:
+				raise CheckpointError(f"'{mod}': adapters attach at run time to gpt.h.<layer>.{{attn.c_attn, attn.c_proj, mlp.c_fc, mlp.c_proj}} of the "
+									  f"{self.cfg.layers} layers only; fold an adapter on another module at load time (materialize_lora)")
+			K, N = shapes[mod + ".weight"]
+			rank = int(A.shape[0])
+			if tuple(Bm.shape) != (K, rank) or tuple(A.shape) != (rank, N):
+				raise CheckpointError(f"'{mod}': lora shapes {tuple(Bm.shape)} x {tuple(A.shape)} do not match weight {(K, N)}")
+			if not 1 <= rank <= LORA_MAX_RANK:
+				raise CheckpointError(f"'{mod}': rank {rank} is outside 1..{LORA_MAX_RANK}")
+			flat[mod + ".lora_A"], flat[mod + ".lora_B"] = A, Bm
+		s = float(scaling if scaling is not None else (file_scaling if file_scaling is not None else 1.0))
+		dev = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in flat.items()}
+		self._loras.pop(name, None)          # a reloaded name becomes the last loaded
+		self._loras[name] = (dev, s)
+		if self.active_lora == name:
+			self.enable_lora(name)
+
+	def _lora_set(self, tensors: Dict[str, torch.Tensor], scaling: float):
+		"""include/ttk.h: ttk_ar_lora_set on named f32 device tensors (`<module>.lora_A` / `<module>.lora_B`); none = every matrix back to its base"""
+		_lib.require_cuda(*tensors.values())
+		for k, t in tensors.items():
+			if t.dtype != torch.float32:
+				raise _lib.TTKError(f"'{k}' is {t.dtype}: adapter tensors go to the device as f32")
+		names = list(tensors)
+		views, keep = _lib.weight_views(tensors, names)
+		with torch.cuda.device(self.device):
+			_lib.check(self.lib.ttk_ar_lora_set(self._h, views if names else None, len(names), float(scaling), _lib.stream_ptr()), "ttk_ar_lora_set")
+		del keep
+
+	def enable_lora(self, name: Optional[str] = None):
+		"""Attach a loaded adapter (None: the only or the last-loaded one): every matrix it covers computes with W + (lora_B lora_A) * scaling from here on,
+		every other one with its base weight -- also those a previously enabled adapter covered.  Refused while a streamed generation is open."""
+		self._require_adapters()
+		self._require_idle()
+		if name is None:
+			if not self._loras:
+				raise _lib.TTKError("no adapter is loaded: call load_lora(name, tensors_or_path) first")
+			name = next(reversed(self._loras))
+		if name not in self._loras:
+			raise _lib.TTKError(f"no adapter named {name!r} is loaded (loaded: {sorted(self._loras)})")
+		tensors, scaling = self._loras[name]
+		self._lora_set(tensors, scaling)
+		self.active_lora = name
+
+	def disable_lora(self):
+		"""Detach: every matrix back to its base weight, bit for bit what a model built without adapters computes."""
+		self._require_adapters()
+		self._require_idle()
+		self._lora_set({}, 1.0)
+		self.active_lora = None
 
 	def compute_embeddings(self, cond_latents, text_inputs, kv_cache=True):
 		"""unified_voice.py:614-630: remembers the prefix, returns the fake id row [b, P+1]."""

@@ -165,6 +165,40 @@ def materialize_lora(state_dict: Mapping[str, torch.Tensor], lora: Optional[Mapp
 	return merged
 
 
+def normalize_lora(tensors: Mapping[str, torch.Tensor]) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+	"""Adapter tensors as a LoRA file or a parametrised state_dict names them -> {module: (lora_A [rank, W.shape[1]], lora_B [W.shape[0], rank])}, for
+	adapters attached at run time (`UnifiedVoice.load_lora`).  Keys are read as `materialize_lora` reads them: `<m>.parametrizations.weight.<i>.lora_{A,B}`
+	and `<m>.lora_{A,B}`; entries without `lora_` in their name (base weights, `...original`) are passed over.  One adapter per module: a file that
+	stacks several parametrization indices on one module is refused here by name (`materialize_lora`, the load-time fold, handles it), as is half a pair."""
+	parts: Dict[str, Dict[Tuple[int, str], torch.Tensor]] = {}
+	for k, v in tensors.items():
+		m = _PARAM_LORA.match(k)
+		idx = int(m["idx"]) if m else -1
+		m = m or _PLAIN_LORA.match(k)
+		if not m:
+			if "lora_" in k:
+				raise CheckpointError(f"'{k}': not an adapter tensor name (<module>.parametrizations.weight.<i>.lora_A|lora_B or <module>.lora_A|lora_B)")
+			continue
+		if not isinstance(v, torch.Tensor) or not v.dtype.is_floating_point:
+			raise CheckpointError(f"'{k}': adapter tensors are floating-point tensors (got {getattr(v, 'dtype', type(v).__name__)})")
+		parts.setdefault(m["mod"], {})[(idx, m["which"])] = v
+	out = {}
+	for mod, p in parts.items():
+		indices = sorted({i for i, _ in p})
+		if len(indices) > 1:
+			raise CheckpointError(f"'{mod}': {len(indices)} stacked adapters (parametrization indices {indices}) on one module cannot be attached at run time; "
+								  f"fold them at load time (materialize_lora / load_autoregressive without adapters=True)")
+		A, Bm = p.get((indices[0], "A")), p.get((indices[0], "B"))
+		if A is None or Bm is None:
+			raise CheckpointError(f"'{mod}': lora_A / lora_B are not both present")
+		if A.dim() != 2 or Bm.dim() != 2 or Bm.shape[1] != A.shape[0]:
+			raise CheckpointError(f"'{mod}': lora_B {tuple(Bm.shape)} x lora_A {tuple(A.shape)} is not a [K, rank] x [rank, N] pair")
+		out[mod] = (A, Bm)
+	if not out:
+		raise CheckpointError("no 'lora_' tensors among the adapter tensors")
+	return out
+
+
 def _count_layers(sd: Mapping[str, torch.Tensor], pattern: str) -> int:
 	rx = re.compile(pattern)
 	idx = {int(m.group(1)) for k in sd for m in [rx.match(k)] if m}
@@ -244,14 +278,24 @@ def load_diffusion_state(path, *, cfg: Optional[DiffusionConfig] = None, state_d
 	return out, cfg
 
 
-def load_autoregressive(path, lora_path=None, *, dtype="bf16", device="cuda", max_batch=16, max_ctx=None, scoring=False, **kw):
+def load_autoregressive(path, lora_path=None, *, dtype="bf16", device="cuda", max_batch=16, max_ctx=None, scoring=False, adapters=False, **kw):
 	"""The counterpart of `load_model("autoregressive")` + the LoRA block of `TTS.__init__` (models/__init__.py:104-110,163-167;
 	inference.py:204-216) returning the libttk-backed `UnifiedVoice`.  `scoring=True` keeps the text head: the model then also computes the
-	teacher-forced losses (`forward(..., return_latent=False)`)."""
+	teacher-forced losses (`forward(..., return_latent=False)`).  `adapters=True`: the base weights are uploaded unmerged and the model can attach,
+	swap and detach adapters afterwards (`UnifiedVoice.load_lora` / `enable_lora` / `disable_lora`); `lora_path`, if given, is loaded as "lora" and
+	enabled.  The default folds `lora_path` into the weights on the host, once."""
 	from .autoregressive import UnifiedVoice
-	sd, cfg = load_autoregressive_state(path, lora_path, scoring=scoring, **kw)
 	extra = {} if max_ctx is None else {"max_ctx": max_ctx}
-	return UnifiedVoice(sd, cfg, dtype=dtype, device=device, max_batch=max_batch, **extra)
+	if not adapters:
+		sd, cfg = load_autoregressive_state(path, lora_path, scoring=scoring, **kw)
+		return UnifiedVoice(sd, cfg, dtype=dtype, device=device, max_batch=max_batch, **extra)
+	lora_scaling = kw.pop("lora_scaling", None)
+	sd, cfg = load_autoregressive_state(path, None, scoring=scoring, **kw)
+	model = UnifiedVoice(sd, cfg, dtype=dtype, device=device, max_batch=max_batch, adapters=True, **extra)
+	if lora_path is not None:
+		model.load_lora("lora", lora_path, scaling=lora_scaling)
+		model.enable_lora("lora")
+	return model
 
 
 def load_diffusion(path, *, dtype="bf16", device="cuda", codes: Optional[bool] = None, **kw):

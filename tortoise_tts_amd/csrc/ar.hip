@@ -125,6 +125,13 @@ struct ttk_ar {
 	WsBuf ws_score;         // ttk_ar_score: row-major logits of both heads, targets, nll rows
 	int B = 0, P = 0, k = 0, ready = 0;
 	int Pmax = 0;           // longest prefix of the batch (capacity checks); == P for one line
+	// run-time adapters (ttk_ar_lora_init / ttk_ar_lora_set): f32 masters of the 4 x layers block matrices, index 4 l + {0 c_attn, 1 attn.c_proj, 2 c_fc, 3 mlp.c_proj},
+	// one f32 scratch of 4d x d, one T-typed scratch for the folded matrix, and which matrices currently hold an adapted copy
+	bool lora_ready = false;
+	std::vector<float*> lora_master;
+	std::vector<char> lora_adapted;
+	float* lora_scratch = nullptr;
+	void* lora_wt = nullptr;
 	~ttk_ar() { attn_pos_slot_release(pos_slot); }      // also the failure path of ttk_ar_create; the workspaces and the arena free themselves after this
 };
 
@@ -640,6 +647,125 @@ int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, cons
 		launch_xent_rows(q.lg, q.ld, q.rows, q.C, q.tg, q.nll, loss_out ? loss_out + i : nullptr, q.out_t, q.T, s);
 	}
 	TTK_TRY(poison_scratch(h, s));
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ run-time LoRA adapters
+// The reference attaches its adapter as a weight parametrization and evaluates W + (B A) s on every forward (models/lora.py:120-123; inference.py:99-104,
+// 204-216).  Here the packed operands of a matrix are rebuilt on the device from a resident f32 master: the update kernel (lora.hip) into the scratch, then
+// pack_mat / pack_fold -- the launches ttk_ar_create ran -- into the buffers the handle already has.  Nothing a captured token step points at moves.
+namespace {
+
+constexpr int LORA_MAX_RANK = 256;
+const char* const LORA_MODULES[4] = {"attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj"};
+
+std::string lora_module(int idx) { return "gpt.h." + std::to_string(idx / 4) + "." + LORA_MODULES[idx % 4]; }
+Mat* lora_mat(ttk_ar* h, int idx) {
+	ARLayer& L = h->L[idx / 4];
+	Mat* m[4] = {&L.attn, &L.proj, &L.fc, &L.proj2};
+	return m[idx % 4];
+}
+struct LoraPair { const ttk_weight_view *A = nullptr, *B = nullptr; };
+
+}  // namespace
+
+extern "C" {
+
+int ttk_ar_lora_init(ttk_ar* h, const ttk_weight_view* w, int n_w) {
+	TTK_REQUIRE(h && w && n_w > 0, TTK_E_ARG, "ttk_ar_lora_init: null argument");
+	TTK_REQUIRE(h->wdt != DT_FP8W, TTK_E_ARG, "ttk_ar_lora_init: run-time adapters are not implemented for dtype TTK_FP8W: the fp8 scale of a matrix follows the adapted "
+				"matrix's absmax, whose reduction synchronises; fold the adapter at load time instead (f32, bf16 and f16 handles take adapters)");
+	TTK_REQUIRE(!h->lora_ready, TTK_E_STATE, "ttk_ar_lora_init: this handle holds its adapter masters already");
+	WeightMap wm(w, n_w);
+	const int d = h->cfg.model_dim, nm = 4 * h->cfg.layers;
+	for (int i = 0; i < nm; ++i) {      // everything is checked before the first allocation
+		const std::string name = lora_module(i) + ".weight";
+		const ttk_weight_view* v = wm.find(name);
+		const Mat* m = lora_mat(h, i);
+		TTK_REQUIRE(v != nullptr, TTK_E_WEIGHT, "ttk_ar_lora_init: missing weight '%s'", name.c_str());
+		TTK_REQUIRE(numel(v) == (int64_t)m->N * m->K, TTK_E_WEIGHT, "ttk_ar_lora_init: weight '%s' has %lld elements, expected %lld", name.c_str(), (long long)numel(v),
+					(long long)m->N * m->K);
+	}
+	std::vector<float*> master(nm, nullptr);
+	for (int i = 0; i < nm; ++i) {
+		const Mat* m = lora_mat(h, i);
+		const size_t bytes = (size_t)m->N * m->K * sizeof(float);
+		TTK_TRY(h->arena.alloc((void**)&master[i], bytes));
+		TTK_HIP(hipMemcpy(master[i], wm.find(lora_module(i) + ".weight")->data, bytes, hipMemcpyDefault));
+	}
+	TTK_TRY(h->arena.alloc((void**)&h->lora_scratch, (size_t)4 * d * d * sizeof(float)));
+	TTK_TRY(h->arena.alloc(&h->lora_wt, (size_t)round_up(4 * d, 128) * d * h->es));      // the largest Npad x Kpad: c_fc
+	h->lora_master.swap(master);
+	h->lora_adapted.assign(nm, 0);
+	h->lora_ready = true;
+	return TTK_OK;
+}
+
+int ttk_ar_lora_set(ttk_ar* h, const ttk_weight_view* adapters, int n, float scaling, void* stream) {
+	TTK_REQUIRE(h && n >= 0 && (adapters || n == 0), TTK_E_ARG, "ttk_ar_lora_set: null argument");
+	TTK_REQUIRE(h->lora_ready, TTK_E_ARG, "ttk_ar_lora_set: this handle keeps no adapter masters: call ttk_ar_lora_init after ttk_ar_create "
+				"(UnifiedVoice(..., adapters=True)) before attaching or detaching adapters");
+	TTK_REQUIRE(n == 0 || (scaling == scaling && scaling - scaling == 0.f), TTK_E_ARG, "ttk_ar_lora_set: scaling %g is not finite", (double)scaling);
+	const int nm = 4 * h->cfg.layers;
+	// all or nothing: every view is checked before the first launch
+	std::map<std::string, int> index;
+	for (int i = 0; i < nm; ++i) index[lora_module(i)] = i;
+	std::vector<LoraPair> plan(nm);
+	for (int i = 0; i < n; ++i) {
+		const ttk_weight_view* v = &adapters[i];
+		TTK_REQUIRE(v->name && v->data, TTK_E_ARG, "ttk_ar_lora_set: adapter tensor %d has no name or no data", i);
+		const std::string name = v->name;
+		const size_t cut = name.size() > 7 ? name.size() - 7 : 0;
+		const std::string tail = name.substr(cut);
+		TTK_REQUIRE(tail == ".lora_A" || tail == ".lora_B", TTK_E_WEIGHT, "ttk_ar_lora_set: '%s' is not named <module>.lora_A or <module>.lora_B", name.c_str());
+		const auto it = index.find(name.substr(0, cut));
+		TTK_REQUIRE(it != index.end(), TTK_E_WEIGHT, "ttk_ar_lora_set: '%s': run-time adapters attach to gpt.h.<layer>.{attn.c_attn, attn.c_proj, mlp.c_fc, mlp.c_proj} "
+					"of the %d layers only (other modules: fold the adapter at load time)", name.c_str(), h->cfg.layers);
+		const ttk_weight_view*& slot = tail == ".lora_A" ? plan[it->second].A : plan[it->second].B;
+		TTK_REQUIRE(slot == nullptr, TTK_E_WEIGHT, "ttk_ar_lora_set: '%s' is given twice", name.c_str());
+		TTK_REQUIRE(v->ndim == 2, TTK_E_WEIGHT, "ttk_ar_lora_set: '%s' has %d dimensions, expected 2", name.c_str(), v->ndim);
+		slot = v;
+	}
+	for (int i = 0; i < nm; ++i) {
+		const LoraPair& p = plan[i];
+		if (!p.A && !p.B) continue;
+		const std::string mod = lora_module(i);
+		TTK_REQUIRE(p.A && p.B, TTK_E_WEIGHT, "ttk_ar_lora_set: '%s.lora_%s' is given without '%s.lora_%s': an adapter is the pair", mod.c_str(), p.A ? "A" : "B", mod.c_str(),
+					p.A ? "B" : "A");
+		const Mat* m = lora_mat(h, i);
+		const int64_t r = p.A->shape[0];
+		TTK_REQUIRE(r >= 1 && r <= LORA_MAX_RANK, TTK_E_WEIGHT, "ttk_ar_lora_set: '%s.lora_A' has rank %lld: ranks 1..%d are supported", mod.c_str(), (long long)r, LORA_MAX_RANK);
+		TTK_REQUIRE(p.A->shape[1] == m->N, TTK_E_WEIGHT, "ttk_ar_lora_set: '%s.lora_A' is [%lld, %lld], expected [rank, %d] for the weight [%d, %d]", mod.c_str(), (long long)r,
+					(long long)p.A->shape[1], m->N, m->K, m->N);
+		TTK_REQUIRE(p.B->shape[0] == m->K && p.B->shape[1] == r, TTK_E_WEIGHT, "ttk_ar_lora_set: '%s.lora_B' is [%lld, %lld], expected [%d, %lld] for the weight [%d, %d] and rank %lld",
+					mod.c_str(), (long long)p.B->shape[0], (long long)p.B->shape[1], m->K, (long long)r, m->K, m->N, (long long)r);
+	}
+	hipStream_t s = (hipStream_t)stream;
+	for (int i = 0; i < nm; ++i) {
+		const LoraPair& p = plan[i];
+		const bool adapt = p.A != nullptr;
+		if (!adapt && !h->lora_adapted[i]) continue;      // base before, base after: its operands are what they should be
+		Mat* m = lora_mat(h, i);
+		const ARLayer& L = h->L[i / 4];
+		const bool folded = m->wfrag_fold != nullptr;
+		const float* src = h->lora_master[i];
+		if (adapt) {
+			launch_lora_update(h->lora_master[i], p.B->data, p.A->data, m->K, m->N, (int)p.A->shape[0], scaling, h->lora_scratch, s);
+			src = h->lora_scratch;
+		} else if (folded) {      // pack_fold scales its source in place: the master stays as it is
+			TTK_HIP(hipMemcpyAsync(h->lora_scratch, h->lora_master[i], (size_t)m->N * m->K * sizeof(float), hipMemcpyDeviceToDevice, s));
+			src = h->lora_scratch;
+		}
+		pack_mat(h->wdt, src, PK_KN, *m, s);
+		if (folded) {
+			const bool first = i % 4 == 0;      // c_attn behind ln_1, c_fc behind ln_2
+			pack_fold(h->dt, h->lora_scratch, first ? L.ln1_g : L.ln2_g, first ? L.ln1_b : L.ln2_b, m->bias, h->lora_wt, *m, s);
+		}
+		h->lora_adapted[i] = adapt;
+	}
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

@@ -84,7 +84,17 @@ __global__ void k_bias_fold(const float* w, const float* beta, const float* b, i
 	const int n = blockIdx.x * blockDim.x + threadIdx.x;
 	if (n >= N) return;
 	double acc = b ? (double)b[n] : 0.0;
-	for (int k = 0; k < K; ++k) acc += (double)beta[k] * (double)w[(int64_t)k * N + n];
+	// acc = fma(beta[k], w[k][n], acc) in rising k -- the fused form the plain loop `acc += beta[k] * w[k][n]` has always compiled to, spelled out so that
+	// the sum keeps its bits while sixteen loads are in flight per wait (one load per wait cost 0.25 ms per matrix: most of an adapter switch, ttk_ar_lora_set)
+	int k = 0;
+	for (; k + 16 <= K; k += 16) {
+		float wv[16];
+#pragma unroll
+		for (int u = 0; u < 16; ++u) wv[u] = w[(int64_t)(k + u) * N + n];
+#pragma unroll
+		for (int u = 0; u < 16; ++u) acc = fma((double)beta[k + u], (double)wv[u], acc);
+	}
+	for (; k < K; ++k) acc = fma((double)beta[k], (double)w[(int64_t)k * N + n], acc);
 	out[n] = (float)acc;
 }
 void launch_bias_fold(const float* w, const float* beta, const float* b, int K, int N, float* out, hipStream_t s) {

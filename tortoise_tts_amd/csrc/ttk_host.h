@@ -111,6 +111,12 @@ int upload_mat(Arena& ar, const WeightMap& wm, int dt, const std::string& wname,
 int fold_layernorm(Arena& ar, const WeightMap& wm, int dt, const std::string& wname, const std::string& bname, const std::string& gname,
 				   const std::string& betaname, Mat* m);
 
+// The launches of the two above on buffers that exist (no allocation, no synchronisation; `s` ordered): create and ttk_ar_lora_set share them.
+//   pack_mat:  device f32 `src` in `layout` -> m.w and, where there is one, m.wfrag (fp8 weights: `src` is rounded already, m.wscale set)
+//   pack_fold: device f32 [K][N] `w` (scaled by gamma IN PLACE) -> m.wfrag_fold, m.csum, m.bias_fold; `wt` is T-typed scratch of Npad x Kpad elements
+void pack_mat(int dt, const float* src, int layout, const Mat& m, hipStream_t s);
+void pack_fold(int dt, float* w, const float* gamma, const float* beta, const float* bias, void* wt, const Mat& m, hipStream_t s);
+
 // ---- the weight-streaming launches of the decode step, each described once (ar.hip).  The handle's token step and ttk_gemv_launch (kernel tests on
 // caller-provided operands) both go through decode_launch: ONE place chooses the kernel family and the waves per workgroup.
 enum DecodeRole { DR_QKV = 0, DR_PROJ, DR_FC, DR_PROJ2, DR_HEAD };      // ln_1 + c_attn, c_proj + residual, ln_2 + c_fc + gelu_new, mlp.c_proj + residual, mel_head

@@ -23,6 +23,26 @@ int upload_f32(Arena& ar, const WeightMap& wm, const std::string& name, int64_t 
 	return TTK_OK;
 }
 
+// The launches behind upload_mat and fold_layernorm, on buffers that exist: what ttk_ar_create runs once per matrix and ttk_ar_lora_set (ar.hip) runs again,
+// on the same Mat, whenever an adapter is attached or detached -- one routine, so that a switched matrix has the bits of a created one.
+void pack_mat(int dt, const float* src, int layout, const Mat& m, hipStream_t s) {
+	const int kdt = kernel_dtype(dt);
+	if (dt == DT_FP8) launch_pack_nk_f8(src, layout, m.N, m.K, m.Npad, m.Kpad, m.wscale, m.w, s, m.ntap);
+	else launch_pack_nk(kdt, src, layout, m.N, m.K, m.Npad, m.Kpad, m.w, s, m.ntap);
+	if (m.wfrag) {
+		if (m.w8) launch_pack_frag_fp8(m.w, m.Npad, m.Kpad, m.wscale, m.wfrag, s);
+		else launch_pack_frag(kdt, m.w, m.Npad, m.Kpad, m.wfrag, s);
+	}
+}
+void pack_fold(int dt, float* w, const float* gamma, const float* beta, const float* bias, void* wt, const Mat& m, hipStream_t s) {
+	if (m.w8) launch_fp8_roundtrip(w, (int64_t)m.N * m.K, m.wscale, s);
+	launch_bias_fold(w, beta, bias, m.K, m.N, m.bias_fold, s);               // from the unscaled weights
+	launch_scale_kn(w, gamma, m.K, m.N, s);
+	launch_pack_nk(dt, w, PK_KN, m.N, m.K, m.Npad, m.Kpad, wt, s, 1);
+	launch_pack_frag(dt, wt, m.Npad, m.Kpad, m.wfrag_fold, s);
+	launch_rowsum(dt, wt, m.Kpad, m.N, m.K, m.csum, s);
+}
+
 int upload_mat(Arena& ar, const WeightMap& wm, int dt, const std::string& wname, const std::string& bname, int layout,
 			   int N, int K, bool frag, Mat* out, int ntap_in) {
 	const ttk_weight_view* v = wm.find(wname);
@@ -50,17 +70,8 @@ int upload_mat(Arena& ar, const WeightMap& wm, int dt, const std::string& wname,
 	}
 	const size_t wbytes = (size_t)ntap * out->Npad * out->Kpad * es;
 	int rc = ar.alloc(&out->w, wbytes);
-	if (rc == TTK_OK) {
-		if (dt == DT_FP8) launch_pack_nk_f8(tmp, layout, N, K, out->Npad, out->Kpad, out->wscale, out->w, 0, ntap);
-		else launch_pack_nk(kdt, tmp, layout, N, K, out->Npad, out->Kpad, out->w, 0, ntap);
-		if (frag && ntap == 1 && dt != DT_FP8) {
-			rc = ar.alloc(&out->wfrag, w8 ? wbytes / 2 : wbytes);
-			if (rc == TTK_OK) {
-				if (w8) launch_pack_frag_fp8(out->w, out->Npad, out->Kpad, out->wscale, out->wfrag, 0);
-				else launch_pack_frag(kdt, out->w, out->Npad, out->Kpad, out->wfrag, 0);
-			}
-		}
-	}
+	if (rc == TTK_OK && frag && ntap == 1 && dt != DT_FP8) rc = ar.alloc(&out->wfrag, w8 ? wbytes / 2 : wbytes);
+	if (rc == TTK_OK) pack_mat(dt, tmp, layout, *out, 0);
 	e = hipDeviceSynchronize();
 	(void)hipFree(tmp);
 	if (rc != TTK_OK) return rc;
@@ -98,12 +109,7 @@ int fold_layernorm(Arena& ar, const WeightMap& wm, int dt, const std::string& wn
 	// of the ROUNDED matrix, in the kernel arithmetic -- what a bf16 handle built from the rounded weights computes, bit for bit.  The folded
 	// operand is a bf16 matrix (gamma o W^ is not on the fp8 grid): these two launches stream 2 bytes per weight, the decode step being bound by
 	// its launch chain, not by weight bytes
-	if (m->w8) launch_fp8_roundtrip(w, (int64_t)N * K, m->wscale, 0);
-	launch_bias_fold(w, be, b, K, N, m->bias_fold, 0);               // from the unscaled weights
-	launch_scale_kn(w, g, K, N, 0);
-	launch_pack_nk(dt, w, PK_KN, N, K, m->Npad, m->Kpad, wt, 0, 1);
-	launch_pack_frag(dt, wt, m->Npad, m->Kpad, m->wfrag_fold, 0);
-	launch_rowsum(dt, wt, m->Kpad, N, K, m->csum, 0);
+	pack_fold(dt, w, g, be, b, wt, *m, 0);
 	e = hipDeviceSynchronize();
 	cleanup();
 	if (e != hipSuccess) { set_error("fold_layernorm('%s'): %s", wname.c_str(), hipGetErrorString(e)); return TTK_E_HIP; }

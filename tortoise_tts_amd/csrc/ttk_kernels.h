@@ -330,4 +330,9 @@ void launch_scale_kn(float* w, const float* gamma, int K, int N, hipStream_t s);
 void launch_rowsum(int dt, const void* w, int64_t ld, int N, int K, float* out, hipStream_t s);
 void launch_bias_fold(const float* w, const float* beta, const float* b, int K, int N, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- run-time LoRA (lora.hip)
+// out[k][n] = W0[k][n] + (sum_r lora_B[k][r] * lora_A[r][n]) * s, all f32 [K][N] / [K][rank] / [rank][N] row-major; products and sums rounded one by one
+// in rising r (never fused): the bits of tests/lora_ref.py's numpy loop.  rank >= 0 (0 copies W0 + 0); every element is read and written by one thread.
+void launch_lora_update(const float* W0, const float* lora_B, const float* lora_A, int K, int N, int rank, float s, float* out, hipStream_t stream);
+
 }  // namespace ttk

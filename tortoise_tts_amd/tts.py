@@ -39,6 +39,30 @@ class TTS:
 		self.conditioning_encoder, self.contextual_embedder, self.tms, self.stft = conditioning_encoder, contextual_embedder, tms, stft
 		self.device = autoregressive.device
 
+	def _adapter_model(self):
+		ar = self.hot.autoregressive
+		if not getattr(ar, "_adapters", False):
+			raise NotImplementedError("the autoregressive model of this TTS was built without adapters=True (UnifiedVoice(..., adapters=True) or "
+									  "load_autoregressive(..., adapters=True)): adapters cannot be attached, swapped or detached on it; a LoRA file given "
+									  "at load time is folded into its weights")
+		return ar
+
+	def load_lora(self, name: str, path, scaling: Optional[float] = None):
+		"""The LoRA block of the reference's `TTS.__init__` (inference.py:204-216) at any time: read the adapter file (or tensor dict) and keep it on the
+		device under `name`; `enable_lora` attaches it."""
+		self._adapter_model().load_lora(name, path, scaling=scaling)
+
+	def enable_lora(self, enabled: Union[bool, str] = True):
+		"""inference.py:99-101.  True: attach the only / last-loaded adapter; a name: attach that one; False: `disable_lora()`."""
+		ar = self._adapter_model()
+		if isinstance(enabled, str):
+			return ar.enable_lora(enabled)
+		return ar.enable_lora() if enabled else ar.disable_lora()
+
+	def disable_lora(self):
+		"""inference.py:103-104: the base voice again, bit for bit."""
+		self._adapter_model().disable_lora()
+
 	def encode_text(self, text: Union[str, torch.Tensor], language: str = "en") -> torch.Tensor:
 		"""inference.py:104-111 over `tokenize` (data.py:279-282: a list of pieces is joined first)."""
 		if isinstance(text, torch.Tensor):
