@@ -175,6 +175,18 @@ int ttk_sample_step_warped(const ttk_sample_args* a, void* stream);
 int ttk_ar_sample_next(ttk_ar* h, const ttk_sample_args* a, void* stream);
 int ttk_ar_decode_next(ttk_ar* h, float* logits_out, float* hidden_out, void* stream);
 
+/* Greedy search: the same token step with do_sample=False (HF `_sample`, HF:generation/utils.py:2925: `next_tokens = torch.argmax(next_token_scores,
+ * dim=-1)`; the reference's fork has the same line in its greedy branch).  Per row, in HF's order: repetition penalty over history[b, 0 : hist_off + col[b]],
+ * suppress mask, typical_mass (the custom processor of `inference_speech(typical_sampling=True)`; 0 or >= 1 = off), then the argmax of the processed
+ * scores, then the bookkeeping of ttk_sample_step unchanged (finished rows get stop_token; tok, ids, history, col, unfinished, live_rows / all_done).
+ * Exact ties go to the LOWEST index: torch.argmax leaves the order among equal values unspecified, so this is the library's choice, as for ttk_beam_step.
+ * NOT READ: q, ldq, temperature, top_k, top_p -- HF builds no warpers without do_sample (it only warns), and greedy search draws nothing; q may be NULL.
+ * No softmax and no exponentiation except inside the typical warper.  1 <= V <= 9216 (the row is held in registers), else TTK_E_ARG.
+ * ttk_ar_greedy_next is to ttk_greedy_step what ttk_ar_sample_next is to ttk_sample_step_warped: the same launch also writes the next decode step's input
+ * row mel_embedding[tok] + mel_pos_embedding[col + 1], from which ttk_ar_decode_next runs.  Each enqueues one kernel; capturable.                     */
+int ttk_greedy_step(const ttk_sample_args* a, void* stream);
+int ttk_ar_greedy_next(ttk_ar* h, const ttk_sample_args* a, void* stream);
+
 /* The Exp(1) noise of torch.multinomial without torch in the token step.  `q.exponential_(1)` on the GPU is a pure function of (generator seed,
  * generator offset, element index, launch geometry) -- ATen's distribution_nullary_kernel over a Philox4_32_10 state (csrc/ttk_rng.h restates
  * the indexing; the state and the uniform conversion are rocRAND's own header code, as in torch's build).  ttk_ar_set_noise makes the mel-head

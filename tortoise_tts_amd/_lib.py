@@ -140,6 +140,8 @@ SYMBOLS = {
 	"ttk_graph_launch": (_I, [_P, _P]),
 	"ttk_exponential_like_torch": (_I, [_P, _L, _L, _L, _L, _L, _L, _P]),
 	"ttk_ar_sample_next": (_I, [_P, C.POINTER(SampleArgs), _P]),
+	"ttk_ar_greedy_next": (_I, [_P, C.POINTER(SampleArgs), _P]),
+	"ttk_greedy_step": (_I, [C.POINTER(SampleArgs), _P]),
 	"ttk_ar_reorder_cache": (_I, [_P, _P, _P]),
 	"ttk_beam_step": (_I, [C.POINTER(BeamArgs), _P]),
 	"ttk_sample_step_warped": (_I, [C.POINTER(SampleArgs), _P]),

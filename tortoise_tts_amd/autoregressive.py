@@ -15,6 +15,8 @@ What runs where
     (seed 0 on every call) and is left where torch's draws would have left it; typical sampling (rare, off by default)
     runs inside the kernel too since round 3 (sampling.py keeps the torch-op forms for `hf_exact_top_p`).
   * the per-token loop .............................................. here; one HIP-graph replay per token.
+  * greedy search (do_sample false or omitted, num_beams 1) ........ libttk  (csrc/sample.hip: the argmax form of the token step, ttk_ar_greedy_next); the
+    same loop and captured step as sampling, no noise armed, nothing drawn from the generator behind the reseed.
   * beam search (num_beams > 1) ..................................... libttk  (csrc/beam.hip: the beam step -- log-softmax, warpers, the
     multinomial without replacement over num_beams * V, HF's running / finished bookkeeping -- and the in-place KV-cache reorder); the loop
     here enqueues {beam step, reorder, decode} per token and polls the done word.
@@ -261,6 +263,11 @@ class UnifiedVoice(_lib.Handle):
 		"""unified_voice.py:632-668 + the sample branch of `generate` (stream_generator.py:213-639, HF `_sample`).
 		Returns int64 [B, L <= max_generate_length], rows padded with stop_mel_token after their EOS.
 
+		do_sample false or omitted (HF's GenerationConfig default) with num_beams 1 is greedy search: the token is the argmax of the processed scores, exact
+		ties to the lowest index.  repetition_penalty, suppress_tokens and typical_sampling / typical_mass act; temperature, top_k and top_p are ignored with
+		one warning, as HF builds no warpers without do_sample; num_return_sequences must be 1.  `generate` reseeds and then draws nothing: the device
+		generator is left at the offset it had directly behind the reseed, and `last_generate["rng_step"]` is 0.
+
 		candidate_shard=(lo, hi) (no reference counterpart; tortoise_tts_amd/dist.py): sample only candidates lo..hi-1 of the
 		`num_return_sequences`, as one rank of a candidate-sharded run.  RNG contract: the rank draws the multinomial noise of ALL
 		candidates per token (the same Philox stream on every rank: `generate` reseeds to 0) and consumes its own rows, so the ids it
@@ -280,6 +287,11 @@ class UnifiedVoice(_lib.Handle):
 			if typical_sampling:
 				raise NotImplementedError("typical_sampling together with beam search is not implemented (num_beams=1 has it)")
 			return self._beam_generate(speech_conditioning_latent, text_inputs, int(num_beams), num_return_sequences, max_generate_length, hf_generate_kwargs)
+		greedy = not hf_generate_kwargs.get("do_sample", False)
+		if greedy and num_return_sequences != 1:
+			# HF: "Greedy methods without beam search do not support `num_return_sequences` different than 1"; the reference's fork (stream_generator.py):
+			# "num_return_sequences has to be 1 ... when doing greedy search"
+			raise ValueError(f"greedy search (do_sample=False, num_beams=1) does not support `num_return_sequences` different than 1 (got {num_return_sequences})")
 		prompt = None
 		if input_tokens is not None:
 			# Prompted continuation (unified_voice.py:651-656; `TTS.inference` never passes it).  The reference tiles the fake prefix and the prompts to
@@ -295,12 +307,19 @@ class UnifiedVoice(_lib.Handle):
 			if bool((prompt == self.stop_mel_token).any()):
 				raise ValueError("input_tokens must not contain the stop token")
 		# omitted keywords mean HF GenerationConfig defaults in the reference (stream_generator.py:262-276): do_sample False (greedy
-		# search, not on the hot path: TTS.inference always samples, inference.py:336), top_k 50, temperature / top_p / penalty 1
-		if not hf_generate_kwargs.get("do_sample", False):
-			raise NotImplementedError("only the sampling branches (do_sample=True) are implemented; pass do_sample=True")
+		# search; TTS.inference always samples, inference.py:336), top_k 50, temperature / top_p / penalty 1
+		if greedy:
+			self._warn_ignored_warpers(hf_generate_kwargs)
 		gen, _ = self._generate(speech_conditioning_latent, text_inputs, num_return_sequences if prompt is None else prompt.shape[0], max_generate_length,
-								typical_mass if typical_sampling else None, hf_generate_kwargs, stream=False, shard=candidate_shard, prompt=prompt)
+								typical_mass if typical_sampling else None, hf_generate_kwargs, stream=False, shard=candidate_shard, prompt=prompt, greedy=greedy)
 		return gen
+
+	@staticmethod
+	def _warn_ignored_warpers(kw):
+		"""HF's GenerationConfig.validate: sampling-only flags that are set while do_sample is false get a warning and play no part"""
+		given = [f"{k}={kw[k]!r}" for k, default in (("temperature", 1.0), ("top_k", 50), ("top_p", 1.0)) if kw.get(k) is not None and kw[k] != default]
+		if given:
+			warnings.warn(f"`do_sample` is false (greedy search): {', '.join(given)} only act in the sampling branches and are ignored", UserWarning, stacklevel=3)
 
 	def inference_speech_lines(self, speech_conditioning_latent, texts, num_return_sequences=1, max_generate_length=None, **hf_generate_kwargs):
 		"""`inference_speech` for several text lines as ONE decode batch (no reference counterpart: TTS.inference walks its lines one by one,
@@ -309,11 +328,13 @@ class UnifiedVoice(_lib.Handle):
 		bit what `inference_speech(latent, texts[g], ...)` returns -- each row keeps the cache length of its own line, every line draws the same
 		[num_return_sequences, V] multinomial noise (the reference reseeds to 0 per line), and line g is cut where its own last row finished.
 		`self.last_generate_lines[g]` says where the generator stands after line g's sampling in the reference (steps, rng_start, rng_step):
-		a caller that draws per line afterwards (TTSHotPath.inference_lines) re-positions it with `position_rng_after_line(g)`."""
+		a caller that draws per line afterwards (TTSHotPath.inference_lines) re-positions it with `position_rng_after_line(g)`.
+		do_sample false or omitted: greedy search as in `inference_speech`, one row per line (num_return_sequences must be 1, up to max_batch lines)."""
 		if hf_generate_kwargs.get("num_beams", 1) not in (None, 1):
 			raise NotImplementedError("beam search over a batch of lines is not implemented: call inference_speech(num_beams=N) per line")
-		if not hf_generate_kwargs.get("do_sample", False):
-			raise NotImplementedError("only the sampling branch (do_sample=True) is implemented; pass do_sample=True")
+		greedy = not hf_generate_kwargs.get("do_sample", False)
+		if greedy and num_return_sequences != 1:
+			raise ValueError(f"greedy search (do_sample=False, num_beams=1) does not support `num_return_sequences` different than 1 (got {num_return_sequences})")
 		texts = list(texts)
 		if any(t.dim() != 2 or t.shape[0] != 1 for t in texts):
 			raise NotImplementedError("texts: a list of [1, Tt] id tensors, one per line")
@@ -331,7 +352,9 @@ class UnifiedVoice(_lib.Handle):
 			return out
 		ts, tm = hf_generate_kwargs.pop("typical_sampling", False), hf_generate_kwargs.pop("typical_mass", .9)
 		typical_mass = tm if ts else None
-		return self._generate_lines(speech_conditioning_latent, texts, num_return_sequences, max_generate_length, hf_generate_kwargs, typical_mass)
+		if greedy:
+			self._warn_ignored_warpers(hf_generate_kwargs)
+		return self._generate_lines(speech_conditioning_latent, texts, num_return_sequences, max_generate_length, hf_generate_kwargs, typical_mass, greedy)
 
 	def position_rng_after_line(self, g: int):
 		"""leave the torch generators as the reference's `generate` on line g alone leaves them (reseeded, advanced by that line's draws)"""
@@ -347,10 +370,12 @@ class UnifiedVoice(_lib.Handle):
 			raise _lib.TTKError(f"prefix {prefix_tokens} + {max_new} new tokens exceed max_ctx={self.max_ctx} or the mel position table ({c.max_mel_seq_len})")
 		return max_new
 
-	def _pipe_key(self, kw, typical_mass):
-		"""(what of the keywords is baked into a generation state, whether the stop token can be sampled at all)"""
+	def _pipe_key(self, kw, typical_mass, greedy=False):
+		"""(what of the keywords is baked into a generation state, whether the stop token can be sampled at all).  The greedy flag is part of the key: a
+		sampling state's captured step is never replayed for greedy search or the reverse; the warpers greedy search ignores are not."""
 		suppress = tuple(kw.get("suppress_tokens") or ())
-		pipe_key = (kw.get("temperature", 1.0), kw.get("top_k", 50), kw.get("top_p", 1.0), kw.get("repetition_penalty", 1.0), suppress, typical_mass)
+		warpers = (None, None, None) if greedy else (kw.get("temperature", 1.0), kw.get("top_k", 50), kw.get("top_p", 1.0))
+		pipe_key = warpers + (kw.get("repetition_penalty", 1.0), suppress, typical_mass, bool(greedy))
 		return pipe_key, self.cfg.stop_mel_token not in suppress
 
 	@contextlib.contextmanager
@@ -376,7 +401,7 @@ class UnifiedVoice(_lib.Handle):
 				if health:
 					self._check_health()
 
-	def _generate_lines(self, cond, texts, C, max_generate_length, kw, typical_mass=None):
+	def _generate_lines(self, cond, texts, C, max_generate_length, kw, typical_mass=None, greedy=False):
 		c = self.cfg
 		self._require_idle()            # a line batch rewrites the KV cache, the noise arming and (through the ring) an open stream's latent buffer
 		G = len(texts)
@@ -384,7 +409,7 @@ class UnifiedVoice(_lib.Handle):
 		if B > self.max_batch:
 			raise _lib.TTKError(f"{G} lines x {C} candidates exceed max_batch={self.max_batch}")
 		max_new = self._max_new(max(int(t.shape[1]) for t in texts) + 4, max_generate_length)
-		pipe_key, can_stop = self._pipe_key(kw, typical_mass)
+		pipe_key, can_stop = self._pipe_key(kw, typical_mass, greedy)
 		seed = kw.get("seed", 0)
 		with self._session(seed, lambda: self._gen_state(B, max_new, pipe_key, C, 0, lines=G), arm=(0,)) as (st, gen, off_start):
 			n = self._token_loop(st, gen, off_start, lambda: self._prefill_lines(cond, texts, C), max_new, can_stop)
@@ -534,7 +559,8 @@ class UnifiedVoice(_lib.Handle):
 
 	def get_generator(self, inputs, max_length=500, **hf_generate_kwargs) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
 		"""unified_voice.py:670-679 / stream_generator.py:911-1190: yields (codes [B], latent [B, model_dim]) per token,
-		latent = final_norm(last hidden) (:1172)."""
+		latent = final_norm(last hidden) (:1172).  Always the sampling loop, whatever `do_sample` says: the reference's `sample_stream` draws every
+		token with torch.multinomial (stream_generator.py:1161) and has no greedy branch."""
 		if self._prefix is None:
 			raise _lib.TTKError("call compute_embeddings first")
 		cond, text = self._prefix
@@ -543,7 +569,7 @@ class UnifiedVoice(_lib.Handle):
 		return self._generate(cond, text, B, n_new, None, hf_generate_kwargs, stream=True)
 
 	# ------------------------------------------------------------------ the token loop
-	def _generate(self, cond, text, num_return_sequences, max_generate_length, typical_mass, kw, stream, shard=None, prompt=None):
+	def _generate(self, cond, text, num_return_sequences, max_generate_length, typical_mass, kw, stream, shard=None, prompt=None, greedy=False):
 		self._require_idle()
 		n_in = 0 if prompt is None else int(prompt.shape[1])
 		if stream and n_in:
@@ -560,7 +586,7 @@ class UnifiedVoice(_lib.Handle):
 		max_new = self._max_new(text.shape[1] + 4, max_generate_length)
 		if n_in >= max_new:      # HF's stopping criterion is only looked at after a token has been appended: the reference would still sample one
 			raise ValueError(f"{n_in} prompt tokens leave no room below max_generate_length={max_new}")
-		pipe_key, can_stop = self._pipe_key(kw, typical_mass)
+		pipe_key, can_stop = self._pipe_key(kw, typical_mass, greedy)
 		if stream:
 			return self._loop_stream(cond, text, B, max_new, pipe_key, can_stop)
 		with self._session(kw.get("seed", 0), lambda: self._gen_state(B, max_new, pipe_key, C, lo), prompt, arm=(lo, n_in)) as (st, gen, off_start):
@@ -572,8 +598,8 @@ class UnifiedVoice(_lib.Handle):
 			return st.ids[:, :n].clone(), None
 
 	def _capture_step(self, st):
-		"""the token step {ttk_ar_decode_next; [typical warper]; exponential_; ttk_ar_sample_next} as it is issued right now (with or without the hidden
-		ring set), captured into a HIP graph.  The caller has run the step eagerly before (warm kernels)."""
+		"""the token step {ttk_ar_decode_next; [typical warper]; exponential_; ttk_ar_sample_next} -- greedy search: {ttk_ar_decode_next; ttk_ar_greedy_next} --
+		as it is issued right now (with or without the hidden ring set), captured into a HIP graph.  The caller has run the step eagerly before (warm kernels)."""
 		torch.cuda.synchronize(self.device)
 		g = torch.cuda.CUDAGraph()
 		# thread-local capture mode: another host thread may be enqueuing (and allocating for) the previous
@@ -634,7 +660,8 @@ class UnifiedVoice(_lib.Handle):
 						st.graph = self._capture_step(st)
 						# no random numbers are drawn inside the captured step when the mel head draws the noise: launch the instantiated
 						# graph directly then -- CUDAGraph.replay() first refills the generator's seed / offset tensors, two launches per token
-						st.graph_exec = st.graph.raw_cuda_graph_exec() if st.own_rng and os.environ.get("TTK_AR_RAW_REPLAY", "1") != "0" else None
+						# (greedy search draws nothing at all)
+						st.graph_exec = st.graph.raw_cuda_graph_exec() if (st.own_rng or st.greedy) and os.environ.get("TTK_AR_RAW_REPLAY", "1") != "0" else None
 					continue
 				if st.graph_exec:
 					_lib.check(self.lib.ttk_graph_launch(st.graph_exec, _lib.stream_ptr()), "ttk_graph_launch")
@@ -817,6 +844,7 @@ class _GenState(_NoiseState):
 		C = B if C is None else C
 		self.lines = lines                                              # lines > 1: B = lines * C rows, every line draws the same [C, V] noise
 		self.B, self.max_new = B, max_new
+		self.greedy = bool(pipe_key[6])                                 # greedy search: the argmax launch, no noise tensor, nothing armed, nothing drawn
 		self.pipe = LogitsPipeline(temperature=pipe_key[0], top_k=pipe_key[1], top_p=pipe_key[2], repetition_penalty=pipe_key[3],
 								   suppress_tokens=pipe_key[4], typical_mass=pipe_key[5], vocab=c.number_mel_codes, device=dev)
 		self.stop = c.stop_mel_token
@@ -827,12 +855,15 @@ class _GenState(_NoiseState):
 		self.col = torch.zeros(B, dtype=torch.long, device=dev)         # per-row output column (all rows move together)
 		# Exp(1) noise of multinomial for ALL C candidates of the call (C == B unless this is one shard of a candidate-sharded run:
 		# every rank draws the same [C, V] block and reads its rows lo..lo+B-1, see inference_speech)
-		self.q = torch.empty((B if lines > 1 else C, c.number_mel_codes), device=dev, dtype=torch.float32)
-		self.qc = torch.empty((C, c.number_mel_codes), device=dev, dtype=torch.float32) if lines > 1 else None      # torch-drawn fallback of a line batch
+		self.q = None if self.greedy else torch.empty((B if lines > 1 else C, c.number_mel_codes), device=dev, dtype=torch.float32)
+		self.qc = torch.empty((C, c.number_mel_codes), device=dev, dtype=torch.float32) if lines > 1 and not self.greedy else None      # torch-drawn fallback of a line batch
 		self.live = torch.zeros(1, dtype=torch.int32, device=dev)        # unfinished rows, decremented on the device
 		self.done = torch.zeros(1, dtype=torch.int32).pin_memory()       # raised by the row that finishes last; polled by the host
 		self.rng_step = None                                             # generator offset consumed by one sample() call
-		self._init_noise(model, C, c.number_mel_codes)
+		if self.greedy:
+			self.model, self.own_rng = model, False                     # (`_session` arms and disarms the noise of states that own it)
+		else:
+			self._init_noise(model, C, c.number_mel_codes)
 		# input_ids as the repetition penalty sees them: the fake prefix ids are all 1 with start_mel last (unified_voice.py:647-649),
 		# i.e. the SET {1, start_mel} whatever the text length (the penalty acts once per distinct id), then the sampled tokens
 		self.history = None
@@ -846,7 +877,8 @@ class _GenState(_NoiseState):
 		self.graphable = self.in_kernel or not p.needs_history      # torch-op penalty: its history slice grows with the host's step count
 		a = _lib.SampleArgs()
 		a.ld, a.B, a.V = self.logits.stride(0), B, c.number_mel_codes
-		a.q, a.ldq = self.q[lo].data_ptr(), self.q.stride(0)
+		if not self.greedy:
+			a.q, a.ldq = self.q[lo].data_ptr(), self.q.stride(0)
 		a.stop_token = self.stop
 		a.unfinished, a.tok, a.ids = self.unfinished.data_ptr(), self.tok.data_ptr(), self.ids.data_ptr()
 		a.ids_ld, a.ids_cols, a.col = self.ids.stride(0), self.ids.shape[1], self.col.data_ptr()
@@ -899,6 +931,9 @@ class _GenState(_NoiseState):
 			a.scores, a.ld = self.scores.data_ptr(), self.scores.stride(0)
 		# multinomial(softmax(scores), 1) == argmax(softmax(scores) / q), q ~ Exp(1) from the torch generator (see sampling.multinomial1)
 		# (own_rng: the mel-head launch that produced self.logits has written q already)
+		if self.greedy:       # HF `_sample` without do_sample: argmax of the processed scores, nothing drawn
+			_lib.check(self.model.lib.ttk_ar_greedy_next(self.model._h, _lib.C.byref(a), _lib.stream_ptr()), "ttk_ar_greedy_next")
+			return
 		if not self.own_rng:
 			if self.lines > 1:
 				self.qc.exponential_(1)

@@ -50,6 +50,11 @@ struct SampleParams {
 
 // grid = B rows, 1024 threads.  Rows up to 9216 wide (8194 mel codes = 9 per thread) stay in registers from the one trip to memory
 // to the argmax; wider rows take the plain three-pass path, which supports suppress + temperature only.
+// GREEDY: the greedy form of the same step (HF `_sample` with do_sample=False, HF:generation/utils.py:2925: next_tokens = torch.argmax(next_token_scores,
+// dim=-1)): the processors and the typical warper as below, then a block argmax of the processed scores themselves, lowest index on ties, and the same
+// bookkeeping.  It reads no q and runs none of temperature / top-k / top-p / softmax; V <= SAMPLE_MAXV only (the host refuses wider rows).  The sampling
+// instantiation is statement for statement the kernel it was before the template.
+template <bool GREEDY>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step(SampleParams p) {
 	__shared__ float red[SAMPLE_THREADS / 64];
 	__shared__ int redi[SAMPLE_THREADS / 64];
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step(SampleParams p) 
 	const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
 	const int V = p.V;
 	const float* s = p.scores + (int64_t)b * p.ld;
-	const float* qq = p.q + (int64_t)b * p.ldq;
+	const float* qq = GREEDY ? nullptr : p.q + (int64_t)b * p.ldq;
 	// ATen divides a tensor by a host scalar as `x * (1 / t)` with the reciprocal rounded to f32 (BinaryDivTrueKernel.cu), and that
 	// is what TemperatureLogitsWarper's `scores / temperature` and the penalty's `score / penalty` run on the GPU.
 	const bool scale = p.inv_t != 1.0f;
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step(SampleParams p) 
 		for (int j = 0; j < SAMPLE_NPT; ++j) {       // unconditional clamped loads: all 18 requests leave before the first use
 			const int i = tid + j * SAMPLE_THREADS, ic = i < V ? i : V - 1;
 			v[j] = s[ic];
-			qv[j] = qq[ic];
+			if constexpr (!GREEDY) qv[j] = qq[ic];
 		}
 		// ---- RepetitionPenaltyLogitsProcessor: every id present in input_ids (prefix ids + tokens generated so far), once
 		if (p.penalty != 1.0f && p.history) {
@@ -167,99 +172,108 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step(SampleParams p) 
 			for (int j = 0; j < SAMPLE_NPT; ++j)
 				if (fkey(d[j]) > prefix) v[j] = -INFINITY;        // sorted_scores > sorted_scores[last_ind]
 		}
-		// ---- TemperatureLogitsWarper
-		if (scale) {
+		if constexpr (GREEDY) {
+			// ---- greedy search (HF `_sample` without do_sample: next_tokens = torch.argmax(next_token_scores, dim=-1)): no warpers, no softmax, no noise
 #pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) v[j] = v[j] * p.inv_t;
-		}
-		// ---- TopKLogitsWarper: scores < (k-th largest) -> -inf
-		if (p.top_k > 0 && p.top_k < V) {
-			unsigned prefix = 0, mask = 0, remaining = (unsigned)p.top_k;
-			for (int pass = 3; pass >= 0; --pass) {
-				const int shift = 8 * pass;
-				if (tid < 256) hist32[tid] = 0;
-				__syncthreads();
-#pragma unroll
-				for (int j = 0; j < SAMPLE_NPT; ++j) {
-					const int i = tid + j * SAMPLE_THREADS;
-					const unsigned k = fkey(v[j]);
-					if (i < V && (k & mask) == prefix) atomicAdd(&hist32[(k >> shift) & 255], 1u);
-				}
-				__syncthreads();
-				if (tid < 64) {
-					int bin; unsigned before;
-					pick_bin<unsigned, true>(hist32, remaining, lane, bin, before);
-					if (tid == 0) { s_bin = bin; s_before = before; }
-				}
-				__syncthreads();
-				prefix |= (unsigned)s_bin << shift;
-				mask |= 0xffu << shift;
-				remaining -= (unsigned)s_before;
+			for (int j = 0; j < SAMPLE_NPT; ++j) {
+				const int i = tid + j * SAMPLE_THREADS;
+				if (i < V && v[j] > best) { best = v[j]; besti = i; }      // strict, ascending i: the lowest index wins a tie (the reductions below keep that rule)
 			}
+		} else {
+			// ---- TemperatureLogitsWarper
+			if (scale) {
 #pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j)
-				if (fkey(v[j]) < prefix) v[j] = -INFINITY;
-		}
-		float m = -INFINITY;
+				for (int j = 0; j < SAMPLE_NPT; ++j) v[j] = v[j] * p.inv_t;
+			}
+			// ---- TopKLogitsWarper: scores < (k-th largest) -> -inf
+			if (p.top_k > 0 && p.top_k < V) {
+				unsigned prefix = 0, mask = 0, remaining = (unsigned)p.top_k;
+				for (int pass = 3; pass >= 0; --pass) {
+					const int shift = 8 * pass;
+					if (tid < 256) hist32[tid] = 0;
+					__syncthreads();
 #pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) m = fmaxf(m, v[j]);
-		m = block_max(m, red, tid);
-		// ---- TopPLogitsWarper: ascending cumulative softmax <= 1 - top_p -> -inf (the largest score always stays)
-		if (p.top_p > 0.f && p.top_p < 1.0f) {
-			float e[SAMPLE_NPT], sum = 0.f;
+					for (int j = 0; j < SAMPLE_NPT; ++j) {
+						const int i = tid + j * SAMPLE_THREADS;
+						const unsigned k = fkey(v[j]);
+						if (i < V && (k & mask) == prefix) atomicAdd(&hist32[(k >> shift) & 255], 1u);
+					}
+					__syncthreads();
+					if (tid < 64) {
+						int bin; unsigned before;
+						pick_bin<unsigned, true>(hist32, remaining, lane, bin, before);
+						if (tid == 0) { s_bin = bin; s_before = before; }
+					}
+					__syncthreads();
+					prefix |= (unsigned)s_bin << shift;
+					mask |= 0xffu << shift;
+					remaining -= (unsigned)s_before;
+				}
 #pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) { e[j] = expf(v[j] - m); sum += e[j]; }
-			sum = block_sum(sum, red, tid);
-			unsigned long long w[SAMPLE_NPT], tot = 0;
+				for (int j = 0; j < SAMPLE_NPT; ++j)
+					if (fkey(v[j]) < prefix) v[j] = -INFINITY;
+			}
+			float m = -INFINITY;
 #pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) { w[j] = (unsigned long long)((e[j] / sum) * 1099511627776.0f); tot += w[j]; }
-			// block total of the integer masses (exact), to keep the target below it: the largest score is never removed
-			if (tid < 256) hist64[tid] = 0;
-			__syncthreads();
-			atomicAdd(&hist64[0], tot);
-			__syncthreads();
-			const unsigned long long total = hist64[0];
-			unsigned long long target = (unsigned long long)((1.0f - p.top_p) * 1099511627776.0f);
-			if (total > 0 && target >= total) target = total - 1;
-			__syncthreads();
-			unsigned prefix = 0, mask = 0;
-			unsigned long long below = 0;
-			for (int pass = 3; pass >= 0; --pass) {
-				const int shift = 8 * pass;
+			for (int j = 0; j < SAMPLE_NPT; ++j) m = fmaxf(m, v[j]);
+			m = block_max(m, red, tid);
+			// ---- TopPLogitsWarper: ascending cumulative softmax <= 1 - top_p -> -inf (the largest score always stays)
+			if (p.top_p > 0.f && p.top_p < 1.0f) {
+				float e[SAMPLE_NPT], sum = 0.f;
+#pragma unroll
+				for (int j = 0; j < SAMPLE_NPT; ++j) { e[j] = expf(v[j] - m); sum += e[j]; }
+				sum = block_sum(sum, red, tid);
+				unsigned long long w[SAMPLE_NPT], tot = 0;
+#pragma unroll
+				for (int j = 0; j < SAMPLE_NPT; ++j) { w[j] = (unsigned long long)((e[j] / sum) * 1099511627776.0f); tot += w[j]; }
+				// block total of the integer masses (exact), to keep the target below it: the largest score is never removed
 				if (tid < 256) hist64[tid] = 0;
 				__syncthreads();
+				atomicAdd(&hist64[0], tot);
+				__syncthreads();
+				const unsigned long long total = hist64[0];
+				unsigned long long target = (unsigned long long)((1.0f - p.top_p) * 1099511627776.0f);
+				if (total > 0 && target >= total) target = total - 1;
+				__syncthreads();
+				unsigned prefix = 0, mask = 0;
+				unsigned long long below = 0;
+				for (int pass = 3; pass >= 0; --pass) {
+					const int shift = 8 * pass;
+					if (tid < 256) hist64[tid] = 0;
+					__syncthreads();
 #pragma unroll
-				for (int j = 0; j < SAMPLE_NPT; ++j) {
-					const unsigned k = fkey(v[j]);
-					if (w[j] && (k & mask) == prefix) atomicAdd(&hist64[(k >> shift) & 255], w[j]);
+					for (int j = 0; j < SAMPLE_NPT; ++j) {
+						const unsigned k = fkey(v[j]);
+						if (w[j] && (k & mask) == prefix) atomicAdd(&hist64[(k >> shift) & 255], w[j]);
+					}
+					__syncthreads();
+					if (tid < 64) {
+						int bin; unsigned long long before;
+						pick_bin<unsigned long long, false>(hist64, target - below, lane, bin, before);
+						if (tid == 0) { s_bin = bin; s_before = before; }
+					}
+					__syncthreads();
+					prefix |= (unsigned)s_bin << shift;
+					mask |= 0xffu << shift;
+					below += s_before;
 				}
-				__syncthreads();
-				if (tid < 64) {
-					int bin; unsigned long long before;
-					pick_bin<unsigned long long, false>(hist64, target - below, lane, bin, before);
-					if (tid == 0) { s_bin = bin; s_before = before; }
-				}
-				__syncthreads();
-				prefix |= (unsigned)s_bin << shift;
-				mask |= 0xffu << shift;
-				below += s_before;
+#pragma unroll
+				for (int j = 0; j < SAMPLE_NPT; ++j)
+					if (fkey(v[j]) < prefix) v[j] = -INFINITY;
 			}
+			// ---- softmax, multinomial(1) = argmax(p / q)
+			float sum = 0.f;
 #pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j)
-				if (fkey(v[j]) < prefix) v[j] = -INFINITY;
+			for (int j = 0; j < SAMPLE_NPT; ++j) { v[j] = expf(v[j] - m); sum += v[j]; }      // exp(-inf) = 0 for removed / padding lanes
+			sum = block_sum(sum, red, tid);
+#pragma unroll
+			for (int j = 0; j < SAMPLE_NPT; ++j) {
+				const int i = tid + j * SAMPLE_THREADS;
+				const float r = (v[j] / sum) / qv[j];
+				if (i < V && r > best) { best = r; besti = i; }          // strict: the lowest index wins a tie, as in ATen's argmax
+			}
 		}
-		// ---- softmax, multinomial(1) = argmax(p / q)
-		float sum = 0.f;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) { v[j] = expf(v[j] - m); sum += v[j]; }      // exp(-inf) = 0 for removed / padding lanes
-		sum = block_sum(sum, red, tid);
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) {
-			const int i = tid + j * SAMPLE_THREADS;
-			const float r = (v[j] / sum) / qv[j];
-			if (i < V && r > best) { best = r; besti = i; }          // strict: the lowest index wins a tie, as in ATen's argmax
-		}
-	} else {
+	} else if constexpr (!GREEDY) {
 		const unsigned char* suppress = p.suppress;
 		const float inv_t = p.inv_t;
 		float m = -INFINITY;
@@ -328,6 +342,24 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step(SampleParams p) 
 	}
 }
 
+// The greedy form (ttk_greedy_step / ttk_ar_greedy_next): q, ldq, temperature, top_k and top_p of the arguments are not read.
+int launch_greedy_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32, hipStream_t stream, const char* who) {
+	TTK_REQUIRE(a && a->scores && a->unfinished && a->tok && a->ids && a->col, TTK_E_ARG, "%s: null argument", who);
+	TTK_REQUIRE(a->B >= 1 && a->V >= 1 && a->V <= SAMPLE_MAXV && a->ld >= a->V, TTK_E_ARG, "%s: bad shape (B %d, V %d; a row of at most %d is held in registers)", who, a->B, a->V,
+				SAMPLE_MAXV);
+	TTK_REQUIRE(a->typical_mass >= 0.f && a->repetition_penalty >= 0.f, TTK_E_ARG, "%s: negative typical_mass / repetition_penalty", who);
+	TTK_REQUIRE(!(a->repetition_penalty > 0.f && a->repetition_penalty != 1.0f) || a->history, TTK_E_ARG, "%s: the repetition penalty needs the history buffer", who);
+	SampleParams p = {};
+	p.scores = a->scores; p.ld = a->ld; p.V = a->V; p.suppress = a->suppress; p.inv_t = 1.0f; p.top_p = 1.0f; p.typical_mass = a->typical_mass;
+	p.penalty = a->repetition_penalty > 0.f ? a->repetition_penalty : 1.0f; p.inv_penalty = 1.0f / p.penalty;
+	p.stop_token = a->stop_token; p.unfinished = a->unfinished; p.tok = a->tok; p.ids = a->ids; p.ids_ld = a->ids_ld; p.ids_cols = a->ids_cols;
+	p.col = a->col; p.history = a->history; p.hist_ld = a->hist_ld; p.hist_off = a->hist_off; p.live_rows = a->live_rows; p.all_done = a->all_done;
+	p.emb = emb; p.pos = pos; p.x_out = x_out; p.d = d; p.pos_rows = pos_rows; p.x_frag = x_frag; p.x_frag_f32 = x_frag_f32;
+	hipLaunchKernelGGL(k_sample_step<true>, dim3(a->B), dim3(SAMPLE_THREADS), 0, stream, p);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
 int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32, hipStream_t stream, const char* who) {
 	TTK_REQUIRE(a && a->scores && a->q && a->unfinished && a->tok && a->ids && a->col, TTK_E_ARG, "%s: null argument", who);
 	TTK_REQUIRE(a->B >= 1 && a->V >= 1 && a->ld >= a->V && a->ldq >= a->V, TTK_E_ARG, "%s: bad shape (B %d, V %d)", who, a->B, a->V);
@@ -345,7 +377,7 @@ int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* 
 	p.stop_token = a->stop_token; p.unfinished = a->unfinished; p.tok = a->tok; p.ids = a->ids; p.ids_ld = a->ids_ld; p.ids_cols = a->ids_cols;
 	p.col = a->col; p.history = a->history; p.hist_ld = a->hist_ld; p.hist_off = a->hist_off; p.live_rows = a->live_rows; p.all_done = a->all_done;
 	p.emb = emb; p.pos = pos; p.x_out = x_out; p.d = d; p.pos_rows = pos_rows; p.x_frag = x_frag; p.x_frag_f32 = x_frag_f32;
-	hipLaunchKernelGGL(k_sample_step, dim3(a->B), dim3(SAMPLE_THREADS), 0, stream, p);
+	hipLaunchKernelGGL(k_sample_step<false>, dim3(a->B), dim3(SAMPLE_THREADS), 0, stream, p);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
@@ -364,6 +396,10 @@ extern "C" int ttk_sample_step(const float* scores, int64_t ld, int B, int V, co
 
 extern "C" int ttk_sample_step_warped(const ttk_sample_args* a, void* stream) {
 	return ttk::launch_sample_step(a, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, (hipStream_t)stream, "ttk_sample_step_warped");
+}
+
+extern "C" int ttk_greedy_step(const ttk_sample_args* a, void* stream) {
+	return ttk::launch_greedy_step(a, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, (hipStream_t)stream, "ttk_greedy_step");
 }
 
 namespace ttk {

@@ -149,6 +149,8 @@ int decode_launch(const DecodeCtx& c, const DecodeLaunch& L, int M, hipStream_t 
 // sample.hip: the fused per-token sampling launch; emb / pos / x_out non-null = also write the next decode step's input rows
 int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 					   hipStream_t stream, const char* who);
+int launch_greedy_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
+					   hipStream_t stream, const char* who);
 
 // beam.hip: the in-place gather of the KV cache's candidate slices that beam search needs per token (ttk_ar_reorder_cache)
 int launch_kv_reorder(void* kc, void* vc, int layers, int max_batch, int H, int max_ctx, size_t es, const int* d_pos, const int64_t* beam_idx, int B,

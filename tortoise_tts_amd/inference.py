@@ -46,6 +46,22 @@ def trim_calm_tokens(codes: torch.Tensor, latents: torch.Tensor) -> torch.Tensor
 	return latents
 
 
+def check_greedy(do_sample, candidates, beam_width):
+	"""do_sample=False is greedy search (UnifiedVoice.inference_speech): one sequence, no beams; refused before anything is sampled"""
+	if do_sample:
+		return
+	if candidates != 1:
+		raise ValueError(f"do_sample=False (greedy search) returns one sequence: candidates must be 1, got {candidates}")
+	if max(1, int(beam_width)) != 1:
+		raise ValueError(f"do_sample=False (greedy search) runs without beams: beam_width must be 1, got {beam_width} (deterministic beam search is not implemented)")
+
+
+def ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p):
+	"""the sampling-only keywords of the `inference_speech` call: greedy search ignores temperature, top-k and top-p, so they are not handed on (and
+	UnifiedVoice does not warn about defaults nobody chose)"""
+	return dict(do_sample=True, top_k=top_k, top_p=top_p, temperature=ar_temp) if do_sample else dict(do_sample=False)
+
+
 def check_diffusion_conditioning(diffusion_conditioning: str, diffusion: DiffusionTTS) -> bool:
 	"""True for "codes" (the diffusion model reads the sampled mel codes, diffusion.py:1493-1497), False for "latents"; refuses what cannot run -- before
 	anything is sampled."""
@@ -201,7 +217,8 @@ class TTSHotPath:
 	def inference(self, text_tokens: torch.Tensor, autoregressive_latents: torch.Tensor, diffusion_latents: torch.Tensor, *,
 				  max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, diffusion_sampler="ddim", cond_free=True, candidates=1,
-				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1, diffusion_conditioning="latents"):
+				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1, diffusion_conditioning="latents",
+				  do_sample=True):
 		"""text_tokens [1, Tt] int64; latents from the reference's conditioning encoders ([1,1024], [1,2048]).
 		latents_for: "all" = the latent pass over every candidate, as the reference runs it before scoring (inference.py:370-379; the benchmarked
 		workload); "winner" = the k = 1 variant: the candidate is chosen first and only its row goes through the dense
@@ -213,10 +230,14 @@ class TTSHotPath:
 		(candidates <= beam_width) and `length_penalty` ranks them.
 		diffusion_conditioning: "latents" = the reference's call (inference.py:370-402); "codes" = the diffusion model reads the sampled, stop-token-fixed
 		mel codes of the chosen candidate themselves (its token branch, diffusion.py:1493-1497) and the dense latent pass is skipped: the calm-token cut
-		applies to the code row as it does to the latent rows, `T` follows from the row's length the same way.  Needs `DiffusionTTS(..., codes=True)`."""
+		applies to the code row as it does to the latent rows, `T` follows from the row's length the same way.  Needs `DiffusionTTS(..., codes=True)`.
+		do_sample (no reference counterpart: inference.py:336 always samples): False = greedy search, the mel codes are a pure function of (voice, text,
+		weights); needs candidates == 1 and beam_width == 1 (ValueError otherwise); `ar_temp`, `top_k` and `top_p` play no part, `repetition_penalty` and
+		`suppress_tokens` act; no CLVP pass (one candidate); the diffusion start noise is drawn where the generator stands behind `generate`'s reseed."""
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
 		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
+		check_greedy(do_sample, candidates, beam_width)
 
 		def mark(name):
 			if phase_marks is not None:
@@ -227,8 +248,8 @@ class TTSHotPath:
 		text_tokens = text_tokens.to(dev)
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		extra = {"suppress_tokens": suppress_tokens} if suppress_tokens else {}
-		codes = ar.inference_speech(autoregressive_latents, text_tokens, do_sample=True, top_k=top_k, top_p=top_p,
-									temperature=ar_temp, num_return_sequences=candidates, num_beams=max(1, beam_width),
+		codes = ar.inference_speech(autoregressive_latents, text_tokens, **ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p),
+									num_return_sequences=candidates, num_beams=max(1, beam_width),
 									length_penalty=length_penalty, repetition_penalty=repetition_penalty,
 									max_generate_length=max_ar_steps, **extra)
 		mark("ar_decode")
@@ -283,7 +304,7 @@ class TTSHotPath:
 	@torch.inference_mode()
 	def inference_lines(self, lines, autoregressive_latents, diffusion_latents, *, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8,
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
-						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents"):
+						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -302,11 +323,13 @@ class TTSHotPath:
 		Batched lines keep that property: each row decodes with its own line's cache length, every line draws the same noise, and before a line's
 		own draws the generators are put where its `generate` alone would have left them (UnifiedVoice.position_rng_after_line).
 		diffusion_conditioning="codes": as in `inference` -- each line's chosen code row is its aligned conditioning, no dense latent pass.
+		do_sample=False: greedy search as in `inference` (candidates must be 1): the lines of a batch decode one row each.
 		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
 		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
+		check_greedy(do_sample, candidates, 1)
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		extra = {"suppress_tokens": suppress_tokens} if suppress_tokens else {}
 		main = torch.cuda.current_stream(dev)
@@ -343,8 +366,8 @@ class TTSHotPath:
 			for i, text_tokens in enumerate(lines):
 				with torch.cuda.stream(s_ar):
 					if i % G == 0:      # sample this line and the next G - 1 as one batch
-						batch_codes = ar.inference_speech_lines(autoregressive_latents, lines[i:i + G], do_sample=True, top_k=top_k, top_p=top_p,
-																temperature=ar_temp, num_return_sequences=candidates, num_beams=1, length_penalty=length_penalty,
+						batch_codes = ar.inference_speech_lines(autoregressive_latents, lines[i:i + G], **ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p),
+																num_return_sequences=candidates, num_beams=1, length_penalty=length_penalty,
 																repetition_penalty=repetition_penalty, max_generate_length=max_ar_steps, **extra)
 					ar.position_rng_after_line(i % G)       # the generators as this line's own `generate` leaves them
 					codes = fix_stop_tokens(batch_codes[i % G], ar.stop_mel_token)

@@ -121,7 +121,7 @@ class TTS:
 	@torch.inference_mode()
 	def inference(self, text: str, references=None, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
-				  seed=None, candidates=1, references_sr: int = 22050) -> Tuple[torch.Tensor, int]:
+				  seed=None, candidates=1, references_sr: int = 22050, do_sample=True) -> Tuple[torch.Tensor, int]:
 		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
 		(wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the `vocoder=` part, "vocoder" the
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
@@ -130,9 +130,17 @@ class TTS:
 		with `length_penalty` -- on the "bigvgan" and "vocoder" branches, line by line; the streaming "hifigan" branch takes no beams.
 		references=None speaks in a random voice (`random_voice`; needs `rlg_auto=` and `rlg_diffuser=`): `set_seed(seed)` then runs BEFORE the voice
 		is drawn, so `seed` fixes the voice, and once more behind it, so the line is sampled as `inference(text, that_voice, seed=seed)` samples it.
-		With references given the order is the reference's: the clip is encoded first, then the seed is set."""
+		With references given the order is the reference's: the clip is encoded first, then the seed is set.
+		do_sample (the reference's `TTS.inference` has no such argument: it always samples, inference.py:336): False speaks every line by greedy search -- the
+		mel codes are then a pure function of (voice, text, weights), whatever `ar_temp`, `top_k`, `top_p` and `seed` are; `seed` still fixes the diffusion
+		noise.  Needs candidates == 1 and beam_width == 1 (ValueError); not available with vocoder_type="hifigan", whose token generator always samples."""
+		from .inference import check_greedy
+		check_greedy(do_sample, candidates, beam_width)
 		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
 			raise NotImplementedError(f"vocoder_type {vocoder_type!r} is unknown ('bigvgan', 'vocoder', 'hifigan')")
+		if not do_sample and vocoder_type == "hifigan":
+			raise NotImplementedError("greedy search (do_sample=False) is not available on the HiFiGAN streaming branch: the reference's streaming generator draws every token "
+									  "(stream_generator.py:1161)")
 		if vocoder_type == "hifigan" and self.hifigan is None:
 			raise NotImplementedError("TTS was built without a HiFiGAN vocoder (hifigan=): the streaming branch, inference.py:250-329, needs one")
 		beam_width = max(1, int(beam_width))                  # inference.py:342
@@ -161,7 +169,7 @@ class TTS:
 									  repetition_penalty=repetition_penalty, length_penalty=length_penalty) for tokens in lines]
 			return torch.concat(wavs, dim=-1), SAMPLE_RATE
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
-				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates)
+				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates, do_sample=do_sample)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
 		if beam_width != 1:                                   # the beams of a line exchange histories every token: lines are sampled one by one
 			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
