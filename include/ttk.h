@@ -388,6 +388,33 @@ int ttk_diff_sample_ddim_lines(ttk_diff* h, float* x, const float* E, int b, int
  * stream stays the reference's.  Equal to n_steps ttk_diff_step calls bit for bit.                                                       */
 int ttk_diff_sample_p(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, void* stream);
 
+/* The rest of the reference sampler's argument space (GaussianDiffusion.ddim_sample with eta :646-694, clip_denoised=False :401-403,
+ * ddim_reverse_sample :696-732), as a second per-step struct beside ttk_step, whose `sampler` field these entries do not read, and a kernel of its
+ * own, k_diffusion_step_ext: the entries above keep their code.                                                                             */
+typedef struct {
+	float sigma;               /* mode 0: eta sqrt((1 - ac_prev) / (1 - ac)) sqrt(1 - ac / ac_prev), f32 as torch computes it (:679-683); 0 reads no noise */
+	float dir;                 /* mode 0: sqrt(1 - ac_prev - sigma^2) (:688); == sqrt_1m_ac_prev at sigma 0 */
+	float sqrt_ac_next, sqrt_1m_ac_next;   /* mode 2: f32 square roots of alphas_cumprod_next and of 1 - it (:724-729) */
+	int mode;                  /* 0 = ddim with eta, 1 = p, 2 = reverse ddim */
+	int clip;                  /* clip_denoised: clamp the predicted x0 to [-1, 1] */
+} ttk_step_ext;
+
+/* Whole loop of one mode (every ext[i].mode equal), on the machinery of ttk_diff_sample_ddim: the time path of all steps at once, the two-stream
+ * integrator pipeline, each update launch writing the next step's operand copy.  Modes 0 and 1 run steps[n-1], ..., steps[0]; mode 2 runs
+ * steps[0], ..., steps[n-1] (x_t -> x_{t+1}: the DDIM encoder).  noise [n_steps, b, in, T] f32, block j for the j-th executed step, as for
+ * ttk_diff_sample_p; NULL is accepted when no step reads it (mode 2; mode 0 with every sigma 0), else TTK_E_ARG.  Mode 0 with sigma 0, dir =
+ * sqrt_1m_ac_prev and clip equals ttk_diff_sample_ddim bit for bit, mode 1 with clip ttk_diff_sample_p.                                      */
+int ttk_diff_sample_ext(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, const ttk_step_ext* ext, int n_steps,
+						const float* noise, void* stream);
+/* One step behind ttk_diff_begin, as ttk_diff_step; pred_xstart (NULL, or [b, in, T] f32): the x0 prediction the step used (after the clamp when
+ * ext->clip), the reference's out["pred_xstart"].  A loop of these equals ttk_diff_sample_ext bit for bit.                                  */
+int ttk_diff_step_ext(ttk_diff* h, float* x, const ttk_step* st, const ttk_step_ext* ext, const float* noise, float* pred_xstart, void* stream);
+/* Kernel form: the update launch alone on caller buffers.  out_c / out_u [nb, 2 C, T] f32 network outputs (out_u read when st->cfk >= 0), x [nb, C, T]
+ * f32 in place, noise / pred_xstart [nb, C, T] f32 or NULL, xcl NULL or the channels-last copy [rep nb T][ldo] of the new x in `xcl_dtype`
+ * (TTK_F32 | TTK_BF16 | TTK_F16; columns C .. ldo are not written).                                                                          */
+int ttk_diffusion_step_ext_rows(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int T,
+								const ttk_step* st, const ttk_step_ext* ext, void* xcl, int ldo, int rep, int xcl_dtype, void* stream);
+
 /* ------------------------------------------------------------------ BigVGAN vocoder
  * The generator of models/bigvgan.py (BigVGAN.__init__ :419-486) on the hot path's kernels.  Weights: the generator's state_dict
  * with weight norm folded into plain `weight` tensors (tortoise_tts_amd/vocoder.py does that), plus "__aa_filter" [12], the Kaiser

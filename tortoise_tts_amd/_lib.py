@@ -48,6 +48,11 @@ class StepC(C.Structure):
 		("sampler", C.c_int), ("nonzero", C.c_int)]
 
 
+class StepExtC(C.Structure):
+	"""ttk_step_ext (include/ttk.h; static_assert'ed in csrc/diff.hip)"""
+	_fields_ = [(n, C.c_float) for n in ("sigma", "dir", "sqrt_ac_next", "sqrt_1m_ac_next")] + [("mode", C.c_int), ("clip", C.c_int)]
+
+
 class SampleArgs(C.Structure):
 	"""ttk_sample_args (include/ttk.h)"""
 	_fields_ = [("scores", C.c_void_p), ("ld", C.c_int64), ("B", C.c_int), ("V", C.c_int), ("q", C.c_void_p), ("ldq", C.c_int64),
@@ -208,6 +213,9 @@ SYMBOLS = {
 	"ttk_diff_sample_ddim": (_I, [_P, _P, _P, _I, _I, C.POINTER(StepC), _I, _P]),
 	"ttk_diff_sample_p": (_I, [_P, _P, _P, _I, _I, C.POINTER(StepC), _I, _P, _P]),
 	"ttk_diff_sample_ddim_lines": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_int), C.POINTER(StepC), _I, _P]),
+	"ttk_diff_sample_ext": (_I, [_P, _P, _P, _I, _I, C.POINTER(StepC), C.POINTER(StepExtC), _I, _P, _P]),
+	"ttk_diff_step_ext": (_I, [_P, _P, C.POINTER(StepC), C.POINTER(StepExtC), _P, _P, _P]),
+	"ttk_diffusion_step_ext_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(StepC), C.POINTER(StepExtC), _P, _I, _I, _I, _P]),
 }
 
 _lib = None

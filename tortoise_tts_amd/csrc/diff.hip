@@ -37,7 +37,8 @@ struct Gn {
 // one sampler step of a loop.  nb: 2b sequences with the conditioning-free evaluation, else b; emb: its row of emb_all; noise: its block (ancestral sampler) or null;
 // layout: the channels-last copy of x is not there yet, the step runs the layout launch; stage_next: its update launch also writes the next step's copy (same batch
 // layout in both; not for ragged batches, whose padding frames must read zero)
-struct StepPlan { const ttk_step* st; int nb; const float* emb; const float* noise; bool layout, stage_next; };
+// ext / pred_xstart: the step runs the extended update (ttk_diff_sample_ext, ttk_diff_step_ext); null on the loops that predate it
+struct StepPlan { const ttk_step* st; int nb; const float* emb; const float* noise; bool layout, stage_next; const ttk_step_ext* ext = nullptr; float* pred_xstart = nullptr; };
 }  // namespace
 
 struct ttk_diff {
@@ -439,18 +440,30 @@ int ttk_diff_begin(ttk_diff* h, const float* E, int b, int T, void* stream) {
 static StepCoefs coefs_of(const ttk_step& st) {
 	return {st.sqrt_recip_ac, st.sqrt_recipm1_ac, st.sqrt_ac_prev, st.sqrt_1m_ac_prev, st.cfk, st.coef1, st.coef2, st.min_log, st.max_log, st.sampler, st.nonzero};
 }
+static_assert(sizeof(ttk_step_ext) == 24, "ttk_step_ext is mirrored by tortoise_tts_amd/_lib.py: StepExtC");
+static StepExt ext_of(const ttk_step_ext& e) { return {e.sigma, e.dir, e.sqrt_ac_next, e.sqrt_1m_ac_next, e.mode, e.clip}; }
+// does the extended update of this step read its noise block?
+static bool ext_reads_noise(const ttk_step& st, const ttk_step_ext& e) { return st.nonzero && (e.mode == 1 || (e.mode == 0 && e.sigma != 0.f)); }
+static int check_ext(const char* who, const ttk_step_ext& e, int i) {
+	TTK_REQUIRE(e.mode >= 0 && e.mode <= 2, TTK_E_ARG, "%s: step %d has mode %d (0 ddim, 1 p, 2 reverse ddim)", who, i, e.mode);
+	TTK_REQUIRE(e.sigma >= 0.f, TTK_E_ARG, "%s: step %d has sigma %g", who, i, (double)e.sigma);
+	return TTK_OK;
+}
 // The steps of a loop in the order they run: steps[n-1], ..., steps[0]; `noise` (ancestral sampler) holds one [b, in, T] draw per step in that order, null for ddim;
 // emb_all has one row per schedule index.  One layout launch per run of steps with the same batch layout: each update launch writes the next step's copy of x.
-static std::vector<StepPlan> plan_steps(ttk_diff* h, const ttk_step* steps, int n, const float* emb_all, int64_t emb_stride, const float* noise) {
+// ascending (the reverse ODE of ttk_diff_sample_ext): steps[0], ..., steps[n-1] instead; ext: the extended update's per-step block, same indexing as steps.
+static std::vector<StepPlan> plan_steps(ttk_diff* h, const ttk_step* steps, int n, const float* emb_all, int64_t emb_stride, const float* noise, const ttk_step_ext* ext = nullptr, bool ascending = false) {
 	const size_t nz = (size_t)h->cur_b * h->cfg.in_channels * h->cur_T;
 	std::vector<StepPlan> plan(n);
 	for (int j = 0; j < n; ++j) {
-		const int i = n - 1 - j;
+		const int i = ascending ? j : n - 1 - j;
+		const int next = ascending ? i + 1 : i - 1;      // the step that runs after this one (outside 0 .. n-1: none)
 		const bool cf = steps[i].cfk >= 0.f;
 		StepPlan& p = plan[j];
 		p.st = &steps[i]; p.nb = cf ? 2 * h->cur_b : h->cur_b; p.emb = emb_all + i * emb_stride; p.noise = noise ? noise + j * nz : nullptr;
 		p.layout = j == 0 || !plan[j - 1].stage_next;
-		p.stage_next = i > 0 && !h->tlen && (steps[i - 1].cfk >= 0.f) == cf;
+		p.stage_next = next >= 0 && next < n && !h->tlen && (steps[next].cfk >= 0.f) == cf;
+		p.ext = ext ? ext + i : nullptr;
 	}
 	return plan;
 }
@@ -462,6 +475,11 @@ static void step_body(ttk_diff* h, float* x, const StepPlan& p, const float* cs,
 	float* out = (float*)h->outb.p;
 	body(h, p.nb, T, p.emb, 0, cs, out, s, cs_consumed);
 	const float* out_u = out + (size_t)b * h->cfg.out_channels * T;
+	if (p.ext) {
+		if (p.stage_next) launch_diffusion_step_ext(out, out_u, x, p.noise, p.pred_xstart, b, Cin, T, coefs_of(*p.st), ext_of(*p.ext), s, h->xcl.p, h->in_pad, rep, elem_kind(h->dt));
+		else launch_diffusion_step_ext(out, out_u, x, p.noise, p.pred_xstart, b, Cin, T, coefs_of(*p.st), ext_of(*p.ext), s);
+		return;
+	}
 	if (p.stage_next) launch_diffusion_step(out, out_u, x, p.noise, b, Cin, T, coefs_of(*p.st), s, h->xcl.p, h->in_pad, rep, elem_kind(h->dt));      // (its padding columns are already zero)
 	else launch_diffusion_step(out, out_u, x, p.noise, b, Cin, T, coefs_of(*p.st), s);
 }
@@ -481,17 +499,26 @@ int ttk_diff_step(ttk_diff* h, float* x, const ttk_step* st, const float* noise,
 }
 
 // The whole sampler loop, both samplers (see plan_steps for the order of steps and noise).
-static int sample_loop(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, int sampler, void* stream, const char* who) {
+// ext (ttk_diff_sample_ext): the extended update with one block per step; `sampler` is then not looked at, the mode of ext[0] decides the order.
+static int sample_loop(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, int sampler, void* stream, const char* who,
+					   const ttk_step_ext* ext = nullptr) {
 	TTK_REQUIRE(h && x && E && steps && n_steps >= 1, TTK_E_ARG, "%s: bad argument", who);
-	TTK_REQUIRE(sampler == 0 || noise, TTK_E_ARG, "%s: the p sampler needs one noise block per step", who);
+	if (ext) {
+		for (int i = 0; i < n_steps; ++i) {
+			TTK_TRY(check_ext(who, ext[i], i));
+			TTK_REQUIRE(ext[i].mode == ext[0].mode, TTK_E_ARG, "%s: step %d has mode %d, step 0 mode %d (one mode per loop)", who, i, ext[i].mode, ext[0].mode);
+			TTK_REQUIRE(noise || !ext_reads_noise(steps[i], ext[i]), TTK_E_ARG, "%s: step %d adds noise (mode %d, sigma %g) but noise is null", who, i, ext[i].mode, (double)ext[i].sigma);
+		}
+	}
+	else TTK_REQUIRE(sampler == 0 || noise, TTK_E_ARG, "%s: the p sampler needs one noise block per step", who);
 	TTK_REQUIRE(h->cfg.out_channels == 2 * h->cfg.in_channels, TTK_E_ARG, "%s: learned-range output needs out = 2 * in channels", who);
 	hipStream_t s = (hipStream_t)stream;
 	TTK_TRY(ttk_diff_begin(h, E, b, T, stream));
 	// the timestep-only work of ALL steps in one pass: [n_steps] rows through time_embed + every emb_layers (weights read once)
 	std::vector<int64_t> ts(n_steps);
-	for (int i = 0; i < n_steps; ++i) { ts[i] = steps[i].t; TTK_REQUIRE(steps[i].sampler == sampler, TTK_E_ARG, "%s: step %d has sampler %d", who, i, steps[i].sampler); }
+	for (int i = 0; i < n_steps; ++i) { ts[i] = steps[i].t; TTK_REQUIRE(ext || steps[i].sampler == sampler, TTK_E_ARG, "%s: step %d has sampler %d", who, i, steps[i].sampler); }
 	TTK_TRY(time_path(h, nullptr, ts.data(), n_steps, s));
-	const std::vector<StepPlan> plan = plan_steps(h, steps, n_steps, (const float*)h->emb_all.p, (int64_t)h->n_emb * 2 * h->cfg.model_channels, noise);
+	const std::vector<StepPlan> plan = plan_steps(h, steps, n_steps, (const float*)h->emb_all.p, (int64_t)h->n_emb * 2 * h->cfg.model_channels, noise, ext, ext && ext[0].mode == 2);
 	// Pipelined over two streams.  The integrator of a step depends on its timestep and the staged embedding only, never on x: the one of
 	// step j+1 runs on the side stream (own scratch lane, the other `cs` buffer) while the body of step j runs here.  Both are chains of
 	// small dependent launches that leave most of the chip idle, so they overlap; one fork and one join edge per step.  Sequential
@@ -574,6 +601,41 @@ int ttk_diff_sample_ddim_lines(ttk_diff* h, float* x, const float* E, int b, int
 
 int ttk_diff_sample_p(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, void* stream) {
 	return sample_loop(h, x, E, b, T, steps, n_steps, noise, 1, stream, "ttk_diff_sample_p");
+}
+
+int ttk_diff_sample_ext(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, const ttk_step_ext* ext, int n_steps, const float* noise, void* stream) {
+	TTK_REQUIRE(ext, TTK_E_ARG, "ttk_diff_sample_ext: null argument");
+	return sample_loop(h, x, E, b, T, steps, n_steps, noise, 0, stream, "ttk_diff_sample_ext", ext);
+}
+
+int ttk_diff_step_ext(ttk_diff* h, float* x, const ttk_step* st, const ttk_step_ext* ext, const float* noise, float* pred_xstart, void* stream) {
+	TTK_REQUIRE(h && x && st && ext, TTK_E_ARG, "ttk_diff_step_ext: null argument");
+	TTK_REQUIRE(h->staged, TTK_E_STATE, "ttk_diff_step_ext: call ttk_diff_begin first");
+	TTK_TRY(check_ext("ttk_diff_step_ext", *ext, 0));
+	TTK_REQUIRE(noise || !ext_reads_noise(*st, *ext), TTK_E_ARG, "ttk_diff_step_ext: the step adds noise (mode %d, sigma %g) but noise is null", ext->mode, (double)ext->sigma);
+	TTK_REQUIRE(h->cfg.out_channels == 2 * h->cfg.in_channels, TTK_E_ARG, "ttk_diff_step_ext: learned-range output needs out = 2 * in channels");
+	hipStream_t s = (hipStream_t)stream;
+	TTK_TRY(time_path(h, nullptr, &st->t, 1, s));
+	StepPlan p = plan_steps(h, st, 1, (const float*)h->emb_all.p, 0, noise, ext)[0];
+	p.pred_xstart = pred_xstart;
+	integrator(h, p.nb, h->cur_T, p.emb, 0, (float*)h->cs.p, s, true);
+	step_body(h, x, p, (const float*)h->cs.p, nullptr, s);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_diffusion_step_ext_rows(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int T, const ttk_step* st,
+								const ttk_step_ext* ext, void* xcl, int ldo, int rep, int xcl_dtype, void* stream) {
+	TTK_REQUIRE(out_c && x && st && ext, TTK_E_ARG, "ttk_diffusion_step_ext_rows: null argument");
+	TTK_REQUIRE(nb >= 1 && C >= 1 && T >= 1, TTK_E_ARG, "ttk_diffusion_step_ext_rows: empty input");
+	TTK_TRY(check_ext("ttk_diffusion_step_ext_rows", *ext, 0));
+	TTK_REQUIRE(out_u || st->cfk < 0.f, TTK_E_ARG, "ttk_diffusion_step_ext_rows: cfk >= 0 mixes in out_u, which is null");
+	TTK_REQUIRE(noise || !ext_reads_noise(*st, *ext), TTK_E_ARG, "ttk_diffusion_step_ext_rows: the step adds noise (mode %d, sigma %g) but noise is null", ext->mode, (double)ext->sigma);
+	TTK_REQUIRE(!xcl || (ldo >= C && rep >= 1 && (xcl_dtype == DT_F32 || xcl_dtype == DT_BF16 || xcl_dtype == DT_F16)), TTK_E_ARG,
+				"ttk_diffusion_step_ext_rows: the channels-last copy needs ldo >= C, rep >= 1 and an f32 / bf16 / f16 type (ldo %d, rep %d, type %d)", ldo, rep, xcl_dtype);
+	launch_diffusion_step_ext(out_c, out_u, x, noise, pred_xstart, nb, C, T, coefs_of(*st), ext_of(*ext), (hipStream_t)stream, xcl, ldo, rep, elem_kind(xcl_dtype));
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
 }
 
 }  // extern "C"

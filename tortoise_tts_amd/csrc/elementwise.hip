@@ -230,4 +230,63 @@ void launch_diffusion_step(const float* out_c, const float* out_u, float* x, con
 	hipLaunchKernelGGL(k_diffusion_step, dim3(grid_for(total)), dim3(256), 0, s, out_c, out_u, x, noise, nb, C, T, c, xcl, ldo, rep, ekind);
 }
 
+// The rest of the reference sampler's argument space on the same operands (k_diffusion_step above is the eta = 0 / clip_denoised=True point of it and stays as it is):
+//   mode 0  DDIM with eta      diffusion.py:675-693   x = x0 sqrt(ac_prev) + dir eps' + (i != 0 ? sigma noise : 0) ; sigma, dir = sqrt(1 - ac_prev - sigma^2) from the host
+//   mode 1  ancestral "p"      as above
+//   mode 2  reverse DDIM       diffusion.py:720-730   x = x0 sqrt(ac_next) + sqrt(1 - ac_next) eps'
+// e.clip: the clamp of x0 (clip_denoised, :401-403); pred_xstart (optional, [nb][C][T] f32): x0 as the step used it.
+// Every rounding is written out, so that a host restatement can follow it bit for bit: contraction is off, and the two sums k_diffusion_step's code object
+// computes fused -- x0 = fma(-sqrt_recipm1_ac, eps, sqrt_recip_ac x) and the posterior mean fma(coef2, x, coef1 x0) -- are fused here by name.  With e.clip,
+// mode 0 at sigma = 0 (dir = sqrt_1m_ac_prev) and mode 1 therefore give k_diffusion_step's bits (tests/test_gpu_sampler_ext.py holds both to that).
+__global__ void k_diffusion_step_ext(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int Tn, StepCoefs k, StepExt e,
+									 void* xcl, int ldo, int rep, int ekind) {
+#pragma clang fp contract(off)
+	const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const int64_t per = (int64_t)C * Tn;
+	if (idx >= nb * per) return;
+	const int b = (int)(idx / per);
+	const int64_t r = idx - b * per;
+	float eps = out_c[(int64_t)b * 2 * per + r];
+	if (k.cfk >= 0.f) {
+		const float eu = out_u[(int64_t)b * 2 * per + r];
+		eps = (1.0f + k.cfk) * eps - k.cfk * eu;
+	}
+	const float xv = x[idx];
+	const float rx = k.sqrt_recip_ac * xv;
+	float x0 = __builtin_fmaf(-k.sqrt_recipm1_ac, eps, rx);
+	if (e.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+	if (pred_xstart) pred_xstart[idx] = x0;
+	float xn;
+	if (e.mode == 1) {
+		const float var = out_c[(int64_t)b * 2 * per + per + r];
+		const float frac = (var + 1.0f) / 2.0f;
+		const float log_var = frac * k.max_log + (1.0f - frac) * k.min_log;
+		const float mean = __builtin_fmaf(k.coef2, xv, k.coef1 * x0);
+		xn = mean + (k.nonzero ? expf(0.5f * log_var) * noise[idx] : 0.f);
+	} else {
+		const float e2 = (rx - x0) / k.sqrt_recipm1_ac;
+		if (e.mode == 0) {
+			xn = x0 * k.sqrt_ac_prev + e.dir * e2;
+			if (k.nonzero && e.sigma != 0.f) xn = xn + e.sigma * noise[idx];
+		} else {
+			xn = x0 * e.sqrt_ac_next + e.sqrt_1m_ac_next * e2;
+		}
+	}
+	x[idx] = xn;
+	if (xcl) {
+		const int c = (int)(r / Tn), t = (int)(r - (int64_t)c * Tn);
+		for (int q = 0; q < rep; ++q) {
+			const int64_t o = (((int64_t)q * nb + b) * Tn + t) * ldo + c;
+			if (ekind == EK_F32) ((float*)xcl)[o] = xn;
+			else if (ekind == EK_F16) ((f16*)xcl)[o] = cvt<f16>(xn);
+			else ((bf16*)xcl)[o] = cvt<bf16>(xn);
+		}
+	}
+}
+void launch_diffusion_step_ext(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int T, StepCoefs c, StepExt e, hipStream_t s,
+							   void* xcl, int ldo, int rep, int ekind) {
+	const int64_t total = (int64_t)nb * C * T;
+	hipLaunchKernelGGL(k_diffusion_step_ext, dim3(grid_for(total)), dim3(256), 0, s, out_c, out_u, x, noise, pred_xstart, nb, C, T, c, e, xcl, ldo, rep, ekind);
+}
+
 }  // namespace ttk

@@ -311,6 +311,11 @@ struct StepCoefs {
 };
 void launch_diffusion_step(const float* out_c, const float* out_u, float* x, const float* noise, int nb, int C, int T,
 						   StepCoefs c, hipStream_t s, void* xcl = nullptr, int ldo = 0, int rep = 0, int ekind = 0);      // xcl: also the next step's channels-last operand copy of x (elementwise.hip)
+// the same epilogue over the rest of the reference sampler's arguments (k_diffusion_step_ext): mode 0 DDIM with eta, 1 ancestral, 2 reverse DDIM; clip: clamp x0;
+// pred_xstart: optional [nb][C][T] f32 output of x0.  `c.sampler` is not read (the mode decides)
+struct StepExt { float sigma, dir, sqrt_ac_next, sqrt_1m_ac_next; int mode, clip; };
+void launch_diffusion_step_ext(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int T, StepCoefs c, StepExt e,
+							   hipStream_t s, void* xcl = nullptr, int ldo = 0, int rep = 0, int ekind = 0);
 
 // ---------------------------------------------------------------- packing (pack.hip)
 enum PackLayout { PK_NK = 0, PK_KN = 1, PK_CONV3 = 2, PK_CONVK = 3, PK_CONVT = 4 };   // CONVK: src[n][k][ntap]; CONVT: src[k][n][ntap]

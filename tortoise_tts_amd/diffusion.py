@@ -268,6 +268,7 @@ class SpacedDiffusion:
 		self.posterior_log_variance_clipped = np.log(np.append(self.posterior_variance[1], self.posterior_variance[1:]))
 		self.posterior_mean_coef1 = betas * np.sqrt(self.alphas_cumprod_prev) / (1.0 - self.alphas_cumprod)
 		self.posterior_mean_coef2 = (1.0 - self.alphas_cumprod_prev) * np.sqrt(alphas) / (1.0 - self.alphas_cumprod)
+		self.alphas_cumprod_next = np.append(self.alphas_cumprod[1:], 0.0)
 
 	def step_coefs(self, i: int, sampler: str) -> _lib.StepC:
 		"""Scalars of step i.  float64 table -> f32 (`.float()`, :1264); the DDIM square roots are taken in f32 on the
@@ -293,43 +294,173 @@ class SpacedDiffusion:
 		s.nonzero = int(i != 0)
 		return s
 
-	def sample_loop(self, model: DiffusionTTS, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-					model_kwargs=None, device=None, progress=False, eta=0.0, sampler="ddim", consume_rng=True):
-		"""diffusion.py:500-508 -> ddim_sample_loop :734-810 / p_sample_loop :556-644.  Returns f32 [b, 100, T]."""
-		sampler = sampler.lower()
-		if sampler not in ("ddim", "p"):
-			raise RuntimeError(f"Sampler not implemented: {sampler}")
-		if not clip_denoised or denoised_fn is not None or cond_fn is not None or eta != 0.0:
-			raise NotImplementedError("only clip_denoised=True, eta=0, no denoised_fn/cond_fn (what inference.py:405-412 uses)")
+	def step_coefs_ext(self, i: int, mode: int, eta: float = 0.0, clip: bool = True) -> _lib.StepExtC:
+		"""The scalars of step i that `step_coefs` does not carry (include/ttk.h: ttk_step_ext).  mode 0 ddim with eta, 1 p, 2 reverse ddim.  As torch computes them
+		on the f32 tensors `_extract_into_tensor` returns: sigma and sqrt(1 - alpha_bar_prev - sigma ** 2) of ddim_sample (:677-688), the square roots of
+		alpha_bar_next of ddim_reverse_sample (:724-729) -- every operation in f32, in the reference's order."""
+		f = np.float32
+		ab, ab_prev, ab_next = f(self.alphas_cumprod[i]), f(self.alphas_cumprod_prev[i]), f(self.alphas_cumprod_next[i])
+		sigma = f(eta) * np.sqrt((f(1) - ab_prev) / (f(1) - ab), dtype=f) * np.sqrt(f(1) - ab / ab_prev, dtype=f)
+		e = _lib.StepExtC()
+		e.sigma = sigma
+		e.dir = np.sqrt(f(1) - ab_prev - sigma * sigma, dtype=f)
+		e.sqrt_ac_next = np.sqrt(ab_next, dtype=f)
+		e.sqrt_1m_ac_next = np.sqrt(f(1) - ab_next, dtype=f)
+		e.mode = int(mode)
+		e.clip = int(bool(clip))
+		return e
+
+	@staticmethod
+	def _check_hooks(denoised_fn, cond_fn):
+		if denoised_fn is not None or cond_fn is not None:
+			raise NotImplementedError("denoised_fn / cond_fn are not supported: a Python callable between the network and the update would put a host round trip "
+									  "into every step of a loop that otherwise runs without one")
+
+	def _model_inputs(self, model, model_kwargs, b: int):
 		if not isinstance(model, DiffusionTTS):
-			raise _lib.TTKError("sample_loop needs the libttk-backed DiffusionTTS (no fallback path)")
+			raise _lib.TTKError("the samplers need the libttk-backed DiffusionTTS (no fallback path)")
 		E = (model_kwargs or {}).get("precomputed_aligned_embeddings")
 		if E is None:
 			raise ValueError("model_kwargs['precomputed_aligned_embeddings'] is required")
-		dev = model.device
-		b, C, T = shape
 		if self.conditioning_free and self.ramp_conditioning_free:
 			assert b == 1, "ramped conditioning-free guidance is batch-1 in the reference (diffusion.py:392)"
+		return E.to(model.device, torch.float32).contiguous()
+
+	def _sample_ext(self, model: DiffusionTTS, x, E, mode: int, eta: float, clip: bool, noise):
+		"""The whole loop of one mode through ttk_diff_sample_ext, x [b, 100, T] f32 on the device in place.  noise: [n, b, 100, T] f32, block j for the j-th
+		executed step, or None when no step reads one (mode 2, mode 0 at eta 0; the library refuses a missing block otherwise)."""
+		n = self.num_timesteps
+		b, _, T = x.shape
+		sampler = "p" if mode == 1 else "ddim"
+		steps = (_lib.StepC * n)(*[self.step_coefs(i, sampler) for i in range(n)])
+		ext = (_lib.StepExtC * n)(*[self.step_coefs_ext(i, mode, eta, clip) for i in range(n)])
+		if noise is not None:
+			noise = noise.to(x.device, torch.float32).contiguous()
+			if tuple(noise.shape) != (n,) + tuple(x.shape):
+				raise ValueError(f"noise must be {(n,) + tuple(x.shape)}, one block per step in running order, got {tuple(noise.shape)}")
+		with torch.cuda.device(x.device):
+			_lib.check(model.lib.ttk_diff_sample_ext(model._h, x.data_ptr(), E.data_ptr(), b, T, steps, ext, n, _lib.ptr(noise), _lib.stream_ptr()),
+					   "ttk_diff_sample_ext")
+		return x
+
+	def sample_loop(self, model: DiffusionTTS, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+					model_kwargs=None, device=None, progress=False, eta=0.0, sampler="ddim", consume_rng=True, step_noise=None):
+		"""diffusion.py:500-508 -> ddim_sample_loop :734-810 / p_sample_loop :556-644.  Returns f32 [b, 100, T].  `eta` and `clip_denoised` act for "ddim",
+		`clip_denoised` for "p" (which ignores eta, as p_sample_loop does not take it); the defaults run the entries they always ran.
+		step_noise (ddim with eta != 0 only): [n, b, 100, T], the per-step randn_like draws in loop order when the caller has made them already (as
+		TTSHotPath.inference_lines does, to keep them in the reference's place in the generator stream); nothing is drawn here then."""
+		sampler = sampler.lower()
+		if sampler not in ("ddim", "p"):
+			raise RuntimeError(f"Sampler not implemented: {sampler}")
+		self._check_hooks(denoised_fn, cond_fn)
+		b, C, T = shape
+		E = self._model_inputs(model, model_kwargs, b)
+		dev = model.device
 		x = (noise if noise is not None else torch.randn(*shape, device=dev)).to(dev, torch.float32).contiguous().clone()
-		E = E.to(dev, torch.float32).contiguous()
 		n = self.num_timesteps
 		with torch.cuda.device(dev):
 			if sampler == "ddim":
-				steps = (_lib.StepC * n)(*[self.step_coefs(i, "ddim") for i in range(n)])
-				_lib.check(model.lib.ttk_diff_sample_ddim(model._h, x.data_ptr(), E.data_ptr(), b, T, steps, n, _lib.stream_ptr()),
-						   "ttk_diff_sample_ddim")
-				# ddim_sample draws (and ignores) one randn_like(x) per step (:685); keep the generator stream aligned
-				# (consume_rng=False: the caller already made these draws, see TTSHotPath.inference_lines)
-				if consume_rng:
+				# ddim_sample draws one randn_like(x) per step (:685).  With eta they are read: drawn here in loop order (or handed in as step_noise) and consumed by
+				# the whole-loop entry.  Without, they are ignored: drawn behind the loop to keep the generator stream aligned (consume_rng=False: the caller
+				# already made these draws, see TTSHotPath.inference_lines)
+				nz = None
+				if eta != 0.0:
+					nz = step_noise if step_noise is not None else torch.stack([torch.randn_like(x) for _ in range(n)])
+				if eta != 0.0 or not clip_denoised:
+					self._sample_ext(model, x, E, 0, float(eta), bool(clip_denoised), nz)
+				else:
+					steps = (_lib.StepC * n)(*[self.step_coefs(i, "ddim") for i in range(n)])
+					_lib.check(model.lib.ttk_diff_sample_ddim(model._h, x.data_ptr(), E.data_ptr(), b, T, steps, n, _lib.stream_ptr()),
+							   "ttk_diff_sample_ddim")
+				if eta == 0.0 and consume_rng:
 					for _ in range(n):
 						torch.randn_like(x)
 			else:
 				# p_sample draws one randn_like(x) per step (:545), in loop order: drawn here, consumed by the whole-loop entry
 				nz = torch.stack([torch.randn_like(x) for _ in range(n)])
-				steps = (_lib.StepC * n)(*[self.step_coefs(i, "p") for i in range(n)])
-				_lib.check(model.lib.ttk_diff_sample_p(model._h, x.data_ptr(), E.data_ptr(), b, T, steps, n, nz.data_ptr(), _lib.stream_ptr()),
-						   "ttk_diff_sample_p")
+				if not clip_denoised:
+					self._sample_ext(model, x, E, 1, 0.0, False, nz)
+				else:
+					steps = (_lib.StepC * n)(*[self.step_coefs(i, "p") for i in range(n)])
+					_lib.check(model.lib.ttk_diff_sample_p(model._h, x.data_ptr(), E.data_ptr(), b, T, steps, n, nz.data_ptr(), _lib.stream_ptr()),
+							   "ttk_diff_sample_p")
 		return x
+
+	# ---- single steps and the generator forms (diffusion.py:510-554, 602-644, 646-732, 768-810): the same update launch behind ttk_diff_begin, with pred_xstart
+	def _index_of(self, t, b: int) -> int:
+		"""`t`: a tensor of one repeated schedule index (or an int), as the reference's loops pass it."""
+		if torch.is_tensor(t):
+			if t.numel() != b or (t != t.reshape(-1)[0]).any():
+				raise ValueError(f"t must hold one schedule index repeated for the batch of {b}, got {t.tolist()}")
+			t = int(t.reshape(-1)[0])
+		if not 0 <= int(t) < self.num_timesteps:
+			raise IndexError(f"schedule index {t} is outside [0, {self.num_timesteps})")
+		return int(t)
+
+	def _single_step(self, model, x, t, mode: int, eta: float, clip: bool, model_kwargs, noise=None) -> Dict[str, torch.Tensor]:
+		"""One step on a copy of x.  noise: the step's randn_like(x); None draws it here exactly where the reference does (ddim_sample :685 and p_sample :545 draw
+		whether or not the value is used; ddim_reverse_sample draws nothing)."""
+		b = x.shape[0]
+		E = self._model_inputs(model, model_kwargs, b)
+		i = self._index_of(t, b)
+		dev = model.device
+		x = x.to(dev, torch.float32).contiguous().clone()
+		T = x.shape[-1]
+		with torch.cuda.device(dev):
+			if mode != 2 and noise is None:
+				noise = torch.randn_like(x)
+			st = self.step_coefs(i, "p" if mode == 1 else "ddim")
+			ext = self.step_coefs_ext(i, mode, eta, clip)
+			reads = mode == 1 or (mode == 0 and ext.sigma != 0.0)
+			nz = noise.to(dev, torch.float32).contiguous() if reads else None
+			px = torch.empty_like(x)
+			_lib.check(model.lib.ttk_diff_begin(model._h, E.data_ptr(), b, T, _lib.stream_ptr()), "ttk_diff_begin")
+			_lib.check(model.lib.ttk_diff_step_ext(model._h, x.data_ptr(), st, ext, _lib.ptr(nz), px.data_ptr(), _lib.stream_ptr()), "ttk_diff_step_ext")
+		return {"sample": x, "pred_xstart": px}
+
+	def p_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None):
+		"""diffusion.py:510-554: x_{t-1} from x_t by the ancestral step -> {"sample", "pred_xstart"}."""
+		self._check_hooks(denoised_fn, cond_fn)
+		return self._single_step(model, x, t, 1, 0.0, bool(clip_denoised), model_kwargs)
+
+	def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, eta=0.0):
+		"""diffusion.py:646-694: x_{t-1} from x_t by DDIM -> {"sample", "pred_xstart"}."""
+		self._check_hooks(denoised_fn, cond_fn)
+		return self._single_step(model, x, t, 0, float(eta), bool(clip_denoised), model_kwargs)
+
+	def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+		"""diffusion.py:696-732: x_{t+1} from x_t by the reverse ODE -> {"sample", "pred_xstart"}."""
+		assert eta == 0.0, "Reverse ODE only for deterministic path"
+		self._check_hooks(denoised_fn, None)
+		return self._single_step(model, x, t, 2, 0.0, bool(clip_denoised), model_kwargs)
+
+	def _loop_progressive(self, step, model, shape, noise, model_kwargs, **kw):
+		img = noise if noise is not None else torch.randn(*shape, device=model.device)
+		for i in reversed(range(self.num_timesteps)):
+			out = step(model, img, torch.tensor([i] * shape[0]), model_kwargs=model_kwargs, **kw)
+			yield out
+			img = out["sample"]
+
+	def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, device=None,
+								  progress=False):
+		"""diffusion.py:602-644: a generator over p_sample's dicts, index n-1 .. 0; the last `sample` equals sample_loop(sampler="p") bit for bit."""
+		self._check_hooks(denoised_fn, cond_fn)
+		return self._loop_progressive(self.p_sample, model, shape, noise, model_kwargs, clip_denoised=clip_denoised)
+
+	def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, device=None,
+									 progress=False, eta=0.0):
+		"""diffusion.py:768-810: a generator over ddim_sample's dicts, index n-1 .. 0; the last `sample` equals sample_loop(sampler="ddim") bit for bit."""
+		self._check_hooks(denoised_fn, cond_fn)
+		return self._loop_progressive(self.ddim_sample, model, shape, noise, model_kwargs, clip_denoised=clip_denoised, eta=eta)
+
+	def ddim_reverse_sample_loop(self, model, x, clip_denoised=True, model_kwargs=None):
+		"""The DDIM encoder: x_0 (a mel in [-1, 1], [b, 100, T]) -> x_n by ddim_reverse_sample at index 0, 1, ..., n-1, as one ttk_diff_sample_ext loop of mode 2.
+		The reference has the step (diffusion.py:696-732) but no loop over it; this is the step called in a Python loop, which is what the fixture of
+		tests/golden/diff_sampler_small.npz records.  Ramped conditioning-free guidance takes the current index i, as p_mean_variance would (:391-393).
+		Draws nothing from the generator.  Returns a new tensor."""
+		E = self._model_inputs(model, model_kwargs, x.shape[0])
+		x = x.to(model.device, torch.float32).contiguous().clone()
+		return self._sample_ext(model, x, E, 2, 0.0, bool(clip_denoised), None)
 
 
 def _sample_loop_lines(self, model: DiffusionTTS, noises, embeddings):

@@ -78,7 +78,7 @@ class HotPathStages:
 
 	def __init__(self, tts: "TTSHotPath", text_tokens, autoregressive_latents, diffusion_latents, *, max_ar_steps=500,
 				 max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0,
-				 diffusion_sampler="ddim", cond_free=True, suppress_tokens=None, phase_marks=None, diffusion_conditioning="latents"):
+				 diffusion_sampler="ddim", cond_free=True, suppress_tokens=None, phase_marks=None, diffusion_conditioning="latents", diffusion_eta=0.0):
 		self.tts, self.ar, self.diff = tts, tts.autoregressive, tts.diffusion
 		if check_diffusion_conditioning(diffusion_conditioning, self.diff):
 			raise NotImplementedError("diffusion_conditioning='codes' is not available on the candidate-sharded path: its ranks exchange every candidate's latents "
@@ -92,8 +92,10 @@ class HotPathStages:
 			self.kw["suppress_tokens"] = suppress_tokens
 		self.diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		self.diffusion_temp, self.sampler = diffusion_temp, diffusion_sampler
-		# dist.ShardStages: the ancestral sampler draws its per-step noise inside the loop, from the generator of the rank that runs it -- such a line stays on its winner's owner
-		self.diffusion_draws_while_running = diffusion_sampler != "ddim"
+		self.eta = float(diffusion_eta) if diffusion_sampler == "ddim" else 0.0      # (the ancestral sampler ignores eta, as the reference's does)
+		# dist.ShardStages: the ancestral sampler draws its per-step noise inside the loop, from the generator of the rank that runs it -- such a line stays on its winner's owner;
+		# so does DDIM with eta != 0, whose per-step draws are read, in generator order
+		self.diffusion_draws_while_running = diffusion_sampler != "ddim" or self.eta != 0.0
 		self.pad_token = self.ar.stop_mel_token
 
 	def _mark(self, name, *extra):
@@ -130,7 +132,7 @@ class HotPathStages:
 		latents = trim_calm_tokens(codes, latents)
 		T = latents.shape[1] * 4 * 24000 // 22050
 		noise = torch.randn((1, 100, T), device=self.ar.device) * self.diffusion_temp
-		if self.sampler == "ddim":
+		if self.sampler == "ddim" and self.eta == 0.0:      # (with eta != 0 the loop itself makes these draws, and reads them)
 			for _ in range(self.diffuser.num_timesteps):
 				torch.randn_like(noise)
 		return latents, noise, T
@@ -148,11 +150,11 @@ class HotPathStages:
 		sampler is ddim with conditioning-free guidance, else one loop per line; each mel bit for bit its own loop's either way"""
 		self._mark("_before_ddim")          # what lies between this line's latent pass and the shared diffusion (later lines' sampling, item moves) is not "ddim"
 		Es = [self.diff.timestep_independent(latents, self.dl, T, False) for latents, _, T in prepared]
-		if len(prepared) > 1 and self.sampler == "ddim" and self.diffuser.conditioning_free:
+		if len(prepared) > 1 and self.sampler == "ddim" and self.diffuser.conditioning_free and self.eta == 0.0:
 			mels = self.diffuser.sample_loop_lines(self.diff, [n for _, n, _ in prepared], Es)
 		else:
 			mels = [self.diffuser.sample_loop(self.diff, (1, 100, T), sampler=self.sampler, noise=n, model_kwargs={"precomputed_aligned_embeddings": E},
-											  progress=False, consume_rng=self.sampler != "ddim") for (_, n, T), E in zip(prepared, Es)]
+											  progress=False, eta=self.eta, consume_rng=self.diffusion_draws_while_running) for (_, n, T), E in zip(prepared, Es)]
 		self._mark("ddim", len(prepared))      # (name, event, lines diffused in this batch): bench.phase_roofline prices the interval with that many lines' work
 		return mels
 
@@ -218,8 +220,11 @@ class TTSHotPath:
 				  max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, diffusion_sampler="ddim", cond_free=True, candidates=1,
 				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1, diffusion_conditioning="latents",
-				  do_sample=True):
+				  do_sample=True, diffusion_eta=0.0):
 		"""text_tokens [1, Tt] int64; latents from the reference's conditioning encoders ([1,1024], [1,2048]).
+		diffusion_eta: DDIM's eta (ddim_sample_loop, diffusion.py:745; the reference's `TTS.inference` leaves it at 0): above 0 the per-step draws the
+		deterministic loop makes and ignores (:685) are read -- 1.0 is the DDPM-variance sampler -- so one set of codes renders differently per seed.
+		The ancestral sampler ignores it.
 		latents_for: "all" = the latent pass over every candidate, as the reference runs it before scoring (inference.py:370-379; the benchmarked
 		workload); "winner" = the k = 1 variant: the candidate is chosen first and only its row goes through the dense
 		pass (the reference's own to-do at :370) -- rows of the pass are independent, so the result is the same bits.
@@ -290,7 +295,7 @@ class TTSHotPath:
 		E = diff.timestep_independent(aligned, diffusion_latents, T, False)
 		noise = torch.randn((1, 100, T), device=dev) * diffusion_temp
 		mel = diffuser.sample_loop(diff, (1, 100, T), sampler=diffusion_sampler, noise=noise,
-								   model_kwargs={"precomputed_aligned_embeddings": E}, progress=False)
+								   model_kwargs={"precomputed_aligned_embeddings": E}, progress=False, eta=float(diffusion_eta))
 		mark("ddim")
 		mels = denormalize_tacotron_mel(mel)[:, :, :T]
 		seconds = T * HOP / SAMPLE_RATE
@@ -304,7 +309,8 @@ class TTSHotPath:
 	@torch.inference_mode()
 	def inference_lines(self, lines, autoregressive_latents, diffusion_latents, *, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8,
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
-						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True):
+						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True,
+						diffusion_eta=0.0):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -324,6 +330,8 @@ class TTSHotPath:
 		own draws the generators are put where its `generate` alone would have left them (UnifiedVoice.position_rng_after_line).
 		diffusion_conditioning="codes": as in `inference` -- each line's chosen code row is its aligned conditioning, no dense latent pass.
 		do_sample=False: greedy search as in `inference` (candidates must be 1): the lines of a batch decode one row each.
+		diffusion_eta != 0: DDIM's per-step draws are kept (the main thread makes them where it made the ignored ones) and every line diffuses in a loop
+		of its own: the ragged batch entry has no form that reads noise.
 		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
@@ -342,15 +350,15 @@ class TTSHotPath:
 			the rows of all lines, each line's mel bit for bit what its own loop gives); a single line takes the single-line entry"""
 			with torch.inference_mode(), torch.cuda.device(dev), torch.cuda.stream(s_df):
 				s_df.wait_event(ready)
-				Es = [diff.timestep_independent(latents, diffusion_latents, T, False) for latents, _, T in group]
+				Es = [diff.timestep_independent(latents, diffusion_latents, T, False) for latents, _, T, _ in group]
 				if len(group) == 1:
-					mel = [diffuser.sample_loop(diff, (1, 100, group[0][2]), sampler="ddim", noise=group[0][1],
+					mel = [diffuser.sample_loop(diff, (1, 100, group[0][2]), sampler="ddim", noise=group[0][1], eta=eta, step_noise=group[0][3],
 												model_kwargs={"precomputed_aligned_embeddings": Es[0]}, progress=False, consume_rng=False)]
 				else:
-					mel = diffuser.sample_loop_lines(diff, [noise for _, noise, _ in group], Es)
-				mels = [denormalize_tacotron_mel(m)[:, :, :T] for m, (_, _, T) in zip(mel, group)]
-				for (latents, noise, _), E in zip(group, Es):
-					for t_ in (latents, noise, E):
+					mel = diffuser.sample_loop_lines(diff, [noise for _, noise, _, _ in group], Es)
+				mels = [denormalize_tacotron_mel(m)[:, :, :T] for m, (_, _, T, _) in zip(mel, group)]
+				for (latents, noise, _, step_noise), E in zip(group, Es):
+					for t_ in (latents, noise, E) + (() if step_noise is None else (step_noise,)):
 						t_.record_stream(s_df)
 				return mels
 
@@ -359,8 +367,9 @@ class TTSHotPath:
 		G = ar_batch_lines or max(1, min(4, ar.max_batch // max(candidates, 1)))
 		G = max(1, min(G, ar.max_batch // max(candidates, 1)))
 		DG = G if ddim_batch_lines is None else max(1, int(ddim_batch_lines))      # lines diffused as one batch (1 = line by line)
-		if not cond_free:
-			DG = 1                                                                     # the ragged batch is laid out as [cond | uncond]
+		eta = float(diffusion_eta)
+		if not cond_free or eta != 0.0:
+			DG = 1                                                                     # the ragged batch is laid out as [cond | uncond], and reads no per-step noise
 		with ThreadPoolExecutor(max_workers=1) as pool:          # one worker: diffusions stay in line order on s_df
 			group, meta = [], []
 			for i, text_tokens in enumerate(lines):
@@ -385,9 +394,13 @@ class TTSHotPath:
 					latents = trim_calm_tokens(codes[best:best + 1], latents)     # host copy of the codes: the AR phase of this line is complete
 					T = latents.shape[1] * 4 * 24000 // 22050
 					noise = torch.randn((1, 100, T), device=dev) * diffusion_temp
-					for _ in range(max_diffusion_steps):                    # DDIM's ignored per-step draws, in reference order
-						torch.randn_like(noise)
-					group.append((latents, noise, T))
+					step_noise = None
+					if eta != 0.0:                                          # DDIM's per-step draws, in reference order: read by this line's loop
+						step_noise = torch.stack([torch.randn_like(noise) for _ in range(max_diffusion_steps)])
+					else:
+						for _ in range(max_diffusion_steps):                    # DDIM's ignored per-step draws, in reference order
+							torch.randn_like(noise)
+					group.append((latents, noise, T, step_noise))
 					meta.append((T, codes))
 					last_of_batch = (i % G == G - 1) or i == len(lines) - 1
 					if len(group) >= DG or last_of_batch:

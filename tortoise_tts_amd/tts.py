@@ -121,7 +121,7 @@ class TTS:
 	@torch.inference_mode()
 	def inference(self, text: str, references=None, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
-				  seed=None, candidates=1, references_sr: int = 22050, do_sample=True) -> Tuple[torch.Tensor, int]:
+				  seed=None, candidates=1, references_sr: int = 22050, do_sample=True, *, diffusion_eta=0.0) -> Tuple[torch.Tensor, int]:
 		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
 		(wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the `vocoder=` part, "vocoder" the
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
@@ -133,7 +133,10 @@ class TTS:
 		With references given the order is the reference's: the clip is encoded first, then the seed is set.
 		do_sample (the reference's `TTS.inference` has no such argument: it always samples, inference.py:336): False speaks every line by greedy search -- the
 		mel codes are then a pure function of (voice, text, weights), whatever `ar_temp`, `top_k`, `top_p` and `seed` are; `seed` still fixes the diffusion
-		noise.  Needs candidates == 1 and beam_width == 1 (ValueError); not available with vocoder_type="hifigan", whose token generator always samples."""
+		noise.  Needs candidates == 1 and beam_width == 1 (ValueError); not available with vocoder_type="hifigan", whose token generator always samples.
+		diffusion_eta (keyword only; DDIM's eta, diffusion.py:745, which the reference's `TTS.inference` leaves at 0): above 0 the sampler reads its
+		per-step noise -- 1.0 is the DDPM-variance sampler -- so the same text and voice render differently per `seed`; 0.0 is the call without it, bit
+		for bit.  The ancestral sampler ignores it; the "hifigan" branch has no diffusion."""
 		from .inference import check_greedy
 		check_greedy(do_sample, candidates, beam_width)
 		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
@@ -169,7 +172,8 @@ class TTS:
 									  repetition_penalty=repetition_penalty, length_penalty=length_penalty) for tokens in lines]
 			return torch.concat(wavs, dim=-1), SAMPLE_RATE
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
-				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates, do_sample=do_sample)
+				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates, do_sample=do_sample,
+				  diffusion_eta=diffusion_eta)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
 		if beam_width != 1:                                   # the beams of a line exchange histories every token: lines are sampled one by one
 			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
@@ -183,12 +187,13 @@ class TTS:
 
 	@torch.inference_mode()
 	def decode_codes(self, codes, references=None, *, max_diffusion_steps=80, diffusion_temp=1.0, diffusion_sampler="ddim", cond_free=True,
-					 vocoder_type="bigvgan", seed=None, references_sr: int = 22050) -> Tuple[torch.Tensor, int]:
+					 vocoder_type="bigvgan", seed=None, references_sr: int = 22050, diffusion_eta=0.0) -> Tuple[torch.Tensor, int]:
 		"""Mel codes -> waveform without the autoregressive model: the diffusion model's token branch (diffusion.py:1493-1497) on `codes`, the sampler and
 		the vocoder as in `inference`.  codes: [1, M] integers (what `encode_audio(...)["codes"]` or the AR sampling give), or a list of such rows --
 		the rows' waveforms come back concatenated in time, each what its own call with the same `seed` gives; with the DDIM sampler and conditioning-free guidance several
 		rows are diffused as one ragged batch (SpacedDiffusion.sample_loop_lines).  The voice is the diffusion latent of `references` (clip tensor(s) or an
 		`encode_audio` dict), or a random voice when None, seeded as in `inference`.  T = M * 4 * 24000 // 22050 frames per row (inference.py:400).
+		diffusion_eta: DDIM's eta as in `inference`; above 0 every row diffuses in a loop of its own.
 		Returns (wav [1, 1, samples], 24000).  vocoder_type "bigvgan" or "vocoder"; "hifigan" is refused: it reads AR latents, which codes alone do not give."""
 		from .diffusion import denormalize_tacotron_mel, get_diffuser
 		from .inference import check_diffusion_conditioning
@@ -214,6 +219,7 @@ class TTS:
 		diff_latent = self.encode_audio(references, references_sr)["latent"][1]
 		seed = set_seed(seed)
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
+		eta = float(diffusion_eta)
 		prepared = []
 		for r in rows:
 			# every row draws from the generators as `seed` leaves them -- the start noise, then DDIM's ignored per-step draws (diffusion.py:685) -- so a row of a
@@ -222,15 +228,18 @@ class TTS:
 			T = r.shape[1] * 4 * 24000 // 22050
 			E = diff.timestep_independent(r.to(self.device), diff_latent, T, False)
 			noise = torch.randn((1, 100, T), device=self.device) * diffusion_temp
-			if diffusion_sampler == "ddim":
+			step_noise = None
+			if diffusion_sampler == "ddim" and eta != 0.0:      # ... which are read then
+				step_noise = torch.stack([torch.randn_like(noise) for _ in range(diffuser.num_timesteps)])
+			elif diffusion_sampler == "ddim":
 				for _ in range(diffuser.num_timesteps):
 					torch.randn_like(noise)
-			prepared.append((E, noise, T))
-		if len(prepared) > 1 and diffusion_sampler == "ddim" and cond_free:
-			mels = diffuser.sample_loop_lines(diff, [n for _, n, _ in prepared], [E for E, _, _ in prepared])
+			prepared.append((E, noise, T, step_noise))
+		if len(prepared) > 1 and diffusion_sampler == "ddim" and cond_free and eta == 0.0:
+			mels = diffuser.sample_loop_lines(diff, [n for _, n, _, _ in prepared], [E for E, _, _, _ in prepared])
 		else:
 			mels = [diffuser.sample_loop(diff, (1, 100, T), sampler=diffusion_sampler, noise=n, model_kwargs={"precomputed_aligned_embeddings": E},
-										 progress=False, consume_rng=diffusion_sampler != "ddim") for E, n, T in prepared]
+										 progress=False, eta=eta, step_noise=sn, consume_rng=diffusion_sampler != "ddim") for E, n, T, sn in prepared]
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference
 		return torch.concat([to_wav(denormalize_tacotron_mel(m)) for m in mels], dim=-1), SAMPLE_RATE
 
