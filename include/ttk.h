@@ -415,6 +415,33 @@ int ttk_diff_step_ext(ttk_diff* h, float* x, const ttk_step* st, const ttk_step_
 int ttk_diffusion_step_ext_rows(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int T,
 								const ttk_step* st, const ttk_step_ext* ext, void* xcl, int ldo, int rep, int xcl_dtype, void* stream);
 
+/* DPM-Solver++(2M) (Lu et al. 2022: data prediction, second-order multistep), the sampler `sample_loop(sampler="dpm++2m")` runs.  No reference counterpart: the
+ * reference raises on any name but ddim / p (:500-508).  One network evaluation pair per step as DDIM, and one step of x0 history:
+ *   x = c_x x + c_d0 x0 + c_d1 x0_prev,   x0 as ttk_step_ext's (guidance mix, fma, the clamp when `clip`)
+ * on a kernel of its own, k_diffusion_step_ms.  The three coefficients come from the host's f64 tables (tortoise_tts_amd/diffusion.py: step_coefs_ms; DESIGN.md has
+ * the formulas); c_d1 == 0 makes the step first order -- DDIM's -- and such a step does not read the history.  `ttk_step.sampler` is not read by these entries.   */
+typedef struct {
+	float c_x;                 /* weight of x: sigma(i-1) / sigma(i); 0 at index 0 */
+	float c_d0;                /* weight of this step's x0; 1 at index 0 */
+	float c_d1;                /* weight of the previous step's x0; 0 at index n-1 (no history yet) and at index 0 (lower-order final step) */
+	int clip;                  /* clip_denoised: clamp the predicted x0 to [-1, 1] */
+} ttk_step_ms;
+
+/* Whole loop, steps[n-1], ..., steps[0] with ms[i] beside steps[i], on the machinery of ttk_diff_sample_ddim (time path of all steps at once, two-stream integrator
+ * pipeline, each update launch writing the next step's operand copy).  The history lives in a grow-only buffer of the handle; every loop writes it before reading
+ * it, so nothing carries over between calls.  ms[n_steps-1].c_d1 != 0 is TTK_E_ARG: there is no history yet.  Equal to n_steps ttk_diff_step_ms calls bit for bit. */
+int ttk_diff_sample_ms(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, const ttk_step_ms* ms, int n_steps, void* stream);
+/* The ragged batch of ttk_diff_sample_ddim_lines under this update, same contract: Tp % 64 == 0, b <= 32, every step with guidance (cfk >= 0), padding frames
+ * ignored on input and undefined on output; element e bit for bit what ttk_diff_sample_ms(b = 1, T = tlen[e]) gives.                                              */
+int ttk_diff_sample_ms_lines(ttk_diff* h, float* x, const float* E, int b, int Tp, const int* tlen, const ttk_step* steps, const ttk_step_ms* ms, int n_steps,
+							 void* stream);
+/* One step behind ttk_diff_begin, as ttk_diff_step_ext.  x0_hist [b, in, T] f32 belongs to the caller: read as x0_prev when ms->c_d1 != 0, then overwritten with
+ * this step's x0; NULL is accepted when ms->c_d1 == 0 (nothing is kept then), else TTK_E_ARG.  pred_xstart: NULL or [b, in, T] f32.                                  */
+int ttk_diff_step_ms(ttk_diff* h, float* x, float* x0_hist, const ttk_step* st, const ttk_step_ms* ms, float* pred_xstart, void* stream);
+/* Kernel form: the update launch alone on caller buffers, operands as ttk_diffusion_step_ext_rows with x0_hist [nb, C, T] f32 in the place of noise.               */
+int ttk_diffusion_step_ms_rows(const float* out_c, const float* out_u, float* x, float* x0_hist, float* pred_xstart, int nb, int C, int T, const ttk_step* st,
+							   const ttk_step_ms* ms, void* xcl, int ldo, int rep, int xcl_dtype, void* stream);
+
 /* ------------------------------------------------------------------ BigVGAN vocoder
  * The generator of models/bigvgan.py (BigVGAN.__init__ :419-486) on the hot path's kernels.  Weights: the generator's state_dict
  * with weight norm folded into plain `weight` tensors (tortoise_tts_amd/vocoder.py does that), plus "__aa_filter" [12], the Kaiser

@@ -53,6 +53,11 @@ class StepExtC(C.Structure):
 	_fields_ = [(n, C.c_float) for n in ("sigma", "dir", "sqrt_ac_next", "sqrt_1m_ac_next")] + [("mode", C.c_int), ("clip", C.c_int)]
 
 
+class StepMsC(C.Structure):
+	"""ttk_step_ms (include/ttk.h; static_assert'ed in csrc/diff.hip)"""
+	_fields_ = [(n, C.c_float) for n in ("c_x", "c_d0", "c_d1")] + [("clip", C.c_int)]
+
+
 class SampleArgs(C.Structure):
 	"""ttk_sample_args (include/ttk.h)"""
 	_fields_ = [("scores", C.c_void_p), ("ld", C.c_int64), ("B", C.c_int), ("V", C.c_int), ("q", C.c_void_p), ("ldq", C.c_int64),
@@ -216,6 +221,10 @@ SYMBOLS = {
 	"ttk_diff_sample_ext": (_I, [_P, _P, _P, _I, _I, C.POINTER(StepC), C.POINTER(StepExtC), _I, _P, _P]),
 	"ttk_diff_step_ext": (_I, [_P, _P, C.POINTER(StepC), C.POINTER(StepExtC), _P, _P, _P]),
 	"ttk_diffusion_step_ext_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(StepC), C.POINTER(StepExtC), _P, _I, _I, _I, _P]),
+	"ttk_diff_sample_ms": (_I, [_P, _P, _P, _I, _I, C.POINTER(StepC), C.POINTER(StepMsC), _I, _P]),
+	"ttk_diff_sample_ms_lines": (_I, [_P, _P, _P, _I, _I, C.POINTER(C.c_int), C.POINTER(StepC), C.POINTER(StepMsC), _I, _P]),
+	"ttk_diff_step_ms": (_I, [_P, _P, _P, C.POINTER(StepC), C.POINTER(StepMsC), _P, _P]),
+	"ttk_diffusion_step_ms_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(StepC), C.POINTER(StepMsC), _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -38,7 +38,11 @@ struct Gn {
 // layout: the channels-last copy of x is not there yet, the step runs the layout launch; stage_next: its update launch also writes the next step's copy (same batch
 // layout in both; not for ragged batches, whose padding frames must read zero)
 // ext / pred_xstart: the step runs the extended update (ttk_diff_sample_ext, ttk_diff_step_ext); null on the loops that predate it
-struct StepPlan { const ttk_step* st; int nb; const float* emb; const float* noise; bool layout, stage_next; const ttk_step_ext* ext = nullptr; float* pred_xstart = nullptr; };
+// ms / x0_hist: the step runs the multistep update (ttk_diff_sample_ms, ttk_diff_sample_ms_lines, ttk_diff_step_ms) on that history buffer
+struct StepPlan {
+	const ttk_step* st; int nb; const float* emb; const float* noise; bool layout, stage_next; const ttk_step_ext* ext = nullptr; float* pred_xstart = nullptr;
+	const ttk_step_ms* ms = nullptr; float* x0_hist = nullptr;
+};
 }  // namespace
 
 struct ttk_diff {
@@ -62,6 +66,7 @@ struct ttk_diff {
 	Lane lane[2];
 	Lane* L = &lane[0];      // the lane the block helpers below enqueue into (host code is sequential: flipped around the side-stream work)
 	WsBuf cs, cs2, xs, h0, csT, xcl, outb, ecl, ms_ecl, temb, e1, e2, se, emb_all, lat_T;
+	WsBuf x0h;              // the x0 history of the multistep sampler's loops (ttk_diff_sample_ms, ttk_diff_sample_ms_lines): [b][in][T] f32, grow-only, written before it is read
 	WsBuf hf0, ms_hf0;      // in_layers of the FIRST integrator ResBlock applied to the staged embedding (+ the GroupNorm statistics of the result): the same in every step
 	hipStream_t side = nullptr;
 	hipEvent_t ev_fork = nullptr, ev_int[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
@@ -449,10 +454,13 @@ static int check_ext(const char* who, const ttk_step_ext& e, int i) {
 	TTK_REQUIRE(e.sigma >= 0.f, TTK_E_ARG, "%s: step %d has sigma %g", who, i, (double)e.sigma);
 	return TTK_OK;
 }
+static_assert(sizeof(ttk_step_ms) == 16, "ttk_step_ms is mirrored by tortoise_tts_amd/_lib.py: StepMsC");
+static StepMs ms_of(const ttk_step_ms& m) { return {m.c_x, m.c_d0, m.c_d1, m.clip}; }
 // The steps of a loop in the order they run: steps[n-1], ..., steps[0]; `noise` (ancestral sampler) holds one [b, in, T] draw per step in that order, null for ddim;
 // emb_all has one row per schedule index.  One layout launch per run of steps with the same batch layout: each update launch writes the next step's copy of x.
 // ascending (the reverse ODE of ttk_diff_sample_ext): steps[0], ..., steps[n-1] instead; ext: the extended update's per-step block, same indexing as steps.
-static std::vector<StepPlan> plan_steps(ttk_diff* h, const ttk_step* steps, int n, const float* emb_all, int64_t emb_stride, const float* noise, const ttk_step_ext* ext = nullptr, bool ascending = false) {
+static std::vector<StepPlan> plan_steps(ttk_diff* h, const ttk_step* steps, int n, const float* emb_all, int64_t emb_stride, const float* noise, const ttk_step_ext* ext = nullptr, bool ascending = false,
+									const ttk_step_ms* ms = nullptr, float* x0_hist = nullptr) {
 	const size_t nz = (size_t)h->cur_b * h->cfg.in_channels * h->cur_T;
 	std::vector<StepPlan> plan(n);
 	for (int j = 0; j < n; ++j) {
@@ -464,6 +472,7 @@ static std::vector<StepPlan> plan_steps(ttk_diff* h, const ttk_step* steps, int 
 		p.layout = j == 0 || !plan[j - 1].stage_next;
 		p.stage_next = next >= 0 && next < n && !h->tlen && (steps[next].cfk >= 0.f) == cf;
 		p.ext = ext ? ext + i : nullptr;
+		p.ms = ms ? ms + i : nullptr; p.x0_hist = x0_hist;
 	}
 	return plan;
 }
@@ -475,6 +484,11 @@ static void step_body(ttk_diff* h, float* x, const StepPlan& p, const float* cs,
 	float* out = (float*)h->outb.p;
 	body(h, p.nb, T, p.emb, 0, cs, out, s, cs_consumed);
 	const float* out_u = out + (size_t)b * h->cfg.out_channels * T;
+	if (p.ms) {
+		if (p.stage_next) launch_diffusion_step_ms(out, out_u, x, p.x0_hist, p.pred_xstart, b, Cin, T, coefs_of(*p.st), ms_of(*p.ms), s, h->xcl.p, h->in_pad, rep, elem_kind(h->dt));
+		else launch_diffusion_step_ms(out, out_u, x, p.x0_hist, p.pred_xstart, b, Cin, T, coefs_of(*p.st), ms_of(*p.ms), s);
+		return;
+	}
 	if (p.ext) {
 		if (p.stage_next) launch_diffusion_step_ext(out, out_u, x, p.noise, p.pred_xstart, b, Cin, T, coefs_of(*p.st), ext_of(*p.ext), s, h->xcl.p, h->in_pad, rep, elem_kind(h->dt));
 		else launch_diffusion_step_ext(out, out_u, x, p.noise, p.pred_xstart, b, Cin, T, coefs_of(*p.st), ext_of(*p.ext), s);
@@ -500,8 +514,9 @@ int ttk_diff_step(ttk_diff* h, float* x, const ttk_step* st, const float* noise,
 
 // The whole sampler loop, both samplers (see plan_steps for the order of steps and noise).
 // ext (ttk_diff_sample_ext): the extended update with one block per step; `sampler` is then not looked at, the mode of ext[0] decides the order.
+// ms (ttk_diff_sample_ms, ttk_diff_sample_ms_lines): the multistep update with one block per step, on the handle's history buffer; `sampler` is not looked at either.
 static int sample_loop(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, int sampler, void* stream, const char* who,
-					   const ttk_step_ext* ext = nullptr) {
+					   const ttk_step_ext* ext = nullptr, const ttk_step_ms* ms = nullptr) {
 	TTK_REQUIRE(h && x && E && steps && n_steps >= 1, TTK_E_ARG, "%s: bad argument", who);
 	if (ext) {
 		for (int i = 0; i < n_steps; ++i) {
@@ -510,15 +525,17 @@ static int sample_loop(ttk_diff* h, float* x, const float* E, int b, int T, cons
 			TTK_REQUIRE(noise || !ext_reads_noise(steps[i], ext[i]), TTK_E_ARG, "%s: step %d adds noise (mode %d, sigma %g) but noise is null", who, i, ext[i].mode, (double)ext[i].sigma);
 		}
 	}
-	else TTK_REQUIRE(sampler == 0 || noise, TTK_E_ARG, "%s: the p sampler needs one noise block per step", who);
+	else if (!ms) TTK_REQUIRE(sampler == 0 || noise, TTK_E_ARG, "%s: the p sampler needs one noise block per step", who);
 	TTK_REQUIRE(h->cfg.out_channels == 2 * h->cfg.in_channels, TTK_E_ARG, "%s: learned-range output needs out = 2 * in channels", who);
 	hipStream_t s = (hipStream_t)stream;
 	TTK_TRY(ttk_diff_begin(h, E, b, T, stream));
 	// the timestep-only work of ALL steps in one pass: [n_steps] rows through time_embed + every emb_layers (weights read once)
 	std::vector<int64_t> ts(n_steps);
-	for (int i = 0; i < n_steps; ++i) { ts[i] = steps[i].t; TTK_REQUIRE(ext || steps[i].sampler == sampler, TTK_E_ARG, "%s: step %d has sampler %d", who, i, steps[i].sampler); }
+	for (int i = 0; i < n_steps; ++i) { ts[i] = steps[i].t; TTK_REQUIRE(ext || ms || steps[i].sampler == sampler, TTK_E_ARG, "%s: step %d has sampler %d", who, i, steps[i].sampler); }
 	TTK_TRY(time_path(h, nullptr, ts.data(), n_steps, s));
-	const std::vector<StepPlan> plan = plan_steps(h, steps, n_steps, (const float*)h->emb_all.p, (int64_t)h->n_emb * 2 * h->cfg.model_channels, noise, ext, ext && ext[0].mode == 2);
+	if (ms) TTK_TRY(h->x0h.reserve((size_t)b * h->cfg.in_channels * T * 4));
+	const std::vector<StepPlan> plan = plan_steps(h, steps, n_steps, (const float*)h->emb_all.p, (int64_t)h->n_emb * 2 * h->cfg.model_channels, noise, ext, ext && ext[0].mode == 2,
+												  ms, ms ? (float*)h->x0h.p : nullptr);
 	// Pipelined over two streams.  The integrator of a step depends on its timestep and the staged embedding only, never on x: the one of
 	// step j+1 runs on the side stream (own scratch lane, the other `cs` buffer) while the body of step j runs here.  Both are chains of
 	// small dependent launches that leave most of the chip idle, so they overlap; one fork and one join edge per step.  Sequential
@@ -573,15 +590,17 @@ int ttk_diff_sample_ddim(ttk_diff* h, float* x, const float* E, int b, int T, co
 // query blocks beyond it, GroupNorm statistics cover exactly its frames, chunked from its first frame, the k = 3 convolutions read zeros beyond
 // its last frame -- and everything else is row-wise, so element e comes out BIT FOR BIT as ttk_diff_sample_ddim(b = 1, T = tlen[e]) gives it,
 // while every GEMM of a step runs over the rows of all elements (2 b Tp instead of 2 T: more than one tile per CU).
-int ttk_diff_sample_ddim_lines(ttk_diff* h, float* x, const float* E, int b, int Tp, const int* tlen, const ttk_step* steps, int n_steps, void* stream) {
-	TTK_REQUIRE(h && x && E && tlen && steps, TTK_E_ARG, "ttk_diff_sample_ddim_lines: null argument");
-	TTK_REQUIRE(b >= 1 && 2 * b <= 64, TTK_E_ARG, "ttk_diff_sample_ddim_lines: %d elements (1..32)", b);
-	TTK_REQUIRE(Tp >= 64 && Tp % 64 == 0, TTK_E_ARG, "ttk_diff_sample_ddim_lines: the slot length %d must be a multiple of 64 frames", Tp);
+// (`ms`: the same batch under the multistep update, ttk_diff_sample_ms_lines: the update is element-wise, so the property carries over)
+static int sample_lines(ttk_diff* h, float* x, const float* E, int b, int Tp, const int* tlen, const ttk_step* steps, int n_steps, void* stream, const char* who,
+						const ttk_step_ms* ms = nullptr) {
+	TTK_REQUIRE(h && x && E && tlen && steps, TTK_E_ARG, "%s: null argument", who);
+	TTK_REQUIRE(b >= 1 && 2 * b <= 64, TTK_E_ARG, "%s: %d elements (1..32)", who, b);
+	TTK_REQUIRE(Tp >= 64 && Tp % 64 == 0, TTK_E_ARG, "%s: the slot length %d must be a multiple of 64 frames", who, Tp);
 	const int C = h->cfg.model_channels;
-	for (int i = 0; i < n_steps; ++i) TTK_REQUIRE(steps[i].cfk >= 0.f, TTK_E_ARG, "ttk_diff_sample_ddim_lines: step %d has no conditioning-free evaluation (the batch is laid out as [cond | uncond])", i);
+	for (int i = 0; i < n_steps; ++i) TTK_REQUIRE(steps[i].cfk >= 0.f, TTK_E_ARG, "%s: step %d has no conditioning-free evaluation (the batch is laid out as [cond | uncond])", who, i);
 	int host_len[128], host_need[128], any_need = 0;
 	for (int e = 0; e < b; ++e) {
-		TTK_REQUIRE(tlen[e] >= 1 && tlen[e] <= Tp, TTK_E_ARG, "ttk_diff_sample_ddim_lines: element %d has %d frames, slot %d", e, tlen[e], Tp);
+		TTK_REQUIRE(tlen[e] >= 1 && tlen[e] <= Tp, TTK_E_ARG, "%s: element %d has %d frames, slot %d", who, e, tlen[e], Tp);
 		// a batch of its own length would take its statistics from the GEMM epilogues iff gemm_fuses_gn_stats says so for that length
 		const int nd = !(h->fuse_stats && gemm_fuses_gn_stats(2 * tlen[e], C, C, tlen[e]));
 		host_len[e] = host_len[b + e] = tlen[e];
@@ -594,9 +613,12 @@ int ttk_diff_sample_ddim_lines(ttk_diff* h, float* x, const float* E, int b, int
 	TTK_HIP(hipStreamSynchronize(s));      // the staging arrays live on this stack frame
 	h->tlen = h->d_tlen;
 	h->need = any_need ? h->d_need : nullptr;
-	const int rc = sample_loop(h, x, E, b, Tp, steps, n_steps, nullptr, 0, stream, "ttk_diff_sample_ddim_lines");
+	const int rc = sample_loop(h, x, E, b, Tp, steps, n_steps, nullptr, 0, stream, who, nullptr, ms);
 	h->tlen = nullptr; h->need = nullptr;
 	return rc;
+}
+int ttk_diff_sample_ddim_lines(ttk_diff* h, float* x, const float* E, int b, int Tp, const int* tlen, const ttk_step* steps, int n_steps, void* stream) {
+	return sample_lines(h, x, E, b, Tp, tlen, steps, n_steps, stream, "ttk_diff_sample_ddim_lines");
 }
 
 int ttk_diff_sample_p(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, int n_steps, const float* noise, void* stream) {
@@ -634,6 +656,54 @@ int ttk_diffusion_step_ext_rows(const float* out_c, const float* out_u, float* x
 	TTK_REQUIRE(!xcl || (ldo >= C && rep >= 1 && (xcl_dtype == DT_F32 || xcl_dtype == DT_BF16 || xcl_dtype == DT_F16)), TTK_E_ARG,
 				"ttk_diffusion_step_ext_rows: the channels-last copy needs ldo >= C, rep >= 1 and an f32 / bf16 / f16 type (ldo %d, rep %d, type %d)", ldo, rep, xcl_dtype);
 	launch_diffusion_step_ext(out_c, out_u, x, noise, pred_xstart, nb, C, T, coefs_of(*st), ext_of(*ext), (hipStream_t)stream, xcl, ldo, rep, elem_kind(xcl_dtype));
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+// ---- DPM-Solver++(2M): the multistep update (k_diffusion_step_ms) behind the same loop machinery.  The argument checks that concern `ms` come first and touch neither
+// the handle nor the device.
+static int check_ms_loop(const char* who, const ttk_step_ms* ms, int n_steps) {
+	TTK_REQUIRE(ms && n_steps >= 1, TTK_E_ARG, "%s: null ms, or no steps", who);
+	TTK_REQUIRE(ms[n_steps - 1].c_d1 == 0.f, TTK_E_ARG, "%s: step %d, the first to run, has c_d1 = %g, but there is no history yet", who, n_steps - 1, (double)ms[n_steps - 1].c_d1);
+	return TTK_OK;
+}
+
+int ttk_diff_sample_ms(ttk_diff* h, float* x, const float* E, int b, int T, const ttk_step* steps, const ttk_step_ms* ms, int n_steps, void* stream) {
+	TTK_TRY(check_ms_loop("ttk_diff_sample_ms", ms, n_steps));
+	return sample_loop(h, x, E, b, T, steps, n_steps, nullptr, 0, stream, "ttk_diff_sample_ms", nullptr, ms);
+}
+
+int ttk_diff_sample_ms_lines(ttk_diff* h, float* x, const float* E, int b, int Tp, const int* tlen, const ttk_step* steps, const ttk_step_ms* ms, int n_steps, void* stream) {
+	TTK_TRY(check_ms_loop("ttk_diff_sample_ms_lines", ms, n_steps));
+	return sample_lines(h, x, E, b, Tp, tlen, steps, n_steps, stream, "ttk_diff_sample_ms_lines", ms);
+}
+
+int ttk_diff_step_ms(ttk_diff* h, float* x, float* x0_hist, const ttk_step* st, const ttk_step_ms* ms, float* pred_xstart, void* stream) {
+	TTK_REQUIRE(ms, TTK_E_ARG, "ttk_diff_step_ms: null ms");
+	TTK_REQUIRE(x0_hist || ms->c_d1 == 0.f, TTK_E_ARG, "ttk_diff_step_ms: c_d1 = %g reads the x0 history, which is null", (double)ms->c_d1);
+	TTK_REQUIRE(h && x && st, TTK_E_ARG, "ttk_diff_step_ms: null argument");
+	TTK_REQUIRE(h->staged, TTK_E_STATE, "ttk_diff_step_ms: call ttk_diff_begin first");
+	TTK_REQUIRE(h->cfg.out_channels == 2 * h->cfg.in_channels, TTK_E_ARG, "ttk_diff_step_ms: learned-range output needs out = 2 * in channels");
+	hipStream_t s = (hipStream_t)stream;
+	TTK_TRY(time_path(h, nullptr, &st->t, 1, s));
+	StepPlan p = plan_steps(h, st, 1, (const float*)h->emb_all.p, 0, nullptr, nullptr, false, ms, x0_hist)[0];
+	p.pred_xstart = pred_xstart;
+	integrator(h, p.nb, h->cur_T, p.emb, 0, (float*)h->cs.p, s, true);
+	step_body(h, x, p, (const float*)h->cs.p, nullptr, s);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_diffusion_step_ms_rows(const float* out_c, const float* out_u, float* x, float* x0_hist, float* pred_xstart, int nb, int C, int T, const ttk_step* st,
+							   const ttk_step_ms* ms, void* xcl, int ldo, int rep, int xcl_dtype, void* stream) {
+	TTK_REQUIRE(ms, TTK_E_ARG, "ttk_diffusion_step_ms_rows: null ms");
+	TTK_REQUIRE(x0_hist || ms->c_d1 == 0.f, TTK_E_ARG, "ttk_diffusion_step_ms_rows: c_d1 = %g reads the x0 history, which is null", (double)ms->c_d1);
+	TTK_REQUIRE(out_c && x && st, TTK_E_ARG, "ttk_diffusion_step_ms_rows: null argument");
+	TTK_REQUIRE(nb >= 1 && C >= 1 && T >= 1, TTK_E_ARG, "ttk_diffusion_step_ms_rows: empty input");
+	TTK_REQUIRE(out_u || st->cfk < 0.f, TTK_E_ARG, "ttk_diffusion_step_ms_rows: cfk >= 0 mixes in out_u, which is null");
+	TTK_REQUIRE(!xcl || (ldo >= C && rep >= 1 && (xcl_dtype == DT_F32 || xcl_dtype == DT_BF16 || xcl_dtype == DT_F16)), TTK_E_ARG,
+				"ttk_diffusion_step_ms_rows: the channels-last copy needs ldo >= C, rep >= 1 and an f32 / bf16 / f16 type (ldo %d, rep %d, type %d)", ldo, rep, xcl_dtype);
+	launch_diffusion_step_ms(out_c, out_u, x, x0_hist, pred_xstart, nb, C, T, coefs_of(*st), ms_of(*ms), (hipStream_t)stream, xcl, ldo, rep, elem_kind(xcl_dtype));
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

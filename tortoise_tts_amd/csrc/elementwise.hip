@@ -289,4 +289,48 @@ void launch_diffusion_step_ext(const float* out_c, const float* out_u, float* x,
 	hipLaunchKernelGGL(k_diffusion_step_ext, dim3(grid_for(total)), dim3(256), 0, s, out_c, out_u, x, noise, pred_xstart, nb, C, T, c, e, xcl, ldo, rep, ekind);
 }
 
+// DPM-Solver++(2M) (Lu et al. 2022, data prediction, multistep): a second-order update that carries one step of x0 history, no reference counterpart
+// (the reference raises on any sampler but ddim / p, diffusion.py:500-508).  x0 is k_diffusion_step_ext's -- guidance mix, fma, the clamp when m.clip -- and
+//   x = c_x x + c_d0 x0 + c_d1 x0_prev        c_x, c_d0, c_d1 from the host's f64 tables (diffusion.py: step_coefs_ms)
+// x0_hist ([nb][C][T] f32, or null when c_d1 == 0): each thread reads its own element as x0_prev and then overwrites it with this step's x0.  A step with
+// c_d1 == 0 (the first of a loop, the last, a forced first-order step) does not read it: the first step's buffer is uninitialised, and 0 * NaN is NaN.
+// Contraction is off and the two fusions are named, as in k_diffusion_step_ext, so that tests/dpmpp_ref.py can follow it bit for bit.
+__global__ void k_diffusion_step_ms(const float* out_c, const float* out_u, float* x, float* x0_hist, float* pred_xstart, int nb, int C, int Tn, StepCoefs k, StepMs m,
+									void* xcl, int ldo, int rep, int ekind) {
+#pragma clang fp contract(off)
+	const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const int64_t per = (int64_t)C * Tn;
+	if (idx >= nb * per) return;
+	const int b = (int)(idx / per);
+	const int64_t r = idx - b * per;
+	float eps = out_c[(int64_t)b * 2 * per + r];
+	if (k.cfk >= 0.f) {
+		const float eu = out_u[(int64_t)b * 2 * per + r];
+		eps = (1.0f + k.cfk) * eps - k.cfk * eu;
+	}
+	const float xv = x[idx];
+	const float rx = k.sqrt_recip_ac * xv;
+	float x0 = __builtin_fmaf(-k.sqrt_recipm1_ac, eps, rx);
+	if (m.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+	if (pred_xstart) pred_xstart[idx] = x0;
+	float xn = __builtin_fmaf(m.c_d0, x0, m.c_x * xv);
+	if (m.c_d1 != 0.f) xn = __builtin_fmaf(m.c_d1, x0_hist[idx], xn);
+	if (x0_hist) x0_hist[idx] = x0;
+	x[idx] = xn;
+	if (xcl) {
+		const int c = (int)(r / Tn), t = (int)(r - (int64_t)c * Tn);
+		for (int q = 0; q < rep; ++q) {
+			const int64_t o = (((int64_t)q * nb + b) * Tn + t) * ldo + c;
+			if (ekind == EK_F32) ((float*)xcl)[o] = xn;
+			else if (ekind == EK_F16) ((f16*)xcl)[o] = cvt<f16>(xn);
+			else ((bf16*)xcl)[o] = cvt<bf16>(xn);
+		}
+	}
+}
+void launch_diffusion_step_ms(const float* out_c, const float* out_u, float* x, float* x0_hist, float* pred_xstart, int nb, int C, int T, StepCoefs c, StepMs m, hipStream_t s,
+							  void* xcl, int ldo, int rep, int ekind) {
+	const int64_t total = (int64_t)nb * C * T;
+	hipLaunchKernelGGL(k_diffusion_step_ms, dim3(grid_for(total)), dim3(256), 0, s, out_c, out_u, x, x0_hist, pred_xstart, nb, C, T, c, m, xcl, ldo, rep, ekind);
+}
+
 }  // namespace ttk

@@ -316,6 +316,11 @@ void launch_diffusion_step(const float* out_c, const float* out_u, float* x, con
 struct StepExt { float sigma, dir, sqrt_ac_next, sqrt_1m_ac_next; int mode, clip; };
 void launch_diffusion_step_ext(const float* out_c, const float* out_u, float* x, const float* noise, float* pred_xstart, int nb, int C, int T, StepCoefs c, StepExt e,
 							   hipStream_t s, void* xcl = nullptr, int ldo = 0, int rep = 0, int ekind = 0);
+// the DPM-Solver++(2M) update (k_diffusion_step_ms): x = c_x x + c_d0 x0 + c_d1 x0_prev on the same x0; x0_hist [nb][C][T] f32 read (when c_d1 != 0) and then
+// overwritten with this step's x0, null allowed at c_d1 == 0; `c.sampler`, `c.nonzero` and the variance scalars are not read
+struct StepMs { float c_x, c_d0, c_d1; int clip; };
+void launch_diffusion_step_ms(const float* out_c, const float* out_u, float* x, float* x0_hist, float* pred_xstart, int nb, int C, int T, StepCoefs c, StepMs m,
+							  hipStream_t s, void* xcl = nullptr, int ldo = 0, int rep = 0, int ekind = 0);
 
 // ---------------------------------------------------------------- packing (pack.hip)
 enum PackLayout { PK_NK = 0, PK_KN = 1, PK_CONV3 = 2, PK_CONVK = 3, PK_CONVT = 4 };   // CONVK: src[n][k][ntap]; CONVT: src[k][n][ntap]

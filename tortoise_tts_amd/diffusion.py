@@ -310,6 +310,37 @@ class SpacedDiffusion:
 		e.clip = int(bool(clip))
 		return e
 
+	def step_coefs_ms(self, i: int, clip: bool = True) -> _lib.StepMsC:
+		"""The three scalars of step i of DPM-Solver++(2M) (Lu et al. 2022; include/ttk.h: ttk_step_ms), x_new = c_x x + c_d0 x0 + c_d1 x0_prev, on the respaced schedule:
+		alpha_i = sqrt(alphas_cumprod[i]), sigma_i = sqrt(1 - alphas_cumprod[i]), lambda_i = log(alpha_i / sigma_i); the step goes from level i to level i - 1 with
+		h = lambda_{i-1} - lambda_i, c_x = sigma_{i-1} / sigma_i, c_d = -alpha_{i-1} expm1(-h).  Index n-1 has no history: (c_x, c_d, 0), DDIM's step.  In between
+		r = (lambda_i - lambda_{i+1}) / h and (c_x, c_d (1 + 1 / 2r), -c_d / 2r).  Index 0 targets alpha_bar = 1, where lambda is infinite: (0, 1, 0), x = x0 as
+		DDIM's last step gives it (the "lower order final" rule).  Float64 throughout, f32 at the end, like `step_coefs_ext`."""
+		n = self.num_timesteps
+		if not 0 <= i < n:
+			raise IndexError(f"schedule index {i} is outside [0, {n})")
+		m = _lib.StepMsC()
+		m.clip = int(bool(clip))
+		if i == 0:
+			m.c_x, m.c_d0, m.c_d1 = 0.0, 1.0, 0.0
+			return m
+		c_x, c_d0, c_d1 = self._coefs_ms_f64(i)
+		m.c_x, m.c_d0, m.c_d1 = np.float32(c_x), np.float32(c_d0), np.float32(c_d1)
+		return m
+
+	def _coefs_ms_f64(self, i: int):
+		"""(c_x, c_d0, c_d1) of `step_coefs_ms` in float64, for 0 < i < n"""
+		n = self.num_timesteps
+		alpha, sigma = np.sqrt(self.alphas_cumprod), np.sqrt(1.0 - self.alphas_cumprod)
+		lam = np.log(alpha / sigma)
+		h = lam[i - 1] - lam[i]
+		c_x = sigma[i - 1] / sigma[i]
+		c_d = -alpha[i - 1] * np.expm1(-h)
+		if i == n - 1:
+			return c_x, c_d, 0.0
+		r = (lam[i] - lam[i + 1]) / h
+		return c_x, c_d * (1.0 + 1.0 / (2.0 * r)), -c_d / (2.0 * r)
+
 	@staticmethod
 	def _check_hooks(denoised_fn, cond_fn):
 		if denoised_fn is not None or cond_fn is not None:
@@ -343,21 +374,42 @@ class SpacedDiffusion:
 					   "ttk_diff_sample_ext")
 		return x
 
+	def _steps_ms(self, clip: bool):
+		n = self.num_timesteps
+		return (_lib.StepC * n)(*[self.step_coefs(i, "ddim") for i in range(n)]), (_lib.StepMsC * n)(*[self.step_coefs_ms(i, clip) for i in range(n)])
+
+	def _sample_ms(self, model: DiffusionTTS, x, E, clip: bool, ms=None):
+		"""The whole DPM-Solver++(2M) loop through ttk_diff_sample_ms, x [b, 100, T] f32 on the device in place.  ms: the per-step blocks when the caller has its own
+		(tests force every c_d1 to 0 to get the first-order solver)."""
+		n = self.num_timesteps
+		b, _, T = x.shape
+		steps, own = self._steps_ms(clip)
+		with torch.cuda.device(x.device):
+			_lib.check(model.lib.ttk_diff_sample_ms(model._h, x.data_ptr(), E.data_ptr(), b, T, steps, own if ms is None else ms, n, _lib.stream_ptr()), "ttk_diff_sample_ms")
+		return x
+
 	def sample_loop(self, model: DiffusionTTS, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
 					model_kwargs=None, device=None, progress=False, eta=0.0, sampler="ddim", consume_rng=True, step_noise=None):
 		"""diffusion.py:500-508 -> ddim_sample_loop :734-810 / p_sample_loop :556-644.  Returns f32 [b, 100, T].  `eta` and `clip_denoised` act for "ddim",
 		`clip_denoised` for "p" (which ignores eta, as p_sample_loop does not take it); the defaults run the entries they always ran.
 		step_noise (ddim with eta != 0 only): [n, b, 100, T], the per-step randn_like draws in loop order when the caller has made them already (as
-		TTSHotPath.inference_lines does, to keep them in the reference's place in the generator stream); nothing is drawn here then."""
+		TTSHotPath.inference_lines does, to keep them in the reference's place in the generator stream); nothing is drawn here then.
+		sampler="dpm++2m" (no reference counterpart: the reference raises on it as on any other name): DPM-Solver++(2M), the second-order multistep solver, through
+		ttk_diff_sample_ms; `clip_denoised` acts, `eta` must be 0 (ValueError: the solver is deterministic).  It draws nothing per step -- there is no reference stream to
+		stay aligned with -- so the generator is left where the start-noise draw (if `noise` is None) leaves it; `consume_rng` and `step_noise` play no part."""
 		sampler = sampler.lower()
-		if sampler not in ("ddim", "p"):
+		if sampler not in ("ddim", "p", "dpm++2m"):
 			raise RuntimeError(f"Sampler not implemented: {sampler}")
+		if sampler == "dpm++2m" and eta != 0.0:
+			raise ValueError(f"sampler 'dpm++2m' is a deterministic solver: eta must be 0, got {eta}")
 		self._check_hooks(denoised_fn, cond_fn)
 		b, C, T = shape
 		E = self._model_inputs(model, model_kwargs, b)
 		dev = model.device
 		x = (noise if noise is not None else torch.randn(*shape, device=dev)).to(dev, torch.float32).contiguous().clone()
 		n = self.num_timesteps
+		if sampler == "dpm++2m":
+			return self._sample_ms(model, x, E, bool(clip_denoised))
 		with torch.cuda.device(dev):
 			if sampler == "ddim":
 				# ddim_sample draws one randn_like(x) per step (:685).  With eta they are read: drawn here in loop order (or handed in as step_noise) and consumed by
@@ -453,6 +505,27 @@ class SpacedDiffusion:
 		self._check_hooks(denoised_fn, cond_fn)
 		return self._loop_progressive(self.ddim_sample, model, shape, noise, model_kwargs, clip_denoised=clip_denoised, eta=eta)
 
+	def dpmpp_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None, device=None, progress=False):
+		"""A generator over the steps of `sample_loop(sampler="dpm++2m")`, index n-1 .. 0, in the form of ddim_sample_loop_progressive: {"sample", "pred_xstart"} per step
+		through ttk_diff_step_ms, the x0 history kept here between the steps; the last `sample` equals the whole loop's bit for bit.  Draws the start noise when `noise` is
+		None and nothing else."""
+		self._check_hooks(denoised_fn, cond_fn)
+		return self._ms_progressive(model, shape, noise, bool(clip_denoised), model_kwargs)
+
+	def _ms_progressive(self, model, shape, noise, clip, model_kwargs):
+		b, _, T = shape
+		E = self._model_inputs(model, model_kwargs, b)
+		dev = model.device
+		x = (noise if noise is not None else torch.randn(*shape, device=dev)).to(dev, torch.float32).contiguous()
+		hist = torch.empty_like(x)      # written by the first step (c_d1 == 0 there: not read)
+		for i in reversed(range(self.num_timesteps)):
+			x, px = x.clone(), torch.empty_like(x)
+			with torch.cuda.device(dev):
+				_lib.check(model.lib.ttk_diff_begin(model._h, E.data_ptr(), b, T, _lib.stream_ptr()), "ttk_diff_begin")
+				_lib.check(model.lib.ttk_diff_step_ms(model._h, x.data_ptr(), hist.data_ptr(), self.step_coefs(i, "ddim"), self.step_coefs_ms(i, clip), px.data_ptr(),
+													  _lib.stream_ptr()), "ttk_diff_step_ms")
+			yield {"sample": x, "pred_xstart": px}
+
 	def ddim_reverse_sample_loop(self, model, x, clip_denoised=True, model_kwargs=None):
 		"""The DDIM encoder: x_0 (a mel in [-1, 1], [b, 100, T]) -> x_n by ddim_reverse_sample at index 0, 1, ..., n-1, as one ttk_diff_sample_ext loop of mode 2.
 		The reference has the step (diffusion.py:696-732) but no loop over it; this is the step called in a Python loop, which is what the fixture of
@@ -463,12 +536,19 @@ class SpacedDiffusion:
 		return self._sample_ext(model, x, E, 2, 0.0, bool(clip_denoised), None)
 
 
-def _sample_loop_lines(self, model: DiffusionTTS, noises, embeddings):
-	"""DDIM loops of several utterances of different length as ONE batch (include/ttk.h: ttk_diff_sample_ddim_lines; no reference counterpart --
+def _sample_loop_lines(self, model: DiffusionTTS, noises, embeddings, sampler="ddim", clip_denoised=True):
+	"""sampler "ddim" (ttk_diff_sample_ddim_lines) or "dpm++2m" (ttk_diff_sample_ms_lines, where `clip_denoised` acts; element i then equals
+	`sample_loop(..., sampler="dpm++2m")` bit for bit).  For "ddim":
+	DDIM loops of several utterances of different length as ONE batch (include/ttk.h: ttk_diff_sample_ddim_lines; no reference counterpart --
 	the reference diffuses a text's lines one after the other, inference.py:237-422).  noises: list of [1, 100, T_i] start noises, embeddings:
 	list of [1, C, T_i] precomputed aligned embeddings.  Returns a list of [1, 100, T_i] f32, element i bit for bit what
 	`sample_loop(model, (1, 100, T_i), noise=noises[i], ...)` returns.  Draws nothing from the torch generator: the caller makes the reference's
 	per-line draws (start noise, DDIM's ignored per-step randn_like) in line order, as TTSHotPath.inference_lines does."""
+	sampler = sampler.lower()
+	if sampler not in ("ddim", "dpm++2m"):
+		raise RuntimeError(f"Sampler not implemented for line batches: {sampler}")
+	if sampler == "ddim" and not clip_denoised:
+		raise NotImplementedError("the ragged DDIM entry clamps x0 (clip_denoised=True); use sample_loop per line")
 	if not self.conditioning_free:
 		raise NotImplementedError("line batches run the conditioned and the conditioning-free evaluation as one [cond | uncond] batch")
 	if not isinstance(model, DiffusionTTS):
@@ -491,8 +571,13 @@ def _sample_loop_lines(self, model: DiffusionTTS, noises, embeddings):
 		n_steps = self.num_timesteps
 		steps = (_lib.StepC * n_steps)(*[self.step_coefs(i, "ddim") for i in range(n_steps)])
 		tlen = (_lib.C.c_int * b)(*Ts)
-		_lib.check(model.lib.ttk_diff_sample_ddim_lines(model._h, x.data_ptr(), E.data_ptr(), b, Tp, tlen, steps, n_steps, _lib.stream_ptr()),
-				   "ttk_diff_sample_ddim_lines")
+		if sampler == "dpm++2m":
+			ms = (_lib.StepMsC * n_steps)(*[self.step_coefs_ms(i, bool(clip_denoised)) for i in range(n_steps)])
+			_lib.check(model.lib.ttk_diff_sample_ms_lines(model._h, x.data_ptr(), E.data_ptr(), b, Tp, tlen, steps, ms, n_steps, _lib.stream_ptr()),
+					   "ttk_diff_sample_ms_lines")
+		else:
+			_lib.check(model.lib.ttk_diff_sample_ddim_lines(model._h, x.data_ptr(), E.data_ptr(), b, Tp, tlen, steps, n_steps, _lib.stream_ptr()),
+					   "ttk_diff_sample_ddim_lines")
 		return [x[i:i + 1, :, :t].contiguous() for i, t in enumerate(Ts)]
 
 

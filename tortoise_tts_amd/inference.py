@@ -62,6 +62,12 @@ def ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p):
 	return dict(do_sample=True, top_k=top_k, top_p=top_p, temperature=ar_temp) if do_sample else dict(do_sample=False)
 
 
+def check_sampler_eta(diffusion_sampler: str, diffusion_eta: float):
+	"""`diffusion_eta` belongs to DDIM; the ancestral sampler ignores it as the reference's does, the deterministic DPM-Solver++(2M) refuses it -- before anything is sampled"""
+	if str(diffusion_sampler).lower() == "dpm++2m" and float(diffusion_eta) != 0.0:
+		raise ValueError(f"diffusion_sampler 'dpm++2m' is a deterministic solver: diffusion_eta must be 0, got {diffusion_eta}")
+
+
 def check_diffusion_conditioning(diffusion_conditioning: str, diffusion: DiffusionTTS) -> bool:
 	"""True for "codes" (the diffusion model reads the sampled mel codes, diffusion.py:1493-1497), False for "latents"; refuses what cannot run -- before
 	anything is sampled."""
@@ -92,9 +98,11 @@ class HotPathStages:
 			self.kw["suppress_tokens"] = suppress_tokens
 		self.diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		self.diffusion_temp, self.sampler = diffusion_temp, diffusion_sampler
+		check_sampler_eta(diffusion_sampler, diffusion_eta)
 		self.eta = float(diffusion_eta) if diffusion_sampler == "ddim" else 0.0      # (the ancestral sampler ignores eta, as the reference's does)
 		# dist.ShardStages: the ancestral sampler draws its per-step noise inside the loop, from the generator of the rank that runs it -- such a line stays on its winner's owner;
 		# so does DDIM with eta != 0, whose per-step draws are read, in generator order
+		# ("dpm++2m" draws nothing while it runs, but its lines stay where "p" lines stay: the name is forwarded and nothing else changes here)
 		self.diffusion_draws_while_running = diffusion_sampler != "ddim" or self.eta != 0.0
 		self.pad_token = self.ar.stop_mel_token
 
@@ -146,12 +154,12 @@ class HotPathStages:
 		return latents, noise, int(noise.shape[-1])
 
 	def run_diffusion(self, prepared):
-		"""mels [1, 100, T_i] of the prepared lines: one ragged DDIM batch (SpacedDiffusion.sample_loop_lines) when there are several and the
-		sampler is ddim with conditioning-free guidance, else one loop per line; each mel bit for bit its own loop's either way"""
+		"""mels [1, 100, T_i] of the prepared lines: one ragged batch (SpacedDiffusion.sample_loop_lines) when there are several and the
+		sampler is ddim (eta 0) or dpm++2m with conditioning-free guidance, else one loop per line; each mel bit for bit its own loop's either way"""
 		self._mark("_before_ddim")          # what lies between this line's latent pass and the shared diffusion (later lines' sampling, item moves) is not "ddim"
 		Es = [self.diff.timestep_independent(latents, self.dl, T, False) for latents, _, T in prepared]
-		if len(prepared) > 1 and self.sampler == "ddim" and self.diffuser.conditioning_free and self.eta == 0.0:
-			mels = self.diffuser.sample_loop_lines(self.diff, [n for _, n, _ in prepared], Es)
+		if len(prepared) > 1 and self.sampler in ("ddim", "dpm++2m") and self.diffuser.conditioning_free and self.eta == 0.0:
+			mels = self.diffuser.sample_loop_lines(self.diff, [n for _, n, _ in prepared], Es, sampler=self.sampler)
 		else:
 			mels = [self.diffuser.sample_loop(self.diff, (1, 100, T), sampler=self.sampler, noise=n, model_kwargs={"precomputed_aligned_embeddings": E},
 											  progress=False, eta=self.eta, consume_rng=self.diffusion_draws_while_running) for (_, n, T), E in zip(prepared, Es)]
@@ -225,6 +233,8 @@ class TTSHotPath:
 		diffusion_eta: DDIM's eta (ddim_sample_loop, diffusion.py:745; the reference's `TTS.inference` leaves it at 0): above 0 the per-step draws the
 		deterministic loop makes and ignores (:685) are read -- 1.0 is the DDPM-variance sampler -- so one set of codes renders differently per seed.
 		The ancestral sampler ignores it.
+		diffusion_sampler: "ddim", "p", or "dpm++2m" -- DPM-Solver++(2M), the second-order multistep solver (no reference counterpart; SpacedDiffusion.sample_loop), meant
+		for fewer `max_diffusion_steps`; it draws nothing per step and refuses diffusion_eta != 0 (ValueError).
 		latents_for: "all" = the latent pass over every candidate, as the reference runs it before scoring (inference.py:370-379; the benchmarked
 		workload); "winner" = the k = 1 variant: the candidate is chosen first and only its row goes through the dense
 		pass (the reference's own to-do at :370) -- rows of the pass are independent, so the result is the same bits.
@@ -243,6 +253,7 @@ class TTSHotPath:
 		dev = ar.device
 		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
 		check_greedy(do_sample, candidates, beam_width)
+		check_sampler_eta(diffusion_sampler, diffusion_eta)
 
 		def mark(name):
 			if phase_marks is not None:
@@ -310,7 +321,7 @@ class TTSHotPath:
 	def inference_lines(self, lines, autoregressive_latents, diffusion_latents, *, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8,
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
 						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True,
-						diffusion_eta=0.0):
+						diffusion_eta=0.0, diffusion_sampler="ddim"):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -332,12 +343,20 @@ class TTSHotPath:
 		do_sample=False: greedy search as in `inference` (candidates must be 1): the lines of a batch decode one row each.
 		diffusion_eta != 0: DDIM's per-step draws are kept (the main thread makes them where it made the ignored ones) and every line diffuses in a loop
 		of its own: the ragged batch entry has no form that reads noise.
+		diffusion_sampler: "ddim", or "dpm++2m" (DPM-Solver++(2M), see `inference`): the main thread then makes a line's start-noise draw only -- the solver draws nothing
+		per step -- and the batches diffuse through the multistep lines entry (SpacedDiffusion.sample_loop_lines(sampler="dpm++2m")); diffusion_eta must be 0.  The
+		ancestral sampler draws inside its loop and is not served here: use `inference` per line.
 		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
 		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
 		check_greedy(do_sample, candidates, 1)
+		if diffusion_sampler not in ("ddim", "dpm++2m"):
+			raise NotImplementedError(f"inference_lines diffuses with 'ddim' or 'dpm++2m', got {diffusion_sampler!r}: the ancestral sampler draws inside its loop, which would "
+									  "put the worker thread into the generator stream; use `inference` per line")
+		check_sampler_eta(diffusion_sampler, diffusion_eta)
+		ms = diffusion_sampler == "dpm++2m"
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		extra = {"suppress_tokens": suppress_tokens} if suppress_tokens else {}
 		main = torch.cuda.current_stream(dev)
@@ -352,10 +371,10 @@ class TTSHotPath:
 				s_df.wait_event(ready)
 				Es = [diff.timestep_independent(latents, diffusion_latents, T, False) for latents, _, T, _ in group]
 				if len(group) == 1:
-					mel = [diffuser.sample_loop(diff, (1, 100, group[0][2]), sampler="ddim", noise=group[0][1], eta=eta, step_noise=group[0][3],
+					mel = [diffuser.sample_loop(diff, (1, 100, group[0][2]), sampler=diffusion_sampler, noise=group[0][1], eta=eta, step_noise=group[0][3],
 												model_kwargs={"precomputed_aligned_embeddings": Es[0]}, progress=False, consume_rng=False)]
 				else:
-					mel = diffuser.sample_loop_lines(diff, [noise for _, noise, _, _ in group], Es)
+					mel = diffuser.sample_loop_lines(diff, [noise for _, noise, _, _ in group], Es, sampler=diffusion_sampler)
 				mels = [denormalize_tacotron_mel(m)[:, :, :T] for m, (_, _, T, _) in zip(mel, group)]
 				for (latents, noise, _, step_noise), E in zip(group, Es):
 					for t_ in (latents, noise, E) + (() if step_noise is None else (step_noise,)):
@@ -395,7 +414,9 @@ class TTSHotPath:
 					T = latents.shape[1] * 4 * 24000 // 22050
 					noise = torch.randn((1, 100, T), device=dev) * diffusion_temp
 					step_noise = None
-					if eta != 0.0:                                          # DDIM's per-step draws, in reference order: read by this line's loop
+					if ms:                                                  # DPM-Solver++(2M) draws nothing per step
+						pass
+					elif eta != 0.0:                                        # DDIM's per-step draws, in reference order: read by this line's loop
 						step_noise = torch.stack([torch.randn_like(noise) for _ in range(max_diffusion_steps)])
 					else:
 						for _ in range(max_diffusion_steps):                    # DDIM's ignored per-step draws, in reference order

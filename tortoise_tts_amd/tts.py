@@ -136,9 +136,13 @@ class TTS:
 		noise.  Needs candidates == 1 and beam_width == 1 (ValueError); not available with vocoder_type="hifigan", whose token generator always samples.
 		diffusion_eta (keyword only; DDIM's eta, diffusion.py:745, which the reference's `TTS.inference` leaves at 0): above 0 the sampler reads its
 		per-step noise -- 1.0 is the DDPM-variance sampler -- so the same text and voice render differently per `seed`; 0.0 is the call without it, bit
-		for bit.  The ancestral sampler ignores it; the "hifigan" branch has no diffusion."""
-		from .inference import check_greedy
+		for bit.  The ancestral sampler ignores it; the "hifigan" branch has no diffusion.
+		diffusion_sampler: "ddim", "p" (the reference's two), or "dpm++2m": DPM-Solver++(2M), a second-order multistep solver meant for fewer
+		`max_diffusion_steps` (SpacedDiffusion.sample_loop; the default sampler and step count are unchanged).  It is deterministic: diffusion_eta != 0 with it is
+		a ValueError.  Several lines go through `TTSHotPath.inference_lines` as they do for DDIM."""
+		from .inference import check_greedy, check_sampler_eta
 		check_greedy(do_sample, candidates, beam_width)
+		check_sampler_eta(diffusion_sampler, diffusion_eta)
 		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
 			raise NotImplementedError(f"vocoder_type {vocoder_type!r} is unknown ('bigvgan', 'vocoder', 'hifigan')")
 		if not do_sample and vocoder_type == "hifigan":
@@ -177,10 +181,10 @@ class TTS:
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
 		if beam_width != 1:                                   # the beams of a line exchange histories every token: lines are sampled one by one
 			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
-		elif len(lines) > 1 and diffusion_sampler == "ddim":
+		elif len(lines) > 1 and diffusion_sampler in ("ddim", "dpm++2m"):
 			# several lines: their sampling as one decode batch, the diffusion of a line under the sampling of later ones (TTSHotPath.inference_lines:
 			# the same waveforms as the line-by-line loop of inference.py:237-422, which is what the else branch runs)
-			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, **kw)]
+			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)]
 		else:
 			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)[0]) for tokens in lines]
 		return torch.concat(wavs, dim=-1), SAMPLE_RATE
@@ -194,9 +198,11 @@ class TTS:
 		rows are diffused as one ragged batch (SpacedDiffusion.sample_loop_lines).  The voice is the diffusion latent of `references` (clip tensor(s) or an
 		`encode_audio` dict), or a random voice when None, seeded as in `inference`.  T = M * 4 * 24000 // 22050 frames per row (inference.py:400).
 		diffusion_eta: DDIM's eta as in `inference`; above 0 every row diffuses in a loop of its own.
+		diffusion_sampler: as in `inference`; with "dpm++2m" a row draws its start noise only, several rows diffuse as one ragged batch, and diffusion_eta != 0 is a ValueError.
 		Returns (wav [1, 1, samples], 24000).  vocoder_type "bigvgan" or "vocoder"; "hifigan" is refused: it reads AR latents, which codes alone do not give."""
 		from .diffusion import denormalize_tacotron_mel, get_diffuser
-		from .inference import check_diffusion_conditioning
+		from .inference import check_diffusion_conditioning, check_sampler_eta
+		check_sampler_eta(diffusion_sampler, diffusion_eta)
 		if vocoder_type == "hifigan":
 			raise NotImplementedError("decode_codes cannot use vocoder_type='hifigan': HiFiGAN turns the autoregressive model's latents into audio (inference.py:250-329), "
 									  "and mel codes alone do not give those; use 'bigvgan' or 'vocoder'")
@@ -235,8 +241,8 @@ class TTS:
 				for _ in range(diffuser.num_timesteps):
 					torch.randn_like(noise)
 			prepared.append((E, noise, T, step_noise))
-		if len(prepared) > 1 and diffusion_sampler == "ddim" and cond_free and eta == 0.0:
-			mels = diffuser.sample_loop_lines(diff, [n for _, n, _, _ in prepared], [E for E, _, _, _ in prepared])
+		if len(prepared) > 1 and diffusion_sampler in ("ddim", "dpm++2m") and cond_free and eta == 0.0:
+			mels = diffuser.sample_loop_lines(diff, [n for _, n, _, _ in prepared], [E for E, _, _, _ in prepared], sampler=diffusion_sampler)
 		else:
 			mels = [diffuser.sample_loop(diff, (1, 100, T), sampler=diffusion_sampler, noise=n, model_kwargs={"precomputed_aligned_embeddings": E},
 										 progress=False, eta=eta, step_noise=sn, consume_rng=diffusion_sampler != "ddim") for E, n, T, sn in prepared]
