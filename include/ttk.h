@@ -187,6 +187,46 @@ int ttk_ar_decode_next(ttk_ar* h, float* logits_out, float* hidden_out, void* st
 int ttk_greedy_step(const ttk_sample_args* a, void* stream);
 int ttk_ar_greedy_next(ttk_ar* h, const ttk_sample_args* a, void* stream);
 
+/* The reference's own samplers (tortoise_tts/samplers.py; the controls of webui.py:251-265, the commented-out arguments of inference.py:154-163) on a second
+ * token-step kernel, k_sample_step_ext (csrc/sample_ext.hip): ttk_sample_step_warped's launch, operands and bookkeeping, with a second struct beside
+ * ttk_sample_args, which keeps its layout.  Per row, in this order (everything not named is ttk_sample_step_warped's):
+ *   repetition_penalty_decay != 0: reptition_penalize(factor = repetition_penalty, decay, one_time=True) (:11-29) REPLACES HF's processor: over
+ *     previous = history[b, hist_off : hist_off + col[b]] (prompt and sampled tokens; NOT the hist_off prefix ids), every distinct token, d = 1 + the number of
+ *     tokens behind its most recent occurrence, gets score *= 1.0f / (float)(repetition_penalty * pow((double)d, (double)decay)) -- a division whatever the
+ *     sign of the score.  repetition_penalty 1 is off, as in the reference.  one_time=False is not built.
+ *   stop_length_penalty != 0: length_penalize (:35-40): score[stop_token] *= 1.0f / (float)pow((double)(col[b] + 1), (double)stop_length_penalty); > 0
+ *     lengthens, < 0 shortens.  (`length_penalty` is HF's beam ranking in this ABI and in the reference's call, hence the name.)
+ *   suppress, typical_mass;
+ *   min_temperature >= 0: dynamic_temperature (:78-91, k = 10, centre 0.5) in the place of the temperature warper, in front of top-k (the reference never wired
+ *     it, there is no other order to match): p_max = 1 / sum exp(s - max), T_dyn = T - (T - T_min) / (1 + exp(-10 (p_max - 0.5))), scores *= 1.0f / (float)T_dyn;
+ *     negative = off;
+ *   top_k, top_p;
+ *   mirostat_tau > 0: mirostat v1 (mirostat_sample :117-158) in the place of the plain draw, on mirostat_mu[b] (the reference's max_surprise; the caller
+ *     sets it to 2 tau before the first token): k from the 101 largest probabilities of softmax(scores) and mu, computed in f64 (a non-finite value = V,
+ *     clamped to [1, V]); the k largest scores stay (equal scores at the threshold stay together, as with top_k); token = argmax over them of
+ *     softmax_kept / q; mu -= eta (log2(1 / P[token]) - tau).  Rows with fewer than 101 finite scores (where the reference raises ZeroDivisionError)
+ *     keep all of them (k = their number) and still update mu.  A finished row's mu may hold anything.  q is ttk_sample_args' noise row, indexed by
+ *     token id: NOT the Philox consumption of the reference's torch.multinomial over the k sorted entries (it depends on k), but the same distribution,
+ *     and the noise block per token of the plain draw, so the caller's generator accounting is that of ttk_sample_step_warped.  0 = off.
+ * Optional outputs, written when non-null: scores_out [B][scores_out_ld] f32 = the scores behind top_p (-inf where removed; HF's output_scores), temp_out [B]
+ * f32 = the temperature applied, mirostat_k [B] int32.
+ * Every field off (0, 0, negative, 0): the result equals ttk_sample_step_warped's bit for bit.  TTK_E_ARG: V > 9216, mirostat_tau > 0 without mirostat_mu,
+ * mirostat_eta < 0, min_temperature > temperature, decay or stop_length_penalty without `history`.  ttk_ar_sample_next_ext is to ttk_sample_step_ext what
+ * ttk_ar_sample_next is to ttk_sample_step_warped.  Each enqueues one kernel and keeps all state in device memory: capturable.                             */
+typedef struct {
+	float repetition_penalty_decay;           /* 0 = HF's processor */
+	float stop_length_penalty;                /* 0 = off */
+	float min_temperature;                    /* < 0 = off; <= temperature */
+	float mirostat_tau;                       /* 0 = off */
+	float mirostat_eta;                       /* >= 0 */
+	double* mirostat_mu;                      /* [B], read and written; required with mirostat_tau > 0 */
+	int* mirostat_k;                          /* [B] or NULL */
+	float* temp_out;                          /* [B] or NULL */
+	float* scores_out; int64_t scores_out_ld; /* [B][scores_out_ld >= V] or NULL */
+} ttk_sample_ext;
+int ttk_sample_step_ext(const ttk_sample_args* a, const ttk_sample_ext* x, void* stream);
+int ttk_ar_sample_next_ext(ttk_ar* h, const ttk_sample_args* a, const ttk_sample_ext* x, void* stream);
+
 /* The Exp(1) noise of torch.multinomial without torch in the token step.  `q.exponential_(1)` on the GPU is a pure function of (generator seed,
  * generator offset, element index, launch geometry) -- ATen's distribution_nullary_kernel over a Philox4_32_10 state (csrc/ttk_rng.h restates
  * the indexing; the state and the uniform conversion are rocRAND's own header code, as in torch's build).  ttk_ar_set_noise makes the mel-head

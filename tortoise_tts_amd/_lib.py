@@ -67,6 +67,12 @@ class SampleArgs(C.Structure):
 				("hist_ld", C.c_int64), ("hist_off", C.c_int64), ("live_rows", C.c_void_p), ("all_done", C.c_void_p), ("typical_mass", C.c_float)]
 
 
+class SampleExt(C.Structure):
+	"""ttk_sample_ext (include/ttk.h; static_assert'ed in csrc/sample_ext.hip)"""
+	_fields_ = [(n, C.c_float) for n in ("repetition_penalty_decay", "stop_length_penalty", "min_temperature", "mirostat_tau", "mirostat_eta")] + [
+		("mirostat_mu", C.c_void_p), ("mirostat_k", C.c_void_p), ("temp_out", C.c_void_p), ("scores_out", C.c_void_p), ("scores_out_ld", C.c_int64)]
+
+
 class BeamArgs(C.Structure):
 	"""ttk_beam_args (include/ttk.h)"""
 	_fields_ = [("logits", C.c_void_p), ("ld", C.c_int64), ("num_beams", C.c_int), ("V", C.c_int), ("q", C.c_void_p), ("suppress", C.c_void_p),
@@ -155,6 +161,8 @@ SYMBOLS = {
 	"ttk_ar_reorder_cache": (_I, [_P, _P, _P]),
 	"ttk_beam_step": (_I, [C.POINTER(BeamArgs), _P]),
 	"ttk_sample_step_warped": (_I, [C.POINTER(SampleArgs), _P]),
+	"ttk_sample_step_ext": (_I, [C.POINTER(SampleArgs), C.POINTER(SampleExt), _P]),
+	"ttk_ar_sample_next_ext": (_I, [_P, C.POINTER(SampleArgs), C.POINTER(SampleExt), _P]),
 	"ttk_ar_latents": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
 	"ttk_ar_score": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
 	"ttk_ar_lora_init": (_I, [_P, C.POINTER(WeightView), _I]),

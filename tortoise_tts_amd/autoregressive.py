@@ -17,6 +17,9 @@ What runs where
   * the per-token loop .............................................. here; one HIP-graph replay per token.
   * greedy search (do_sample false or omitted, num_beams 1) ........ libttk  (csrc/sample.hip: the argmax form of the token step, ttk_ar_greedy_next); the
     same loop and captured step as sampling, no noise armed, nothing drawn from the generator behind the reseed.
+  * the reference's own samplers (tortoise_tts/samplers.py: decayed repetition penalty, stop-length penalty, dynamic temperature, mirostat; keywords of
+    `inference_speech` / `get_generator`) ............................ libttk  (csrc/sample_ext.hip: a second token-step kernel, ttk_ar_sample_next_ext, launched in
+    ttk_ar_sample_next's place only when one of them is on; same loop, same captured step, same noise per token).
   * beam search (num_beams > 1) ..................................... libttk  (csrc/beam.hip: the beam step -- log-softmax, warpers, the
     multinomial without replacement over num_beams * V, HF's running / finished bookkeeping -- and the in-place KV-cache reorder); the loop
     here enqueues {beam step, reorder, decode} per token and polls the done word.
@@ -90,6 +93,25 @@ def score_inputs(cfg: ARConfig, text_inputs, text_lengths, mel_codes, wav_length
 				codes[b, end:] = cfg.stop_mel_token
 	pad = torch.nn.functional.pad
 	return text, codes, pad(text, (0, 2), value=cfg.stop_text_token), pad(codes, (0, 2), value=cfg.stop_mel_token)
+
+
+# The reference's own samplers (tortoise_tts/samplers.py; the commented-out arguments of its inference, inference.py:154-163): keyword, value that means "off".
+# Any of them on moves the token step to the second sampling kernel (include/ttk.h: ttk_sample_ext, ttk_ar_sample_next_ext); all off is the launch it always was.
+SAMPLER_KNOBS = (("repetition_penalty_decay", 0.0), ("stop_length_penalty", 0.0), ("min_temperature", None), ("mirostat_tau", 0.0), ("mirostat_eta", 0.1))
+NO_KNOBS = tuple(default for _, default in SAMPLER_KNOBS)
+MIROSTAT_RANKS = 101      # probabilities mirostat's estimate of the Zipf slope reads (samplers.py:121-125)
+
+
+def pop_sampler_knobs(kw) -> tuple:
+	"""take the sampler knobs out of a generate keyword dict: (decay, stop-length penalty, min_temperature or None, tau, eta), normalised so that every way of
+	saying "off" gives NO_KNOBS' entry (a state is keyed by them)"""
+	decay, stop_len, min_t, tau, eta = (kw.pop(name, default) for name, default in SAMPLER_KNOBS)
+	decay, stop_len, tau = float(decay or 0.0), float(stop_len or 0.0), float(tau or 0.0)
+	min_t = None if min_t is None or float(min_t) < 0 else float(min_t)
+	eta = 0.1 if eta is None else float(eta)
+	if tau < 0 or eta < 0:
+		raise ValueError(f"mirostat_tau ({tau}) and mirostat_eta ({eta}) must not be negative")
+	return decay, stop_len, min_t, tau, (eta if tau > 0 else 0.1)
 
 
 LORA_MAX_RANK = 256      # csrc/ar.hip: ttk_ar_lora_set
@@ -268,6 +290,13 @@ class UnifiedVoice(_lib.Handle):
 		one warning, as HF builds no warpers without do_sample; num_return_sequences must be 1.  `generate` reseeds and then draws nothing: the device
 		generator is left at the offset it had directly behind the reseed, and `last_generate["rng_step"]` is 0.
 
+		The reference's own samplers (tortoise_tts/samplers.py; the controls of its web UI, never wired into its `generate` call) are keywords here, sampling branch
+		only: repetition_penalty_decay (reptition_penalize: `repetition_penalty` divided in, grown by distance ** decay from a token's latest occurrence, over the
+		sampled and prompt tokens), stop_length_penalty (length_penalize on the stop token: > 0 longer, < 0 shorter; `length_penalty` stays HF's beam ranking),
+		min_temperature (dynamic_temperature: from `temperature` down to it as the row's largest probability rises), mirostat_tau / mirostat_eta (mirostat v1 in
+		the place of the plain draw; needs top_k 0 or >= 101).  Defaults (0, 0, None, 0, 0.1) are the call without them, bit for bit.  With any of them on the
+		token step runs on a second kernel (csrc/sample_ext.hip); the noise consumed per token, and so the generator offset afterwards, does not change.
+
 		candidate_shard=(lo, hi) (no reference counterpart; tortoise_tts_amd/dist.py): sample only candidates lo..hi-1 of the
 		`num_return_sequences`, as one rank of a candidate-sharded run.  RNG contract: the rank draws the multinomial noise of ALL
 		candidates per token (the same Philox stream on every rank: `generate` reseeds to 0) and consumes its own rows, so the ids it
@@ -276,6 +305,9 @@ class UnifiedVoice(_lib.Handle):
 		if text_inputs.shape[0] != 1:
 			raise NotImplementedError("one text line per call, as inference.py:244-246 does")
 		num_beams = hf_generate_kwargs.get("num_beams", 1) or 1
+		knobs = pop_sampler_knobs(hf_generate_kwargs)
+		self._check_sampler_knobs(knobs, hf_generate_kwargs, greedy=not hf_generate_kwargs.get("do_sample", False), num_beams=num_beams, shard=candidate_shard,
+								  typical=typical_sampling)
 		if num_beams != 1:
 			# the beam-sample branch of `generate` (HF `_beam_search`, do_sample=True): csrc/beam.hip
 			if not hf_generate_kwargs.get("do_sample", False):
@@ -311,8 +343,36 @@ class UnifiedVoice(_lib.Handle):
 		if greedy:
 			self._warn_ignored_warpers(hf_generate_kwargs)
 		gen, _ = self._generate(speech_conditioning_latent, text_inputs, num_return_sequences if prompt is None else prompt.shape[0], max_generate_length,
-								typical_mass if typical_sampling else None, hf_generate_kwargs, stream=False, shard=candidate_shard, prompt=prompt, greedy=greedy)
+								typical_mass if typical_sampling else None, hf_generate_kwargs, stream=False, shard=candidate_shard, prompt=prompt, greedy=greedy, knobs=knobs)
 		return gen
+
+	def _check_sampler_knobs(self, knobs, kw, greedy=False, num_beams=1, shard=None, typical=False):
+		"""what the reference's samplers (SAMPLER_KNOBS) do not combine with, refused before anything is sampled; nothing to check when all are off"""
+		if knobs == NO_KNOBS:
+			return
+		decay, stop_len, min_t, tau, _ = knobs
+		on = ", ".join(f"{name}={v!r}" for (name, default), v in zip(SAMPLER_KNOBS[:4], knobs) if v != default)
+		if num_beams != 1:
+			raise NotImplementedError(f"{on}: the reference's samplers run in the token step of the sampling branch (num_beams=1); the beam step does not take them")
+		if greedy and (tau > 0 or min_t is not None):
+			raise ValueError(f"{on}: mirostat and the dynamic temperature are samplers -- they shape a draw, and greedy search (do_sample false or omitted) draws nothing; pass do_sample=True")
+		if greedy:
+			raise NotImplementedError(f"{on}: the decayed repetition penalty and the stop-length penalty are built into the sampling token step only; greedy search "
+									  "(do_sample false or omitted) takes repetition_penalty without a decay")
+		if shard is not None:
+			raise NotImplementedError(f"{on}: a candidate-sharded run does not take the reference's samplers (candidate_shard needs them off)")
+		temperature, top_k, top_p = kw.get("temperature", 1.0) or 1.0, kw.get("top_k", 50) or 0, kw.get("top_p", 1.0)
+		if self.cfg.number_mel_codes > 9216:
+			raise NotImplementedError(f"{on}: the sampling kernel that runs the reference's samplers holds a row of at most 9216 scores in registers "
+									  f"(number_mel_codes = {self.cfg.number_mel_codes})")
+		if self.hf_exact_top_p and (typical or (top_p is not None and top_p < 1.0)):
+			raise NotImplementedError(f"{on}: with hf_exact_top_p the top-p / typical warpers run as torch ops in FRONT of the sampling kernel, behind which these samplers "
+									  "would come too late (their place is before the warpers); build the model without hf_exact_top_p, or leave top_p / typical_sampling off")
+		if min_t is not None and min_t > temperature:
+			raise ValueError(f"min_temperature={min_t} exceeds temperature={temperature}: the dynamic temperature falls from `temperature` to `min_temperature`")
+		if tau > 0 and 0 < top_k < MIROSTAT_RANKS:
+			raise ValueError(f"mirostat_tau={tau} with top_k={top_k}: mirostat estimates the slope of the distribution from its {MIROSTAT_RANKS} most likely tokens, and "
+							 f"fewer survive top_k (the reference divides by zero there; an omitted top_k is HF's default 50): pass top_k=0 or top_k >= {MIROSTAT_RANKS}")
 
 	@staticmethod
 	def _warn_ignored_warpers(kw):
@@ -343,7 +403,10 @@ class UnifiedVoice(_lib.Handle):
 		hf_generate_kwargs.pop("input_tokens", None)
 		hf_generate_kwargs.pop("kv_cache", None)
 		typical = bool(hf_generate_kwargs.get("typical_sampling", False))
-		if len(texts) == 1 or (typical and self.hf_exact_top_p):      # one line, or HF's warpers as torch ops in front of the kernel (built per call): the per-line calls
+		knobs_on = pop_sampler_knobs(dict(hf_generate_kwargs)) != NO_KNOBS      # the reference's samplers: line by line (each line's mirostat state is its own call's)
+		if not knobs_on:
+			pop_sampler_knobs(hf_generate_kwargs)
+		if len(texts) == 1 or (typical and self.hf_exact_top_p) or knobs_on:      # one line, or HF's warpers as torch ops in front of the kernel (built per call): the per-line calls
 			out, self.last_generate_lines = [], []
 			for t in texts:
 				out.append(self.inference_speech(speech_conditioning_latent, t, num_return_sequences=num_return_sequences,
@@ -370,12 +433,13 @@ class UnifiedVoice(_lib.Handle):
 			raise _lib.TTKError(f"prefix {prefix_tokens} + {max_new} new tokens exceed max_ctx={self.max_ctx} or the mel position table ({c.max_mel_seq_len})")
 		return max_new
 
-	def _pipe_key(self, kw, typical_mass, greedy=False):
+	def _pipe_key(self, kw, typical_mass, greedy=False, knobs=NO_KNOBS):
 		"""(what of the keywords is baked into a generation state, whether the stop token can be sampled at all).  The greedy flag is part of the key: a
-		sampling state's captured step is never replayed for greedy search or the reverse; the warpers greedy search ignores are not."""
+		sampling state's captured step is never replayed for greedy search or the reverse; the warpers greedy search ignores are not.  The reference's samplers
+		(`pop_sampler_knobs`) follow at indices 7..11."""
 		suppress = tuple(kw.get("suppress_tokens") or ())
 		warpers = (None, None, None) if greedy else (kw.get("temperature", 1.0), kw.get("top_k", 50), kw.get("top_p", 1.0))
-		pipe_key = warpers + (kw.get("repetition_penalty", 1.0), suppress, typical_mass, bool(greedy))
+		pipe_key = warpers + (kw.get("repetition_penalty", 1.0), suppress, typical_mass, bool(greedy)) + tuple(knobs)
 		return pipe_key, self.cfg.stop_mel_token not in suppress
 
 	@contextlib.contextmanager
@@ -566,10 +630,12 @@ class UnifiedVoice(_lib.Handle):
 		cond, text = self._prefix
 		n_new = max_length - inputs.shape[1]
 		B = hf_generate_kwargs.pop("num_return_sequences", 1) or 1
-		return self._generate(cond, text, B, n_new, None, hf_generate_kwargs, stream=True)
+		knobs = pop_sampler_knobs(hf_generate_kwargs)          # the reference's samplers, as in `inference_speech`
+		self._check_sampler_knobs(knobs, hf_generate_kwargs)
+		return self._generate(cond, text, B, n_new, None, hf_generate_kwargs, stream=True, knobs=knobs)
 
 	# ------------------------------------------------------------------ the token loop
-	def _generate(self, cond, text, num_return_sequences, max_generate_length, typical_mass, kw, stream, shard=None, prompt=None, greedy=False):
+	def _generate(self, cond, text, num_return_sequences, max_generate_length, typical_mass, kw, stream, shard=None, prompt=None, greedy=False, knobs=NO_KNOBS):
 		self._require_idle()
 		n_in = 0 if prompt is None else int(prompt.shape[1])
 		if stream and n_in:
@@ -586,7 +652,7 @@ class UnifiedVoice(_lib.Handle):
 		max_new = self._max_new(text.shape[1] + 4, max_generate_length)
 		if n_in >= max_new:      # HF's stopping criterion is only looked at after a token has been appended: the reference would still sample one
 			raise ValueError(f"{n_in} prompt tokens leave no room below max_generate_length={max_new}")
-		pipe_key, can_stop = self._pipe_key(kw, typical_mass, greedy)
+		pipe_key, can_stop = self._pipe_key(kw, typical_mass, greedy, knobs)
 		if stream:
 			return self._loop_stream(cond, text, B, max_new, pipe_key, can_stop)
 		with self._session(kw.get("seed", 0), lambda: self._gen_state(B, max_new, pipe_key, C, lo), prompt, arm=(lo, n_in)) as (st, gen, off_start):
@@ -866,9 +932,19 @@ class _GenState(_NoiseState):
 			self._init_noise(model, C, c.number_mel_codes)
 		# input_ids as the repetition penalty sees them: the fake prefix ids are all 1 with start_mel last (unified_voice.py:647-649),
 		# i.e. the SET {1, start_mel} whatever the text length (the penalty acts once per distinct id), then the sampled tokens
+		# the reference's samplers (SAMPLER_KNOBS): any of them on, and the token step is the second kernel's (ttk_ar_sample_next_ext); the decayed penalty and
+		# the stop-length penalty read the history behind the two prefix ids, mirostat keeps one f64 surprise budget per row
+		decay, stop_len, min_t, self.tau, eta = pipe_key[7:12]
+		self.ext = None
 		self.history = None
-		if self.pipe.needs_history:
+		if self.pipe.needs_history or decay != 0.0 or stop_len != 0.0:
 			self.history = torch.ones((B, 2 + max_new), dtype=torch.long, device=dev)
+		if tuple(pipe_key[7:12]) != NO_KNOBS:
+			self.mu = torch.zeros(B, dtype=torch.float64, device=dev)
+			x = _lib.SampleExt()
+			x.repetition_penalty_decay, x.stop_length_penalty, x.min_temperature = decay, stop_len, -1.0 if min_t is None else min_t
+			x.mirostat_tau, x.mirostat_eta, x.mirostat_mu = self.tau, eta, self.mu.data_ptr()
+			self.ext = x
 		# every processor and warper runs inside the fused kernel (V <= 9216: the row lives in registers), the typical-sampling warper included
 		# (round 3).  With hf_exact_top_p the cumulative-mass warpers (top-p, typical) run as torch ops in front of it instead, in HF's order, which
 		# means the processors then run as torch ops too and the kernel sees finished scores for that part
@@ -910,6 +986,8 @@ class _GenState(_NoiseState):
 		self.col.zero_()
 		self.live.fill_(self.B)
 		self.done.zero_()
+		if self.ext is not None:
+			self.mu.fill_(2.0 * self.tau)         # mirostat's max_surprise starts at 2 tau (samplers.py:133-134): a reused state never starts from the previous call's value
 		if self.history is not None:
 			self.history.fill_(1)
 			self.history[:, 1] = c.start_mel_token
@@ -940,6 +1018,9 @@ class _GenState(_NoiseState):
 				self.q.view(self.lines, *self.qc.shape).copy_(self.qc)
 			else:
 				self.q.exponential_(1)
+		if self.ext is not None:      # the reference's samplers: the same launch shape on the second kernel, its state (mu) in device memory -- capturable as the other
+			_lib.check(self.model.lib.ttk_ar_sample_next_ext(self.model._h, _lib.C.byref(a), _lib.C.byref(self.ext), _lib.stream_ptr()), "ttk_ar_sample_next_ext")
+			return
 		_lib.check(self.model.lib.ttk_ar_sample_next(self.model._h, _lib.C.byref(a), _lib.stream_ptr()), "ttk_ar_sample_next")
 
 

@@ -527,6 +527,15 @@ int ttk_ar_greedy_next(ttk_ar* h, const ttk_sample_args* a, void* stream) {
 							  (hipStream_t)stream, "ttk_ar_greedy_next");
 }
 
+int ttk_ar_sample_next_ext(ttk_ar* h, const ttk_sample_args* a, const ttk_sample_ext* x, void* stream) {
+	TTK_REQUIRE(h && a && x, TTK_E_ARG, "ttk_ar_sample_next_ext: null argument");
+	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_sample_next_ext: call ttk_ar_prefill first");
+	TTK_REQUIRE(a->B == h->B && a->V == h->cfg.number_mel_codes, TTK_E_ARG, "ttk_ar_sample_next_ext: shape (B %d, V %d) is not the prefilled one (B %d, V %d)",
+				a->B, a->V, h->B, h->cfg.number_mel_codes);
+	return launch_sample_step_ext(a, x, h->mel_emb, h->mel_pos, h->x, h->cfg.model_dim, h->cfg.max_mel_seq_len, h->lnfold ? h->x_frag : nullptr, elem_kind(h->dt),
+								  (hipStream_t)stream, "ttk_ar_sample_next_ext");
+}
+
 int ttk_ar_reorder_cache(ttk_ar* h, const int64_t* beam_idx, void* stream) {
 	TTK_REQUIRE(h && beam_idx, TTK_E_ARG, "ttk_ar_reorder_cache: null argument");
 	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_reorder_cache: call ttk_ar_prefill first");

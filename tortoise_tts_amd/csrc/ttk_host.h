@@ -151,6 +151,9 @@ int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* 
 					   hipStream_t stream, const char* who);
 int launch_greedy_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 					   hipStream_t stream, const char* who);
+// sample_ext.hip: the same step over the reference's samplers.py (ttk_sample_ext), on a kernel of its own
+int launch_sample_step_ext(const ttk_sample_args* a, const ttk_sample_ext* x, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
+						   hipStream_t stream, const char* who);
 
 // beam.hip: the in-place gather of the KV cache's candidate slices that beam search needs per token (ttk_ar_reorder_cache)
 int launch_kv_reorder(void* kc, void* vc, int layers, int max_batch, int H, int max_ctx, size_t es, const int* d_pos, const int64_t* beam_idx, int B,

@@ -62,6 +62,22 @@ def ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p):
 	return dict(do_sample=True, top_k=top_k, top_p=top_p, temperature=ar_temp) if do_sample else dict(do_sample=False)
 
 
+def ar_sampler_knobs(min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+	"""the reference's own samplers (tortoise_tts/samplers.py) under the names its `inference` keeps commented out (inference.py:154-163: min_ar_temp,
+	repetition_penalty_decay, mirostat_tau, mirostat_eta; stop_length_penalty is samplers.py's length_penalize -- `length_penalty` is HF's beam ranking) as
+	keywords of `UnifiedVoice.inference_speech`: only what is switched on, so the default call is the call it always was"""
+	kw = {}
+	if min_ar_temp is not None:
+		kw["min_temperature"] = min_ar_temp
+	if repetition_penalty_decay:
+		kw["repetition_penalty_decay"] = repetition_penalty_decay
+	if stop_length_penalty:
+		kw["stop_length_penalty"] = stop_length_penalty
+	if mirostat_tau:
+		kw.update(mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta)
+	return kw
+
+
 def check_sampler_eta(diffusion_sampler: str, diffusion_eta: float):
 	"""`diffusion_eta` belongs to DDIM; the ancestral sampler ignores it as the reference's does, the deterministic DPM-Solver++(2M) refuses it -- before anything is sampled"""
 	if str(diffusion_sampler).lower() == "dpm++2m" and float(diffusion_eta) != 0.0:
@@ -228,8 +244,10 @@ class TTSHotPath:
 				  max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, diffusion_sampler="ddim", cond_free=True, candidates=1,
 				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1, diffusion_conditioning="latents",
-				  do_sample=True, diffusion_eta=0.0):
+				  do_sample=True, diffusion_eta=0.0, min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
 		"""text_tokens [1, Tt] int64; latents from the reference's conditioning encoders ([1,1024], [1,2048]).
+		min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta: the reference's own samplers (tortoise_tts/samplers.py; see
+		`UnifiedVoice.inference_speech`), off by default; sampling only, beam_width 1.
 		diffusion_eta: DDIM's eta (ddim_sample_loop, diffusion.py:745; the reference's `TTS.inference` leaves it at 0): above 0 the per-step draws the
 		deterministic loop makes and ignores (:685) are read -- 1.0 is the DDPM-variance sampler -- so one set of codes renders differently per seed.
 		The ancestral sampler ignores it.
@@ -267,7 +285,8 @@ class TTSHotPath:
 		codes = ar.inference_speech(autoregressive_latents, text_tokens, **ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p),
 									num_return_sequences=candidates, num_beams=max(1, beam_width),
 									length_penalty=length_penalty, repetition_penalty=repetition_penalty,
-									max_generate_length=max_ar_steps, **extra)
+									max_generate_length=max_ar_steps, **extra,
+									**ar_sampler_knobs(min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta))
 		mark("ar_decode")
 		codes = fix_stop_tokens(codes, ar.stop_mel_token)
 		B, M = codes.shape
@@ -321,7 +340,8 @@ class TTSHotPath:
 	def inference_lines(self, lines, autoregressive_latents, diffusion_latents, *, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8,
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
 						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True,
-						diffusion_eta=0.0, diffusion_sampler="ddim"):
+						diffusion_eta=0.0, diffusion_sampler="ddim", min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0,
+						mirostat_eta=0.1):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -346,6 +366,8 @@ class TTSHotPath:
 		diffusion_sampler: "ddim", or "dpm++2m" (DPM-Solver++(2M), see `inference`): the main thread then makes a line's start-noise draw only -- the solver draws nothing
 		per step -- and the batches diffuse through the multistep lines entry (SpacedDiffusion.sample_loop_lines(sampler="dpm++2m")); diffusion_eta must be 0.  The
 		ancestral sampler draws inside its loop and is not served here: use `inference` per line.
+		min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta: the reference's own samplers, as in `inference`; with one of them
+		on the lines of a batch are sampled one after the other (UnifiedVoice.inference_speech_lines), each with its own sampler state.
 		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
@@ -359,6 +381,7 @@ class TTSHotPath:
 		ms = diffusion_sampler == "dpm++2m"
 		diffuser = get_diffuser(steps=max_diffusion_steps, cond_free=cond_free)
 		extra = {"suppress_tokens": suppress_tokens} if suppress_tokens else {}
+		extra.update(ar_sampler_knobs(min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta))
 		main = torch.cuda.current_stream(dev)
 		s_ar, s_df = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
 		s_ar.wait_stream(main)

@@ -121,7 +121,8 @@ class TTS:
 	@torch.inference_mode()
 	def inference(self, text: str, references=None, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
-				  seed=None, candidates=1, references_sr: int = 22050, do_sample=True, *, diffusion_eta=0.0) -> Tuple[torch.Tensor, int]:
+				  seed=None, candidates=1, references_sr: int = 22050, do_sample=True, *, diffusion_eta=0.0, min_ar_temp=None, repetition_penalty_decay=0.0,
+				  stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1) -> Tuple[torch.Tensor, int]:
 		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
 		(wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the `vocoder=` part, "vocoder" the
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
@@ -139,8 +140,15 @@ class TTS:
 		for bit.  The ancestral sampler ignores it; the "hifigan" branch has no diffusion.
 		diffusion_sampler: "ddim", "p" (the reference's two), or "dpm++2m": DPM-Solver++(2M), a second-order multistep solver meant for fewer
 		`max_diffusion_steps` (SpacedDiffusion.sample_loop; the default sampler and step count are unchanged).  It is deterministic: diffusion_eta != 0 with it is
-		a ValueError.  Several lines go through `TTSHotPath.inference_lines` as they do for DDIM."""
+		a ValueError.  Several lines go through `TTSHotPath.inference_lines` as they do for DDIM.
+		min_ar_temp, repetition_penalty_decay, mirostat_tau, mirostat_eta (keyword only; the arguments the reference's `inference` keeps commented out,
+		inference.py:154-163, for the samplers of its tortoise_tts/samplers.py) and stop_length_penalty (its length_penalize; `length_penalty` is HF's beam
+		ranking): the dynamic temperature's lower end, the distance decay of `repetition_penalty`, mirostat v1's target surprise and learning rate, the power
+		of the length that divides the stop token's score (> 0 longer lines).  Off by default (None, 0, 0, 0.1, 0): the call without them, bit for bit.  They
+		act on the sampling branch on every vocoder branch; not with beam_width > 1 or do_sample=False (see `UnifiedVoice.inference_speech`)."""
 		from .inference import check_greedy, check_sampler_eta
+		knobs = dict(min_ar_temp=min_ar_temp, repetition_penalty_decay=repetition_penalty_decay, stop_length_penalty=stop_length_penalty, mirostat_tau=mirostat_tau,
+					 mirostat_eta=mirostat_eta)
 		check_greedy(do_sample, candidates, beam_width)
 		check_sampler_eta(diffusion_sampler, diffusion_eta)
 		if vocoder_type not in ("bigvgan", "vocoder", "hifigan"):
@@ -173,11 +181,11 @@ class TTS:
 			lines.append(tokens)
 		if vocoder_type == "hifigan":
 			wavs = [self._hifigan_wav(tokens, ar_latent, max_ar_steps=max_ar_steps, ar_temp=ar_temp, top_p=top_p, top_k=top_k,
-									  repetition_penalty=repetition_penalty, length_penalty=length_penalty) for tokens in lines]
+									  repetition_penalty=repetition_penalty, length_penalty=length_penalty, **knobs) for tokens in lines]
 			return torch.concat(wavs, dim=-1), SAMPLE_RATE
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
 				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates, do_sample=do_sample,
-				  diffusion_eta=diffusion_eta)
+				  diffusion_eta=diffusion_eta, **knobs)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
 		if beam_width != 1:                                   # the beams of a line exchange histories every token: lines are sampled one by one
 			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
@@ -270,15 +278,17 @@ class TTS:
 		return self.univnet.inference(mels, z)
 
 	def hifigan_chunks(self, tokens: torch.Tensor, ar_latent: torch.Tensor, *, max_ar_steps=500, ar_temp=0.8, top_p=1.0, top_k=0, repetition_penalty=1.0,
-					   length_penalty=1.0):
+					   length_penalty=1.0, min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
 		"""One line of the HiFiGAN branch (inference.py:250-320) as a generator of waveform chunks [1, samples]: `compute_embeddings` ->
 		`get_generator` -> `HiFiGAN.stream`.  The first chunk is there after 60 tokens, while sampling goes on.  `max_length` is
 		min(500, prefix + max_ar_steps): the reference hard-codes 500 in total (stream_generator defaults) and ignores `max_ar_steps`; the
-		default call is the same."""
+		default call is the same.  min_ar_temp ... mirostat_eta: the reference's own samplers, as in `inference`; off by default."""
+		from .inference import ar_sampler_knobs
 		ar = self.hot.autoregressive
 		inputs = ar.compute_embeddings(ar_latent, tokens)
 		pairs = ar.get_generator(inputs=inputs, max_length=min(500, inputs.shape[1] + max_ar_steps), top_k=top_k, top_p=top_p, temperature=ar_temp,
-								 do_sample=True, num_return_sequences=1, length_penalty=length_penalty, repetition_penalty=repetition_penalty)
+								 do_sample=True, num_return_sequences=1, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+								 **ar_sampler_knobs(min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta))
 		chunks = self.hifigan.stream(pairs, ar_latent)
 		while True:
 			with torch.inference_mode():      # per step, not around the yield: the consumer's own mode is its own between two chunks
