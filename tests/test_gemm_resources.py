@@ -49,34 +49,41 @@ def kernel_name(sym):
 	return f"k_gemm<{t},{bm},{bn},{nwm},{nwn},{ns},{ROLES[role]}{',LONGK' if longk else ''}>"
 
 
-def gemm_code_object(tmp_path, tools=TOOLS):
-	"""(tool paths, path of the gfx950 code object taken out of csrc/build/gemm.o)"""
+def gemm_code_object(tmp_path, tools=TOOLS, obj=GEMM_O):
+	"""(tool paths, path of the gfx950 code object taken out of csrc/build/gemm.o, or out of another object file of the build)"""
 	paths = {t: shutil.which(t, path=LLVM_BIN) for t in tools}
 	if not all(paths.values()):
 		pytest.skip(f"ROCm LLVM tools missing under {LLVM_BIN}: {[t for t, p in paths.items() if not p]}")
 	_lib.build()
-	fatbin, co = str(tmp_path / "gemm.fatbin"), str(tmp_path / "gemm.gfx950.co")
-	subprocess.run([paths["llvm-objcopy"], f"--dump-section=.hip_fatbin={fatbin}", GEMM_O, str(tmp_path / "discard.o")], check=True, capture_output=True)
+	stem = os.path.splitext(os.path.basename(obj))[0]
+	fatbin, co = str(tmp_path / f"{stem}.fatbin"), str(tmp_path / f"{stem}.gfx950.co")
+	subprocess.run([paths["llvm-objcopy"], f"--dump-section=.hip_fatbin={fatbin}", obj, str(tmp_path / "discard.o")], check=True, capture_output=True)
 	subprocess.run([paths["clang-offload-bundler"], "--unbundle", "--type=o", f"--input={fatbin}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
 					f"--output={co}"], check=True, capture_output=True)
 	return paths, co
 
 
-def gemm_kernel_resources(tmp_path):
-	paths, co = gemm_code_object(tmp_path)
+def kernel_metadata(tmp_path, keys, symbol, obj=GEMM_O):
+	"""{kernel symbol: tuple of the integer fields `keys`} from the code-object notes of `obj`, for the kernels whose symbol matches the pattern `symbol`"""
+	paths, co = gemm_code_object(tmp_path, obj=obj)
 	notes = subprocess.run([paths["llvm-readelf"], "--notes", co], check=True, capture_output=True, text=True).stdout
 	out = {}
 	for block in re.split(r"\n\s*- \.(?=agpr_count|args)", notes):
 		name = re.search(r"^\s*\.name:\s+(\S+)", block, re.M)
-		if not name or not re.match(r"_ZN3ttk\d+k_gemm", name.group(1)):
+		if not name or not re.match(symbol, name.group(1)):
 			continue
 
 		def field(key):
 			v = re.search(rf"^\s*\.{key}:\s+(\d+)", block, re.M)
 			assert v, f"{name.group(1)}: no .{key} in the code-object metadata"
 			return int(v.group(1))
-		out[kernel_name(name.group(1))] = (field("vgpr_spill_count"), field("sgpr_spill_count"), field("private_segment_fixed_size"))
+		out[name.group(1)] = tuple(field(k) for k in keys)
 	return out
+
+
+def gemm_kernel_resources(tmp_path):
+	res = kernel_metadata(tmp_path, ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"), r"_ZN3ttk\d+k_gemm")
+	return {kernel_name(sym): v for sym, v in res.items()}
 
 
 def test_gemm_kernels_have_no_spills_or_scratch_beyond_the_allowlist(tmp_path):

@@ -509,31 +509,26 @@ int ttk_ar_decode_next(ttk_ar* h, float* logits_out, float* hidden_out, void* st
 	return decode_impl(h, nullptr, logits_out, hidden_out, stream, "ttk_ar_decode_next");
 }
 
-int ttk_ar_sample_next(ttk_ar* h, const ttk_sample_args* a, void* stream) {
-	TTK_REQUIRE(h && a, TTK_E_ARG, "ttk_ar_sample_next: null argument");
-	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_sample_next: call ttk_ar_prefill first");
-	TTK_REQUIRE(a->B == h->B && a->V == h->cfg.number_mel_codes, TTK_E_ARG, "ttk_ar_sample_next: shape (B %d, V %d) is not the prefilled one (B %d, V %d)",
-				a->B, a->V, h->B, h->cfg.number_mel_codes);
-	return launch_sample_step(a, h->mel_emb, h->mel_pos, h->x, h->cfg.model_dim, h->cfg.max_mel_seq_len, h->lnfold ? h->x_frag : nullptr, elem_kind(h->dt),
-							  (hipStream_t)stream, "ttk_ar_sample_next");
+// The token step behind a decode step, on the handle's embedding tables and input row: the sampling launch, its greedy form, or with `x` the one over the
+// reference's samplers.
+static int sample_next(ttk_ar* h, const ttk_sample_args* a, const ttk_sample_ext* x, bool greedy, void* stream, const char* who) {
+	TTK_REQUIRE(h && a, TTK_E_ARG, "%s: null argument", who);
+	TTK_REQUIRE(h->ready, TTK_E_STATE, "%s: call ttk_ar_prefill first", who);
+	TTK_REQUIRE(a->B == h->B && a->V == h->cfg.number_mel_codes, TTK_E_ARG, "%s: shape (B %d, V %d) is not the prefilled one (B %d, V %d)", who, a->B, a->V, h->B,
+				h->cfg.number_mel_codes);
+	const int d = h->cfg.model_dim, pos_rows = h->cfg.max_mel_seq_len, kind = elem_kind(h->dt);
+	void* x_frag = h->lnfold ? h->x_frag : nullptr;
+	if (x) return launch_sample_step_ext(a, x, h->mel_emb, h->mel_pos, h->x, d, pos_rows, x_frag, kind, (hipStream_t)stream, who);
+	return (greedy ? launch_greedy_step : launch_sample_step)(a, h->mel_emb, h->mel_pos, h->x, d, pos_rows, x_frag, kind, (hipStream_t)stream, who);
 }
 
-int ttk_ar_greedy_next(ttk_ar* h, const ttk_sample_args* a, void* stream) {
-	TTK_REQUIRE(h && a, TTK_E_ARG, "ttk_ar_greedy_next: null argument");
-	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_greedy_next: call ttk_ar_prefill first");
-	TTK_REQUIRE(a->B == h->B && a->V == h->cfg.number_mel_codes, TTK_E_ARG, "ttk_ar_greedy_next: shape (B %d, V %d) is not the prefilled one (B %d, V %d)",
-				a->B, a->V, h->B, h->cfg.number_mel_codes);
-	return launch_greedy_step(a, h->mel_emb, h->mel_pos, h->x, h->cfg.model_dim, h->cfg.max_mel_seq_len, h->lnfold ? h->x_frag : nullptr, elem_kind(h->dt),
-							  (hipStream_t)stream, "ttk_ar_greedy_next");
-}
+int ttk_ar_sample_next(ttk_ar* h, const ttk_sample_args* a, void* stream) { return sample_next(h, a, nullptr, false, stream, "ttk_ar_sample_next"); }
+
+int ttk_ar_greedy_next(ttk_ar* h, const ttk_sample_args* a, void* stream) { return sample_next(h, a, nullptr, true, stream, "ttk_ar_greedy_next"); }
 
 int ttk_ar_sample_next_ext(ttk_ar* h, const ttk_sample_args* a, const ttk_sample_ext* x, void* stream) {
-	TTK_REQUIRE(h && a && x, TTK_E_ARG, "ttk_ar_sample_next_ext: null argument");
-	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_sample_next_ext: call ttk_ar_prefill first");
-	TTK_REQUIRE(a->B == h->B && a->V == h->cfg.number_mel_codes, TTK_E_ARG, "ttk_ar_sample_next_ext: shape (B %d, V %d) is not the prefilled one (B %d, V %d)",
-				a->B, a->V, h->B, h->cfg.number_mel_codes);
-	return launch_sample_step_ext(a, x, h->mel_emb, h->mel_pos, h->x, h->cfg.model_dim, h->cfg.max_mel_seq_len, h->lnfold ? h->x_frag : nullptr, elem_kind(h->dt),
-								  (hipStream_t)stream, "ttk_ar_sample_next_ext");
+	TTK_REQUIRE(x, TTK_E_ARG, "ttk_ar_sample_next_ext: null argument");
+	return sample_next(h, a, x, false, stream, "ttk_ar_sample_next_ext");
 }
 
 int ttk_ar_reorder_cache(ttk_ar* h, const int64_t* beam_idx, void* stream) {

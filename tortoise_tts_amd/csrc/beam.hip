@@ -4,7 +4,7 @@
 // `generate` runs for `TTS.inference(beam_width > 1)` (inference.py:161,342) -- and `_reorder_cache` (unified_voice.py:257-265).
 //
 // The step is two launches of num_beams workgroups:
-//   k_beam_scores  row b in registers (as in sample.hip): log_softmax, processors and warpers on the log-probs, + running score; the
+//   k_beam_scores  row b in registers (as in sample.hip, on the stages of sample_stages.h): log_softmax, processors and warpers on the log-probs, + running score; the
 //                  accumulated row goes to scratch with its maximum and its sum of exponentials;
 //   k_beam_select  softmax over the flat [num_beams * V] from those partials, / q, the row's 2 * num_beams largest (that many rounds of a
 //                  block argmax over registers); the workgroup that arrives last merges the num_beams lists and does the bookkeeping of
@@ -14,7 +14,7 @@
 #include "ttk_common.h"
 #include "ttk_kernels.h"
 #include "ttk_host.h"
-#include "sample_prims.h"
+#include "sample_stages.h"
 #include "beam_book.h"
 
 namespace ttk {
@@ -113,50 +113,6 @@ __device__ __forceinline__ int* work_cand_i(const BeamParams& p) { return p.work
 __device__ __forceinline__ int* work_ticket(const BeamParams& p) { return p.work + 2 * p.N + 4 * p.N * p.N; }
 __device__ __forceinline__ int64_t* seq_half(const BeamParams& p, int half, int finished) { return p.seqs + ((int64_t)(half * 2 + finished) * p.N) * p.max_new; }
 
-// key of the k-th largest of the row (TopKLogitsWarper's `torch.topk(scores, k)[0][..., -1]`): 4-pass radix descent over counts, as in sample.hip
-__device__ __forceinline__ unsigned kth_largest_key(const float (&v)[SAMPLE_NPT], int V, unsigned k, int tid, int lane, unsigned* hist32, int* s_bin, unsigned long long* s_before) {
-	unsigned prefix = 0, mask = 0, remaining = k;
-	for (int pass = 3; pass >= 0; --pass) {
-		const int shift = 8 * pass;
-		if (tid < 256) hist32[tid] = 0;
-		__syncthreads();
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) {
-			const int i = tid + j * SAMPLE_THREADS;
-			const unsigned key = fkey(v[j]);
-			if (i < V && (key & mask) == prefix) atomicAdd(&hist32[(key >> shift) & 255], 1u);
-		}
-		__syncthreads();
-		if (tid < 64) {
-			int bin; unsigned before;
-			pick_bin<unsigned, true>(hist32, remaining, lane, bin, before);
-			if (tid == 0) { *s_bin = bin; *s_before = before; }
-		}
-		__syncthreads();
-		prefix |= (unsigned)*s_bin << shift;
-		mask |= 0xffu << shift;
-		remaining -= (unsigned)*s_before;
-	}
-	return prefix;
-}
-
-// block argmax of (value, index), the lowest index winning a tie; every thread returns the winner
-__device__ __forceinline__ void block_argmax(float& best, int& besti, float* red, int* redi, int tid) {
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) {
-		const float ov = __shfl_xor(best, off);
-		const int oi = __shfl_xor(besti, off);
-		if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-	}
-	__syncthreads();
-	if ((tid & 63) == 0) { red[tid >> 6] = best; redi[tid >> 6] = besti; }
-	__syncthreads();
-	best = red[0]; besti = redi[0];
-#pragma unroll
-	for (int w = 1; w < SAMPLE_THREADS / 64; ++w)
-		if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
-}
-
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_scores(BeamParams p) {
 	__shared__ float red[SAMPLE_THREADS / 64];
 	__shared__ unsigned seen[SAMPLE_MAXV / 32];
@@ -192,21 +148,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_scores(BeamParams p) {
 	}
 	// ---- RepetitionPenaltyLogitsProcessor over flat_running_sequences[b] = prefix ids + this beam's own tokens (log-probs are <= 0: multiplied)
 	if (p.penalty != 1.0f) {
-		for (int i = tid; i < SAMPLE_MAXV / 32; i += SAMPLE_THREADS) seen[i] = 0;
-		__syncthreads();
 		const int64_t* hrow = seq_half(p, (int)(c & 1), 0) + (int64_t)b * p.max_new;
-		for (int64_t i = tid; i < c + 2; i += SAMPLE_THREADS) {
-			const int64_t t = i == 0 ? p.prefix0 : (i == 1 ? p.prefix1 : hrow[i - 2]);
-			if (t >= 0 && t < V) atomicOr(&seen[t >> 5], 1u << (t & 31));
-		}
-		__syncthreads();
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) {
-			const int i = tid + j * SAMPLE_THREADS;
-			if (i < V && ((seen[i >> 5] >> (i & 31)) & 1)) v[j] = v[j] < 0.f ? v[j] * p.penalty : v[j] * p.inv_penalty;
-		}
+		mark_seen(seen, V, c + 2, tid, [&](int64_t i) { return i == 0 ? p.prefix0 : (i == 1 ? p.prefix1 : hrow[i - 2]); });
+		penalize_seen(v, V, seen, p.penalty, p.inv_penalty, tid);
 	}
-	// ---- SuppressTokensLogitsProcessor
+	// ---- SuppressTokensLogitsProcessor (not the shared suppress_mask: the padding lanes are -inf already, and with it this kernel came out ~90 instructions longer)
 	if (p.suppress) {
 #pragma unroll
 		for (int j = 0; j < SAMPLE_NPT; ++j) {
@@ -220,61 +166,16 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_scores(BeamParams p) {
 		for (int j = 0; j < SAMPLE_NPT; ++j) v[j] = v[j] * p.inv_t;
 	}
 	// ---- TopKLogitsWarper(top_k = max(top_k, 2)): scores < (k-th largest) -> -inf
-	if (p.top_k > 0 && p.top_k < V) {
-		const unsigned kth = kth_largest_key(v, V, (unsigned)(p.top_k > 2 ? p.top_k : 2), tid, lane, hist32, &s_bin, &s_before);
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j)
-			if (fkey(v[j]) < kth) v[j] = -INFINITY;
-	}
+	if (p.top_k > 0 && p.top_k < V) drop_below(v, kth_largest_key(v, V, (unsigned)(p.top_k > 2 ? p.top_k : 2), tid, lane, hist32, &s_bin, &s_before));
 	// ---- TopPLogitsWarper(min_tokens_to_keep = 2): ascending cumulative softmax <= 1 - top_p -> -inf, the two largest scores always stay
-	//      (exact fixed-point masses, see sample.hip for how that differs from torch's f32 cumsum at a tie)
 	if (p.top_p > 0.f && p.top_p < 1.0f) {
 		float m = -INFINITY;
 #pragma unroll
 		for (int j = 0; j < SAMPLE_NPT; ++j) m = fmaxf(m, v[j]);
 		m = block_max(m, red, tid);
-		float e[SAMPLE_NPT], sum = 0.f;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) { e[j] = expf(v[j] - m); sum += e[j]; }
-		sum = block_sum(sum, red, tid);
-		unsigned long long w[SAMPLE_NPT], tot = 0;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) { w[j] = (unsigned long long)((e[j] / sum) * 1099511627776.0f); tot += w[j]; }
-		if (tid < 256) hist64[tid] = 0;
-		__syncthreads();
-		atomicAdd(&hist64[0], tot);
-		__syncthreads();
-		const unsigned long long total = hist64[0];
-		unsigned long long target = (unsigned long long)((1.0f - p.top_p) * 1099511627776.0f);
-		if (total > 0 && target >= total) target = total - 1;
-		__syncthreads();
-		unsigned prefix = 0, mask = 0;
-		unsigned long long below = 0;
-		for (int pass = 3; pass >= 0; --pass) {
-			const int shift = 8 * pass;
-			if (tid < 256) hist64[tid] = 0;
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) {
-				const unsigned key = fkey(v[j]);
-				if (w[j] && (key & mask) == prefix) atomicAdd(&hist64[(key >> shift) & 255], w[j]);
-			}
-			__syncthreads();
-			if (tid < 64) {
-				int bin; unsigned long long before;
-				pick_bin<unsigned long long, false>(hist64, target - below, lane, bin, before);
-				if (tid == 0) { s_bin = bin; s_before = before; }
-			}
-			__syncthreads();
-			prefix |= (unsigned)s_bin << shift;
-			mask |= 0xffu << shift;
-			below += s_before;
-		}
+		const unsigned cut = top_p_cut(v, m, p.top_p, tid, lane, red, hist64, &s_bin, &s_before);
 		const unsigned second = kth_largest_key(v, V, 2u, tid, lane, hist32, &s_bin, &s_before);
-		const unsigned cut = prefix < second ? prefix : second;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j)
-			if (fkey(v[j]) < cut) v[j] = -INFINITY;
+		drop_below(v, cut < second ? cut : second);
 	}
 	// ---- + running_beam_scores[b]; the row's share of the flat softmax
 	const float run = p.scores[b];
@@ -327,7 +228,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_select(BeamParams p) {
 			const int i = tid + j * SAMPLE_THREADS;
 			if (!((removed >> j) & 1) && i < V && r[j] > best) { best = r[j]; besti = i; }
 		}
-		block_argmax(best, besti, red, redi, tid);
+		block_argmax<true>(best, besti, red, redi, tid);
 		if (besti < V && (besti & (SAMPLE_THREADS - 1)) == tid) removed |= 1u << (besti / SAMPLE_THREADS);
 		if (tid == 0) { cand_r[it] = __float_as_int(best); cand_i[it] = besti < V ? b * V + besti : 0x7fffffff; }
 	}
@@ -350,7 +251,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_select(BeamParams p) {
 	for (int it = 0; it < K; ++it) {
 		float best = cr;
 		int besti = ci;
-		block_argmax(best, besti, red, redi, tid);
+		block_argmax<true>(best, besti, red, redi, tid);
 		if (besti == ci) { cr = -2.0f; ci = 0x7fffffff; }      // flat indices are unique: only the owner matches (or nobody is left)
 		if (tid == 0) top_i[it] = besti;
 	}

@@ -1,35 +1,38 @@
 // The reference's own samplers (tortoise_tts/samplers.py: reptition_penalize, length_penalize, dynamic_temperature, mirostat_sample) on a second fused
-// token step, k_sample_step_ext, beside k_sample_step (sample.hip), whose text and code object stay what they are: the benchmarked token step never
-// launches this kernel.  Same launch shape (one block of 1024 threads per row, V <= SAMPLE_MAXV, the row in registers), same bookkeeping tail.
+// token step, k_sample_step_ext, beside k_sample_step (sample.hip): the benchmarked token step never launches this kernel.  Same launch shape (one block
+// of 1024 threads per row, V <= SAMPLE_MAXV, the row in registers), same operands (a SampleParams inside SampleExtParams), and the same stages wherever
+// the chain is HF's: both kernels call the one definition in sample_stages.h.
 //
-// Chain per row -- "as k_sample_step" = statement for statement what k_sample_step<false> does:
-//   1. repetition penalty.  decay == 0: HF's RepetitionPenaltyLogitsProcessor, as k_sample_step.  decay != 0: reptition_penalize(factor = penalty, decay,
-//      one_time=True) (samplers.py:11-29) INSTEAD: `previous` = history[b, hist_off : hist_off + col[b]] (prompt + sampled tokens, not the two prefix ids);
-//      every distinct token of it, with d = 1 + the number of tokens behind its most recent occurrence, gets score *= 1.0f / (float)(penalty * pow(d, decay))
-//      -- a division whatever the sign of the score (unlike HF's), in ATen's reciprocal-multiply form as the existing penalty.  The "latest position" table
-//      is 16 bits per token in LDS (the words of the `seen` bitmap of the other form lie in the same array).  penalty == 1 is off (the reference returns early).
+// Chain per row -- "shared" = the stage of sample_stages.h that k_sample_step<false> calls as well; the rest is this file's:
+//   1. repetition penalty.  decay == 0: HF's RepetitionPenaltyLogitsProcessor, shared (mark_seen, penalize_seen).  decay != 0: reptition_penalize(factor =
+//      penalty, decay, one_time=True) (samplers.py:11-29) INSTEAD: `previous` = history[b, hist_off : hist_off + col[b]] (prompt + sampled tokens, not the
+//      two prefix ids); every distinct token of it, with d = 1 + the number of tokens behind its most recent occurrence, gets
+//      score *= 1.0f / (float)(penalty * pow(d, decay)) -- a division whatever the sign of the score (unlike HF's), in ATen's reciprocal-multiply form as
+//      the shared penalty.  The "latest position" table is 16 bits per token in LDS (the words of the `seen` bitmap of the other form lie in the same array).
+//      penalty == 1 is off (the reference returns early).
 //   2. stop-length penalty: length_penalize (:35-40) on the stop token, score *= 1.0f / (float)pow(len(previous) + 1, factor); factor 0 = off.
-//   3. suppress mask, typical warper: as k_sample_step.
-//   4. temperature: as k_sample_step, or with min_temperature >= 0 dynamic_temperature (:78-91, k = 10, centre 0.5) per row: p_max = 1 / sum exp(s - max)
+//   3. suppress mask, typical warper: shared (suppress_mask, typical_warper).
+//   4. temperature: HF's warper, or with min_temperature >= 0 dynamic_temperature (:78-91, k = 10, centre 0.5) per row: p_max = 1 / sum exp(s - max)
 //      (f32 block sums), T_dyn = T - (T - T_min) / (1 + exp(-10 (p_max - 0.5))) in f64, scores *= 1.0f / (float)T_dyn.  It sits where HF's temperature
 //      warper sits, in front of top-k: the reference never wired dynamic_temperature into its generate call, so there is no other order to match.
-//   5. top-k, top-p: as k_sample_step.
-//   6. draw: argmax(softmax / q) as k_sample_step, or with mirostat_tau > 0 mirostat v1 (mirostat_sample, :117-158) on one f64 `mu` per row (the
-//      reference's max_surprise; the caller sets it to 2 tau before the first token): P = softmax(scores); from the 101 largest P, descending,
+//   5. top-k, top-p: shared (kth_largest_key, top_p_cut, drop_below).
+//   6. draw: shared (draw: argmax(softmax / q)), or with mirostat_tau > 0 mirostat v1 (mirostat_sample, :117-158) in front of it, on one f64 `mu` per row
+//      (the reference's max_surprise; the caller sets it to 2 tau before the first token): P = softmax(scores); from the 101 largest P, descending,
 //      s = sum ln(P_i / P_i+1) ln t_i / sum ln^2 t_i with t_i = (i + 2) / (i + 1), eps = s - 1, k = rint(((eps 2^mu) / (1 - V^-eps))^(1 / s)) + 1 in f64
-//      (Python's round is half-to-even, as rint), clamped to [1, V], a non-finite value = V; the k largest scores stay (radix descent as top-k: a group of
-//      equal scores at the threshold stays whole); token = argmax over the kept of softmax_kept / q; mu -= eta (log2(1 / P[token]) - tau).
+//      (Python's round is half-to-even, as rint), clamped to [1, V], a non-finite value = V; the k largest scores stay (kth_largest_key: a group of
+//      equal scores at the threshold stays whole); token = the shared draw over the kept; mu -= eta (log2(1 / P[token]) - tau).
 //      Only the 101 largest VALUES are needed and equal values sort identically: a count-select of the 101st largest score, the at most 100 strictly larger
 //      probabilities compacted into LDS and rank-sorted there -- no sort of the row.  Fewer than 101 finite scores (where the reference raises
 //      ZeroDivisionError): every survivor stays (k = their number) and mu is still updated.  A finished row's mu may hold anything.
 //      Deviation: the reference draws with torch.multinomial over the k sorted entries, whose Philox consumption depends on k and would cost a host round
 //      trip per token.  Here q is the same noise row, indexed by token id, that the default draw consumes: the same distribution over the kept tokens, and
 //      exactly the noise block per token that k_sample_step consumes, so the caller's generator accounting does not change.
+//   7. bookkeeping and the next decode step's input row: shared (block_argmax, finish_token, next_input_row).
 // Optional outputs (tests, diagnosis; HF's output_scores in shape): scores_out = the scores behind stage 5 (-inf where removed), temp_out, mirostat_k.
 #include "ttk_common.h"
 #include "ttk_kernels.h"
 #include "ttk_host.h"
-#include "sample_prims.h"
+#include "sample_stages.h"
 
 namespace ttk {
 
@@ -38,50 +41,12 @@ static_assert(sizeof(ttk_sample_ext) == 64, "ttk_sample_ext layout (tortoise_tts
 constexpr int MIRO_N = 100;              // ratios of compute_k (samplers.py:121): the 101 largest probabilities
 
 struct SampleExtParams {
-	// k_sample_step's operands (sample.hip: SampleParams)
-	const float* scores; int64_t ld; int V;
-	const float* q; int64_t ldq;
-	const unsigned char* suppress; float inv_t;
-	int top_k; float top_p; float penalty, inv_penalty;
-	float typical_mass;
-	int64_t stop_token;
-	int64_t *unfinished, *tok, *ids; int64_t ids_ld, ids_cols; int64_t* col;
-	int64_t* history; int64_t hist_ld, hist_off;
-	int *live_rows, *all_done;
-	const float *emb, *pos; float* x_out; int d, pos_rows;
-	void* x_frag; int x_frag_f32;
+	SampleParams s;                      // k_sample_step's operands: what the shared stages take
 	// the reference's samplers
 	float temperature;                   // T of the dynamic temperature
 	float decay, stop_len, min_t, tau, eta;
 	double* mu; int* miro_k; float* temp_out; float* scores_out; int64_t scores_out_ld;
 };
-
-// key of the k-th largest of the row's scores (k >= 1): the radix descent of k_sample_step's top-k over counts, k given per call
-__device__ __forceinline__ unsigned kth_largest_key(const float (&v)[SAMPLE_NPT], int V, unsigned k, int tid, int lane, unsigned* hist32, int* s_bin, unsigned long long* s_before) {
-	unsigned prefix = 0, mask = 0, remaining = k;
-	for (int pass = 3; pass >= 0; --pass) {
-		const int shift = 8 * pass;
-		if (tid < 256) hist32[tid] = 0;
-		__syncthreads();
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) {
-			const int i = tid + j * SAMPLE_THREADS;
-			const unsigned key = fkey(v[j]);
-			if (i < V && (key & mask) == prefix) atomicAdd(&hist32[(key >> shift) & 255], 1u);
-		}
-		__syncthreads();
-		if (tid < 64) {
-			int bin; unsigned before;
-			pick_bin<unsigned, true>(hist32, remaining, lane, bin, before);
-			if (tid == 0) { *s_bin = bin; *s_before = before; }
-		}
-		__syncthreads();
-		prefix |= (unsigned)*s_bin << shift;
-		mask |= 0xffu << shift;
-		remaining -= (unsigned)*s_before;
-	}
-	return prefix;
-}
 
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtParams p) {
 	__shared__ float red[SAMPLE_THREADS / 64];
@@ -96,12 +61,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 	__shared__ double miro_num[MIRO_N], miro_den[MIRO_N];
 	__shared__ int s_cnt, s_k, s_tok;
 	__shared__ float s_pthr, s_ptok;
+	const SampleParams& sp = p.s;
 	const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-	const int V = p.V;
-	const float* s = p.scores + (int64_t)b * p.ld;
-	const float* qq = p.q + (int64_t)b * p.ldq;
-	const bool scale = p.inv_t != 1.0f;
-	const int64_t c0 = p.col[b];
+	const int V = sp.V;
+	const float* s = sp.scores + (int64_t)b * sp.ld;
+	const float* qq = sp.q + (int64_t)b * sp.ldq;
+	const bool scale = sp.inv_t != 1.0f;
+	const int64_t c0 = sp.col[b];
 	float best = -INFINITY;
 	int besti = 0x7fffffff;
 	unsigned* seen = last16;
@@ -113,27 +79,16 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 	}
 	if (p.decay == 0.f) {
 		// ---- RepetitionPenaltyLogitsProcessor: every id present in input_ids (prefix ids + tokens generated so far), once
-		if (p.penalty != 1.0f && p.history) {
-			for (int i = tid; i < SAMPLE_MAXV / 32; i += SAMPLE_THREADS) seen[i] = 0;
-			__syncthreads();
-			const int64_t* hrow = p.history + (int64_t)b * p.hist_ld;
-			const int64_t n = p.hist_off + c0;
-			for (int64_t i = tid; i < n; i += SAMPLE_THREADS) {
-				const int64_t t = hrow[i];
-				if (t >= 0 && t < V) atomicOr(&seen[t >> 5], 1u << (t & 31));
-			}
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) {
-				const int i = tid + j * SAMPLE_THREADS;
-				if (i < V && ((seen[i >> 5] >> (i & 31)) & 1)) v[j] = v[j] < 0.f ? v[j] * p.penalty : v[j] * p.inv_penalty;
-			}
+		if (sp.penalty != 1.0f && sp.history) {
+			const int64_t* hrow = sp.history + (int64_t)b * sp.hist_ld;
+			mark_seen(seen, V, sp.hist_off + c0, tid, [&](int64_t i) { return hrow[i]; });
+			penalize_seen(v, V, seen, sp.penalty, sp.inv_penalty, tid);
 		}
-	} else if (p.penalty != 1.0f && p.history) {
+	} else if (sp.penalty != 1.0f && sp.history) {
 		// ---- reptition_penalize(one_time=True): the latest position of every token of `previous`, then one division per distinct token
 		for (int i = tid; i < SAMPLE_MAXV / 2; i += SAMPLE_THREADS) last16[i] = 0;
 		__syncthreads();
-		const int64_t* hrow = p.history + (int64_t)b * p.hist_ld + p.hist_off;
+		const int64_t* hrow = sp.history + (int64_t)b * sp.hist_ld + sp.hist_off;
 		const int n = (int)(c0 < 65534 ? c0 : 65534);            // (16-bit entries; the host refuses id buffers that long)
 		for (int i = tid; i < n; i += SAMPLE_THREADS) {
 			const int64_t t = hrow[i];
@@ -156,7 +111,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 			const unsigned at = i < V ? (last16[i >> 1] >> ((i & 1) * 16)) & 0xffffu : 0u;
 			if (at) {
 				const double dist = (double)(n - (int)at + 1);
-				const float mul = 1.0f / (float)((double)p.penalty * pow(dist, (double)p.decay));
+				const float mul = 1.0f / (float)((double)sp.penalty * pow(dist, (double)p.decay));
 #pragma unroll
 				for (int jj = 0; jj < SAMPLE_NPT; ++jj)
 					if (jj == j) v[jj] = v[jj] * mul;
@@ -164,81 +119,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 		}
 	}
 	// ---- length_penalize on the stop token: its owner thread alone
-	if (p.stop_len != 0.f && p.stop_token >= 0 && p.stop_token < V && tid == (int)(p.stop_token % SAMPLE_THREADS)) {
-		const int js = (int)(p.stop_token / SAMPLE_THREADS);
+	if (p.stop_len != 0.f && sp.stop_token >= 0 && sp.stop_token < V && tid == (int)(sp.stop_token % SAMPLE_THREADS)) {
+		const int js = (int)(sp.stop_token / SAMPLE_THREADS);
 		const float mul = 1.0f / (float)pow((double)(c0 + 1), (double)p.stop_len);
 #pragma unroll
 		for (int jj = 0; jj < SAMPLE_NPT; ++jj)
 			if (jj == js) v[jj] = v[jj] * mul;
 	}
-	// ---- SuppressTokensLogitsProcessor
-#pragma unroll
-	for (int j = 0; j < SAMPLE_NPT; ++j) {
-		const int i = tid + j * SAMPLE_THREADS, ic = i < V ? i : V - 1;
-		const float t = (p.suppress && p.suppress[ic]) ? -INFINITY : v[j];
-		v[j] = i < V ? t : -INFINITY;
-	}
-	// ---- TypicalLogitsWarper: as k_sample_step
-	if (p.typical_mass > 0.f && p.typical_mass < 1.0f) {
-		float m0 = -INFINITY;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) m0 = fmaxf(m0, v[j]);
-		m0 = block_max(m0, red, tid);
-		float e[SAMPLE_NPT], sum = 0.f;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) { e[j] = expf(v[j] - m0); sum += e[j]; }
-		sum = block_sum(sum, red, tid);
-		const float lse = m0 + logf(sum);
-		float d[SAMPLE_NPT], hpart = 0.f;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) {
-			const float lp = v[j] - lse, pr = e[j] / sum;
-			d[j] = lp;                                        // log p (kept; becomes the distance below)
-			if (v[j] != -INFINITY) hpart -= pr * lp;          // nansum: removed tokens contribute (-inf * 0) = nan -> skipped
-		}
-		const float H = block_sum(hpart, red, tid);
-		unsigned long long w[SAMPLE_NPT], tot = 0;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) {
-			w[j] = (unsigned long long)((e[j] / sum) * 1099511627776.0f); tot += w[j];
-			d[j] = v[j] != -INFINITY ? fabsf(-d[j] - H) : INFINITY;      // |-logp - H|; removed tokens sort last (inf), as abs(inf - H) does
-		}
-		if (tid < 256) hist64[tid] = 0;
-		__syncthreads();
-		atomicAdd(&hist64[0], tot);
-		__syncthreads();
-		const unsigned long long total = hist64[0];
-		// first position (ascending distance) whose cumulative mass is NOT < mass  <=>  running total >= ceil(mass * total)  <=>  > that - 1
-		unsigned long long target = (unsigned long long)((double)p.typical_mass * (double)total);
-		if (target >= total && total > 0) target = total - 1;
-		if (target > 0) target -= 1;
-		__syncthreads();
-		unsigned prefix = 0, mask = 0;
-		unsigned long long below = 0;
-		for (int pass = 3; pass >= 0; --pass) {
-			const int shift = 8 * pass;
-			if (tid < 256) hist64[tid] = 0;
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) {
-				const unsigned k = fkey(d[j]);
-				if (w[j] && (k & mask) == prefix) atomicAdd(&hist64[(k >> shift) & 255], w[j]);
-			}
-			__syncthreads();
-			if (tid < 64) {
-				int bin; unsigned long long before;
-				pick_bin<unsigned long long, false>(hist64, target - below, lane, bin, before);
-				if (tid == 0) { s_bin = bin; s_before = before; }
-			}
-			__syncthreads();
-			prefix |= (unsigned)s_bin << shift;
-			mask |= 0xffu << shift;
-			below += s_before;
-		}
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j)
-			if (fkey(d[j]) > prefix) v[j] = -INFINITY;        // sorted_scores > sorted_scores[last_ind]
-	}
+	suppress_mask(v, V, sp.suppress, tid);
+	if (sp.typical_mass > 0.f && sp.typical_mass < 1.0f) typical_warper(v, sp.typical_mass, tid, lane, red, hist64, &s_bin, &s_before);
 	if (p.min_t >= 0.f) {
 		// ---- dynamic_temperature: the temperature falls from T to T_min as the row's largest probability rises through 0.5
 		float m0 = -INFINITY;
@@ -259,86 +148,18 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 		// ---- TemperatureLogitsWarper
 		if (scale) {
 #pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) v[j] = v[j] * p.inv_t;
+			for (int j = 0; j < SAMPLE_NPT; ++j) v[j] = v[j] * sp.inv_t;
 		}
 		if (p.temp_out && tid == 0) p.temp_out[b] = p.temperature;
 	}
 	// ---- TopKLogitsWarper: scores < (k-th largest) -> -inf
-	if (p.top_k > 0 && p.top_k < V) {
-		unsigned prefix = 0, mask = 0, remaining = (unsigned)p.top_k;
-		for (int pass = 3; pass >= 0; --pass) {
-			const int shift = 8 * pass;
-			if (tid < 256) hist32[tid] = 0;
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) {
-				const int i = tid + j * SAMPLE_THREADS;
-				const unsigned k = fkey(v[j]);
-				if (i < V && (k & mask) == prefix) atomicAdd(&hist32[(k >> shift) & 255], 1u);
-			}
-			__syncthreads();
-			if (tid < 64) {
-				int bin; unsigned before;
-				pick_bin<unsigned, true>(hist32, remaining, lane, bin, before);
-				if (tid == 0) { s_bin = bin; s_before = before; }
-			}
-			__syncthreads();
-			prefix |= (unsigned)s_bin << shift;
-			mask |= 0xffu << shift;
-			remaining -= (unsigned)s_before;
-		}
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j)
-			if (fkey(v[j]) < prefix) v[j] = -INFINITY;
-	}
+	if (sp.top_k > 0 && sp.top_k < V) drop_below(v, kth_largest_key(v, V, (unsigned)sp.top_k, tid, lane, hist32, &s_bin, &s_before));
 	float m = -INFINITY;
 #pragma unroll
 	for (int j = 0; j < SAMPLE_NPT; ++j) m = fmaxf(m, v[j]);
 	m = block_max(m, red, tid);
 	// ---- TopPLogitsWarper: ascending cumulative softmax <= 1 - top_p -> -inf (the largest score always stays)
-	if (p.top_p > 0.f && p.top_p < 1.0f) {
-		float e[SAMPLE_NPT], sum = 0.f;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) { e[j] = expf(v[j] - m); sum += e[j]; }
-		sum = block_sum(sum, red, tid);
-		unsigned long long w[SAMPLE_NPT], tot = 0;
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j) { w[j] = (unsigned long long)((e[j] / sum) * 1099511627776.0f); tot += w[j]; }
-		// block total of the integer masses (exact), to keep the target below it: the largest score is never removed
-		if (tid < 256) hist64[tid] = 0;
-		__syncthreads();
-		atomicAdd(&hist64[0], tot);
-		__syncthreads();
-		const unsigned long long total = hist64[0];
-		unsigned long long target = (unsigned long long)((1.0f - p.top_p) * 1099511627776.0f);
-		if (total > 0 && target >= total) target = total - 1;
-		__syncthreads();
-		unsigned prefix = 0, mask = 0;
-		unsigned long long below = 0;
-		for (int pass = 3; pass >= 0; --pass) {
-			const int shift = 8 * pass;
-			if (tid < 256) hist64[tid] = 0;
-			__syncthreads();
-#pragma unroll
-			for (int j = 0; j < SAMPLE_NPT; ++j) {
-				const unsigned k = fkey(v[j]);
-				if (w[j] && (k & mask) == prefix) atomicAdd(&hist64[(k >> shift) & 255], w[j]);
-			}
-			__syncthreads();
-			if (tid < 64) {
-				int bin; unsigned long long before;
-				pick_bin<unsigned long long, false>(hist64, target - below, lane, bin, before);
-				if (tid == 0) { s_bin = bin; s_before = before; }
-			}
-			__syncthreads();
-			prefix |= (unsigned)s_bin << shift;
-			mask |= 0xffu << shift;
-			below += s_before;
-		}
-#pragma unroll
-		for (int j = 0; j < SAMPLE_NPT; ++j)
-			if (fkey(v[j]) < prefix) v[j] = -INFINITY;
-	}
+	if (sp.top_p > 0.f && sp.top_p < 1.0f) drop_below(v, top_p_cut(v, m, sp.top_p, tid, lane, red, hist64, &s_bin, &s_before));
 	if (p.scores_out) {
 		float* so = p.scores_out + (int64_t)b * p.scores_out_ld;
 #pragma unroll
@@ -402,55 +223,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 			// instead of being carried across it -- 13 registers, the difference between 125 and a spill at the 128 a 1024-thread block may hold)
 #pragma unroll
 			for (int j = 0; j < SAMPLE_NPT; ++j) asm volatile("" : "+v"(v[j]));
-			if (keep < V) {
-				const unsigned cut = kth_largest_key(v, V, (unsigned)keep, tid, lane, hist32, &s_bin, &s_before);
-#pragma unroll
-				for (int j = 0; j < SAMPLE_NPT; ++j)
-					if (fkey(v[j]) < cut) v[j] = -INFINITY;
-			}
+			if (keep < V) drop_below(v, kth_largest_key(v, V, (unsigned)keep, tid, lane, hist32, &s_bin, &s_before));
 			if (p.miro_k && tid == 0) p.miro_k[b] = keep;
 		} else if (p.miro_k && tid == 0) p.miro_k[b] = finite;
 	}
-	// ---- softmax, multinomial(1) = argmax(p / q)
-	float sum = 0.f;
-#pragma unroll
-	for (int j = 0; j < SAMPLE_NPT; ++j) { v[j] = expf(v[j] - m); sum += v[j]; }      // exp(-inf) = 0 for removed / padding lanes
-	sum = block_sum(sum, red, tid);
-#pragma unroll
-	for (int j = 0; j < SAMPLE_NPT; ++j) {
-		const int i = tid + j * SAMPLE_THREADS;
-		const float r = (v[j] / sum) / qq[i < V ? i : V - 1];
-		if (i < V && r > best) { best = r; besti = i; }          // strict: the lowest index wins a tie, as in ATen's argmax
-	}
-	// wave then block reduction of (value, index) with the same tie rule
-#pragma unroll
-	for (int off = 32; off > 0; off >>= 1) {
-		const float ov = __shfl_xor(best, off);
-		const int oi = __shfl_xor(besti, off);
-		if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-	}
-	__syncthreads();
-	if ((tid & 63) == 0) { red[tid >> 6] = best; redi[tid >> 6] = besti; }
-	__syncthreads();
+	draw(v, m, V, tid, red, best, besti, [&](int j) { const int i = tid + j * SAMPLE_THREADS; return qq[i < V ? i : V - 1]; });
+	block_argmax<false>(best, besti, red, redi, tid);
 	if (tid == 0) {
-		for (int w = 1; w < SAMPLE_THREADS / 64; ++w)
-			if (red[w] > best || (red[w] == best && redi[w] < besti)) { best = red[w]; besti = redi[w]; }
-		if (besti >= V) besti = 0;                       // all-NaN / empty row: ATen returns index 0 as well
+		s_next = finish_token(sp, b, c0, besti);
 		s_tok = besti;
-		const int64_t live = p.unfinished[b];
-		const int64_t nxt = (int64_t)besti * live + p.stop_token * (1 - live);
-		p.tok[b] = nxt;
-		if (c0 < p.ids_cols) p.ids[(int64_t)b * p.ids_ld + c0] = nxt;
-		if (p.history) p.history[(int64_t)b * p.hist_ld + p.hist_off + c0] = nxt;
-		p.col[b] = c0 + 1;
-		const int64_t still = live * (nxt != p.stop_token ? 1 : 0);
-		p.unfinished[b] = still;
-		s_next = nxt;
-		// (the stopping flag of k_sample_step)
-		if (p.live_rows && live != 0 && still == 0) {
-			if (__hip_atomic_fetch_add(p.live_rows, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1 && p.all_done)
-				__hip_atomic_store(p.all_done, (int)(c0 + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-		}
 	}
 	if (p.tau > 0.f) {
 		// ---- mirostat: mu -= eta (surprise of the token drawn - tau), the surprise from the softmax of the WHOLE row (prob_original)
@@ -467,37 +248,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_step_ext(SampleExtPar
 		__syncthreads();
 		if (tid == 0) p.mu[b] -= (double)p.eta * (log2(1.0 / (double)s_ptok) - (double)p.tau);
 	}
-	if (p.x_out) {
-		// the row the following decode step starts from: mel_embedding[next] + mel_pos_embedding[k + 1], as k_sample_step
-		__syncthreads();
-		const int64_t nxt = s_next;
-		int64_t pi = c0 + 2;
-		pi = pi < p.pos_rows ? pi : p.pos_rows - 1;      // guard; the host validates lengths up front
-		const float4* e = (const float4*)(p.emb + nxt * p.d);
-		const float4* w = (const float4*)(p.pos + pi * p.d);
-		float4* o = (float4*)(p.x_out + (int64_t)b * p.d);
-		for (int i = tid; i < p.d / 4; i += SAMPLE_THREADS) {
-			const float4 a = e[i], c = w[i];
-			const float4 v4 = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
-			o[i] = v4;
-			if (p.x_frag) {
-				const int n = 4 * i;
-				const int64_t fi = TTK_FRAG_INDEX(b, n, p.d / 32);
-				store4_kind(p.x_frag, fi, v4, p.x_frag_f32);
-			}
-		}
-	}
+	next_input_row(sp, b, c0, &s_next, tid);
 }
 
 int launch_sample_step_ext(const ttk_sample_args* a, const ttk_sample_ext* x, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 						   hipStream_t stream, const char* who) {
-	TTK_REQUIRE(a && x && a->scores && a->q && a->unfinished && a->tok && a->ids && a->col, TTK_E_ARG, "%s: null argument", who);
-	TTK_REQUIRE(a->B >= 1 && a->V >= 1 && a->ld >= a->V && a->ldq >= a->V, TTK_E_ARG, "%s: bad shape (B %d, V %d)", who, a->B, a->V);
+	TTK_TRY(check_sample_args(a, who, true, false));
+	TTK_REQUIRE(x, TTK_E_ARG, "%s: null argument", who);
 	TTK_REQUIRE(a->V <= SAMPLE_MAXV, TTK_E_ARG, "%s: V %d exceeds the %d scores a row holds in registers", who, a->V, SAMPLE_MAXV);
-	TTK_REQUIRE(a->temperature > 0.f, TTK_E_ARG, "%s: temperature must be positive", who);
-	TTK_REQUIRE(a->typical_mass >= 0.f, TTK_E_ARG, "%s: negative typical_mass", who);
-	TTK_REQUIRE(a->top_p >= 0.f && a->repetition_penalty >= 0.f, TTK_E_ARG, "%s: negative top_p / repetition_penalty", who);
-	TTK_REQUIRE(!(a->repetition_penalty > 0.f && a->repetition_penalty != 1.0f) || a->history, TTK_E_ARG, "%s: the repetition penalty needs the history buffer", who);
 	TTK_REQUIRE((x->repetition_penalty_decay == 0.f && x->stop_length_penalty == 0.f) || a->history, TTK_E_ARG,
 				"%s: repetition_penalty_decay / stop_length_penalty need the history buffer", who);
 	TTK_REQUIRE(x->repetition_penalty_decay == 0.f || a->ids_cols < 65534, TTK_E_ARG, "%s: repetition_penalty_decay keeps 16-bit positions (ids_cols %lld)", who, (long long)a->ids_cols);
@@ -506,12 +264,7 @@ int launch_sample_step_ext(const ttk_sample_args* a, const ttk_sample_ext* x, co
 	TTK_REQUIRE(!(x->mirostat_tau > 0.f) || x->mirostat_mu, TTK_E_ARG, "%s: mirostat needs mirostat_mu, one double per row", who);
 	TTK_REQUIRE(!x->scores_out || x->scores_out_ld >= a->V, TTK_E_ARG, "%s: scores_out_ld %lld is below V %d", who, (long long)x->scores_out_ld, a->V);
 	SampleExtParams p = {};
-	p.scores = a->scores; p.ld = a->ld; p.V = a->V; p.q = a->q; p.ldq = a->ldq; p.suppress = a->suppress; p.inv_t = 1.0f / a->temperature;
-	p.top_k = a->top_k; p.top_p = a->top_p; p.typical_mass = a->typical_mass;
-	p.penalty = a->repetition_penalty > 0.f ? a->repetition_penalty : 1.0f; p.inv_penalty = 1.0f / p.penalty;
-	p.stop_token = a->stop_token; p.unfinished = a->unfinished; p.tok = a->tok; p.ids = a->ids; p.ids_ld = a->ids_ld; p.ids_cols = a->ids_cols;
-	p.col = a->col; p.history = a->history; p.hist_ld = a->hist_ld; p.hist_off = a->hist_off; p.live_rows = a->live_rows; p.all_done = a->all_done;
-	p.emb = emb; p.pos = pos; p.x_out = x_out; p.d = d; p.pos_rows = pos_rows; p.x_frag = x_frag; p.x_frag_f32 = x_frag_f32;
+	p.s = fill_sample_params(a, emb, pos, x_out, d, pos_rows, x_frag, x_frag_f32);
 	p.temperature = a->temperature; p.decay = x->repetition_penalty_decay; p.stop_len = x->stop_length_penalty;
 	p.min_t = x->min_temperature >= 0.f ? x->min_temperature : -1.0f;      // (a NaN is off as well)
 	p.tau = x->mirostat_tau; p.eta = x->mirostat_eta; p.mu = x->mirostat_mu; p.miro_k = x->mirostat_k; p.temp_out = x->temp_out;

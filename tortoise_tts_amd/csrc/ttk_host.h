@@ -151,7 +151,7 @@ int launch_sample_step(const ttk_sample_args* a, const float* emb, const float* 
 					   hipStream_t stream, const char* who);
 int launch_greedy_step(const ttk_sample_args* a, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 					   hipStream_t stream, const char* who);
-// sample_ext.hip: the same step over the reference's samplers.py (ttk_sample_ext), on a kernel of its own
+// sample_ext.hip: the same step over the reference's samplers.py (ttk_sample_ext), on a kernel of its own built from the same stages (sample_stages.h)
 int launch_sample_step_ext(const ttk_sample_args* a, const ttk_sample_ext* x, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 						   hipStream_t stream, const char* who);
 
