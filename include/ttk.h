@@ -760,7 +760,9 @@ typedef struct {
 int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ the GroupNorm32-apply kernels on caller-provided operands
- * No reference counterpart: exposed so every launch form of csrc/norm.hip's GroupNorm-apply can be run on the same input and statistics (the forms owe the same bits).
+ * No reference counterpart: exposed so every launch form of csrc/norm.hip's GroupNorm-apply can be run on the same input and statistics (the forms owe the same
+ * bits: tests/test_gpu_gn_forms.py) and so the generic form and the chunk statistics can be held, element by element, to a float64 GroupNorm of the same operands
+ * (tests/test_gpu_norm_forms.py with tests/norm_ref.py).
  * out [nb][Tout][C] = act( gn(x) * gamma + beta [ * (1 + scale[b]) + shift[b] ] ) over x f32 [nb][T][C], 32 groups; C = 128, 256, 512 or 1024.
  *   ms: f32 [nb][32][ceil(T / (65536 / C))][3] chunk statistics (count, mean, M2); stats != 0: computed from x by this call first, else read as the caller left them.
  *   scale / shift: null or f32 rows ss_stride apart per batch element (0: shared).  row_idx: null (Tout == T) or device int [Tout] into [0, T).
@@ -780,6 +782,26 @@ typedef struct {
 	int stats, form;
 } ttk_gn_desc;
 int ttk_gn_apply(int dtype, const ttk_gn_desc* d, void* stream);
+
+/* ------------------------------------------------------------------ the LayerNorm kernel on caller-provided operands
+ * No reference counterpart: exposed so both instantiations of csrc/norm.hip's k_layernorm (d <= 1024 and d <= 4096) can be tested against a float64 LayerNorm of
+ * the same operands, element by element (tests/test_gpu_norm_forms.py with tests/norm_ref.py).
+ * out[r] = LN(x[r]; g1, b1), then optionally LN(.; g2, b2) on top, over rows r < rows of x f32 [rows][ldx], d columns each, eps 1e-5.
+ *   out: out_f32 ? f32 : dtype (TTK_F32, TTK_BF16 or TTK_F16); row-major [rows][ldo], or (frag != 0) the skinny GEMV's A-fragment order
+ *   [ceil(rows / 16)][d / 32][64][8] (ldo unused; rows >= `rows` of the last tile are not written).
+ *   out2: null or f32 [rows][d], a second, row-major copy of the result.  out2_idx: null or device int64[1]: the copy goes to out2 + out2_idx[0] * out2_stride
+ *   (a ring slot, out2_stride in floats).  out2_base: null or device int64[1] holding the address that replaces out2 (read at launch time on the device).
+ *   d % 4 == 0 and 4 <= d <= 4096 (frag: d % 32 == 0); ldx >= d, ldx % 4 == 0; ldo >= d; x, g1, b1, g2, b2 and out2 16-byte aligned; out2_stride % 4 == 0.
+ * Returns TTK_E_ARG with a message, and launches nothing, when a precondition the kernel relies on fails. */
+typedef struct {
+	const float* x; int64_t ldx;
+	int rows, d;
+	const float* g1; const float* b1; const float* g2; const float* b2;
+	void* out; int64_t ldo;
+	int out_f32, frag;
+	float* out2; const int64_t* out2_idx; int64_t out2_stride; const int64_t* out2_base;
+} ttk_ln_desc;
+int ttk_layernorm_rows(int dtype, const ttk_ln_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ the weight-streaming decode launches on caller-provided operands
  * No reference counterpart: exposed so every launch form of csrc/skinny.hip (k_skinny) and csrc/gemv.hip (k_gemv) can be tested against a float64

@@ -1,7 +1,7 @@
 """Every launch form of GroupNorm-apply (csrc/norm.hip) through `ttk_gn_apply`: the generic kernel (form 1), the 4-row strips of k_gn_apply_c1024 (form 2) and the
 three instantiations of k_gn_apply_c1024_even (forms 3, 4, 5: up to 9, 12, 18 rows per thread).  norm.hip says of each that it does the generic kernel's arithmetic
 in the generic kernel's order: on the same input and the same statistics every form owes the generic form's BYTES.  That is all this file asserts -- exact equality
-and finiteness, no tolerance anywhere; how accurate GroupNorm is stays with the network-level oracle tests.
+and finiteness, no tolerance anywhere; how accurate the generic form is, and with it every other, is held to a float64 reference by tests/test_gpu_norm_forms.py.
 
 `out` starts as NaN with canary rows behind it, the statistics buffer as NaN in front of the statistics launch (chunks past a ragged sequence's end stay NaN: a
 kernel that uses them fails).  One process, no environment knobs."""

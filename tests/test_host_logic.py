@@ -34,6 +34,7 @@ def test_struct_layouts_match_header_sizes():
 	assert ctypes.sizeof(_lib.GemmSeg) == 32 and ctypes.sizeof(_lib.GemmDesc) == 496   # ttk_gemm_seg / ttk_gemm_desc (static_assert'ed in csrc/ttk_host.hip)
 	assert ctypes.sizeof(_lib.AttnDesc) == 96 and ctypes.sizeof(_lib.AttnDecodeDesc) == 80   # ttk_attn_desc / ttk_attn_decode_desc (static_assert'ed in csrc/ttk_host.hip)
 	assert ctypes.sizeof(_lib.GnDesc) == 144                        # ttk_gn_desc (static_assert'ed in csrc/ttk_host.hip)
+	assert ctypes.sizeof(_lib.LnDesc) == 112                        # ttk_ln_desc (static_assert'ed in csrc/ttk_host.hip)
 	assert ctypes.sizeof(_lib.GemvMatConfigC) == 16 and ctypes.sizeof(_lib.GemvDesc) == 184   # ttk_gemv_mat_config / ttk_gemv_desc (static_assert'ed in csrc/ttk_host.hip)
 	from tortoise_tts_amd.vocoder import VocConfigC
 	assert ctypes.sizeof(VocConfigC) == (2 + 8 + 8 + 2 + 4 + 12 + 2) * 4          # ttk_voc_config: 38 ints

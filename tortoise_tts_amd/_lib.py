@@ -117,6 +117,13 @@ class GnDesc(C.Structure):
 				("pf_taps", C.c_int), ("stats", C.c_int), ("form", C.c_int)]
 
 
+class LnDesc(C.Structure):
+	"""ttk_ln_desc (include/ttk.h)"""
+	_fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("rows", C.c_int), ("d", C.c_int), ("g1", C.c_void_p), ("b1", C.c_void_p), ("g2", C.c_void_p),
+				("b2", C.c_void_p), ("out", C.c_void_p), ("ldo", C.c_int64), ("out_f32", C.c_int), ("frag", C.c_int), ("out2", C.c_void_p),
+				("out2_idx", C.c_void_p), ("out2_stride", C.c_int64), ("out2_base", C.c_void_p)]
+
+
 class GemvMatConfigC(C.Structure):
 	"""ttk_gemv_mat_config (include/ttk.h)"""
 	_fields_ = [(n, C.c_int) for n in ("dtype", "layout", "N", "K")]
@@ -209,6 +216,7 @@ SYMBOLS = {
 	"ttk_attn_fwd": (_I, [_I, C.POINTER(AttnDesc), _P]),
 	"ttk_attn_decode": (_I, [_I, C.POINTER(AttnDecodeDesc), _P]),
 	"ttk_gn_apply": (_I, [_I, C.POINTER(GnDesc), _P]),
+	"ttk_layernorm_rows": (_I, [_I, C.POINTER(LnDesc), _P]),
 	"ttk_gemv_mat_create": (_I, [C.POINTER(_P), C.POINTER(GemvMatConfigC), C.POINTER(WeightView), _I]),
 	"ttk_gemv_mat_destroy": (_I, [_P]),
 	"ttk_gemv_launch": (_I, [_P, C.POINTER(GemvDesc), _P]),

@@ -4,6 +4,9 @@
 //   GroupNorm32: /root/reference/tortoise_tts/models/arch_utils.py:24-44 (32 groups, float math, eps 1e-5),
 //                used by ResBlock diffusion.py:1338-1372 and AttentionBlock arch_utils.py:163,186
 // Internal layout is channels-last [nb][T][C], so a group is (T rows) x (C/32 contiguous channels).
+// k_layernorm, k_gn_stats and the generic k_gn_apply are held to a float64 reference of the caller's operands with a derived per-element bound
+// (tests/test_gpu_norm_forms.py through ttk_layernorm_rows / ttk_gn_apply; the bound and a float32 emulation of the arithmetic below: tests/norm_ref.py);
+// the other GroupNorm-apply forms owe the generic form's bytes (tests/test_gpu_gn_forms.py).
 #include <stdint.h>
 
 #include "ttk_common.h"
@@ -16,6 +19,8 @@ namespace ttk {
 // NI = float4 slots per lane (d <= 256 * NI).  NI = 4 (d <= 1024: the decode step's ln_f + final_norm launch, one per token): the affine parameters of BOTH
 // norms are requested together with the row -- loaded where they are used they were two more dependent round trips behind the reductions (7.3 us per
 // launch in the kernel trace for 16 rows); NI = 16 keeps them at their use (64 float4 of parameters per lane would not fit the register file).
+// Both instantiations, idle and partly idle lanes (d = 64, 192, 768, 1056), ldx != d, rows % 4 != 0, the second pass over the first pass's output, fragment order
+// and the out2 / ring path run in isolation in tests/test_gpu_norm_forms.py; what the kernel takes for granted is refused by ttk_layernorm_rows (ttk_host.hip).
 template <typename OT, int NI>
 __global__ void k_layernorm(const float* x, int64_t ldx, int rows, int d, const float* g1, const float* b1,
 							const float* g2, const float* b2, OT* out, int64_t ldo, int frag, float* out2, const int64_t* out2_idx, int64_t out2_stride, const int64_t* out2_base) {
@@ -100,6 +105,7 @@ void launch_layernorm(int dt, const float* x, int64_t ldx, int rows, int d, cons
 // stats: grid (32 groups, nb, nchunks).  Each workgroup holds its (rows x cpg) chunk (<= 2048 values) in registers, computes the
 // chunk's (count, mean, M2) with an exact two-pass, and writes the triple; the consumer merges the chunk triples with Chan's
 // parallel-variance formula (k_gn_apply), so no second reduction launch and no atomics (bitwise reproducible).
+// tests/test_gpu_norm_forms.py reads the triples back: exact counts, mean and M2 inside their bounds, chunks past a ragged sequence's end untouched.
 __global__ __launch_bounds__(256) void k_gn_stats(const float* x, int T, int C, int rows_per_chunk, float* part, const int* tlen, const int* need) {
 	const int g = blockIdx.x, b = blockIdx.y, ch = blockIdx.z, cpg = C / 32;
 	if (need && !need[b]) return;             // this sequence keeps the triples the producing GEMM's epilogue wrote
@@ -150,6 +156,8 @@ void launch_gn_stats(const float* x, int nb, int T, int C, float* part, hipStrea
 // GN_PASSES rows per thread: a block's fixed cost (merging 32 groups x nchunks triples, the barrier) is paid once per strip of 256 / (C/4) * GN_PASSES
 // rows.  2 = 1088 blocks of 2 rows at T = 1088; 1, 4 and 8 (8 = 272 blocks of 8 rows) were tried against it with tests/diag/ddim_ab.py and lost, and with few
 // rows in all (short clips, the latent conditioner) the small strips keep the launch spread over the chip.
+// This form is the one held to float64 (tests/test_gpu_norm_forms.py: C = 128 .. 1024, 1 .. 64 chunks, tlen, row_idx, every output kind); the C = 1024 kernels below
+// are tied to its bytes.
 template <typename OT>
 __global__ __launch_bounds__(256) void k_gn_apply(GnApplyParams p) {
 	constexpr int GN_PASSES = 2;

@@ -313,6 +313,33 @@ extern "C" int ttk_gn_apply(int dtype, const ttk_gn_desc* d, void* stream) {
 	return TTK_OK;
 }
 
+// LayerNorm on caller-provided operands (include/ttk.h): the descriptor is launch_layernorm's argument list, the launch is launch_layernorm.  Everything
+// k_layernorm takes for granted is checked here: float4 loads of x and the affine vectors and float4 stores to out2 (16-byte alignment, d, ldx and the ring stride
+// multiples of 4), 4 / 16 float4 slots per lane (d <= 4096), whole 32-column k-steps in fragment order, rows that do not overlap.
+static_assert(sizeof(ttk_ln_desc) == 112, "ttk_ln_desc layout (tortoise_tts_amd/_lib.py mirrors it)");
+extern "C" int ttk_layernorm_rows(int dtype, const ttk_ln_desc* d, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_layernorm_rows: null descriptor");
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16 || dtype == TTK_F16, TTK_E_ARG, "ttk_layernorm_rows: dtype must be TTK_F32, TTK_BF16 or TTK_F16, got %d", dtype);
+	TTK_REQUIRE(d->x && d->g1 && d->b1 && d->out, TTK_E_ARG, "ttk_layernorm_rows: null x, g1, b1 or out");
+	TTK_REQUIRE(!d->g2 == !d->b2, TTK_E_ARG, "ttk_layernorm_rows: g2 and b2 come together");
+	TTK_REQUIRE(d->rows >= 1, TTK_E_ARG, "ttk_layernorm_rows: need rows >= 1, got %d", d->rows);
+	TTK_REQUIRE(d->d >= 4 && d->d % 4 == 0 && d->d <= 4096, TTK_E_ARG, "ttk_layernorm_rows: d must be a multiple of 4 in 4 .. 4096 (one wave holds a row), got %d", d->d);
+	TTK_REQUIRE(!d->frag || d->d % 32 == 0, TTK_E_ARG, "ttk_layernorm_rows: frag needs d %% 32 == 0 (whole k-steps), got %d", d->d);
+	TTK_REQUIRE(d->ldx >= d->d && d->ldx % 4 == 0, TTK_E_ARG, "ttk_layernorm_rows: ldx must be >= d and %% 4 == 0, got %lld", (long long)d->ldx);
+	TTK_REQUIRE(d->frag || d->ldo >= d->d, TTK_E_ARG, "ttk_layernorm_rows: ldo < d (row-major output)");
+	for (const void* q : {(const void*)d->x, (const void*)d->g1, (const void*)d->b1, (const void*)d->g2, (const void*)d->b2, (const void*)d->out2})
+		TTK_REQUIRE(((uintptr_t)q & 15) == 0, TTK_E_ARG, "ttk_layernorm_rows: x, g1, b1, g2, b2 and out2 must be 16-byte aligned");
+	TTK_REQUIRE(((uintptr_t)d->out & ((d->out_f32 || dtype == TTK_F32) ? 3 : 1)) == 0, TTK_E_ARG, "ttk_layernorm_rows: out is misaligned for its element type");
+	TTK_REQUIRE(((uintptr_t)d->out2_idx & 7) == 0 && ((uintptr_t)d->out2_base & 7) == 0, TTK_E_ARG, "ttk_layernorm_rows: out2_idx and out2_base must be 8-byte aligned");
+	TTK_REQUIRE(!d->out2_idx || d->out2 || d->out2_base, TTK_E_ARG, "ttk_layernorm_rows: out2_idx without out2 or out2_base: a ring slot of nothing");
+	TTK_REQUIRE(d->out2_stride >= 0 && d->out2_stride % 4 == 0, TTK_E_ARG, "ttk_layernorm_rows: out2_stride must be >= 0 and %% 4 == 0, got %lld", (long long)d->out2_stride);
+	launch_layernorm(dtype, d->x, d->ldx, d->rows, d->d, d->g1, d->b1, d->g2, d->b2, d->out, d->ldo, d->out_f32 ? 1 : 0, (hipStream_t)stream, d->frag ? 1 : 0,
+					 d->out2, d->out2_idx, d->out2_stride, d->out2_base);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
 extern "C" int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream) {
 	using namespace ttk;
 	TTK_REQUIRE(d, TTK_E_ARG, "ttk_attn_decode: null descriptor");
