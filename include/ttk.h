@@ -803,6 +803,44 @@ typedef struct {
 } ttk_ln_desc;
 int ttk_layernorm_rows(int dtype, const ttk_ln_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ the vocoders' own kernels on caller-provided operands
+ * No reference counterpart: exposed so the location-variable convolution (csrc/univnet.hip: k_lvc, k_lvc_mfma), the narrow-channel MFMA convolution with its
+ * weight packing (csrc/hifigan.hip: k_hifi_conv_mfma, k_hifi_pack_frag) and the anti-aliased snake activation (csrc/voc.hip: k_snake_aa) can be held, element by
+ * element, to a float64 reference of the same operands (tests/test_gpu_voc_forms.py with tests/voc_ref.py).  Each goes through the launcher its handle uses.
+ * All three return TTK_E_ARG with a message, and launch nothing, when a precondition the kernel relies on fails.
+ *
+ * ttk_lvc_rows: one LVC layer with its gated update over B sequences of L rows, CG = 16 or 32 channels, dtype TTK_F32 | TTK_BF16 (T):
+ *     o[t][n] = kbias[f][layer][n] + sum_i sum_k lrelu_0.2(y)[t + k - 1][i] kern[f][layer][i][n][k],   f = t / hop, rows outside [0, L) of a sequence zero
+ *     x[t][c] += sigmoid(o[t][c]) tanh(o[t][c + CG]);   at[t][c] = T(lrelu_0.2(x[t][c]))
+ *   y f32 [B * L][CG]; kern T [B * Tc][kstride], kstride = n_layers * CG * 2 CG * 3; kbias f32 [B * Tc][bstride], bstride = n_layers * 2 CG; x f32 [B * L][CG],
+ *   updated in place; at T [B * L][lda] (columns CG .. lda are not written).  1 <= hop, ceil(L / hop) <= Tc, 0 <= layer < n_layers <= 4, lda >= CG, B <= 65535;
+ *   x and at overlap neither each other nor an input.  TTK_BF16 with CG = 32 runs k_lvc_mfma (which rounds lrelu(y) to bf16), everything else k_lvc.          */
+typedef struct {
+	const float* y; const void* kern; const float* kbias;
+	float* x; void* at;
+	int B, L, CG, hop, Tc, layer, n_layers, lda;
+} ttk_lvc_desc;
+int ttk_lvc_rows(int dtype, const ttk_lvc_desc* d, void* stream);
+/* ttk_hifi_conv_rows: one 'same' dilated Conv1d C -> C (C = 32 or 64, bf16 operands, f32 accumulation) over one sequence of L rows with its fused epilogue:
+ *     v[t][n] = bias[n] + sum_k sum_i a[t + (k - (K - 1) / 2) dil][i] bf16(w[n][i][k])      rows outside [0, L) zero
+ *     mode 0: at_out = bf16(lrelu_0.1(v));   1: xout = v + xres, at_out = bf16(lrelu_0.1(xout));   2: mrf = v + xres;   3: mrf += v + xres
+ *   a bf16 [L][lda], lda >= C, lda % 8 == 0, 16-byte aligned; w f32 [C][C][k] (Conv1d's layout, on the device; packed by this call the way ttk_hifigan_create
+ *   packs it: to bf16 [k][Npad][Kpad], then to B-fragment order), bias f32 [C]; k odd in 1..11, dil >= 1, and the weights plus the 256-row window with its halo
+ *   within 160 KiB of LDS.  xres, xout, mrf f32 [L][C], at_out bf16 [L][ldo] (ldo >= C; columns C .. ldo are not written): each is required in the modes that read
+ *   or write it and ignored in the others.  xres == xout is allowed; at_out, xout and mrf must not overlap a, xout and mrf must not overlap xres otherwise.
+ *   The call synchronises `stream` and frees the packed weights before it returns.                                                                         */
+typedef struct {
+	const void* a; int lda;
+	const float* w; const float* bias;
+	int L, C, k, dil, mode;
+	const float* xres; float* xout; void* at_out; int ldo; float* mrf;
+} ttk_hifi_conv_desc;
+int ttk_hifi_conv_rows(const ttk_hifi_conv_desc* d, void* stream);
+/* ttk_snake_rows: Activation1d with SnakeBeta over x f32 [B * L][C] -> y T [B * L][C] (dtype TTK_F32 | TTK_BF16): 2x up-sampling with the 12-tap low-pass filt12
+ * (replicate padding, gain 2), z = up + invb sin(up a)^2, low-pass and decimation by 2 (replicate padding).  a, invb f32 [C] as the kernel reads them (already
+ * exponentiated; invb = 1 / (b + 1e-9)), filt12 f32 [12].  C % 4 == 0, x, a, invb 16-byte aligned, x and y do not overlap.                               */
+int ttk_snake_rows(int dtype, const float* x, int B, int L, int C, const float* a, const float* invb, const float* filt12, void* y, void* stream);
+
 /* ------------------------------------------------------------------ the weight-streaming decode launches on caller-provided operands
  * No reference counterpart: exposed so every launch form of csrc/skinny.hip (k_skinny) and csrc/gemv.hip (k_gemv) can be tested against a float64
  * LN(x) W^T + b of the same operands, element by element (tests/test_gpu_skinny_forms.py).

@@ -124,6 +124,18 @@ class LnDesc(C.Structure):
 				("out2_idx", C.c_void_p), ("out2_stride", C.c_int64), ("out2_base", C.c_void_p)]
 
 
+class LvcDesc(C.Structure):
+	"""ttk_lvc_desc (include/ttk.h)"""
+	_fields_ = [("y", C.c_void_p), ("kern", C.c_void_p), ("kbias", C.c_void_p), ("x", C.c_void_p), ("at", C.c_void_p)] + \
+			   [(n, C.c_int) for n in ("B", "L", "CG", "hop", "Tc", "layer", "n_layers", "lda")]
+
+
+class HifiConvDesc(C.Structure):
+	"""ttk_hifi_conv_desc (include/ttk.h)"""
+	_fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("L", C.c_int), ("C", C.c_int), ("k", C.c_int), ("dil", C.c_int),
+				("mode", C.c_int), ("xres", C.c_void_p), ("xout", C.c_void_p), ("at_out", C.c_void_p), ("ldo", C.c_int), ("mrf", C.c_void_p)]
+
+
 class GemvMatConfigC(C.Structure):
 	"""ttk_gemv_mat_config (include/ttk.h)"""
 	_fields_ = [(n, C.c_int) for n in ("dtype", "layout", "N", "K")]
@@ -217,6 +229,9 @@ SYMBOLS = {
 	"ttk_attn_decode": (_I, [_I, C.POINTER(AttnDecodeDesc), _P]),
 	"ttk_gn_apply": (_I, [_I, C.POINTER(GnDesc), _P]),
 	"ttk_layernorm_rows": (_I, [_I, C.POINTER(LnDesc), _P]),
+	"ttk_lvc_rows": (_I, [_I, C.POINTER(LvcDesc), _P]),
+	"ttk_hifi_conv_rows": (_I, [C.POINTER(HifiConvDesc), _P]),
+	"ttk_snake_rows": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 	"ttk_gemv_mat_create": (_I, [C.POINTER(_P), C.POINTER(GemvMatConfigC), C.POINTER(WeightView), _I]),
 	"ttk_gemv_mat_destroy": (_I, [_P]),
 	"ttk_gemv_launch": (_I, [_P, C.POINTER(GemvDesc), _P]),

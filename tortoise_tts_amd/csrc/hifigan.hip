@@ -156,6 +156,8 @@ enum { HM_ACT = 0, HM_RES = 1, HM_MRF_SET = 2, HM_MRF_ADD = 3 };
 
 // See the file header.  a bf16 [L][lda] (the operand copy), wfrag from k_hifi_pack_frag, grid ceil(L / 256), 256 threads,
 // dynamic LDS = k C C * 2 + (256 + (k - 1) dil) * (C + 8) * 2 bytes.  xres may alias xout; at_out must not alias a.
+// Packing, both widths and every mode run in isolation against a float64 convolution with a per-element bound in tests/test_gpu_voc_forms.py (through
+// ttk_hifi_conv_rows below; the bound and a replica of the fragment order and the tiling: tests/voc_ref.py).
 template <int C>
 __global__ __launch_bounds__(256) void k_hifi_conv_mfma(const bf16* __restrict__ a, int lda, const bf16* __restrict__ wfrag, const float* __restrict__ bias,
 														int L, int k, int dil, int mode, const float* xres, float* xout, bf16* at_out, int ldo, float* mrf) {
@@ -452,6 +454,54 @@ int ttk_hifigan_inference(ttk_hifigan* h, const float* latents, int n, float* au
 	}
 	hipLaunchKernelGGL(k_hifi_post, dim3(grid_for(L)), dim3(256), (size_t)7 * ch * 4, s, y, L, ch, h->post_w, h->post_b, audio);
 	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+// One k_hifi_conv_mfma launch on caller-provided operands (include/ttk.h).  The weights take the handle's route -- upload_mat with PK_CONVK, then pack_frag --
+// into an arena of this call's own, freed after the stream has been synchronised; what the kernel takes for granted is refused before anything is allocated.
+int ttk_hifi_conv_rows(const ttk_hifi_conv_desc* d, void* stream) {
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_hifi_conv_rows: null descriptor");
+	TTK_REQUIRE(d->a && d->w && d->bias, TTK_E_ARG, "ttk_hifi_conv_rows: null argument (a, w and bias are required)");
+	TTK_REQUIRE(d->C == 32 || d->C == 64, TTK_E_ARG, "ttk_hifi_conv_rows: C = %d has no instantiation (32 or 64)", d->C);
+	TTK_REQUIRE(d->k >= 1 && d->k <= 11 && d->k % 2 == 1, TTK_E_ARG, "ttk_hifi_conv_rows: kernel size %d unsupported (odd, 1..11)", d->k);
+	TTK_REQUIRE(d->dil >= 1 && d->dil <= 4096, TTK_E_ARG, "ttk_hifi_conv_rows: dilation %d unsupported (1..4096)", d->dil);
+	TTK_REQUIRE(narrow_lds(d->C, d->k, d->dil) <= (size_t)kLdsMax, TTK_E_ARG, "ttk_hifi_conv_rows: C = %d, k = %d, dilation %d need %zu bytes of LDS (at most %d)", d->C,
+				d->k, d->dil, narrow_lds(d->C, d->k, d->dil), kLdsMax);
+	TTK_REQUIRE(d->L >= 1 && d->L <= (1 << 24), TTK_E_ARG, "ttk_hifi_conv_rows: L = %d out of range (1..2^24)", d->L);
+	TTK_REQUIRE(d->lda >= d->C && d->lda % 8 == 0, TTK_E_ARG, "ttk_hifi_conv_rows: lda must be >= C and a multiple of 8 (lda %d, C %d)", d->lda, d->C);
+	TTK_REQUIRE(((uintptr_t)d->a & 15) == 0, TTK_E_ARG, "ttk_hifi_conv_rows: a must be 16-byte aligned");
+	TTK_REQUIRE(d->mode >= HM_ACT && d->mode <= HM_MRF_ADD, TTK_E_ARG, "ttk_hifi_conv_rows: mode %d unknown (0..3)", d->mode);
+	const bool mrf_mode = d->mode == HM_MRF_SET || d->mode == HM_MRF_ADD;
+	TTK_REQUIRE(d->mode == HM_ACT || d->xres, TTK_E_ARG, "ttk_hifi_conv_rows: mode %d needs xres", d->mode);
+	TTK_REQUIRE(d->mode != HM_RES || d->xout, TTK_E_ARG, "ttk_hifi_conv_rows: mode 1 needs xout");
+	TTK_REQUIRE(mrf_mode || d->at_out, TTK_E_ARG, "ttk_hifi_conv_rows: mode %d needs at_out", d->mode);
+	TTK_REQUIRE(!mrf_mode || d->mrf, TTK_E_ARG, "ttk_hifi_conv_rows: mode %d needs mrf", d->mode);
+	TTK_REQUIRE(mrf_mode || d->ldo >= d->C, TTK_E_ARG, "ttk_hifi_conv_rows: ldo < C (%d < %d)", d->ldo, d->C);
+	TTK_REQUIRE(((uintptr_t)d->w & 3) == 0 && ((uintptr_t)d->bias & 3) == 0 && ((uintptr_t)d->xres & 3) == 0 && ((uintptr_t)d->xout & 3) == 0 &&
+				((uintptr_t)d->mrf & 3) == 0 && ((uintptr_t)d->at_out & 1) == 0, TTK_E_ARG, "ttk_hifi_conv_rows: a buffer is misaligned for its element type");
+	const size_t ab = (size_t)d->L * d->lda * 2, xb = (size_t)d->L * d->C * 4, ob = (size_t)d->L * (mrf_mode ? 0 : d->ldo) * 2;
+	auto overlap = [](const void* p, size_t n, const void* q, size_t m) { return (const char*)p < (const char*)q + m && (const char*)q < (const char*)p + n; };
+	TTK_REQUIRE(mrf_mode || !overlap(d->at_out, ob, d->a, ab), TTK_E_ARG, "ttk_hifi_conv_rows: at_out overlaps a (a workgroup reads its neighbours' rows of a)");
+	TTK_REQUIRE(d->mode != HM_RES || !overlap(d->xout, xb, d->a, ab), TTK_E_ARG, "ttk_hifi_conv_rows: xout overlaps a");
+	TTK_REQUIRE(!mrf_mode || !overlap(d->mrf, xb, d->a, ab), TTK_E_ARG, "ttk_hifi_conv_rows: mrf overlaps a");
+	TTK_REQUIRE(d->mode != HM_RES || d->xout == d->xres || !overlap(d->xout, xb, d->xres, xb), TTK_E_ARG,
+				"ttk_hifi_conv_rows: xout overlaps xres without being xres (only the element-for-element update is allowed)");
+	TTK_REQUIRE(!mrf_mode || !overlap(d->mrf, xb, d->xres, xb), TTK_E_ARG, "ttk_hifi_conv_rows: mrf overlaps xres");
+	TTK_REQUIRE(d->mode != HM_RES || (!overlap(d->at_out, ob, d->xout, xb) && !overlap(d->at_out, ob, d->xres, xb)), TTK_E_ARG,
+				"ttk_hifi_conv_rows: at_out overlaps xres or xout");
+	hipStream_t s = (hipStream_t)stream;
+	Arena arena;
+	ttk_weight_view view = {};
+	view.name = "weight"; view.data = d->w; view.ndim = 3; view.shape[0] = d->C; view.shape[1] = d->C; view.shape[2] = d->k;
+	WeightMap wm(&view, 1);
+	Mat m;
+	bf16* frag = nullptr;
+	TTK_TRY(upload_mat(arena, wm, DT_BF16, "weight", "", PK_CONVK, d->C, d->C, false, &m, d->k));
+	TTK_TRY(pack_frag(arena, m, d->C, d->k, &frag));
+	launch_narrow(d->C, d->a, d->lda, frag, d->bias, d->L, d->k, d->dil, d->mode, d->xres, d->xout, d->at_out, d->ldo, d->mrf, s);
+	const hipError_t e = hipGetLastError();
+	TTK_HIP(hipStreamSynchronize(s));       // the launch reads `frag`: the arena goes only after it
+	TTK_HIP(e);
 	return TTK_OK;
 }
 

@@ -85,7 +85,8 @@ __global__ void k_act_rows(ActRows p) {
 //   o[t][n]  = bias[l][n] + sum_i sum_k lrelu(y)[t + k - 1][i] * kern[l][layer][i][n][k],   l = t / hop,  rows outside [0, L) zero
 //   x[t][c] += sigmoid(o[t][c]) * tanh(o[t][c + CG]);   at[t][c] = T(lrelu(x[t][c]))
 // y f32 [B * L][CG] (the dilated conv's output before its LeakyReLU), kern T [B * Tc][kstride], kbias f32 [B * Tc][bstride].
-// Grid (ceil(L / 64), B), 256 threads.  See the file header for the tiling.
+// Grid (ceil(L / 64), B), 256 threads.  See the file header for the tiling.  Both kernels run in isolation, against a float64 reference of this definition with a
+// per-element bound, in tests/test_gpu_voc_forms.py (through ttk_lvc_rows below; the bound and a replica of the indexing: tests/voc_ref.py).
 template <typename T, int CG>
 __global__ __launch_bounds__(256) void k_lvc(const float* __restrict__ y, const T* __restrict__ kern, const float* __restrict__ kbias, float* x, T* at,
 											 int L, int hop, int Tc, int layer, int kstride, int bstride, int lda) {
@@ -375,6 +376,37 @@ int ttk_univnet_inference(ttk_univnet* h, const float* mel, const float* z, int 
 	launch_act(dt, act_cl(x, (int64_t)L * C, C, B, L, C, 1, 3, at, lda), s);
 	conv_valid(dt, at, lda, h->conv_post, 7, B * (L + 6), L + 6, y, s);
 	hipLaunchKernelGGL(k_tanh_out<>, tanh_out_grid(B, Tm * hop), dim3(256), 0, s, y, B, L + 6, Tm * hop, audio);   // conv_post's Tanh, inference :312-313
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+// One LVC launch on caller-provided operands (include/ttk.h), through launch_lvc_t: what k_lvc / k_lvc_mfma take for granted is refused here.
+int ttk_lvc_rows(int dtype, const ttk_lvc_desc* d, void* stream) {
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_lvc_rows: null descriptor");
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16, TTK_E_ARG, "ttk_lvc_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(d->y && d->kern && d->kbias && d->x && d->at, TTK_E_ARG, "ttk_lvc_rows: null argument (y, kern, kbias, x and at are all required)");
+	TTK_REQUIRE(d->CG == 16 || d->CG == 32, TTK_E_ARG, "ttk_lvc_rows: CG = %d has no instantiation (16 or 32)", d->CG);
+	TTK_REQUIRE(d->B >= 1 && d->B <= 65535 && d->L >= 1 && d->L <= (1 << 30), TTK_E_ARG, "ttk_lvc_rows: B = %d, L = %d out of range (B 1..65535, L 1..2^30)", d->B, d->L);
+	TTK_REQUIRE(d->hop >= 1, TTK_E_ARG, "ttk_lvc_rows: hop = %d (must be >= 1)", d->hop);
+	TTK_REQUIRE(d->Tc >= 1 && (d->L + d->hop - 1) / d->hop <= d->Tc, TTK_E_ARG, "ttk_lvc_rows: L = %d rows at hop %d need %d frames, Tc = %d", d->L, d->hop,
+				(d->L + d->hop - 1) / d->hop, d->Tc);
+	TTK_REQUIRE(d->n_layers >= 1 && d->n_layers <= 4 && d->layer >= 0 && d->layer < d->n_layers, TTK_E_ARG,
+				"ttk_lvc_rows: layer %d of n_layers %d out of range (0 <= layer < n_layers <= 4)", d->layer, d->n_layers);
+	TTK_REQUIRE(d->lda >= d->CG, TTK_E_ARG, "ttk_lvc_rows: lda < CG (%d < %d)", d->lda, d->CG);
+	const size_t es = dtype == TTK_BF16 ? 2 : 4;
+	TTK_REQUIRE(((uintptr_t)d->y & 3) == 0 && ((uintptr_t)d->kbias & 3) == 0 && ((uintptr_t)d->x & 3) == 0 && ((uintptr_t)d->kern & (es - 1)) == 0 &&
+				((uintptr_t)d->at & (es - 1)) == 0, TTK_E_ARG, "ttk_lvc_rows: a buffer is misaligned for its element type");
+	const int kstride = d->n_layers * d->CG * 2 * d->CG * 3, bstride = d->n_layers * 2 * d->CG;
+	const size_t rows = (size_t)d->B * d->L, frames = (size_t)d->B * d->Tc;
+	const size_t xb = rows * d->CG * 4, atb = rows * d->lda * es;
+	auto overlap = [](const void* p, size_t n, const void* q, size_t m) { return (const char*)p < (const char*)q + m && (const char*)q < (const char*)p + n; };
+	TTK_REQUIRE(!overlap(d->x, xb, d->y, xb) && !overlap(d->x, xb, d->kern, frames * kstride * es) && !overlap(d->x, xb, d->kbias, frames * bstride * 4), TTK_E_ARG,
+				"ttk_lvc_rows: x overlaps an input (a workgroup reads its neighbours' rows of y while x is updated)");
+	TTK_REQUIRE(!overlap(d->at, atb, d->y, xb) && !overlap(d->at, atb, d->x, xb) && !overlap(d->at, atb, d->kern, frames * kstride * es) &&
+				!overlap(d->at, atb, d->kbias, frames * bstride * 4), TTK_E_ARG, "ttk_lvc_rows: at overlaps another operand");
+	by_f32_bf16(dtype == TTK_BF16 ? DT_BF16 : DT_F32, [&](auto t) {
+		launch_lvc_t<decltype(t)>(d->CG, d->y, d->kern, d->kbias, d->x, d->at, d->B, d->L, d->hop, d->Tc, d->layer, kstride, bstride, d->lda, (hipStream_t)stream);
+	});
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

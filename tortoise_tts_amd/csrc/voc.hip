@@ -48,6 +48,8 @@ template <> __device__ __forceinline__ float snake_sin<bf16>(float x) { return _
 //   z[s]   = up[s] + inv_b * sin(up[s] * a)^2
 //   y[t]   = sum_k z[clamp(2t + k - 5, 0, 2L - 1)] * g[k]
 // (the zero-stuffed transposed convolution of UpSample1d written per output phase; clamps are the two replicate paddings)
+// Both forms run in isolation at L = 1 .. 70 against a float64 reference of this definition with a per-element bound in tests/test_gpu_voc_forms.py (through
+// ttk_snake_rows below; the bound, with the measured error of __sinf, and a replica of the register indexing: tests/voc_ref.py).
 template <typename T>
 __global__ __launch_bounds__(256) void k_snake_aa(const float* x, int L, int C, const float* a_, const float* invb_, const float* g_, T* y, int64_t rows) {
 	const int c4 = C / 4;
@@ -278,6 +280,26 @@ int ttk_voc_inference(ttk_voc* h, const float* mel, int B, int Tm, float* audio,
 	launch_snake(dt, y, L, ch, h->act_post, h->filt, at, M, s);
 	conv_same(dt, at, ch, h->conv_post, 7, 1, M, L, nullptr, hb, 1, s);                  // [M][1] f32
 	hipLaunchKernelGGL(k_tanh_out<>, tanh_out_grid(B, Tm * hop), dim3(256), 0, s, hb, B, L, Tm * hop, audio);      // forward :507-508, inference :531-533
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+// One k_snake_aa launch on caller-provided operands (include/ttk.h), through launch_snake: what the kernel takes for granted is refused here.
+int ttk_snake_rows(int dtype, const float* x, int B, int L, int C, const float* a, const float* invb, const float* filt12, void* y, void* stream) {
+	TTK_REQUIRE(dtype == TTK_F32 || dtype == TTK_BF16, TTK_E_ARG, "ttk_snake_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(x && a && invb && filt12 && y, TTK_E_ARG, "ttk_snake_rows: null argument");
+	TTK_REQUIRE(B >= 1 && L >= 1 && (int64_t)B * L <= ((int64_t)1 << 30), TTK_E_ARG, "ttk_snake_rows: B = %d, L = %d out of range (B, L >= 1, B * L <= 2^30)", B, L);
+	TTK_REQUIRE(C >= 4 && C % 4 == 0 && C <= 8192, TTK_E_ARG, "ttk_snake_rows: C = %d unsupported (a multiple of 4, 4..8192: a thread owns four channels)", C);
+	TTK_REQUIRE((int64_t)B * L * C <= ((int64_t)1 << 32), TTK_E_ARG, "ttk_snake_rows: %d x %d x %d elements are too many for one launch", B, L, C);
+	TTK_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)invb & 15) == 0, TTK_E_ARG, "ttk_snake_rows: x, a and invb must be 16-byte aligned");
+	const size_t es = dtype == TTK_BF16 ? 2 : 4;
+	TTK_REQUIRE(((uintptr_t)filt12 & 3) == 0 && ((uintptr_t)y & (es - 1)) == 0, TTK_E_ARG, "ttk_snake_rows: filt12 or y is misaligned for its element type");
+	const size_t n = (size_t)B * L * C;
+	TTK_REQUIRE(!((const char*)x < (const char*)y + n * es && (const char*)y < (const char*)x + n * 4), TTK_E_ARG,
+				"ttk_snake_rows: x and y overlap (a thread reads 13 rows of x)");
+	Snake sn;
+	sn.a = const_cast<float*>(a); sn.invb = const_cast<float*>(invb);
+	launch_snake(dtype == TTK_BF16 ? DT_BF16 : DT_F32, x, L, C, sn, filt12, y, (int64_t)B * L, (hipStream_t)stream);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
