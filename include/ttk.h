@@ -260,6 +260,14 @@ int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* te
  * ttk_ar_prefill_lines.                                                                                                                  */
 int ttk_ar_reorder_cache(ttk_ar* h, const int64_t* beam_idx, void* stream);
 
+/* The same gather for a batch of lines, each searched by rows_per_line beams (ttk_beam_step_lines): valid only after ttk_ar_prefill_lines with that
+ * rows_per_line (TTK_E_STATE otherwise).  beam_idx = device int64 [B], global over the batch: entry g * rows_per_line + b holds g * rows_per_line + source
+ * beam.  Rows [d_pos[1], d_pos[0]) of all B slices move; in lines mode d_pos[1] is the length of the longest prefix: every line's right-aligned prefix lies
+ * below it, in the slice of the line's first candidate, and never moves.  An entry outside its own line's range
+ * [g * rows_per_line, (g + 1) * rows_per_line) moves nothing, as an out-of-range entry of ttk_ar_reorder_cache does; an identity beam_idx returns before the
+ * first load.  B <= 16.                                                                                                                     */
+int ttk_ar_reorder_cache_lines(ttk_ar* h, const int64_t* beam_idx, int rows_per_line, void* stream);
+
 /* One step of `_beam_search` for one text line, steps b to g (HF:generation/utils.py:3386-3508), batch_size 1, early_stopping False,
  * pad = eos = stop_token.  With c = col[0] tokens generated so far:
  *   b. per beam row: log_softmax(logits) (:3388), then the processors and warpers ON THE LOG-PROBS in HF's order (:3389; the semantics of
@@ -298,6 +306,19 @@ typedef struct {
 	int* all_done;                            /* optional */
 } ttk_beam_args;
 int ttk_beam_step(const ttk_beam_args* a, void* stream);
+
+/* The same step for n_lines text lines searched together as one decode batch, n_lines >= 1 and n_lines * num_beams <= 16 rows (no reference counterpart:
+ * the reference searches line by line).  The same struct; every state array has a leading [n_lines] dimension: logits has n_lines * num_beams rows
+ * (line g's beams are rows g * num_beams ...), q is [n_lines][num_beams * V] (ttk_ar_set_noise with rng_args[5] = num_beams gives every line the flat tensor
+ * of its own call), col [n_lines][num_beams], seqs [n_lines][2][2][num_beams][L], scores [n_lines][2][num_beams], state [n_lines][2 * num_beams + 2],
+ * acc [n_lines][num_beams * V], work [n_lines][4 * num_beams^2 + 2 * num_beams + 1], tok and beam_idx [n_lines * num_beams].  Workgroup x serves line
+ * x / num_beams with that line's slices; the last workgroup of a line to arrive does that line's bookkeeping; lines read none of each other's words, so
+ * every line's state is bit for bit what ttk_beam_step leaves on that line alone -- with two differences.  beam_idx is global: entry g * num_beams + b holds
+ * g * num_beams + source beam, what ttk_ar_reorder_cache_lines takes.  And the step that ends line g's search (its count goes to that line's
+ * state[2 * num_beams + 1]) writes stop_token to the line's tok rows and the identity to its beam_idx rows: the decode and the reorder go on for the other
+ * lines, every later step returns at entry for this one.  *all_done (optional) is written, non-zero, by the step that ends the last unfinished line.
+ * Two launches; capturable.                                                                                                                  */
+int ttk_beam_step_lines(const ttk_beam_args* a, int n_lines, void* stream);
 
 /* hipGraphLaunch of an instantiated graph the caller captured around libttk launches (torch.cuda.CUDAGraph.raw_cuda_graph_exec()): the
  * token step replayed without torch.cuda.CUDAGraph.replay()'s prologue, which fills the generator's seed / offset tensors -- two launches per

@@ -179,6 +179,8 @@ SYMBOLS = {
 	"ttk_greedy_step": (_I, [C.POINTER(SampleArgs), _P]),
 	"ttk_ar_reorder_cache": (_I, [_P, _P, _P]),
 	"ttk_beam_step": (_I, [C.POINTER(BeamArgs), _P]),
+	"ttk_ar_reorder_cache_lines": (_I, [_P, _P, _I, _P]),
+	"ttk_beam_step_lines": (_I, [C.POINTER(BeamArgs), _I, _P]),
 	"ttk_sample_step_warped": (_I, [C.POINTER(SampleArgs), _P]),
 	"ttk_sample_step_ext": (_I, [C.POINTER(SampleArgs), C.POINTER(SampleExt), _P]),
 	"ttk_ar_sample_next_ext": (_I, [_P, C.POINTER(SampleArgs), C.POINTER(SampleExt), _P]),

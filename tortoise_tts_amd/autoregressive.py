@@ -22,9 +22,10 @@ What runs where
     ttk_ar_sample_next's place only when one of them is on; same loop, same captured step, same noise per token).
   * beam search (num_beams > 1) ..................................... libttk  (csrc/beam.hip: the beam step -- log-softmax, warpers, the
     multinomial without replacement over num_beams * V, HF's running / finished bookkeeping -- and the in-place KV-cache reorder); the loop
-    here enqueues {beam step, reorder, decode} per token and polls the done word.
+    here enqueues {beam step, reorder, decode} per token and polls the done word; `beam_search_lines` does so for several lines as one decode batch
+    (ttk_beam_step_lines, ttk_ar_reorder_cache_lines: a search state per line, lines x beams <= 16 rows).
 
-How the host layer is laid out: four drivers -- `_generate` (+ `_token_loop`), `_generate_lines`, `_beam_generate`, `_loop_stream` -- differ in their loop and
+How the host layer is laid out: five drivers -- `_generate` (+ `_token_loop`), `_generate_lines`, `_beam_generate`, `beam_search_lines`, `_loop_stream` -- differ in their loop and
 in how they account for the torch generator; what they share is written once:
   * `_session` ........ one generation on the handle: refusal while a stream is open, device guard, reseed, state reset, noise armed; disarmed again
                         however the body ends, health flags read
@@ -391,7 +392,7 @@ class UnifiedVoice(_lib.Handle):
 		a caller that draws per line afterwards (TTSHotPath.inference_lines) re-positions it with `position_rng_after_line(g)`.
 		do_sample false or omitted: greedy search as in `inference_speech`, one row per line (num_return_sequences must be 1, up to max_batch lines)."""
 		if hf_generate_kwargs.get("num_beams", 1) not in (None, 1):
-			raise NotImplementedError("beam search over a batch of lines is not implemented: call inference_speech(num_beams=N) per line")
+			raise NotImplementedError("this entry samples: beam search over a batch of lines is beam_search_lines(latent, texts, num_beams=N)")
 		greedy = not hf_generate_kwargs.get("do_sample", False)
 		if greedy and num_return_sequences != 1:
 			raise ValueError(f"greedy search (do_sample=False, num_beams=1) does not support `num_return_sequences` different than 1 (got {num_return_sequences})")
@@ -496,35 +497,13 @@ class UnifiedVoice(_lib.Handle):
 		longest returned beam and padded with the stop token (step 5, :3510-3523).  The search ends on the device (the done word of ttk_beam_step);
 		the host looks at it LAG tokens late, and the steps enqueued past the end are no-ops that draw nothing from the torch generator."""
 		self._require_idle()
-		if R > N:
-			raise ValueError(f"`num_return_sequences` ({R}) has to be smaller or equal to `num_beams` ({N}).")
-		if N > min(16, self.max_batch):
-			raise _lib.TTKError(f"{N} beams exceed min(16, max_batch={self.max_batch})")
-		top_k = kw.get("top_k", 50) or 0
-		if 0 < top_k < 2 * N:
-			raise ValueError(f"top_k={top_k} keeps fewer tokens than the 2 * num_beams = {2 * N} continuations a beam step selects; which of the removed "
-							 "(probability 0) ones torch.multinomial would pick is unspecified: use top_k=0 or top_k >= 2 * num_beams")
+		self._check_beams(N, R, kw)
 		max_new = self._max_new(text.shape[1] + 4, max_generate_length)
 		if max_new < 1:
 			raise ValueError("max_generate_length must be at least 1")
 		with self._session(kw.get("seed", 0), lambda: _BeamState(self, N, max_new, kw)) as (st, gen, off_start):
 			st.logits.copy_(self._prefill(cond, text, N))
-			n, poll = 0, _StopPoll()
-			while True:
-				st.step()
-				n += 1
-				if n >= max_new:
-					break
-				if st.own_rng:
-					ended = poll.step_complete() and int(st.done[0])
-				else:                                        # torch draws the noise: a step past the end would consume generator state
-					torch.cuda.synchronize(self.device)
-					ended = int(st.done[0])
-				if ended:
-					break
-				_lib.check(self.lib.ttk_ar_reorder_cache(self._h, st.beam_idx.data_ptr(), _lib.stream_ptr()), "ttk_ar_reorder_cache")
-				self._decode(st.tok, st.logits)
-			torch.cuda.synchronize(self.device)
+			self._beam_loop(st, max_new)
 			state = st.state.tolist()
 			steps = state[2 * N + 1]
 			if steps <= 0:
@@ -534,6 +513,99 @@ class UnifiedVoice(_lib.Handle):
 			self.last_generate = dict(steps=steps, rng_start=off_start, rng_step=(gen.get_offset() - off_start) // steps)
 			length = max(state[N:N + R])
 			return st.seqs[steps & 1, 1, :R, :length].clone()
+
+	def _beam_loop(self, st, max_new):
+		"""the token loop of a beam search, one line or several, from the prefill's logits in `st.logits` until the device reports the end of the (last) search or
+		max_new steps are enqueued; returns when the device has finished"""
+		n, poll = 0, _StopPoll()
+		while True:
+			st.step()
+			n += 1
+			if n >= max_new:
+				break
+			if st.own_rng:
+				ended = poll.step_complete() and int(st.done[0])
+			else:                                        # torch draws the noise: a step past the end would consume generator state
+				torch.cuda.synchronize(self.device)
+				ended = int(st.done[0])
+			if ended:
+				break
+			st.reorder_cache()
+			self._decode(st.tok, st.logits)
+		torch.cuda.synchronize(self.device)
+
+	def _check_beams(self, N, R, kw, G=1):
+		"""what a beam search of G lines x N beams returning R sequences per line cannot be asked for; raised before the first device call"""
+		if R > N:
+			raise ValueError(f"`num_return_sequences` ({R}) has to be smaller or equal to `num_beams` ({N}).")
+		if G * N > min(16, self.max_batch):
+			raise _lib.TTKError(f"{N} beams exceed min(16, max_batch={self.max_batch})" if G == 1 else
+								f"{G} lines x {N} beams exceed min(16, max_batch={self.max_batch})")
+		top_k = kw.get("top_k", 50) or 0
+		if 0 < top_k < 2 * N:
+			raise ValueError(f"top_k={top_k} keeps fewer tokens than the 2 * num_beams = {2 * N} continuations a beam step selects; which of the removed "
+							 "(probability 0) ones torch.multinomial would pick is unspecified: use top_k=0 or top_k >= 2 * num_beams")
+
+	def beam_search_lines(self, speech_conditioning_latent, texts, num_beams, num_return_sequences=1, max_generate_length=None, **hf_generate_kwargs):
+		"""`inference_speech(..., num_beams=N)` for several text lines as ONE decode batch of G lines x N beams <= 16 rows (no reference counterpart: the
+		reference searches line by line, and every line streams the GPT-2 weights once per token for its N rows).  texts: list of [1, Tt_g] id tensors.  Returns a
+		list of int64 [num_return_sequences, L_g]: element g is bit for bit what `inference_speech(latent, texts[g], num_beams=N, ...)` returns.  Per token
+		{ttk_beam_step_lines; ttk_ar_reorder_cache_lines; ttk_ar_decode}: every line has its own search state and draws the flat [1, N * V] noise of its own call; a
+		line whose search is over rides along (stop tokens, identity reorder) until the last one ends.  `last_generate_lines[g]` is line g's own (steps,
+		rng_start, rng_step, seed), for `position_rng_after_line`; the generators are left where the last line's own call leaves them.  One line is that call.
+		This is the beam-sample branch: do_sample may be omitted (it is True); False, input_tokens, typical_sampling, candidate_shard and the reference's sampler
+		knobs are refused as `inference_speech(num_beams=N)` refuses them."""
+		N, R = int(num_beams), num_return_sequences
+		kw = hf_generate_kwargs
+		texts = list(texts)
+		if any(t.dim() != 2 or t.shape[0] != 1 for t in texts) or not texts:
+			raise NotImplementedError("texts: a list of [1, Tt] id tensors, one per line")
+		if N < 2:
+			raise ValueError(f"beam search needs num_beams >= 2 (got {num_beams}): inference_speech_lines samples a batch of lines without beams")
+		if kw.get("num_beams", N) not in (None, N):
+			raise ValueError(f"num_beams is given twice ({num_beams} and {kw['num_beams']})")
+		kw.pop("num_beams", None)
+		kw.pop("kv_cache", None)
+		knobs = pop_sampler_knobs(kw)
+		self._check_sampler_knobs(knobs, kw, num_beams=N)
+		if not kw.pop("do_sample", True):
+			raise NotImplementedError("beam search is implemented for the sampling branch only (do_sample=True, as TTS.inference passes it)")
+		if kw.pop("input_tokens", None) is not None:
+			raise NotImplementedError("beam search takes no input_tokens (prompted continuation runs on the sampling branch, num_beams=1)")
+		if kw.pop("candidate_shard", None) is not None:
+			raise NotImplementedError("beam search is not sharded over ranks: the beams of a line exchange histories every token (candidate_shard needs num_beams=1)")
+		typical = kw.pop("typical_sampling", False)
+		kw.pop("typical_mass", None)
+		if typical:
+			raise NotImplementedError("typical_sampling together with beam search is not implemented (num_beams=1 has it)")
+		G = len(texts)
+		self._require_idle()
+		self._check_beams(N, R, kw, G)
+		max_new = self._max_new(max(int(t.shape[1]) for t in texts) + 4, max_generate_length)
+		if max_new < 1:
+			raise ValueError("max_generate_length must be at least 1")
+		seed = kw.get("seed", 0)
+		if G == 1:
+			out = [self.inference_speech(speech_conditioning_latent, texts[0], num_return_sequences=R, max_generate_length=max_generate_length, do_sample=True,
+										 num_beams=N, **kw)]
+			self.last_generate_lines = [dict(self.last_generate, seed=seed)]
+			return out
+		with self._session(seed, lambda: _BeamState(self, N, max_new, kw, lines=G)) as (st, gen, off_start):
+			st.logits.copy_(self._prefill_lines(speech_conditioning_latent, texts, N))
+			self._beam_loop(st, max_new)
+			state = st.state.tolist()
+			if any(row[2 * N + 1] <= 0 for row in state):
+				raise _lib.TTKError("beam search did not end within max_generate_length steps (a done word of ttk_beam_step_lines is unset)")
+			# one torch.multinomial per step of a line's own call: what every line's own search would have consumed
+			rng_step = st.noise_step if st.own_rng else (gen.get_offset() - off_start) // max(row[2 * N + 1] for row in state)
+			out, self.last_generate_lines = [], []
+			for g, row in enumerate(state):
+				steps, length = row[2 * N + 1], max(row[N:N + R])
+				out.append(st.seqs[g, steps & 1, 1, :R, :length].clone())
+				self.last_generate_lines.append(dict(steps=steps, rng_start=off_start, rng_step=rng_step, seed=seed))
+			self.position_rng_after_line(G - 1)
+			self.last_generate = {k: v for k, v in self.last_generate_lines[-1].items() if k != "seed"}
+			return out
 
 	def _require_idle(self):
 		"""one generation at a time per handle: the KV cache, the noise arming and the latent ring of an open streamed generation are the handle's (the
@@ -1025,24 +1097,28 @@ class _GenState(_NoiseState):
 
 
 class _BeamState(_NoiseState):
-	"""Device state of one beam search (include/ttk.h: ttk_beam_args) and the noise arming of its flat [num_beams * V] multinomial."""
+	"""Device state of one beam search (include/ttk.h: ttk_beam_args) and the noise arming of its flat [num_beams * V] multinomial.  lines = G > 1: the state
+	of G searches stepped together (ttk_beam_step_lines), every array with a leading [G]."""
 
-	def __init__(self, model: UnifiedVoice, N, max_new, kw):
+	def __init__(self, model: UnifiedVoice, N, max_new, kw, lines=1):
 		c, dev = model.cfg, model.device
 		V = c.number_mel_codes
-		self.N = N
-		self.logits = torch.empty((N, V), device=dev, dtype=torch.float32)
-		self.q = torch.empty((1, N * V), device=dev, dtype=torch.float32)      # the tensor torch.multinomial draws its noise for: [batch 1, N * V]
-		self.col = torch.zeros(N, dtype=torch.long, device=dev)
-		self.seqs = torch.full((2, 2, N, max_new), c.stop_mel_token, dtype=torch.long, device=dev)
-		self.scores = torch.full((2, N), -1e9, dtype=torch.float32, device=dev)
-		self.scores[0, 0] = 0.0
-		self.state = torch.zeros(2 * N + 2, dtype=torch.int32, device=dev)
-		self.state[2 * N] = 1
-		self.acc = torch.empty(N * V, dtype=torch.float32, device=dev)
-		self.work = torch.zeros(4 * N * N + 2 * N + 1, dtype=torch.int32, device=dev)
-		self.tok = torch.zeros(N, dtype=torch.long, device=dev)
-		self.beam_idx = torch.arange(N, dtype=torch.long, device=dev)
+		self.N, self.lines = N, lines
+		G = lines
+		self.logits = torch.empty((G * N, V), device=dev, dtype=torch.float32)
+		self.q = torch.empty((G, N * V), device=dev, dtype=torch.float32)      # per line the tensor torch.multinomial draws its noise for: [batch 1, N * V]
+		self.col = torch.zeros(G * N, dtype=torch.long, device=dev)
+		self.seqs = torch.full((G, 2, 2, N, max_new), c.stop_mel_token, dtype=torch.long, device=dev)
+		self.scores = torch.full((G, 2, N), -1e9, dtype=torch.float32, device=dev)
+		self.scores[:, 0, 0] = 0.0
+		self.state = torch.zeros((G, 2 * N + 2), dtype=torch.int32, device=dev)
+		self.state[:, 2 * N] = 1
+		self.acc = torch.empty(G * N * V, dtype=torch.float32, device=dev)
+		self.work = torch.zeros((G, 4 * N * N + 2 * N + 1), dtype=torch.int32, device=dev)
+		self.tok = torch.zeros(G * N, dtype=torch.long, device=dev)
+		self.beam_idx = torch.arange(G * N, dtype=torch.long, device=dev)
+		if G == 1:                                                              # one line: the arrays of ttk_beam_step, as `_beam_generate` reads them
+			self.seqs, self.scores, self.state, self.work = self.seqs[0], self.scores[0], self.state[0], self.work[0]
 		self.done = torch.zeros(1, dtype=torch.int32).pin_memory()
 		self._init_noise(model, 1, N * V)
 		suppress = tuple(kw.get("suppress_tokens") or ())
@@ -1072,10 +1148,24 @@ class _BeamState(_NoiseState):
 		"""(a beam state is built per call, in its start state)"""
 
 	def arm_noise(self, gen):
-		"""the mel-head launches of this search write q for their logits: N rows of V = the flat tensor, numbered by the step counter"""
-		self._arm(gen, gen.get_offset(), 0, 0, self.q)
+		"""the mel-head launches of this search write q for their logits: N rows of V = the flat tensor, numbered by the step counter (several lines: groups
+		of N rows, every line drawing the flat tensor of its own call)"""
+		self._arm(gen, gen.get_offset(), 0, self.N if self.lines > 1 else 0, self.q)
+
+	def reorder_cache(self):
+		"""the KV cache follows the beams the step kept (`_reorder_cache`): inside every line when there are several"""
+		m = self.model
+		if self.lines > 1:
+			_lib.check(m.lib.ttk_ar_reorder_cache_lines(m._h, self.beam_idx.data_ptr(), self.N, _lib.stream_ptr()), "ttk_ar_reorder_cache_lines")
+			return
+		_lib.check(m.lib.ttk_ar_reorder_cache(m._h, self.beam_idx.data_ptr(), _lib.stream_ptr()), "ttk_ar_reorder_cache")
 
 	def step(self):
 		if not self.own_rng:
-			self.q.exponential_(1)
+			self.q[:1].exponential_(1)                   # one line's [1, N * V] draw ...
+			if self.lines > 1:
+				self.q[1:].copy_(self.q[:1].expand(self.lines - 1, -1))      # ... is every line's: each call of its own reseeds and draws the same
+		if self.lines > 1:
+			_lib.check(self.model.lib.ttk_beam_step_lines(_lib.C.byref(self.args), self.lines, _lib.stream_ptr()), "ttk_beam_step_lines")
+			return
 		_lib.check(self.model.lib.ttk_beam_step(_lib.C.byref(self.args), _lib.stream_ptr()), "ttk_beam_step")

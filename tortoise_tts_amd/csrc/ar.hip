@@ -108,6 +108,7 @@ struct ttk_ar {
 	int pos_slot = -1;
 	int2* d_rowinfo;        // per candidate {first cache row, first candidate of its line}: line batches (ttk_ar_prefill_lines), prefixes right-aligned
 	int lines_mode = 0;     // the current generation was started by ttk_ar_prefill_lines: the attention launches read d_rowinfo
+	int rows_per_line = 0;  // ... with this many candidates per line (ttk_ar_reorder_cache_lines gathers inside a line only)
 	float *x, *qbuf;        // decode residual stream / scaled queries [max_batch][d]
 	void *attn_out, *hbuf;  // T, A-fragment order: [frag_rows][d] (attention output; the head's normalised rows), [frag_rows][4d] (MLP activations)
 	void* x_frag = nullptr; // T copy of x in A-fragment order [m_tile][d/32][64][8]: operand of the folded-LayerNorm launches
@@ -474,7 +475,7 @@ int ttk_ar_prefill_lines(ttk_ar* h, const float* cond_latents, const int64_t* te
 	launch_set_int(h->d_pos, Smax, s);
 	launch_set_int(h->d_pos + 1, Smax, s);
 	TTK_TRY(poison_scratch(h, s));
-	h->B = B; h->P = h->Pmax = Smax - 1; h->k = 0; h->ready = 1; h->lines_mode = 1;
+	h->B = B; h->P = h->Pmax = Smax - 1; h->k = 0; h->ready = 1; h->lines_mode = 1; h->rows_per_line = rows_per_line;
 	h->shared_rows = Smax;
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
@@ -536,8 +537,18 @@ int ttk_ar_reorder_cache(ttk_ar* h, const int64_t* beam_idx, void* stream) {
 	TTK_REQUIRE(h->ready, TTK_E_STATE, "ttk_ar_reorder_cache: call ttk_ar_prefill first");
 	TTK_REQUIRE(!h->lines_mode, TTK_E_STATE, "ttk_ar_reorder_cache: the candidates of a line batch (ttk_ar_prefill_lines) keep their own histories");
 	// rows [d_pos[1], d_pos[0]) of every slice; the shared prefix lives in slice 0 alone and is what every beam reads, whatever the order
-	return launch_kv_reorder(h->kc, h->vc, h->cfg.layers, h->cfg.max_batch, h->cfg.heads, h->cfg.max_ctx, h->es, h->d_pos, beam_idx, h->B, (hipStream_t)stream,
+	return launch_kv_reorder(h->kc, h->vc, h->cfg.layers, h->cfg.max_batch, h->cfg.heads, h->cfg.max_ctx, h->es, h->d_pos, beam_idx, h->B, h->B, (hipStream_t)stream,
 							 "ttk_ar_reorder_cache");
+}
+
+int ttk_ar_reorder_cache_lines(ttk_ar* h, const int64_t* beam_idx, int rows_per_line, void* stream) {
+	TTK_REQUIRE(h && beam_idx, TTK_E_ARG, "ttk_ar_reorder_cache_lines: null argument");
+	TTK_REQUIRE(h->ready && h->lines_mode && h->rows_per_line == rows_per_line, TTK_E_STATE,
+				"ttk_ar_reorder_cache_lines: call ttk_ar_prefill_lines with rows_per_line=%d first", rows_per_line);
+	// rows [d_pos[1], d_pos[0]) of all B slices: d_pos[1] is Smax here -- every line's right-aligned prefix lies below it, in the slice of the line's first
+	// candidate, and stays; above it every candidate's rows are its own, and a line's beams exchange them among themselves only
+	return launch_kv_reorder(h->kc, h->vc, h->cfg.layers, h->cfg.max_batch, h->cfg.heads, h->cfg.max_ctx, h->es, h->d_pos, beam_idx, h->B, rows_per_line,
+							 (hipStream_t)stream, "ttk_ar_reorder_cache_lines");
 }
 
 int ttk_ar_set_noise(ttk_ar* h, const int64_t* rng_args, const int64_t* draws, float* q) {

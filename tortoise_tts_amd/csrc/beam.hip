@@ -1,4 +1,4 @@
-// Beam search on the AR decode: the in-place KV-cache reorder and the fused beam step (include/ttk.h: ttk_ar_reorder_cache, ttk_beam_step).
+// Beam search on the AR decode: the in-place KV-cache reorder and the fused beam step (include/ttk.h: ttk_ar_reorder_cache[_lines], ttk_beam_step[_lines]).
 //
 // Reference: HF `_beam_search` with do_sample=True (HF:generation/utils.py:3208-3509 and its helpers :2988-3204) -- what the reference's forked
 // `generate` runs for `TTS.inference(beam_width > 1)` (inference.py:161,342) -- and `_reorder_cache` (unified_voice.py:257-265).
@@ -11,6 +11,8 @@
 //                  steps d to g on 2 * num_beams candidates -- a few hundred scalar operations by one thread, then a parallel copy of the
 //                  token histories into the other half of the double-buffered sequence store.
 // Everything position-dependent (tokens generated, which half is current, the done word) is device state: the pair can be captured.
+// Several text lines searched as one decode batch (ttk_beam_step_lines): the same two kernels on n_lines * num_beams workgroups, workgroup x serving line
+// x / num_beams with that line's slice of every state array -- the last workgroup OF A LINE to arrive merges that line's lists; lines never read each other's words.
 #include "ttk_common.h"
 #include "ttk_kernels.h"
 #include "ttk_host.h"
@@ -31,6 +33,7 @@ struct ReorderParams {
 	int layers, H, max_ctx, row_bytes;
 	const int* d_pos;                                 // [0] valid cache rows, [1] rows of the shared prefix
 	const int64_t* beam_idx; int B;
+	int rows_per_line;                                // a source outside its destination's line [g * rows_per_line, (g + 1) * rows_per_line) is out of range (B: one line)
 };
 
 // loads of slices I, I + 1, ..., B - 1 on the way down, their stores on the way back: every load of the thread precedes its first store, and each
@@ -52,10 +55,12 @@ template <int B>
 __global__ __launch_bounds__(256) void k_kv_reorder(ReorderParams p) {
 	int src[B];
 	bool identity = true, bad = false;
+	int lo = 0;                                       // first row of destination b's line
 #pragma unroll
 	for (int b = 0; b < B; ++b) {
 		const int64_t s = p.beam_idx[b];
-		bad |= s < 0 || s >= B;
+		if (b == lo + p.rows_per_line) lo = b;
+		bad |= s < lo || s >= lo + p.rows_per_line;      // (B is a multiple of rows_per_line: inside the line is inside [0, B))
 		identity &= s == b;
 		src[b] = (int)s;
 	}
@@ -82,13 +87,14 @@ static void launch_kv_reorder_n(const ReorderParams& p, int n, hipStream_t s) {
 }
 
 int launch_kv_reorder(void* kc, void* vc, int layers, int max_batch, int H, int max_ctx, size_t es, const int* d_pos, const int64_t* beam_idx, int B,
-					  hipStream_t s, const char* who) {
+					  int rows_per_line, hipStream_t s, const char* who) {
 	TTK_REQUIRE(B >= 1 && B <= BEAM_MAX && B <= max_batch, TTK_E_ARG, "%s: %d rows; the reorder gathers at most %d slices (max_batch %d)", who, B, BEAM_MAX, max_batch);
+	TTK_REQUIRE(rows_per_line >= 1 && B % rows_per_line == 0, TTK_E_ARG, "%s: %d rows are not lines of %d", who, B, rows_per_line);
 	ReorderParams p = {};
 	p.kc = (char*)kc; p.vc = (char*)vc;
 	p.row_bytes = (int)(64 * es);
 	p.head_bytes = (size_t)max_ctx * p.row_bytes; p.slice_bytes = (size_t)H * p.head_bytes; p.layer_bytes = (size_t)max_batch * p.slice_bytes;
-	p.layers = layers; p.H = H; p.max_ctx = max_ctx; p.d_pos = d_pos; p.beam_idx = beam_idx; p.B = B;
+	p.layers = layers; p.H = H; p.max_ctx = max_ctx; p.d_pos = d_pos; p.beam_idx = beam_idx; p.B = B; p.rows_per_line = rows_per_line;
 	launch_kv_reorder_n<BEAM_MAX>(p, B, s);      // one instantiation per row count: the gather is B registers wide, fully unrolled
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
@@ -106,7 +112,22 @@ struct BeamParams {
 	int64_t *col, *seqs; float* scores; int* state;
 	float* acc; int* work;
 	int64_t *tok, *beam_idx; int* all_done;
+	int G;                                            // ttk_beam_step_lines: lines in the batch, every array above [G][...]; 0 = ttk_beam_step
 };
+// The workgroup's line: every per-line pointer of p moved to the slice of line blockIdx.x / N, once, at kernel entry.  Returns the beam blockIdx.x % N and
+// leaves the line in *g.  Scalar work on kernel arguments and the workgroup id (a subtraction loop of at most 16 rounds, no division routine): no vector register.
+__device__ __forceinline__ int beam_line(BeamParams& p, int* g) {
+	const int N = p.N;
+	int b = blockIdx.x, line = 0;
+	while (b >= N) { b -= N; ++line; }
+	const int64_t rows = (int64_t)line * N;
+	p.logits += rows * p.ld; p.q += rows * p.V; p.acc += rows * p.V;
+	p.col += rows; p.tok += rows; p.beam_idx += rows;
+	p.seqs += rows * 4 * p.max_new; p.scores += 2 * rows; p.state += line * (2 * N + 2);
+	p.work += line * (4 * N * N + 2 * N + 1);
+	*g = line;
+	return b;
+}
 // work: [0, 2N) the rows' {max, sum of exp} as float bits; then N x 2N candidate values (float bits), N x 2N flat indices, the arrival ticket
 __device__ __forceinline__ int* work_cand_r(const BeamParams& p) { return p.work + 2 * p.N; }
 __device__ __forceinline__ int* work_cand_i(const BeamParams& p) { return p.work + 2 * p.N + 2 * p.N * p.N; }
@@ -121,8 +142,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_scores(BeamParams p) {
 	__shared__ int s_bin;
 	__shared__ unsigned long long s_before;
 	const int N = p.N, V = p.V;
-	if (p.state[2 * N + 1]) return;                   // the search is over (uniform)
-	const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+	int g;
+	const int b = beam_line(p, &g);                   // from here on p is the line's
+	if (p.state[2 * N + 1]) return;                   // the line's search is over (uniform)
+	const int tid = threadIdx.x, lane = tid & 63;
 	const int64_t c = p.col[0];
 	const float* s = p.logits + (int64_t)b * p.ld;
 	float v[SAMPLE_NPT];
@@ -202,8 +225,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_select(BeamParams p) {
 	__shared__ int top_i[BEAM_KEEP_MAX];
 	__shared__ BeamBook book;                         // the bookkeeping's small tables (one thread works on them; LDS rather than private: indexing them costs no scratch)
 	const int N = p.N, V = p.V, K = 2 * N;
-	if (p.state[2 * N + 1]) return;                   // the search is over (uniform; the word is written behind every workgroup's arrival below)
-	const int b = blockIdx.x, tid = threadIdx.x;
+	const int* state0 = p.state;                      // line 0's state: the done words of all lines are read from here when this line ends
+	int g;
+	const int b = beam_line(p, &g);                   // from here on p is the line's
+	if (p.state[2 * N + 1]) return;                   // the line's search is over (uniform; the word is written behind every workgroup's arrival below)
+	const int tid = threadIdx.x;
 	// ---- softmax over the flat [N * V] from the rows' partials, / q
 	float M = -INFINITY;
 	for (int i = 0; i < N; ++i) M = fmaxf(M, __int_as_float(p.work[2 * i]));
@@ -266,6 +292,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_select(BeamParams p) {
 			book.lp[j] = p.acc[idx];                                       // torch.gather(accumulated_log_probs, topk_indices)
 		}
 		s_over = beam_bookkeep(book, N, c, p.max_new, p.stop_token, p.length_penalty, p.scores, p.state, p.tok, p.beam_idx);
+		if (p.G) {
+			// beam_idx is global over the batch: entry g * N + b holds g * N + source beam.  The step that ends the line leaves the stop token and the
+			// identity instead: the decode and the reorder go on for the other lines and must find nothing to move or to look up in this line's rows
+			for (int n = 0; n < N; ++n) {
+				if (s_over) p.tok[n] = p.stop_token;
+				p.beam_idx[n] = (int64_t)g * N + (s_over ? n : p.beam_idx[n]);
+			}
+		}
 	}
 	__syncthreads();
 	// ---- sequences of the next iteration into the other half: running[n] = old running[run_src[n]] + its token; finished[n] likewise or kept
@@ -286,33 +320,51 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_beam_select(BeamParams p) {
 		for (int n = 0; n < N; ++n) p.col[n] = c + 1;
 		*work_ticket(p) = 0;
 		if (s_over) {
-			p.state[2 * N + 1] = (int)(c + 1);
-			if (p.all_done) __hip_atomic_store(p.all_done, (int)(c + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+			// the batch is over with its last line.  Two lines may end in this launch, in two workgroups: each stores its done word, fences, and only then reads the
+			// others' -- of two such store / fence / load sequences at least one sees the other's store, so at least one of them reports the end (both write the same c + 1:
+			// the lines of a batch step together).  ttk_beam_step (G = 0) has no other line to read
+			__hip_atomic_store(p.state + 2 * N + 1, (int)(c + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			__threadfence();
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the store has been acknowledged before the first load is issued, whatever the fence expands to)
+			int running = 0;
+			for (int l = 0; l < p.G; ++l) running += __hip_atomic_load(state0 + l * (2 * N + 2) + 2 * N + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+			if (!running && p.all_done) __hip_atomic_store(p.all_done, (int)(c + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 		}
 	}
 }
 
 }  // namespace ttk
 
-extern "C" int ttk_beam_step(const ttk_beam_args* a, void* stream) {
+// n_lines 0: ttk_beam_step (one line, tok / beam_idx of the ending step as the bookkeeping leaves them)
+static int beam_step(const ttk_beam_args* a, int n_lines, void* stream, const char* who) {
 	using namespace ttk;
-	TTK_REQUIRE(a && a->logits && a->q && a->col && a->seqs && a->scores && a->state && a->acc && a->work && a->tok && a->beam_idx, TTK_E_ARG, "ttk_beam_step: null argument");
-	TTK_REQUIRE(a->num_beams >= 2 && a->num_beams <= BEAM_MAX, TTK_E_ARG, "ttk_beam_step: num_beams %d outside 2..%d", a->num_beams, BEAM_MAX);
-	TTK_REQUIRE(a->V >= 2 * a->num_beams && a->V <= SAMPLE_MAXV && a->ld >= a->V, TTK_E_ARG, "ttk_beam_step: V %d outside %d..%d (the row is held in registers), or ld < V",
+	TTK_REQUIRE(a && a->logits && a->q && a->col && a->seqs && a->scores && a->state && a->acc && a->work && a->tok && a->beam_idx, TTK_E_ARG, "%s: null argument", who);
+	TTK_REQUIRE(a->num_beams >= 2 && a->num_beams <= BEAM_MAX, TTK_E_ARG, "%s: num_beams %d outside 2..%d", who, a->num_beams, BEAM_MAX);
+	TTK_REQUIRE(a->V >= 2 * a->num_beams && a->V <= SAMPLE_MAXV && a->ld >= a->V, TTK_E_ARG, "%s: V %d outside %d..%d (the row is held in registers), or ld < V", who,
 				a->V, 2 * a->num_beams, SAMPLE_MAXV);
-	TTK_REQUIRE(a->temperature > 0.f, TTK_E_ARG, "ttk_beam_step: temperature must be positive");
-	TTK_REQUIRE(a->top_k == 0 || a->top_k >= 2 * a->num_beams, TTK_E_ARG, "ttk_beam_step: top_k %d keeps fewer than the 2 * num_beams = %d continuations a step selects",
+	TTK_REQUIRE(a->temperature > 0.f, TTK_E_ARG, "%s: temperature must be positive", who);
+	TTK_REQUIRE(a->top_k == 0 || a->top_k >= 2 * a->num_beams, TTK_E_ARG, "%s: top_k %d keeps fewer than the 2 * num_beams = %d continuations a step selects", who,
 				a->top_k, 2 * a->num_beams);
-	TTK_REQUIRE(a->top_p >= 0.f && a->repetition_penalty >= 0.f, TTK_E_ARG, "ttk_beam_step: negative top_p / repetition_penalty");
-	TTK_REQUIRE(a->max_new >= 1, TTK_E_ARG, "ttk_beam_step: max_new %d", a->max_new);
+	TTK_REQUIRE(a->top_p >= 0.f && a->repetition_penalty >= 0.f, TTK_E_ARG, "%s: negative top_p / repetition_penalty", who);
+	TTK_REQUIRE(a->max_new >= 1, TTK_E_ARG, "%s: max_new %d", who, a->max_new);
+	const int lines = n_lines ? n_lines : 1;
+	TTK_REQUIRE(lines >= 1 && lines * a->num_beams <= BEAM_MAX, TTK_E_ARG, "%s: %d lines x %d beams exceed %d rows", who, n_lines, a->num_beams, BEAM_MAX);
 	BeamParams p = {};
 	p.logits = a->logits; p.ld = a->ld; p.N = a->num_beams; p.V = a->V; p.q = a->q; p.suppress = a->suppress; p.inv_t = 1.0f / a->temperature;
 	p.top_k = a->top_k; p.top_p = a->top_p; p.penalty = a->repetition_penalty > 0.f ? a->repetition_penalty : 1.0f; p.inv_penalty = 1.0f / p.penalty;
 	p.length_penalty = a->length_penalty; p.stop_token = a->stop_token; p.prefix0 = a->prefix_ids[0]; p.prefix1 = a->prefix_ids[1]; p.max_new = a->max_new;
 	p.col = a->col; p.seqs = a->seqs; p.scores = a->scores; p.state = a->state; p.acc = a->acc; p.work = a->work; p.tok = a->tok; p.beam_idx = a->beam_idx;
-	p.all_done = a->all_done;
-	hipLaunchKernelGGL(k_beam_scores, dim3(p.N), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, p);
-	hipLaunchKernelGGL(k_beam_select, dim3(p.N), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, p);
+	p.all_done = a->all_done; p.G = n_lines;
+	hipLaunchKernelGGL(k_beam_scores, dim3(lines * p.N), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, p);
+	hipLaunchKernelGGL(k_beam_select, dim3(lines * p.N), dim3(SAMPLE_THREADS), 0, (hipStream_t)stream, p);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
+}
+
+extern "C" int ttk_beam_step(const ttk_beam_args* a, void* stream) { return beam_step(a, 0, stream, "ttk_beam_step"); }
+
+extern "C" int ttk_beam_step_lines(const ttk_beam_args* a, int n_lines, void* stream) {
+	using namespace ttk;
+	TTK_REQUIRE(n_lines >= 1, TTK_E_ARG, "ttk_beam_step_lines: %d lines", n_lines);
+	return beam_step(a, n_lines, stream, "ttk_beam_step_lines");
 }

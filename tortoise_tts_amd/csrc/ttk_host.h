@@ -155,9 +155,10 @@ int launch_greedy_step(const ttk_sample_args* a, const float* emb, const float* 
 int launch_sample_step_ext(const ttk_sample_args* a, const ttk_sample_ext* x, const float* emb, const float* pos, float* x_out, int d, int pos_rows, void* x_frag, int x_frag_f32,
 						   hipStream_t stream, const char* who);
 
-// beam.hip: the in-place gather of the KV cache's candidate slices that beam search needs per token (ttk_ar_reorder_cache)
+// beam.hip: the in-place gather of the KV cache's candidate slices that beam search needs per token (ttk_ar_reorder_cache[_lines]); the B rows are lines of
+// rows_per_line candidates (B: one line), and a source outside its destination's line counts as out of range
 int launch_kv_reorder(void* kc, void* vc, int layers, int max_batch, int H, int max_ctx, size_t es, const int* d_pos, const int64_t* beam_idx, int B,
-					  hipStream_t s, const char* who);
+					  int rows_per_line, hipStream_t s, const char* who);
 
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 

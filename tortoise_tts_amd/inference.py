@@ -341,7 +341,7 @@ class TTSHotPath:
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
 						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True,
 						diffusion_eta=0.0, diffusion_sampler="ddim", min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0,
-						mirostat_eta=0.1):
+						mirostat_eta=0.1, beam_width=1):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -368,12 +368,16 @@ class TTSHotPath:
 		ancestral sampler draws inside its loop and is not served here: use `inference` per line.
 		min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta: the reference's own samplers, as in `inference`; with one of them
 		on the lines of a batch are sampled one after the other (UnifiedVoice.inference_speech_lines), each with its own sampler state.
+		beam_width > 1: as in `inference` -- every line is sampled by beam search, `candidates` <= beam_width finished beams come back per line -- with the lines of a
+		batch searched together (UnifiedVoice.beam_search_lines): min(4, max_batch // beam_width, 16 // beam_width) lines of beam_width rows each; everything behind
+		the sampling is as for beam_width 1.
 		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
 		from_codes = check_diffusion_conditioning(diffusion_conditioning, diff)
-		check_greedy(do_sample, candidates, 1)
+		beam_width = max(1, int(beam_width))
+		check_greedy(do_sample, candidates, beam_width)
 		if diffusion_sampler not in ("ddim", "dpm++2m"):
 			raise NotImplementedError(f"inference_lines diffuses with 'ddim' or 'dpm++2m', got {diffusion_sampler!r}: the ancestral sampler draws inside its loop, which would "
 									  "put the worker thread into the generator stream; use `inference` per line")
@@ -406,8 +410,10 @@ class TTSHotPath:
 
 		out, pending = [], []
 		lines = [t.to(dev) for t in lines]
-		G = ar_batch_lines or max(1, min(4, ar.max_batch // max(candidates, 1)))
-		G = max(1, min(G, ar.max_batch // max(candidates, 1)))
+		rows = max(candidates, 1) if beam_width == 1 else beam_width      # decode rows a line occupies
+		fit = (ar.max_batch if beam_width == 1 else min(ar.max_batch, 16)) // rows      # (the beam step and the cache reorder serve at most 16 rows)
+		G = ar_batch_lines or max(1, min(4, fit))
+		G = max(1, min(G, fit))
 		DG = G if ddim_batch_lines is None else max(1, int(ddim_batch_lines))      # lines diffused as one batch (1 = line by line)
 		eta = float(diffusion_eta)
 		if not cond_free or eta != 0.0:
@@ -416,7 +422,11 @@ class TTSHotPath:
 			group, meta = [], []
 			for i, text_tokens in enumerate(lines):
 				with torch.cuda.stream(s_ar):
-					if i % G == 0:      # sample this line and the next G - 1 as one batch
+					if i % G == 0 and beam_width > 1:      # this line and the next G - 1 beam-searched as one batch
+						batch_codes = ar.beam_search_lines(autoregressive_latents, lines[i:i + G], beam_width, **ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p),
+														   num_return_sequences=candidates, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
+														   max_generate_length=max_ar_steps, **extra)
+					elif i % G == 0:      # sample this line and the next G - 1 as one batch
 						batch_codes = ar.inference_speech_lines(autoregressive_latents, lines[i:i + G], **ar_sampling_kwargs(do_sample, ar_temp, top_k, top_p),
 																num_return_sequences=candidates, num_beams=1, length_penalty=length_penalty,
 																repetition_penalty=repetition_penalty, max_generate_length=max_ar_steps, **extra)

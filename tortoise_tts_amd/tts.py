@@ -128,7 +128,8 @@ class TTS:
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
 		diffusion model (see `_hifigan_wav`; the reference returns [1, samples] on that branch, here the shape is that of the other two).
 		beam_width > 1 (inference.py:342: num_beams) samples every line by beam search -- `candidates` <= beam_width finished beams come back, ranked
-		with `length_penalty` -- on the "bigvgan" and "vocoder" branches, line by line; the streaming "hifigan" branch takes no beams.
+		with `length_penalty` -- on the "bigvgan" and "vocoder" branches; several lines are searched together as one decode batch (TTSHotPath.inference_lines), each
+		line's result what its own search gives; the streaming "hifigan" branch takes no beams.
 		references=None speaks in a random voice (`random_voice`; needs `rlg_auto=` and `rlg_diffuser=`): `set_seed(seed)` then runs BEFORE the voice
 		is drawn, so `seed` fixes the voice, and once more behind it, so the line is sampled as `inference(text, that_voice, seed=seed)` samples it.
 		With references given the order is the reference's: the clip is encoded first, then the seed is set.
@@ -187,14 +188,13 @@ class TTS:
 				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates, do_sample=do_sample,
 				  diffusion_eta=diffusion_eta, **knobs)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
-		if beam_width != 1:                                   # the beams of a line exchange histories every token: lines are sampled one by one
-			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
-		elif len(lines) > 1 and diffusion_sampler in ("ddim", "dpm++2m"):
-			# several lines: their sampling as one decode batch, the diffusion of a line under the sampling of later ones (TTSHotPath.inference_lines:
-			# the same waveforms as the line-by-line loop of inference.py:237-422, which is what the else branch runs)
-			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)]
+		if len(lines) > 1 and diffusion_sampler in ("ddim", "dpm++2m"):
+			# several lines: their sampling as one decode batch -- beam_width > 1: the beams of a line exchange histories among themselves, the lines of a batch are
+			# searched together -- , the diffusion of a line under the sampling of later ones (TTSHotPath.inference_lines: the same waveforms as the line-by-line
+			# loop of inference.py:237-422, which is what the else branch runs)
+			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)]
 		else:
-			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, **kw)[0]) for tokens in lines]
+			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
 		return torch.concat(wavs, dim=-1), SAMPLE_RATE
 
 	@torch.inference_mode()
