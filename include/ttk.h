@@ -348,6 +348,23 @@ int ttk_ar_latents(ttk_ar* h, const float* cond, const int64_t* text, int Tt, co
 int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, float* loss_out,
 				 float* nll_text_out, float* nll_mel_out, float* text_logits_out, float* mel_logits_out, void* stream);
 
+/* The GPT-2 attention maps of that same teacher-forced pass: what get_logits(..., get_attns=True) returns (unified_voice.py:508-516, which
+ * forward(return_attentions=True) reaches at :593-602; HF eager attention, HF:models/gpt2/modeling_gpt2.py:144-226).  The sequence has S = Tt + M + 5 rows:
+ * 0 conditioning latent, 1 start_text, 2 .. Tt+1 the text, Tt+2 stop_text, Tt+3 start_mel, Tt+4 .. Tt+3+M the codes, Tt+4+M stop_mel.
+ *   P[q][k] = softmax over k <= q of 0.125 q_q . k_k on the q and k columns the layer's c_attn GEMM wrote (in the 16-bit modes the rounded values the pass
+ *   itself used), accumulated in f32, stored as f32 in every dtype, exactly 0 for k > q.
+ * ttk_ar_attentions: layers[n_layers] (host, distinct, each in [0, layers))  ->  out f32 [n_layers][B][H][S][S] (device), layers[j]'s maps at index j.
+ * ttk_ar_text_attention: layer_head[n][2] (host, {layer, head} pairs)  ->  out f32 [B][n][M][Tt] (device), the text-alignment block of pair i at index i:
+ *   A[m][t] = P[Tt+3+m][2+t], row Tt+3+m being the row that predicts code m.  Its rows do not sum to 1.
+ * Both run the dense pass of ttk_ar_latents and read each selected layer's q and k from the pass's own qkv buffer right behind the c_attn GEMM; the pass
+ * stops behind the last selected layer.  cond [B, D] f32, text [B, Tt] int64, codes [B, M] int64.  B is not bound by max_batch; the KV cache and the
+ * state of a running generation are not touched; adapted (ttk_ar_lora_set) and fp8-weight handles give the maps of what they compute.
+ * TTK_E_ARG with a message: an empty or out-of-range selection, a repeated layer, an output of 2 GiB or more (select fewer layers / heads).   */
+int ttk_ar_attentions(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, const int* layers, int n_layers,
+					  float* out, void* stream);
+int ttk_ar_text_attention(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, const int* layer_head, int n,
+						  float* out, void* stream);
+
 /* Run-time LoRA adapters on a live handle (the reference: TTS.enable_lora / disable_lora, inference.py:99-104, and the weight parametrization
  * W + (lora_B lora_A) * alpha / rank of models/lora.py:120-123, 136-145).  The adapted matrices are the 4 x layers HF Conv1D weights
  * gpt.h.<l>.{attn.c_attn, attn.c_proj, mlp.c_fc, mlp.c_proj}.weight, [K_in][N_out]; lora_B is [K_in][rank], lora_A [rank][N_out].
@@ -779,6 +796,33 @@ typedef struct {
 	int shared_rows, variant, pos_line;
 } ttk_attn_decode_desc;
 int ttk_attn_decode(int dtype, const ttk_attn_decode_desc* d, void* stream);
+
+/* ------------------------------------------------------------------ attention maps, alignment cost and DTW on caller-provided operands (csrc/align.hip)
+ * ttk_attn_probs: the causal softmax probabilities HF's eager GPT-2 attention returns with output_attentions (HF:models/gpt2/modeling_gpt2.py:144-226; reached by
+ *   get_logits(get_attns=True), unified_voice.py:508-516), which ttk_attn_fwd never materialises.  qkv [nb*T][ld] is addressed as ttk_attn_desc addresses it; head dim 64.
+ *   out f32 [nb][n_sel][R][C]: rows [r0, r0 + R) and columns [c0, c0 + C) of the T x T map of head heads[i] (device int [n_sel], each in [0, H); an entry
+ *   outside is skipped), P[q][k] = softmax over k' <= q of scale q.k', 0 for k > q.  The full map is the window (0, T, 0, T); a window's elements are bit for
+ *   bit the full map's.  n_sel == 0 launches nothing.
+ * ttk_align_prepare: the alignment cost of per-head blocks A f32 [nb][n_sel][M][Tt] (no reference counterpart; the word-timestamp recipe of OpenAI Whisper,
+ *   whisper/timing.py, with mel codes as the time axis): every row standardised over the text axis (population std; a row of std 0 becomes zeros), a median
+ *   filter of odd `width` <= 15 along M with reflect padding (M <= width / 2: no filter), the mean over the heads as sequential f32 adds in list order and one
+ *   division; cost f32 [nb][M][Tt] = -mean, matrix (optional, same shape) = mean.
+ * ttk_dtw: D[0][0] = 0, borders +inf, D[i][j] = cost[i-1][j-1] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) in f32, on ties the first of (diagonal, i-1, j-1);
+ *   D f32 [nb][(M+1)(Tt+1)] is the caller's workspace, trace u8 [nb][M][Tt] holds 0 / 1 / 2 for the three, total f32 [nb] = D[M][Tt].  The path is read
+ *   from the trace on the host.  M <= 606, Tt <= 404 (max_mel_tokens + 2, max_text_tokens + 2 of the largest configuration) in both.
+ * All three return TTK_E_ARG with a message when a precondition the kernels rely on fails. */
+typedef struct {
+	const void* qkv; int64_t ld;
+	int q_off, k_off, head_stride, nb, T, H;
+	float scale;
+	int n_sel;
+	const int* heads;
+	float* out;
+	int r0, R, c0, C;
+} ttk_attn_probs_desc;
+int ttk_attn_probs(int dtype, const ttk_attn_probs_desc* d, void* stream);
+int ttk_align_prepare(const float* A, int nb, int n_sel, int M, int Tt, int width, float* cost, float* matrix, void* stream);
+int ttk_dtw(const float* cost, int nb, int M, int Tt, float* D, unsigned char* trace, float* total, void* stream);
 
 /* ------------------------------------------------------------------ the GroupNorm32-apply kernels on caller-provided operands
  * No reference counterpart: exposed so every launch form of csrc/norm.hip's GroupNorm-apply can be run on the same input and statistics (the forms owe the same

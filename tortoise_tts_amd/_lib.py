@@ -109,6 +109,13 @@ class AttnDecodeDesc(C.Structure):
 				("shared_rows", C.c_int), ("variant", C.c_int), ("pos_line", C.c_int)]
 
 
+class AttnProbsDesc(C.Structure):
+	"""ttk_attn_probs_desc (include/ttk.h; static_assert'ed in csrc/align.hip)"""
+	_fields_ = [("qkv", C.c_void_p), ("ld", C.c_int64), ("q_off", C.c_int), ("k_off", C.c_int), ("head_stride", C.c_int), ("nb", C.c_int), ("T", C.c_int),
+				("H", C.c_int), ("scale", C.c_float), ("n_sel", C.c_int), ("heads", C.c_void_p), ("out", C.c_void_p), ("r0", C.c_int), ("R", C.c_int),
+				("c0", C.c_int), ("C", C.c_int)]
+
+
 class GnDesc(C.Structure):
 	"""ttk_gn_desc (include/ttk.h)"""
 	_fields_ = [("x", C.c_void_p), ("ms", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
@@ -186,6 +193,11 @@ SYMBOLS = {
 	"ttk_ar_sample_next_ext": (_I, [_P, C.POINTER(SampleArgs), C.POINTER(SampleExt), _P]),
 	"ttk_ar_latents": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
 	"ttk_ar_score": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+	"ttk_ar_attentions": (_I, [_P, _P, _P, _I, _P, _I, _I, C.POINTER(C.c_int), _I, _P, _P]),
+	"ttk_ar_text_attention": (_I, [_P, _P, _P, _I, _P, _I, _I, C.POINTER(C.c_int), _I, _P, _P]),
+	"ttk_attn_probs": (_I, [_I, C.POINTER(AttnProbsDesc), _P]),
+	"ttk_align_prepare": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
+	"ttk_dtw": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
 	"ttk_ar_lora_init": (_I, [_P, C.POINTER(WeightView), _I]),
 	"ttk_ar_lora_set": (_I, [_P, C.POINTER(WeightView), _I, C.c_float, _P]),
 	"ttk_xent_rows": (_I, [_P, _L, _I, _I, _P, _P, _P, _P, _I, _P]),

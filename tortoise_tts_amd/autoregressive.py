@@ -239,7 +239,10 @@ class UnifiedVoice(_lib.Handle):
 		"""unified_voice.py:544-612, text first.  return_latent=True (what inference uses, with clip_inputs=False: inference.py:371-379): f32
 		[B, M', model_dim].  return_latent=False, the reference's default: (loss_text, loss_mel, mel_logits) -- the mean teacher-forced
 		cross-entropies as 0-dim f32 device tensors and the mel logits [B, number_mel_codes, M' + 2] f32; `self.loss` holds the two losses as in the
-		reference and `self.last_nll` the per-token rows {"text": [B, Tt' + 2], "mel": [B, M' + 2]} (F.cross_entropy(reduction="none"))."""
+		reference and `self.last_nll` the per-token rows {"text": [B, Tt' + 2], "mel": [B, M' + 2]} (F.cross_entropy(reduction="none")).
+		return_attentions=True stays refused here: the reference's `forward` unpacks the tuple of maps that `get_logits(get_attns=True)` returns (:508-516) into
+		two names (:593), so it returns layer 1's map on a 2-layer model and raises at any other depth -- not an interface to copy.  The maps themselves, all
+		layers or a subset, come from `attentions(latent, text, codes)`."""
 		if raw_mels is not None or not text_first or return_attentions:
 			raise NotImplementedError("forward is implemented text first on mel codes: text_first=False, raw_mels and return_attentions are not")
 		if not return_latent and not self.scoring:
@@ -279,6 +282,127 @@ class UnifiedVoice(_lib.Handle):
 		return r
 
 	__call__ = forward
+
+	# ------------------------------------------------------------------ attention maps and the text-to-audio alignment
+	def _dense_inputs(self, latent, text_inputs, mel_codes):
+		"""(cond [B, D] f32, text [B, Tt], codes [B, M] int64), contiguous on the device; one latent / one text row serve every code row.  The ids are
+		validated where they live, as `forward` does (an id outside its table must not reach the embedding kernels): for device tensors that is a min and a
+		max reduction and a host read each, for host tensors plain host work; with B > 1 the shared latent / text row is copied B times on the device."""
+		codes = torch.as_tensor(mel_codes)
+		text = torch.as_tensor(text_inputs)
+		codes, text = (codes[None] if codes.dim() == 1 else codes), (text[None] if text.dim() == 1 else text)
+		if codes.dim() != 2 or text.dim() != 2 or codes.dtype.is_floating_point or text.dtype.is_floating_point or not codes.shape[1] or not text.shape[1]:
+			raise ValueError("text_inputs and mel_codes are non-empty [B, T] (or [T]) integer id tensors")
+		check_ids(text, self.cfg.number_text_tokens + 1, "text token")
+		check_ids(codes, self.cfg.number_mel_codes, "mel code")
+		B = codes.shape[0]
+		cond = latent.to(self.device, torch.float32)
+		cond = cond[None] if cond.dim() == 1 else cond
+		if text.shape[0] not in (1, B) or cond.shape[0] not in (1, B):
+			raise ValueError(f"one latent and one text row, or one per code row (B={B}); got {cond.shape[0]} and {text.shape[0]}")
+		text = text.to(self.device, torch.int64).expand(B, -1).contiguous()
+		return cond.expand(B, -1).contiguous(), text, codes.to(self.device, torch.int64).contiguous()
+
+	def _attentions(self, cond, text, codes, layers):
+		_lib.require_cuda(cond, text, codes)
+		layers = list(range(self.cfg.layers)) if layers is None else [int(l) for l in layers]
+		if not layers:
+			raise ValueError("attentions: the layer list is empty")
+		B, Tt, M = codes.shape[0], text.shape[1], codes.shape[1]
+		S = Tt + M + 5
+		if len(layers) * B * self.cfg.heads * S * S * 4 >= 2 ** 31:      # (the C entry refuses the same; here before the allocation)
+			raise _lib.TTKError(f"attentions: {len(layers)} layers x B={B} x {self.cfg.heads} heads x {S} x {S} f32 is an output of 2 GiB or more: select fewer layers")
+		out = torch.empty((len(layers), B, self.cfg.heads, S, S), device=self.device, dtype=torch.float32)
+		arr = (_lib.C.c_int * len(layers))(*layers)
+		with torch.cuda.device(self.device):
+			_lib.check(self.lib.ttk_ar_attentions(self._h, cond.data_ptr(), text.data_ptr(), Tt, codes.data_ptr(), M, B, arr, len(layers), out.data_ptr(),
+												  _lib.stream_ptr()), "ttk_ar_attentions")
+		return tuple(out[j] for j in range(len(layers)))
+
+	def attentions(self, latent, text_inputs, mel_codes, layers=None):
+		"""The GPT-2 attention maps of the teacher-forced pass -- what the reference's `get_logits(get_attns=True)` returns (unified_voice.py:508-516) -- on ids
+		that are clipped and padded as `forward` leaves them, for a subset of the layers (None: all): a tuple with one f32 tensor [B, heads, S, S] per entry of `layers`, S = Tt + M + 5 (include/ttk.h: ttk_ar_attentions names the rows).  The dense
+		pass stops behind the last selected layer."""
+		return self._attentions(*self._dense_inputs(latent, text_inputs, mel_codes), layers)
+
+	def _alignment_heads(self, heads):
+		from .alignment import default_heads
+		heads = default_heads(self.cfg.layers, self.cfg.heads) if heads is None else [(int(l), int(h)) for l, h in heads]
+		if not heads:
+			raise ValueError("text_alignment: the head list is empty")
+		for l, h in heads:
+			if not (0 <= l < self.cfg.layers and 0 <= h < self.cfg.heads):
+				raise ValueError(f"text_alignment: (layer {l}, head {h}) is outside {self.cfg.layers} layers x {self.cfg.heads} heads")
+		return heads
+
+	def _text_attention(self, cond, text, codes, heads):
+		"""f32 [B, n, M, Tt]: the text-alignment block A[m][t] = P[Tt + 3 + m][2 + t] of every (layer, head) of `heads` (include/ttk.h: ttk_ar_text_attention)"""
+		_lib.require_cuda(cond, text, codes)
+		B, Tt, M, n = codes.shape[0], text.shape[1], codes.shape[1], len(heads)
+		out = torch.empty((B, n, M, Tt), device=self.device, dtype=torch.float32)
+		arr = (_lib.C.c_int * (2 * n))(*[v for lh in heads for v in lh])
+		with torch.cuda.device(self.device):
+			_lib.check(self.lib.ttk_ar_text_attention(self._h, cond.data_ptr(), text.data_ptr(), Tt, codes.data_ptr(), M, B, arr, n, out.data_ptr(), _lib.stream_ptr()),
+					   "ttk_ar_text_attention")
+		return out
+
+	def _align_blocks(self, blocks, median_width, keep_matrix=True):
+		"""blocks f32 [nb, n, M, Tt] on the device -> (matrix [nb, M, Tt] device or None, traces u8 numpy [nb, M, Tt], totals f32 numpy [nb]): the cost
+		(csrc/align.hip: k_align_prepare), the DTW table and trace (k_dtw), and ONE copy to the host that carries trace and totals together"""
+		import numpy as np
+		median_width = int(median_width)
+		if median_width < 1 or median_width > 15 or median_width % 2 == 0:
+			raise ValueError(f"median_width must be odd and in 1..15, got {median_width}")
+		nb, n, M, Tt = blocks.shape
+		new = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)
+		cost, matrix, D = new(nb, M, Tt), (new(nb, M, Tt) if keep_matrix else None), new(nb, (M + 1) * (Tt + 1))
+		nt = (nb * M * Tt + 3) // 4 * 4
+		packed = torch.empty(nt + 4 * nb, device=self.device, dtype=torch.uint8)      # [trace | totals]
+		with torch.cuda.device(self.device):
+			_lib.check(self.lib.ttk_align_prepare(blocks.data_ptr(), nb, n, M, Tt, median_width, cost.data_ptr(), _lib.ptr(matrix), _lib.stream_ptr()), "ttk_align_prepare")
+			_lib.check(self.lib.ttk_dtw(cost.data_ptr(), nb, M, Tt, D.data_ptr(), packed.data_ptr(), packed.data_ptr() + nt, _lib.stream_ptr()), "ttk_dtw")
+		host = packed.cpu().numpy()      # the one synchronisation
+		return matrix, host[:nb * M * Tt].reshape(nb, M, Tt), host[nt:].view(np.float32).copy()
+
+	def text_alignment(self, latent, text_inputs, mel_codes, heads=None, median_width=7):
+		"""Which text token each mel code came from: the monotone text-to-audio path through the attention of the teacher-forced pass (no reference
+		counterpart; OpenAI Whisper's word-timestamp recipe with mel codes as the time axis -- the steps are listed in include/ttk.h at ttk_align_prepare and
+		ttk_dtw).  heads: a list of (layer, head), None = every head of layers >= layers / 2 -- a guess from similar models that nothing here can check on a
+		trained checkpoint (`rank_alignment_heads` scores the heads of one).  median_width: odd, <= 15.
+		Returns {"matrix": f32 [B, M, Tt] on the device (the negated cost), "path": per sequence (text indices, mel indices) int64 numpy arrays,
+		"token_start": int64 numpy [B, Tt] in mel-code units, "total": f32 numpy [B], the path's cost}.  One dense pass that stops behind the last selected
+		layer, the map kernel on the selected heads, two small kernels and one copy to the host that carries trace and totals; the backtrace runs there.  In
+		front of the pass: the id validation and input copies of `_dense_inputs` (device reductions with host reads when the ids are device tensors; pass host
+		tensors to keep that on the host) and the upload of the head list from pageable host memory, which the host waits for.  Sequences of one call share Tt
+		and M: lines of different length take one call each."""
+		import numpy as np
+		from . import alignment as A
+		heads = self._alignment_heads(heads)
+		cond, text, codes = self._dense_inputs(latent, text_inputs, mel_codes)
+		matrix, traces, totals = self._align_blocks(self._text_attention(cond, text, codes, heads), median_width)
+		paths = [A.backtrace(t) for t in traces]
+		starts = np.stack([A.token_starts(ti, mi, text.shape[1]) for ti, mi in paths])
+		return {"matrix": matrix, "path": paths, "token_start": starts, "total": totals, "heads": heads}
+
+	def rank_alignment_heads(self, latent, text_inputs, mel_codes, median_width=7):
+		"""[((layer, head), score)] over every head, best first: the mean of that head's own standardised and median-filtered block along its own DTW path,
+		averaged over the sequences -- high where a head's attention follows one monotone path through the text.  For picking `heads` on a trained
+		checkpoint.  The blocks and the per-head cost / DTW run on the device (each head as a sequence of its own); the ranking is host logic."""
+		from . import alignment as A
+		heads = [(l, h) for l in range(self.cfg.layers) for h in range(self.cfg.heads)]
+		cond, text, codes = self._dense_inputs(latent, text_inputs, mel_codes)
+		blocks = self._text_attention(cond, text, codes, heads)
+		B, n, M, Tt = blocks.shape
+		scores = [0.0] * n
+		per = max(1, 65535 // n)      # sequences per launch: a launch takes at most 65535 (sequence, head) pairs
+		for b0 in range(0, B, per):
+			part = blocks[b0:b0 + per].reshape(-1, 1, M, Tt)
+			matrix, traces, _ = self._align_blocks(part, median_width)
+			matrix = matrix.cpu().numpy()
+			for i, trace in enumerate(traces):
+				ti, mi = A.backtrace(trace)
+				scores[i % n] += float(matrix[i, mi, ti].mean()) / B
+		return sorted(zip(heads, scores), key=lambda hs: -hs[1])
 
 	def inference_speech(self, speech_conditioning_latent, text_inputs, input_tokens=None, num_return_sequences=1,
 						 max_generate_length=None, typical_sampling=False, typical_mass=.9, kv_cache=True, candidate_shard=None,

@@ -7,6 +7,9 @@
 #include "ttk_common.h"
 #include "ttk_conv.h"
 
+#include <algorithm>
+#include <array>
+
 using namespace ttk;
 
 namespace {
@@ -124,6 +127,8 @@ struct ttk_ar {
 	int lean = 1;           // decode launches on the compile-time-specialised kernels of gemv.hip where one exists (TTK_AR_LEAN=0: k_skinny everywhere)
 	WsBuf ws_x, ws_a, ws_qkv, ws_ao, ws_h;
 	WsBuf ws_score;         // ttk_ar_score: row-major logits of both heads, targets, nll rows
+	WsBuf ws_tap;           // ttk_ar_attentions / ttk_ar_text_attention: the device lists {head}, {output slot} of the selection
+	std::vector<int> tap_host;      // ... and their host copy (alive until the upload has run)
 	int B = 0, P = 0, k = 0, ready = 0;
 	int Pmax = 0;           // longest prefix of the batch (capacity checks); == P for one line
 	// run-time adapters (ttk_ar_lora_init / ttk_ar_lora_set): f32 masters of the 4 x layers block matrices, index 4 l + {0 c_attn, 1 attn.c_proj, 2 c_fc, 3 mlp.c_proj},
@@ -145,7 +150,16 @@ static int poison_scratch(ttk_ar* h, hipStream_t s) {
 	return TTK_OK;
 }
 
-static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipStream_t s, int kv_row0 = 0, int kv_t0 = 0) {
+// A tap into the dense pass (ttk_ar_attentions, ttk_ar_text_attention): behind the c_attn GEMM of a layer with selected heads, k_attn_probs (align.hip) reads
+// that layer's q and k columns from ws_qkv and writes the window [r0, r0 + R) x [c0, c0 + C) of each selected head's map; the pass ends behind layer `last`.
+struct AttnTap {
+	struct Layer { int first = 0, count = 0; float* out = nullptr; };      // entries [first, first + count) of the device lists; where this layer's maps go
+	std::vector<Layer> layer;
+	const int* heads = nullptr; const int* slots = nullptr;
+	int n_out = 0, r0 = 0, R = 0, c0 = 0, C = 0, last = -1;
+};
+
+static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipStream_t s, int kv_row0 = 0, int kv_t0 = 0, const AttnTap* tap = nullptr) {
 	const int d = h->cfg.model_dim, H = h->cfg.heads, dt = h->dt;
 	const int rows = B * S;
 	TTK_TRY(h->ws_a.reserve((size_t)rows * d * h->es));
@@ -161,6 +175,17 @@ static int dense_forward(ttk_ar* h, float* x, int B, int S, bool write_kv, hipSt
 			char* kc = (char*)h->kc + ((size_t)l * h->kv_layer_stride + row0) * h->es;
 			char* vc = (char*)h->vc + ((size_t)l * h->kv_layer_stride + row0) * h->es;
 			launch_kv_scatter(dt, h->ws_qkv.p, B, S, H, kc, vc, h->cfg.max_ctx, s, kv_t0);
+		}
+		if (tap) {
+			const AttnTap::Layer& t = tap->layer[l];
+			if (t.count) {
+				AttnProbsParams q = {};
+				q.qkv = h->ws_qkv.p; q.ld = 3 * d; q.q_off = 0; q.k_off = d; q.head_stride = 64; q.scale = 0.125f; q.nb = B; q.T = S; q.H = H;
+				q.heads = tap->heads + t.first; q.slots = tap->slots ? tap->slots + t.first : nullptr; q.n_sel = t.count; q.n_out = tap->n_out;
+				q.r0 = tap->r0; q.R = tap->R; q.c0 = tap->c0; q.C = tap->C; q.out = t.out;
+				launch_attn_probs(dt, q, s);
+			}
+			if (l == tap->last) return TTK_OK;
 		}
 		AttnParams a = {};
 		a.qkv = h->ws_qkv.p; a.ld = 3 * d; a.q_off = 0; a.k_off = d; a.v_off = 2 * d; a.head_stride = 64;
@@ -673,6 +698,82 @@ int ttk_ar_score(ttk_ar* h, const float* cond, const int64_t* text, int Tt, cons
 	TTK_TRY(poison_scratch(h, s));
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
+}
+
+// the dense pass of ttk_ar_latents with a tap: `sel` = {layer, head, output slot} triples, grouped by layer here; a layer's maps go to out + out_index[layer] * out_stride
+static int tapped_pass(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, std::vector<std::array<int, 3>>& sel, bool with_slots,
+					   AttnTap& tap, float* out, const std::vector<int>& out_index, int64_t out_stride, void* stream, const char* who) {
+	const ttk_ar_config& c = h->cfg;
+	TTK_REQUIRE(B >= 1 && B <= 65535 && Tt >= 1 && M >= 1, TTK_E_ARG, "%s: empty input (B=%d Tt=%d M=%d)", who, B, Tt, M);
+	TTK_REQUIRE(Tt + 2 <= c.max_text_seq_len, TTK_E_ARG, "%s: %d text tokens exceed the position table", who, Tt);
+	TTK_REQUIRE(M + 2 <= c.max_mel_seq_len, TTK_E_ARG, "%s: %d mel codes exceed the position table (%d)", who, M, c.max_mel_seq_len - 2);
+	const int S = Tt + M + 5, d = c.model_dim;
+	TTK_REQUIRE((int64_t)B * S * 4 * d * (int64_t)h->es < (1ll << 31), TTK_E_ARG, "%s: B=%d x (Tt=%d + M=%d) makes a GEMM operand of 2 GiB or more (32-bit buffer offsets): run the batch in parts",
+				who, B, Tt, M);
+	std::stable_sort(sel.begin(), sel.end(), [](const std::array<int, 3>& a, const std::array<int, 3>& b) { return a[0] < b[0]; });
+	const int n = (int)sel.size();
+	tap.layer.assign(c.layers, AttnTap::Layer());
+	h->tap_host.assign(2 * (size_t)n, 0);
+	for (int i = 0; i < n; ++i) {
+		AttnTap::Layer& L = tap.layer[sel[i][0]];
+		if (L.count++ == 0) { L.first = i; L.out = out + out_index[sel[i][0]] * out_stride; }
+		h->tap_host[i] = sel[i][1]; h->tap_host[n + i] = sel[i][2];
+		tap.last = sel[i][0];
+	}
+	hipStream_t s = (hipStream_t)stream;
+	TTK_TRY(h->ws_tap.reserve(2 * (size_t)n * sizeof(int)));
+	TTK_HIP(hipMemcpyAsync(h->ws_tap.p, h->tap_host.data(), 2 * (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+	tap.heads = (const int*)h->ws_tap.p;
+	tap.slots = with_slots ? tap.heads + n : nullptr;
+	TTK_TRY(h->ws_x.reserve((size_t)B * S * d * sizeof(float)));
+	float* x = (float*)h->ws_x.p;
+	const int64_t total = (int64_t)B * S * (d / 4);
+	hipLaunchKernelGGL(k_build_latent_emb, dim3(grid_for(total)), dim3(256), 0, s, cond, text, Tt, codes, M, B, d,
+					   h->text_emb, h->text_pos, h->mel_emb, h->mel_pos, c.start_text_token, c.stop_text_token, c.start_mel_token, c.stop_mel_token, x);
+	TTK_TRY(dense_forward(h, x, B, S, false, s, 0, 0, &tap));
+	TTK_TRY(poison_scratch(h, s));
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_ar_attentions(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, const int* layers, int n_layers, float* out, void* stream) {
+	TTK_REQUIRE(h && cond && text && codes && layers && out, TTK_E_ARG, "ttk_ar_attentions: null argument");
+	const int nl = h->cfg.layers, H = h->cfg.heads;
+	TTK_REQUIRE(n_layers >= 1 && n_layers <= nl, TTK_E_ARG, "ttk_ar_attentions: select 1..%d layers, got %d", nl, n_layers);
+	std::vector<int> index(nl, -1);
+	for (int j = 0; j < n_layers; ++j) {
+		TTK_REQUIRE(layers[j] >= 0 && layers[j] < nl, TTK_E_ARG, "ttk_ar_attentions: layer %d is outside [0, %d)", layers[j], nl);
+		TTK_REQUIRE(index[layers[j]] < 0, TTK_E_ARG, "ttk_ar_attentions: layer %d is selected twice", layers[j]);
+		index[layers[j]] = j;
+	}
+	const int64_t S = (int64_t)Tt + M + 5, per_layer = (int64_t)B * H * S * S;
+	TTK_REQUIRE(Tt >= 1 && M >= 1 && B >= 1, TTK_E_ARG, "ttk_ar_attentions: empty input (B=%d Tt=%d M=%d)", B, Tt, M);
+	TTK_REQUIRE(per_layer * n_layers * 4 < (1ll << 31), TTK_E_ARG,
+				"ttk_ar_attentions: %d layers x B=%d x %d heads x %lld x %lld f32 is an output of 2 GiB or more: select fewer layers", n_layers, B, H, (long long)S, (long long)S);
+	std::vector<std::array<int, 3>> sel;
+	for (int j = 0; j < n_layers; ++j)
+		for (int hd = 0; hd < H; ++hd) sel.push_back({layers[j], hd, hd});
+	AttnTap tap;
+	tap.n_out = H; tap.r0 = 0; tap.R = (int)S; tap.c0 = 0; tap.C = (int)S;
+	return tapped_pass(h, cond, text, Tt, codes, M, B, sel, false, tap, out, index, per_layer, stream, "ttk_ar_attentions");
+}
+
+int ttk_ar_text_attention(ttk_ar* h, const float* cond, const int64_t* text, int Tt, const int64_t* codes, int M, int B, const int* layer_head, int n, float* out, void* stream) {
+	TTK_REQUIRE(h && cond && text && codes && layer_head && out, TTK_E_ARG, "ttk_ar_text_attention: null argument");
+	const int nl = h->cfg.layers, H = h->cfg.heads;
+	TTK_REQUIRE(n >= 1 && n <= 65535, TTK_E_ARG, "ttk_ar_text_attention: select 1..65535 (layer, head) pairs, got %d", n);
+	std::vector<std::array<int, 3>> sel;
+	for (int i = 0; i < n; ++i) {
+		const int l = layer_head[2 * i], hd = layer_head[2 * i + 1];
+		TTK_REQUIRE(l >= 0 && l < nl && hd >= 0 && hd < H, TTK_E_ARG, "ttk_ar_text_attention: pair %d = (layer %d, head %d) is outside %d layers x %d heads", i, l, hd, nl, H);
+		sel.push_back({l, hd, i});
+	}
+	TTK_REQUIRE(Tt >= 1 && M >= 1 && B >= 1, TTK_E_ARG, "ttk_ar_text_attention: empty input (B=%d Tt=%d M=%d)", B, Tt, M);
+	TTK_REQUIRE((int64_t)B * n * M * Tt * 4 < (1ll << 31), TTK_E_ARG,
+				"ttk_ar_text_attention: B=%d x %d heads x M=%d x Tt=%d f32 is an output of 2 GiB or more: select fewer heads", B, n, M, Tt);
+	AttnTap tap;
+	tap.n_out = n; tap.r0 = Tt + 3; tap.R = M; tap.c0 = 2; tap.C = Tt;
+	return tapped_pass(h, cond, text, Tt, codes, M, B, sel, true, tap, out, std::vector<int>(nl, 0), 0, stream, "ttk_ar_text_attention");
 }
 
 }  // extern "C"

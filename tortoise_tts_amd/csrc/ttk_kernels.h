@@ -275,6 +275,28 @@ void attn_pos_slot_release(int slot);
 // copy k/v of a dense qkv buffer [B*S][3d] (GPT-2 order q|k|v, head h at h*64) into the cache rows [0,S)
 void launch_kv_scatter(int dt, const void* qkv, int B, int S, int H, void* kcache, void* vcache, int max_ctx, hipStream_t s, int t0 = 0);
 
+// ---------------------------------------------------------------- attention maps and alignment (align.hip)
+// out[b][slot][q - r0][k - c0] = softmax_{k' <= q}(scale q.k')[k] (0 for k > q) for rows [r0, r0 + R), columns [c0, c0 + C) of the T x T map of
+// head heads[i] of sequence b; slot = slots ? slots[i] : i.  qkv is addressed as in AttnParams.  f32 output for every dt.
+struct AttnProbsParams {
+	const void* qkv; int64_t ld;          // T [nb*T][ld]
+	int q_off, k_off, head_stride;
+	float scale;
+	int nb, T, H;
+	const int* heads;                     // device int [n_sel]; an entry outside [0, H) is skipped
+	const int* slots;                     // device int [n_sel] or null; an entry outside [0, n_out) is skipped
+	int n_sel, n_out;
+	int r0, R, c0, C;
+	float* out;                           // f32 [nb][n_out][R][C]
+};
+void launch_attn_probs(int dt, const AttnProbsParams& p, hipStream_t s);      // n_sel == 0: launches nothing
+// A f32 [nb][n_sel][M][Tt] -> cost (and, optional, matrix = -cost) f32 [nb][M][Tt]; width odd, <= 15
+void launch_align_prepare(const float* A, int nb, int n_sel, int M, int Tt, int width, float* cost, float* matrix, hipStream_t s);
+// cost f32 [nb][M][Tt] -> D f32 [nb][(M + 1)(Tt + 1)] (workspace), trace u8 [nb][M][Tt], total f32 [nb]
+void launch_dtw(const float* cost, int nb, int M, int Tt, float* D, unsigned char* trace, float* total, hipStream_t s);
+constexpr int ALIGN_MAX_M = 606, ALIGN_MAX_TT = 404;      // max_mel_tokens + 2, max_text_tokens + 2 of the largest configuration
+const char* align_shape_refusal(int nb, int M, int Tt);   // null, or what stands against the shape
+
 // ---------------------------------------------------------------- row cross-entropy (xent.hip)
 // nll[r] = logsumexp(logits[r][0..C)) - logits[r][target[r]], one pass per row; mean (optional) = the rows summed in the fixed order include/ttk.h
 // documents, / rows; logits_t (optional) = the same logits as f32 [rows / T][C][T].  Columns [C, ld) are never read.

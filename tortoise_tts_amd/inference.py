@@ -95,6 +95,16 @@ def check_diffusion_conditioning(diffusion_conditioning: str, diffusion: Diffusi
 	return diffusion_conditioning == "codes"
 
 
+def line_alignment(ar, autoregressive_latents, text_tokens, raw_codes, best, heads=None):
+	"""`UnifiedVoice.text_alignment` of one line's chosen candidate on its code row as sampled (before `fix_stop_tokens`), on the current stream; the dict also
+	holds "codes": that row [1, M]"""
+	row = raw_codes[best:best + 1]
+	al_row = autoregressive_latents if autoregressive_latents.shape[0] == 1 else autoregressive_latents[best:best + 1]
+	r = ar.text_alignment(al_row, text_tokens, row, heads=heads)
+	r["codes"] = row
+	return r
+
+
 class HotPathStages:
 	"""`dist.ShardStages` on the libttk-backed modules: what one rank of a candidate-sharded utterance runs (dist.sharded_candidates)."""
 
@@ -244,8 +254,12 @@ class TTSHotPath:
 				  max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, diffusion_sampler="ddim", cond_free=True, candidates=1,
 				  suppress_tokens=None, return_all=False, phase_marks=None, latents_for="all", beam_width=1, diffusion_conditioning="latents",
-				  do_sample=True, diffusion_eta=0.0, min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+				  do_sample=True, diffusion_eta=0.0, min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1,
+				  return_timings=False, alignment_heads=None):
 		"""text_tokens [1, Tt] int64; latents from the reference's conditioning encoders ([1,1024], [1,2048]).
+		return_timings (no reference counterpart): True appends the line's alignment to the result -- (mels, seconds[, aux], alignment): what
+		`UnifiedVoice.text_alignment` (heads: `alignment_heads`, None = its default set) returns for the chosen candidate's code row as it was sampled, BEFORE the
+		stop-token rewrite, plus "codes": that row [1, M].  One dense pass behind the latent pass; everything else is the call without the argument, bit for bit.
 		min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta: the reference's own samplers (tortoise_tts/samplers.py; see
 		`UnifiedVoice.inference_speech`), off by default; sampling only, beam_width 1.
 		diffusion_eta: DDIM's eta (ddim_sample_loop, diffusion.py:745; the reference's `TTS.inference` leaves it at 0): above 0 the per-step draws the
@@ -288,6 +302,7 @@ class TTSHotPath:
 									max_generate_length=max_ar_steps, **extra,
 									**ar_sampler_knobs(min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta))
 		mark("ar_decode")
+		raw = codes
 		codes = fix_stop_tokens(codes, ar.stop_mel_token)
 		B, M = codes.shape
 		wav_lengths = torch.tensor([M * ar.mel_length_compression])
@@ -317,6 +332,7 @@ class TTSHotPath:
 		if (latents_for == "all" or from_codes) and self.clvp is not None and B > 1:
 			scores = self.clvp(text_tokens, codes, return_loss=False)
 			best = int(torch.argmax(scores))
+		alignment = (line_alignment(ar, autoregressive_latents, text_tokens, raw, best, alignment_heads),) if return_timings else ()
 		if from_codes:
 			aligned = trim_calm_tokens(codes[best:best + 1], codes[best:best + 1])
 		else:
@@ -333,15 +349,15 @@ class TTSHotPath:
 			aux = dict(codes=codes, latents=latents, E=E, noise=noise, mel=mel, scores=scores, best=best)
 			if from_codes:
 				aux["aligned"] = aligned      # the code row the diffusion model read (`latents` is None: no dense pass ran)
-			return mels, seconds, aux
-		return mels, seconds
+			return (mels, seconds, aux) + alignment
+		return (mels, seconds) + alignment
 
 	@torch.inference_mode()
 	def inference_lines(self, lines, autoregressive_latents, diffusion_latents, *, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8,
 						diffusion_temp=1.0, top_p=1.0, top_k=0, repetition_penalty=1.0, length_penalty=1.0, cond_free=True,
 						candidates=1, suppress_tokens=None, ar_batch_lines=None, ddim_batch_lines=None, diffusion_conditioning="latents", do_sample=True,
 						diffusion_eta=0.0, diffusion_sampler="ddim", min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0,
-						mirostat_eta=0.1, beam_width=1):
+						mirostat_eta=0.1, beam_width=1, return_timings=False, alignment_heads=None):
 		"""The reference's `for line in lines` loop (inference.py:237-422) software-pipelined and batched:
 		(1) the autoregressive sampling of up to `ar_batch_lines` consecutive lines runs as ONE decode batch (UnifiedVoice.inference_speech_lines:
 		the GPT-2 weights are streamed once per token for all of them; default: as many as fit max_batch, at most 4; 1 = one line per batch);
@@ -371,7 +387,9 @@ class TTSHotPath:
 		beam_width > 1: as in `inference` -- every line is sampled by beam search, `candidates` <= beam_width finished beams come back per line -- with the lines of a
 		batch searched together (UnifiedVoice.beam_search_lines): min(4, max_batch // beam_width, 16 // beam_width) lines of beam_width rows each; everything behind
 		the sampling is as for beam_width 1.
-		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes)."""
+		`lines`: list of [1, Tt] int64 token tensors.  Returns a list of (mels [1, 100, T], seconds, codes).
+		return_timings / alignment_heads: as in `inference` -- the tuples are then (mels, seconds, codes, alignment); a line's alignment is issued on the sampling stream
+		right behind that line's latent pass, so it runs under the diffusion of the lines before it."""
 		from concurrent.futures import ThreadPoolExecutor
 		ar, diff = self.autoregressive, self.diffusion
 		dev = ar.device
@@ -431,7 +449,8 @@ class TTSHotPath:
 																num_return_sequences=candidates, num_beams=1, length_penalty=length_penalty,
 																repetition_penalty=repetition_penalty, max_generate_length=max_ar_steps, **extra)
 					ar.position_rng_after_line(i % G)       # the generators as this line's own `generate` leaves them
-					codes = fix_stop_tokens(batch_codes[i % G], ar.stop_mel_token)
+					raw = batch_codes[i % G]
+					codes = fix_stop_tokens(raw, ar.stop_mel_token)
 					B, M = codes.shape
 					best = 0                                                # candidate choice as in `inference`
 					if self.clvp is not None and B > 1:
@@ -443,6 +462,7 @@ class TTSHotPath:
 						al_row = autoregressive_latents if autoregressive_latents.shape[0] == 1 else autoregressive_latents[best:best + 1]
 						latents = ar.forward(al_row, text_tokens, torch.tensor([text_tokens.shape[1]], dtype=torch.int32), codes[best:best + 1],
 											 torch.tensor([M * ar.mel_length_compression]), return_latent=True, clip_inputs=False)
+					alignment = line_alignment(ar, autoregressive_latents, text_tokens, raw, best, alignment_heads) if return_timings else None
 					latents = trim_calm_tokens(codes[best:best + 1], latents)     # host copy of the codes: the AR phase of this line is complete
 					T = latents.shape[1] * 4 * 24000 // 22050
 					noise = torch.randn((1, 100, T), device=dev) * diffusion_temp
@@ -455,7 +475,7 @@ class TTSHotPath:
 						for _ in range(max_diffusion_steps):                    # DDIM's ignored per-step draws, in reference order
 							torch.randn_like(noise)
 					group.append((latents, noise, T, step_noise))
-					meta.append((T, codes))
+					meta.append((T, codes, alignment))
 					last_of_batch = (i % G == G - 1) or i == len(lines) - 1
 					if len(group) >= DG or last_of_batch:
 						ready = torch.cuda.Event()
@@ -463,8 +483,8 @@ class TTSHotPath:
 						pending.append((pool.submit(diffuse, group, ready), meta))
 						group, meta = [], []
 			for fut, meta in pending:
-				for mels, (T, codes) in zip(fut.result(), meta):
-					out.append((mels, T * HOP / SAMPLE_RATE, codes))
+				for mels, (T, codes, alignment) in zip(fut.result(), meta):
+					out.append((mels, T * HOP / SAMPLE_RATE, codes) + ((alignment,) if return_timings else ()))
 		main.wait_stream(s_ar)
 		main.wait_stream(s_df)
 		return out

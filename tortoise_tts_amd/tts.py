@@ -25,6 +25,12 @@ def set_seed(seed=None) -> int:
 	return seed
 
 
+def _collect_codes(pairs, sink):
+	for codes, latent in pairs:
+		sink.append(codes)
+		yield codes, latent
+
+
 class TTS:
 	def __init__(self, autoregressive, diffusion, tokenizer, *, vocoder=None, clvp=None, conditioning_encoder=None, contextual_embedder=None,
 				 tms: Optional[M.TorchMelSpectrogram] = None, stft: Optional[M.TacotronSTFT] = None, univnet=None, hifigan=None, dvae=None,
@@ -122,7 +128,8 @@ class TTS:
 	def inference(self, text: str, references=None, max_ar_steps=500, max_diffusion_steps=80, ar_temp=0.8, diffusion_temp=1.0, top_p=1.0, top_k=0,
 				  repetition_penalty=1.0, length_penalty=1.0, beam_width=1, diffusion_sampler="ddim", cond_free=True, vocoder_type="bigvgan",
 				  seed=None, candidates=1, references_sr: int = 22050, do_sample=True, *, diffusion_eta=0.0, min_ar_temp=None, repetition_penalty_decay=0.0,
-				  stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1) -> Tuple[torch.Tensor, int]:
+				  stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1, return_timings=False,
+				  alignment_heads=None) -> Union[Tuple[torch.Tensor, int], Tuple[torch.Tensor, int, list]]:
 		"""inference.py:142-425: every line of `text` spoken in the voice of `references` (clip tensor(s), or the dict `encode_audio` returns) ->
 		(wav [1, 1, samples] -- the lines concatenated in time -- , 24000).  vocoder_type "bigvgan" runs the `vocoder=` part, "vocoder" the
 		`univnet=` part (see `_univnet_wav` for its noise), "hifigan" the `hifigan=` part on the AR latents as they are sampled, without the
@@ -146,7 +153,15 @@ class TTS:
 		inference.py:154-163, for the samplers of its tortoise_tts/samplers.py) and stop_length_penalty (its length_penalize; `length_penalty` is HF's beam
 		ranking): the dynamic temperature's lower end, the distance decay of `repetition_penalty`, mirostat v1's target surprise and learning rate, the power
 		of the length that divides the stop token's score (> 0 longer lines).  Off by default (None, 0, 0, 0.1, 0): the call without them, bit for bit.  They
-		act on the sampling branch on every vocoder branch; not with beam_width > 1 or do_sample=False (see `UnifiedVoice.inference_speech`)."""
+		act on the sampling branch on every vocoder branch; not with beam_width > 1 or do_sample=False (see `UnifiedVoice.inference_speech`).
+		return_timings (keyword; no reference counterpart): True returns (wav, 24000, timings) -- one list of (word, start_s, end_s) per line, from
+		`UnifiedVoice.text_alignment` (heads: `alignment_heads`, a list of (layer, head); None = its default set) on the line's chosen code row as it was sampled,
+		before the stop-token rewrite; a word is a run of tokens between `[SPACE]` tokens, seconds = code index * mel_length_compression / 22050.  Entries are
+		clipped to the line's audio length (what the calm-token trim left of it) and offset by the samples of the lines before it.  Available on all three vocoder
+		branches: "bigvgan" / "vocoder" align behind each line's latent pass (`TTSHotPath.inference` / `inference_lines`), "hifigan" runs one dense pass on the
+		streamed codes after the line's stream has ended.  `self.last_alignments` then holds, per line, the `text_alignment` dict plus "codes" (the aligned row
+		[1, M]): `align(line, codes, voice)` gives that line's entries without clip and offset.  wav and sr are bit for bit those of the call without the
+		argument, which issues the launches it always did."""
 		from .inference import check_greedy, check_sampler_eta
 		knobs = dict(min_ar_temp=min_ar_temp, repetition_penalty_decay=repetition_penalty_decay, stop_length_penalty=stop_length_penalty, mirostat_tau=mirostat_tau,
 					 mirostat_eta=mirostat_eta)
@@ -180,22 +195,67 @@ class TTS:
 			if tokens.shape[1] == 0:
 				raise ValueError("empty line (the reference fails inside the embedding here)")
 			lines.append(tokens)
+		align_kw = dict(return_timings=True, alignment_heads=alignment_heads) if return_timings else {}
 		if vocoder_type == "hifigan":
-			wavs = [self._hifigan_wav(tokens, ar_latent, max_ar_steps=max_ar_steps, ar_temp=ar_temp, top_p=top_p, top_k=top_k,
-									  repetition_penalty=repetition_penalty, length_penalty=length_penalty, **knobs) for tokens in lines]
-			return torch.concat(wavs, dim=-1), SAMPLE_RATE
+			wavs, alignments = [], []
+			for tokens in lines:
+				streamed = [] if return_timings else None
+				wavs.append(self._hifigan_wav(tokens, ar_latent, max_ar_steps=max_ar_steps, ar_temp=ar_temp, top_p=top_p, top_k=top_k,
+											  repetition_penalty=repetition_penalty, length_penalty=length_penalty, codes_out=streamed, **knobs))
+				if return_timings:      # one dense pass on the streamed codes, after the stream has ended
+					from .inference import line_alignment
+					alignments.append(line_alignment(self.hot.autoregressive, ar_latent, tokens, torch.stack(streamed, dim=1), 0, alignment_heads))
+			return self._with_timings(torch.concat(wavs, dim=-1), wavs, lines, alignments) if return_timings else (torch.concat(wavs, dim=-1), SAMPLE_RATE)
 		kw = dict(max_ar_steps=max_ar_steps, max_diffusion_steps=max_diffusion_steps, ar_temp=ar_temp, diffusion_temp=diffusion_temp, top_p=top_p, top_k=top_k,
 				  repetition_penalty=repetition_penalty, length_penalty=length_penalty, cond_free=cond_free, candidates=candidates, do_sample=do_sample,
-				  diffusion_eta=diffusion_eta, **knobs)
+				  diffusion_eta=diffusion_eta, **knobs, **align_kw)
 		to_wav = self._univnet_wav if vocoder_type == "vocoder" else self.hot.vocoder.inference     # a line's mel [1, 100, T] -> its waveform
 		if len(lines) > 1 and diffusion_sampler in ("ddim", "dpm++2m"):
 			# several lines: their sampling as one decode batch -- beam_width > 1: the beams of a line exchange histories among themselves, the lines of a batch are
 			# searched together -- , the diffusion of a line under the sampling of later ones (TTSHotPath.inference_lines: the same waveforms as the line-by-line
 			# loop of inference.py:237-422, which is what the else branch runs)
-			wavs = [to_wav(mels) for mels, _, _ in self.hot.inference_lines(lines, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)]
+			res = self.hot.inference_lines(lines, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)
 		else:
-			wavs = [to_wav(self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw)[0]) for tokens in lines]
-		return torch.concat(wavs, dim=-1), SAMPLE_RATE
+			res = [self.hot.inference(tokens, ar_latent, diff_latent, diffusion_sampler=diffusion_sampler, beam_width=beam_width, **kw) for tokens in lines]
+		wavs = [to_wav(r[0]) for r in res]
+		wav = torch.concat(wavs, dim=-1)
+		return self._with_timings(wav, wavs, lines, [r[-1] for r in res]) if return_timings else (wav, SAMPLE_RATE)
+
+	def _with_timings(self, wav, wavs, lines, alignments):
+		"""(wav, 24000, timings): each line's alignment as words, clipped to the line's audio and offset by the samples before it"""
+		from . import alignment as AL
+		self.last_alignments = alignments
+		timings, offset = [], 0
+		for tokens, w, r in zip(lines, wavs, alignments):
+			t = AL.word_timings(self.tokenizer, tokens[0].tolist(), r["token_start"][0], r["codes"].shape[1], self.hot.autoregressive.mel_length_compression)
+			timings.append(AL.clip_and_offset(t, w.shape[-1] / SAMPLE_RATE, offset / SAMPLE_RATE))
+			offset += w.shape[-1]
+		return wav, SAMPLE_RATE, timings
+
+	def _word_timings(self, tokens: torch.Tensor, codes: torch.Tensor, ar_latent: torch.Tensor, heads=None, median_width: int = 7):
+		"""[(word, start_s, end_s)] of one line: tokens [1, Tt], codes [1, M]"""
+		from . import alignment as AL
+		ar = self.hot.autoregressive
+		r = ar.text_alignment(ar_latent, tokens, codes, heads=heads, median_width=median_width)
+		return AL.word_timings(self.tokenizer, tokens[0].tolist(), r["token_start"][0], codes.shape[1], ar.mel_length_compression)
+
+	@torch.inference_mode()
+	def align(self, text_line: Union[str, torch.Tensor], codes: torch.Tensor, references=None, *, references_sr: int = 22050, alignment_heads=None, median_width: int = 7):
+		"""Word timings of mel codes that exist already (for `decode_codes` / `resynthesize` users, or the "codes" of `last_alignments`): [(word, start_s, end_s)] of ONE
+		line of text against codes [1, M] (or [M]), seconds = code index * mel_length_compression / 22050, in the voice of `references` (clip tensor(s) or an
+		`encode_audio` dict; None: a random voice from the current generator state).  See `UnifiedVoice.text_alignment`; `alignment_heads` is its `heads`."""
+		if isinstance(text_line, str) and "\n" in text_line:
+			raise ValueError("align takes one line of text: lines of different length are aligned one call each")
+		tokens = self.encode_text(text_line).to(self.device)
+		tokens = tokens[None] if tokens.dim() == 1 else tokens
+		codes = torch.as_tensor(codes)
+		codes = codes[None] if codes.dim() == 1 else codes
+		if tokens.shape[1] == 0 or codes.dim() != 2 or codes.shape[0] != 1 or codes.shape[1] == 0:
+			raise ValueError("align: one non-empty line of text and codes [1, M]")
+		if references is None:
+			references = self.random_voice()
+		ar_latent = self.encode_audio(references, references_sr)["latent"][0]
+		return self._word_timings(tokens, codes.to(self.device), ar_latent, alignment_heads, median_width)
 
 	@torch.inference_mode()
 	def decode_codes(self, codes, references=None, *, max_diffusion_steps=80, diffusion_temp=1.0, diffusion_sampler="ddim", cond_free=True,
@@ -278,17 +338,20 @@ class TTS:
 		return self.univnet.inference(mels, z)
 
 	def hifigan_chunks(self, tokens: torch.Tensor, ar_latent: torch.Tensor, *, max_ar_steps=500, ar_temp=0.8, top_p=1.0, top_k=0, repetition_penalty=1.0,
-					   length_penalty=1.0, min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1):
+					   length_penalty=1.0, min_ar_temp=None, repetition_penalty_decay=0.0, stop_length_penalty=0.0, mirostat_tau=0.0, mirostat_eta=0.1, codes_out=None):
 		"""One line of the HiFiGAN branch (inference.py:250-320) as a generator of waveform chunks [1, samples]: `compute_embeddings` ->
 		`get_generator` -> `HiFiGAN.stream`.  The first chunk is there after 60 tokens, while sampling goes on.  `max_length` is
 		min(500, prefix + max_ar_steps): the reference hard-codes 500 in total (stream_generator defaults) and ignores `max_ar_steps`; the
-		default call is the same.  min_ar_temp ... mirostat_eta: the reference's own samplers, as in `inference`; off by default."""
+		default call is the same.  min_ar_temp ... mirostat_eta: the reference's own samplers, as in `inference`; off by default.
+		codes_out: a list that receives every streamed code tensor [1] as it is yielded (views of the generator's own buffer: no launch is added)."""
 		from .inference import ar_sampler_knobs
 		ar = self.hot.autoregressive
 		inputs = ar.compute_embeddings(ar_latent, tokens)
 		pairs = ar.get_generator(inputs=inputs, max_length=min(500, inputs.shape[1] + max_ar_steps), top_k=top_k, top_p=top_p, temperature=ar_temp,
 								 do_sample=True, num_return_sequences=1, length_penalty=length_penalty, repetition_penalty=repetition_penalty,
 								 **ar_sampler_knobs(min_ar_temp, repetition_penalty_decay, stop_length_penalty, mirostat_tau, mirostat_eta))
+		if codes_out is not None:
+			pairs = _collect_codes(pairs, codes_out)
 		chunks = self.hifigan.stream(pairs, ar_latent)
 		while True:
 			with torch.inference_mode():      # per step, not around the yield: the consumer's own mode is its own between two chunks
