@@ -906,6 +906,42 @@ int ttk_hifi_conv_rows(const ttk_hifi_conv_desc* d, void* stream);
  * exponentiated; invb = 1 / (b + 1e-9)), filt12 f32 [12].  C % 4 == 0, x, a, invb 16-byte aligned, x and y do not overlap.                               */
 int ttk_snake_rows(int dtype, const float* x, int B, int L, int C, const float* a, const float* invb, const float* filt12, void* y, void* stream);
 
+/* ------------------------------------------------------------------ the side networks' own kernels on caller-provided operands
+ * No reference counterpart: exposed so the kernels of the conditioning encoders, the classifier's AttentionBlocks and CLVP that the hot path does not share
+ * (csrc/ttk_attn_block.h: k_cond_gn, k_attn_rowwave; csrc/cond.hip: k_cond_im2col, k_cond_pool; csrc/clvp.hip: k_embed_rows, k_rmsnorm, k_rotary, k_geglu,
+ * k_mean_rows, k_clvp_score) can be held, element by element, to a float64 reference of the same operands (tests/test_gpu_side_forms.py with tests/side_ref.py).
+ * Each goes through the launch function its handle uses.  dtype (T) is TTK_F32 | TTK_BF16.  Every one returns TTK_E_ARG with a message, and launches nothing, when
+ * a precondition its kernel relies on fails.
+ *
+ * ttk_block_gn_rows: out T [nb][T][C] = gn(x) gamma + beta over x f32 [nb][T][C], `groups` groups of C / groups channels (any width), two-pass biased variance,
+ *   eps 1e-5.  C % groups == 0, nb <= 65535.
+ * ttk_attn_rowwave: ttk_attn_fwd's operation for head width 128 (out column h * 128 + d), one wave per query row, f32 arithmetic with the scores of a row in LDS:
+ *   1 <= T <= 3584.  The descriptor is ttk_attn_desc; causal, tlen, out_f8 and form must be 0 / null.  head_stride >= 128, every head inside ld, ldo >= H * 128;
+ *   qkv aligned to 8 elements, ld, k_off and head_stride multiples of 8 (k is read 8 elements at a time); qkv and out do not overlap.
+ * ttk_cond_im2col_rows: out T [nb * Tout][Kpad], out[(b, t)][c * taps + j] = src[b * sb + c * sc + (t * stride + j - pad) * st] where that position lies in
+ *   [0, Tin), else 0; columns Cin * taps .. Kpad are zeros.  src f32 with element strides (sb, sc, st): channels-first or channels-last.  Kpad >= Cin * taps.
+ * ttk_cond_pool_rows: out f32 [nb][C] = row 0 (mode 0) or the mean over the T rows, added in rising t and divided once (mode 1), of x f32 [nb][T][C].             */
+int ttk_block_gn_rows(int dtype, const float* x, int nb, int T, int C, int groups, const float* gamma, const float* beta, void* out, void* stream);
+int ttk_attn_rowwave(int dtype, const ttk_attn_desc* d, void* stream);
+int ttk_cond_im2col_rows(int dtype, const float* src, int64_t sb, int64_t sc, int64_t st, int nb, int Cin, int Tin, int Tout, int taps, int stride, int pad, int Kpad,
+						 void* out, void* stream);
+int ttk_cond_pool_rows(const float* x, int nb, int T, int C, int mode, float* out, void* stream);
+/* ttk_clvp_embed_rows: out f32 [B * S][d] = emb[clamp(ids[b * batch_stride_ids + t], 0, vocab - 1)], emb f32 [vocab][d]; d % 64 == 0, batch_stride_ids >= S, emb and
+ *   out 16-byte aligned.
+ * ttk_clvp_rmsnorm_rows: y T [rows][d] = x / max(|x| d^-1/2, 1e-8) g over x f32 [rows][d] (a zero row gives zeros); d % 64 == 0, x and g 16-byte aligned.
+ * ttk_clvp_rotary_rows: the rotary embedding IN PLACE on features 0..31 of every head of q, k and v of qkv T [B * S][3 * H * 64]: for i < 16,
+ *   (x_i, x_{i+16}) -> (x_i cos a - x_{i+16} sin a, x_{i+16} cos a + x_i sin a), a = (row % S) inv_freq[i], inv_freq f32 [16]; features 32..63 are not touched.
+ * ttk_clvp_geglu_rows: out T [rows][inner] = h[r][c] gelu(h[r][inner + c]) over h T [rows][2 * inner], gelu exact (erf); h and out do not overlap.
+ * ttk_clvp_mean_rows: out T [B][d] = the mean over the S rows of x f32 [B][S][d], added in rising t and divided once; d % 64 == 0.
+ * ttk_clvp_latent_score: scores f32 [B] = <t, s_b> / (max(|t|, 1e-12) max(|s_b|, 1e-12)) exp(temperature[0]), t = text_latents row 0 (Bt == 1) or b (Bt == B),
+ *   latents f32 [.][d], temperature device f32 [1]; d % 64 == 0.                                                                                              */
+int ttk_clvp_embed_rows(const float* emb, int vocab, int d, const int64_t* ids, int B, int S, int batch_stride_ids, float* out, void* stream);
+int ttk_clvp_rmsnorm_rows(int dtype, const float* x, int64_t rows, int d, const float* g, void* y, void* stream);
+int ttk_clvp_rotary_rows(int dtype, void* qkv, int B, int S, int H, const float* inv_freq, void* stream);
+int ttk_clvp_geglu_rows(int dtype, const void* h, int64_t rows, int inner, void* out, void* stream);
+int ttk_clvp_mean_rows(int dtype, const float* x, int B, int S, int d, void* out, void* stream);
+int ttk_clvp_latent_score(const float* text_latents, int Bt, const float* speech_latents, int B, int d, const float* temperature, float* scores, void* stream);
+
 /* ------------------------------------------------------------------ the weight-streaming decode launches on caller-provided operands
  * No reference counterpart: exposed so every launch form of csrc/skinny.hip (k_skinny) and csrc/gemv.hip (k_gemv) can be tested against a float64
  * LN(x) W^T + b of the same operands, element by element (tests/test_gpu_skinny_forms.py).

@@ -1,5 +1,7 @@
 """CLVP scoring on libttk against the reference model's scores (tests/golden/clvp_small.npz) and the oracle.
-GPU only; calls go through the C ABI (`ttk_clvp_*`)."""
+GPU only; calls go through the C ABI (`ttk_clvp_*`).
+These are model-level checks of one score per candidate; CLVP's own kernels (embedding rows, RMSNorm, rotary, GEGLU, the mean over positions, the score) are
+held element by element to a float64 reference in tests/test_gpu_side_forms.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,5 +1,7 @@
 """Conditioning-latent encoders on libttk against the reference's `get_conditioning` outputs
-(tests/golden/cond_small.npz, cond_full.npz) and the oracle.  GPU only; calls go through the C ABI (`ttk_cond_*`)."""
+(tests/golden/cond_small.npz, cond_full.npz) and the oracle.  GPU only; calls go through the C ABI (`ttk_cond_*`).
+These are model-level checks of one pooled latent; the encoders' own kernels (GroupNorm, the row-wave attention, im2col, pooling) are held element by element
+to a float64 reference in tests/test_gpu_side_forms.py."""
 import numpy as np
 import pytest
 import torch

@@ -246,6 +246,16 @@ SYMBOLS = {
 	"ttk_lvc_rows": (_I, [_I, C.POINTER(LvcDesc), _P]),
 	"ttk_hifi_conv_rows": (_I, [C.POINTER(HifiConvDesc), _P]),
 	"ttk_snake_rows": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+	"ttk_block_gn_rows": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+	"ttk_attn_rowwave": (_I, [_I, C.POINTER(AttnDesc), _P]),
+	"ttk_cond_im2col_rows": (_I, [_I, _P, _L, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+	"ttk_cond_pool_rows": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+	"ttk_clvp_embed_rows": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P]),
+	"ttk_clvp_rmsnorm_rows": (_I, [_I, _P, _L, _I, _P, _P, _P]),
+	"ttk_clvp_rotary_rows": (_I, [_I, _P, _I, _I, _I, _P, _P]),
+	"ttk_clvp_geglu_rows": (_I, [_I, _P, _L, _I, _P, _P]),
+	"ttk_clvp_mean_rows": (_I, [_I, _P, _I, _I, _I, _P, _P]),
+	"ttk_clvp_latent_score": (_I, [_P, _I, _P, _I, _I, _P, _P, _P]),
 	"ttk_gemv_mat_create": (_I, [C.POINTER(_P), C.POINTER(GemvMatConfigC), C.POINTER(WeightView), _I]),
 	"ttk_gemv_mat_destroy": (_I, [_P]),
 	"ttk_gemv_launch": (_I, [_P, C.POINTER(GemvDesc), _P]),

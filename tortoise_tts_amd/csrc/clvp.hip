@@ -102,6 +102,33 @@ __global__ __launch_bounds__(64) void k_clvp_score(const float* tl, int Bt, cons
 	if (lane == 0) scores[b] = ts / (fmaxf(sqrtf(tt), 1e-12f) * fmaxf(sqrtf(ss), 1e-12f)) * expf(*temperature);
 }
 
+// The launches of the kernels above, each described once: encode_t / ttk_clvp_score and the entry points on caller-provided operands both go through them.
+void launch_embed_rows(const float* emb, int vocab, int d, const int64_t* ids, int B, int S, int ids_stride, float* out, hipStream_t s) {
+	const int64_t rows = (int64_t)B * S, total = rows * (d / 4);
+	hipLaunchKernelGGL(k_embed_rows, dim3(grid_for(total)), dim3(256), 0, s, emb, ids, (int64_t)S, ids_stride, out, rows, d, vocab);
+}
+template <typename T>
+void launch_rmsnorm(const float* x, int64_t rows, int d, const float* g, T* y, hipStream_t s) {
+	hipLaunchKernelGGL((k_rmsnorm<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, g, y);
+}
+template <typename T>
+void launch_rotary(T* qkv, int64_t rows, int S, int H, const float* inv_freq, hipStream_t s) {
+	const int64_t total = rows * 3 * H * 16;
+	hipLaunchKernelGGL((k_rotary<T>), dim3(grid_for(total)), dim3(256), 0, s, qkv, rows, S, H, inv_freq);
+}
+template <typename T>
+void launch_geglu(const T* h, int64_t rows, int inner, T* out, hipStream_t s) {
+	const int64_t total = rows * inner;
+	hipLaunchKernelGGL((k_geglu<T>), dim3(grid_for(total)), dim3(256), 0, s, h, rows, inner, out);
+}
+template <typename T>
+void launch_mean_rows(const float* x, int B, int S, int d, T* out, hipStream_t s) {
+	hipLaunchKernelGGL((k_mean_rows<T>), dim3(grid_for(B * d)), dim3(256), 0, s, x, B, S, d, out);
+}
+void launch_clvp_score(const float* tl, int Bt, const float* sl, int B, int d, const float* temperature, float* scores, hipStream_t s) {
+	hipLaunchKernelGGL(k_clvp_score, dim3(B), dim3(64), 0, s, tl, Bt, sl, d, temperature, scores);
+}
+
 struct EncLayer { float *g_attn = nullptr, *g_ff = nullptr; Mat qkv, out, ff1, ff2; };
 struct Encoder { float* emb = nullptr; int vocab = 0; std::vector<EncLayer> L; float *norm_g = nullptr, *norm_b = nullptr; Mat to_latent; };
 
@@ -142,33 +169,24 @@ void encode_t(ttk_clvp* h, const Ws& w, const Encoder& e, const int64_t* ids, in
 	char* base = (char*)h->ws.p;
 	float* x = (float*)(base + w.x);
 	T *xn = (T*)(base + w.xn), *qkv = (T*)(base + w.qkv), *ao = (T*)(base + w.ao);
-	{
-		const int64_t total = rows * (d / 4);
-		hipLaunchKernelGGL(k_embed_rows, dim3(grid_for(total)), dim3(256), 0, s, e.emb, ids, (int64_t)S, ids_stride, x, rows, d, e.vocab);
-	}
+	launch_embed_rows(e.emb, e.vocab, d, ids, B, S, ids_stride, x, s);
 	for (const EncLayer& L : e.L) {
-		hipLaunchKernelGGL((k_rmsnorm<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, L.g_attn, xn);
+		launch_rmsnorm<T>(x, rows, d, L.g_attn, xn, s);
 		gemm_plain(dt, xn, d, L.qkv, (int)rows, nullptr, qkv, 0, s);
-		{
-			const int64_t total = rows * 3 * H * 16;
-			hipLaunchKernelGGL((k_rotary<T>), dim3(grid_for(total)), dim3(256), 0, s, qkv, rows, S, H, h->inv_freq);
-		}
+		launch_rotary<T>(qkv, rows, S, H, h->inv_freq, s);
 		AttnParams a = {};
 		a.qkv = qkv; a.ld = 3 * d; a.q_off = 0; a.k_off = d; a.v_off = 2 * d; a.head_stride = 64; a.out = ao; a.ldo = d;
 		a.nb = B; a.T = S; a.H = H; a.causal = 0; a.bias = nullptr; a.scale = 0.125f;
 		launch_attn_fwd(dt, a, s);
 		gemm_plain(dt, ao, d, L.out, (int)rows, x, x, 1, s);
-		hipLaunchKernelGGL((k_rmsnorm<T>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, d, L.g_ff, xn);
+		launch_rmsnorm<T>(x, rows, d, L.g_ff, xn, s);
 		gemm_plain(dt, xn, d, L.ff1, (int)rows, nullptr, qkv, 0, s);
-		{
-			const int64_t total = rows * inner;
-			hipLaunchKernelGGL((k_geglu<T>), dim3(grid_for(total)), dim3(256), 0, s, qkv, rows, inner, ao);
-		}
+		launch_geglu<T>(qkv, rows, inner, ao, s);
 		gemm_plain(dt, ao, inner, L.ff2, (int)rows, x, x, 1, s);
 	}
 	float* xf = (float*)qkv;                                         // final LayerNorm output, f32 [rows][d] (the qkv buffer is free now)
 	launch_layernorm(dt, x, d, (int)rows, d, e.norm_g, e.norm_b, nullptr, nullptr, xf, d, 1, s);
-	hipLaunchKernelGGL((k_mean_rows<T>), dim3(grid_for(B * d)), dim3(256), 0, s, xf, B, S, d, xn);
+	launch_mean_rows<T>(xf, B, S, d, xn, s);
 	gemm_plain(dt, xn, d, e.to_latent, B, nullptr, latent, 1, s);
 }
 
@@ -237,7 +255,81 @@ int ttk_clvp_score(ttk_clvp* h, const int64_t* text, int Bt, int Tt, const int64
 		encode_t<T>(h, w, h->text, text, Bt, Tt, Tt, tl, s);
 		encode_t<T>(h, w, h->speech, codes, B, M, M, sl, s);
 	});
-	hipLaunchKernelGGL(k_clvp_score, dim3(B), dim3(64), 0, s, tl, Bt, sl, d, h->temperature, scores);
+	launch_clvp_score(tl, Bt, sl, B, d, h->temperature, scores, s);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+// ---- the encoders' small kernels on caller-provided operands (tests/test_gpu_side_forms.py), through the launches encode_t and ttk_clvp_score use
+static bool side_dtype(int dtype) { return dtype == TTK_F32 || dtype == TTK_BF16; }
+static bool aligned_to(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
+static const int64_t kMaxElems = (int64_t)1 << 38;      // elements of one launch: 2^30 workgroups of 256 threads
+
+int ttk_clvp_embed_rows(const float* emb, int vocab, int d, const int64_t* ids, int B, int S, int batch_stride_ids, float* out, void* stream) {
+	TTK_REQUIRE(emb && ids && out, TTK_E_ARG, "ttk_clvp_embed_rows: null argument");
+	TTK_REQUIRE(vocab >= 1 && B >= 1 && S >= 1, TTK_E_ARG, "ttk_clvp_embed_rows: vocab = %d, B = %d, S = %d out of range (each >= 1)", vocab, B, S);
+	TTK_REQUIRE(d >= 64 && d % 64 == 0, TTK_E_ARG, "ttk_clvp_embed_rows: d = %d is not a positive multiple of 64", d);
+	TTK_REQUIRE(batch_stride_ids >= S, TTK_E_ARG, "ttk_clvp_embed_rows: batch_stride_ids = %d < S = %d", batch_stride_ids, S);
+	TTK_REQUIRE((int64_t)B * S * d <= kMaxElems, TTK_E_ARG, "ttk_clvp_embed_rows: %d x %d x %d elements are too many for one launch", B, S, d);
+	TTK_REQUIRE(aligned_to(emb, 16) && aligned_to(out, 16) && aligned_to(ids, 8), TTK_E_ARG, "ttk_clvp_embed_rows: emb and out must be 16-byte aligned (float4 copies), ids 8-byte aligned");
+	launch_embed_rows(emb, vocab, d, ids, B, S, batch_stride_ids, out, (hipStream_t)stream);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_clvp_rmsnorm_rows(int dtype, const float* x, int64_t rows, int d, const float* g, void* y, void* stream) {
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_clvp_rmsnorm_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(x && g && y, TTK_E_ARG, "ttk_clvp_rmsnorm_rows: null argument");
+	TTK_REQUIRE(rows >= 1 && rows <= ((int64_t)1 << 31), TTK_E_ARG, "ttk_clvp_rmsnorm_rows: rows = %lld out of range (1..2^31)", (long long)rows);
+	TTK_REQUIRE(d >= 64 && d % 64 == 0, TTK_E_ARG, "ttk_clvp_rmsnorm_rows: d = %d is not a positive multiple of 64", d);
+	TTK_REQUIRE(aligned_to(x, 16) && aligned_to(g, 16) && aligned_to(y, dtype == TTK_BF16 ? 2 : 4), TTK_E_ARG, "ttk_clvp_rmsnorm_rows: x and g must be 16-byte aligned (float4 loads), y for its element type");
+	by_f32_bf16(dtype, [&](auto t) { using T = decltype(t); launch_rmsnorm<T>(x, rows, d, g, (T*)y, (hipStream_t)stream); });
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_clvp_rotary_rows(int dtype, void* qkv, int B, int S, int H, const float* inv_freq, void* stream) {
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_clvp_rotary_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(qkv && inv_freq, TTK_E_ARG, "ttk_clvp_rotary_rows: null argument");
+	TTK_REQUIRE(B >= 1 && S >= 1 && H >= 1 && H <= 1024, TTK_E_ARG, "ttk_clvp_rotary_rows: B = %d, S = %d, H = %d out of range (each >= 1, H <= 1024)", B, S, H);
+	TTK_REQUIRE((int64_t)B * S * 3 * H * 16 <= kMaxElems, TTK_E_ARG, "ttk_clvp_rotary_rows: %d x %d rows of %d heads are too many for one launch", B, S, H);
+	TTK_REQUIRE(aligned_to(qkv, dtype == TTK_BF16 ? 2 : 4) && aligned_to(inv_freq, 4), TTK_E_ARG, "ttk_clvp_rotary_rows: qkv or inv_freq is misaligned for its element type");
+	by_f32_bf16(dtype, [&](auto t) { using T = decltype(t); launch_rotary<T>((T*)qkv, (int64_t)B * S, S, H, inv_freq, (hipStream_t)stream); });
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_clvp_geglu_rows(int dtype, const void* h, int64_t rows, int inner, void* out, void* stream) {
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_clvp_geglu_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(h && out, TTK_E_ARG, "ttk_clvp_geglu_rows: null argument");
+	TTK_REQUIRE(rows >= 1 && inner >= 1 && rows <= kMaxElems / inner, TTK_E_ARG, "ttk_clvp_geglu_rows: rows = %lld, inner = %d out of range", (long long)rows, inner);
+	const int64_t es = dtype == TTK_BF16 ? 2 : 4;
+	TTK_REQUIRE(aligned_to(h, es) && aligned_to(out, es), TTK_E_ARG, "ttk_clvp_geglu_rows: h or out is misaligned for its element type");
+	TTK_REQUIRE(!((const char*)h < (const char*)out + rows * inner * es && (const char*)out < (const char*)h + rows * 2 * inner * es), TTK_E_ARG,
+				"ttk_clvp_geglu_rows: h and out overlap");
+	by_f32_bf16(dtype, [&](auto t) { using T = decltype(t); launch_geglu<T>((const T*)h, rows, inner, (T*)out, (hipStream_t)stream); });
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_clvp_mean_rows(int dtype, const float* x, int B, int S, int d, void* out, void* stream) {
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_clvp_mean_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(x && out, TTK_E_ARG, "ttk_clvp_mean_rows: null argument");
+	TTK_REQUIRE(B >= 1 && S >= 1 && d >= 64 && d % 64 == 0 && (int64_t)B * d <= ((int64_t)1 << 30), TTK_E_ARG,
+				"ttk_clvp_mean_rows: B = %d, S = %d, d = %d out of range (B, S >= 1, d a positive multiple of 64, B * d <= 2^30)", B, S, d);
+	TTK_REQUIRE(aligned_to(x, 4) && aligned_to(out, dtype == TTK_BF16 ? 2 : 4), TTK_E_ARG, "ttk_clvp_mean_rows: x or out is misaligned for its element type");
+	by_f32_bf16(dtype, [&](auto t) { using T = decltype(t); launch_mean_rows<T>(x, B, S, d, (T*)out, (hipStream_t)stream); });
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_clvp_latent_score(const float* text_latents, int Bt, const float* speech_latents, int B, int d, const float* temperature, float* scores, void* stream) {
+	TTK_REQUIRE(text_latents && speech_latents && temperature && scores, TTK_E_ARG, "ttk_clvp_latent_score: null argument");
+	TTK_REQUIRE(B >= 1 && (Bt == 1 || Bt == B), TTK_E_ARG, "ttk_clvp_latent_score: bad shape (Bt = %d, B = %d: Bt == 1 or Bt == B)", Bt, B);
+	TTK_REQUIRE(d >= 64 && d % 64 == 0, TTK_E_ARG, "ttk_clvp_latent_score: d = %d is not a positive multiple of 64", d);
+	TTK_REQUIRE(aligned_to(text_latents, 4) && aligned_to(speech_latents, 4) && aligned_to(temperature, 4) && aligned_to(scores, 4), TTK_E_ARG,
+				"ttk_clvp_latent_score: an operand is misaligned");
+	launch_clvp_score(text_latents, Bt, speech_latents, B, d, temperature, scores, (hipStream_t)stream);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }

@@ -49,6 +49,17 @@ __global__ __launch_bounds__(256) void k_cond_pool(const float* __restrict__ x, 
 	out[(int64_t)b * C + c] = s;
 }
 
+// The launches of the two kernels above, each described once: encode_t and the entry points on caller-provided operands both go through them.
+template <typename T>
+void launch_cond_im2col(const float* src, int64_t sb, int64_t sc, int64_t st, int nb, int Cin, int Tin, int Tout, int taps, int stride, int pad, int Kpad, T* out,
+						hipStream_t s) {
+	const int64_t total = (int64_t)nb * Tout * Kpad;
+	hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total)), dim3(256), 0, s, src, sb, sc, st, Cin, Tin, Tout, taps, stride, pad, Kpad, total, out);
+}
+void launch_cond_pool(const float* x, int nb, int T, int C, int mode, float* out, hipStream_t s) {
+	hipLaunchKernelGGL(k_cond_pool, dim3(grid_for(C), nb), dim3(256), 0, s, x, T, C, mode, out);
+}
+
 }  // namespace
 
 struct ttk_cond {
@@ -83,25 +94,20 @@ int encode_t(ttk_cond* h, const float* mel, int b, int Tf, float* out, hipStream
 	char* sp = (char*)h->ws.p + o_sp;
 	{
 		T* a0 = (T*)(sp + o_a0);
-		const int64_t total = (int64_t)b * T1 * h->stem0.Kpad;
 		if (down4) {
 			float* y = (float*)(sp + o_y);
 			T* a1 = (T*)(sp + o_a1);
-			hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total)), dim3(256), 0, s, mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1,
-							   c.in_channels, Tf, T1, 3, 2, 1, h->stem0.Kpad, total, a0);
+			launch_cond_im2col<T>(mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1, b, c.in_channels, Tf, T1, 3, 2, 1, h->stem0.Kpad, a0, s);
 			gemm_plain(dt, a0, h->stem0.Kpad, h->stem0, b * T1, nullptr, y, 1, s);
-			const int64_t total1 = rows * h->stem1.Kpad;
-			hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total1)), dim3(256), 0, s, y, (int64_t)T1 * (C / 2), (int64_t)1, (int64_t)(C / 2),
-							   C / 2, T1, T2, 3, 2, 1, h->stem1.Kpad, total1, a1);
+			launch_cond_im2col<T>(y, (int64_t)T1 * (C / 2), (int64_t)1, (int64_t)(C / 2), b, C / 2, T1, T2, 3, 2, 1, h->stem1.Kpad, a1, s);
 			gemm_plain(dt, a1, h->stem1.Kpad, h->stem1, (int)rows, nullptr, x, 1, s);
 		} else {
-			hipLaunchKernelGGL((k_cond_im2col<T>), dim3(grid_for(total)), dim3(256), 0, s, mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1,
-							   c.in_channels, Tf, Tf, 1, 1, 0, h->stem0.Kpad, total, a0);
+			launch_cond_im2col<T>(mel, (int64_t)c.in_channels * Tf, (int64_t)Tf, (int64_t)1, b, c.in_channels, Tf, Tf, 1, 1, 0, h->stem0.Kpad, a0, s);
 			gemm_plain(dt, a0, h->stem0.Kpad, h->stem0, (int)rows, nullptr, x, 1, s);
 		}
 	}
 	attn_blocks<T>(dt, h->blocks, x, b, T2, C, h->groups, c.num_heads, (T*)(sp + o_a), (T*)(sp + o_qkv), (T*)(sp + o_ao), s);
-	hipLaunchKernelGGL(k_cond_pool, dim3(grid_for(C), b), dim3(256), 0, s, x, T2, C, c.pool, out);
+	launch_cond_pool(x, b, T2, C, c.pool, out, s);
 	TTK_HIP(hipGetLastError());
 	return TTK_OK;
 }
@@ -151,6 +157,81 @@ int ttk_cond_encode(ttk_cond* h, const float* mel, int b, int T, float* out, voi
 	TTK_REQUIRE(b >= 1 && T >= 1, TTK_E_ARG, "ttk_cond_encode: empty input (b=%d T=%d)", b, T);
 	TTK_REQUIRE(T <= 8192, TTK_E_ARG, "ttk_cond_encode: %d frames exceed the 8192-frame limit of a conditioning clip", T);
 	return by_f32_bf16(h->dt, [&](auto t) { return encode_t<decltype(t)>(h, mel, b, T, out, (hipStream_t)stream); });
+}
+
+// ---- the AttentionBlock's and the stem's own kernels on caller-provided operands (tests/test_gpu_side_forms.py), through the launches encode_t and attn_blocks use
+static bool side_dtype(int dtype) { return dtype == TTK_F32 || dtype == TTK_BF16; }
+static bool aligned_to(const void* p, size_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
+
+int ttk_block_gn_rows(int dtype, const float* x, int nb, int T, int C, int groups, const float* gamma, const float* beta, void* out, void* stream) {
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_block_gn_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(x && gamma && beta && out, TTK_E_ARG, "ttk_block_gn_rows: null argument");
+	TTK_REQUIRE(nb >= 1 && nb <= 65535 && T >= 1 && C >= 1 && groups >= 1, TTK_E_ARG, "ttk_block_gn_rows: nb = %d, T = %d, C = %d, groups = %d out of range (each >= 1, nb <= 65535)", nb, T, C, groups);
+	TTK_REQUIRE(C % groups == 0, TTK_E_ARG, "ttk_block_gn_rows: C = %d is not a multiple of groups = %d", C, groups);
+	TTK_REQUIRE((int64_t)T * (C / groups) <= INT32_MAX, TTK_E_ARG, "ttk_block_gn_rows: %d rows x %d channels per group exceed one workgroup's int index", T, C / groups);
+	TTK_REQUIRE(aligned_to(x, 4) && aligned_to(gamma, 4) && aligned_to(beta, 4) && aligned_to(out, dtype == TTK_BF16 ? 2 : 4), TTK_E_ARG,
+				"ttk_block_gn_rows: an operand is misaligned for its element type");
+	by_f32_bf16(dtype, [&](auto t) { using OT = decltype(t); launch_cond_gn<OT>(x, nb, T, C, groups, gamma, beta, (OT*)out, (hipStream_t)stream); });
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_attn_rowwave(int dtype, const ttk_attn_desc* d, void* stream) {
+	TTK_REQUIRE(d, TTK_E_ARG, "ttk_attn_rowwave: null descriptor");
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_attn_rowwave: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(d->qkv && d->out, TTK_E_ARG, "ttk_attn_rowwave: null qkv or out");
+	TTK_REQUIRE(!d->causal && !d->tlen && !d->out_f8 && d->form == 0, TTK_E_ARG, "ttk_attn_rowwave: causal, tlen, out_f8 and form are not served by the row-wave kernel");
+	TTK_REQUIRE(d->nb >= 1 && d->nb <= 65535 && d->H >= 1 && d->H <= 65535, TTK_E_ARG, "ttk_attn_rowwave: nb = %d, H = %d out of range (1..65535)", d->nb, d->H);
+	TTK_REQUIRE(d->T >= 1 && d->T <= kRowWaveMaxT, TTK_E_ARG, "ttk_attn_rowwave: T = %d outside 1..%d (the scores of 4 query rows live in LDS)", d->T, kRowWaveMaxT);
+	TTK_REQUIRE(d->q_off >= 0 && d->k_off >= 0 && d->v_off >= 0 && d->head_stride >= 128, TTK_E_ARG, "ttk_attn_rowwave: negative offset or head_stride < 128 (the head width is 128)");
+	const int64_t span = (int64_t)(d->H - 1) * d->head_stride + 128;
+	TTK_REQUIRE(d->ld <= ((int64_t)1 << 30) && d->ldo <= ((int64_t)1 << 30) && d->q_off + span <= d->ld && d->k_off + span <= d->ld && d->v_off + span <= d->ld, TTK_E_ARG, "ttk_attn_rowwave: ld = %lld does not hold %d heads of width 128 at the given offsets",
+				(long long)d->ld, d->H);
+	TTK_REQUIRE(d->ldo >= (int64_t)d->H * 128, TTK_E_ARG, "ttk_attn_rowwave: ldo = %lld < H * 128", (long long)d->ldo);
+	const size_t es = dtype == TTK_BF16 ? 2 : 4;
+	TTK_REQUIRE(aligned_to(d->qkv, 8 * es) && d->ld % 8 == 0 && d->k_off % 8 == 0 && d->head_stride % 8 == 0, TTK_E_ARG,
+				"ttk_attn_rowwave: k is read 8 elements at a time: qkv must be aligned to 8 elements (16-byte aligned at least) and ld, k_off, head_stride multiples of 8");
+	TTK_REQUIRE(aligned_to(d->out, es) && (!d->bias || aligned_to(d->bias, 4)), TTK_E_ARG, "ttk_attn_rowwave: out or bias is misaligned for its element type");
+	{
+		const char *a = (const char*)d->qkv, *o = (const char*)d->out;
+		const int64_t rows = (int64_t)d->nb * d->T;
+		TTK_REQUIRE(!(a < o + rows * d->ldo * (int64_t)es && o < a + rows * d->ld * (int64_t)es), TTK_E_ARG, "ttk_attn_rowwave: qkv and out overlap");
+	}
+	AttnParams ap = {};
+	ap.qkv = d->qkv; ap.ld = d->ld; ap.q_off = d->q_off; ap.k_off = d->k_off; ap.v_off = d->v_off; ap.head_stride = d->head_stride;
+	ap.out = d->out; ap.ldo = d->ldo; ap.nb = d->nb; ap.T = d->T; ap.H = d->H; ap.causal = 0; ap.bias = d->bias; ap.scale = d->scale;
+	by_f32_bf16(dtype, [&](auto t) { launch_attn_rowwave<decltype(t)>(ap, (hipStream_t)stream); });
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_cond_im2col_rows(int dtype, const float* src, int64_t sb, int64_t sc, int64_t st, int nb, int Cin, int Tin, int Tout, int taps, int stride, int pad, int Kpad,
+						 void* out, void* stream) {
+	TTK_REQUIRE(side_dtype(dtype), TTK_E_ARG, "ttk_cond_im2col_rows: bad dtype %d (f32 or bf16)", dtype);
+	TTK_REQUIRE(src && out, TTK_E_ARG, "ttk_cond_im2col_rows: null argument");
+	TTK_REQUIRE(nb >= 1 && Cin >= 1 && Tin >= 1 && Tout >= 1 && taps >= 1 && stride >= 1 && pad >= 0, TTK_E_ARG,
+				"ttk_cond_im2col_rows: nb = %d, Cin = %d, Tin = %d, Tout = %d, taps = %d, stride = %d, pad = %d out of range", nb, Cin, Tin, Tout, taps, stride, pad);
+	TTK_REQUIRE((int64_t)Cin * taps <= Kpad, TTK_E_ARG, "ttk_cond_im2col_rows: Kpad = %d < Cin * taps = %lld", Kpad, (long long)Cin * taps);
+	TTK_REQUIRE((int64_t)(Tout - 1) * stride + taps <= INT32_MAX, TTK_E_ARG, "ttk_cond_im2col_rows: source positions exceed an int");
+	TTK_REQUIRE((int64_t)nb * Tout * Kpad <= ((int64_t)1 << 38), TTK_E_ARG, "ttk_cond_im2col_rows: %d x %d x %d elements are too many for one launch", nb, Tout, Kpad);
+	TTK_REQUIRE(sb >= 0 && sc >= 1 && st >= 1, TTK_E_ARG, "ttk_cond_im2col_rows: strides must be positive (sb = %lld, sc = %lld, st = %lld)", (long long)sb, (long long)sc, (long long)st);
+	TTK_REQUIRE(aligned_to(src, 4) && aligned_to(out, dtype == TTK_BF16 ? 2 : 4), TTK_E_ARG, "ttk_cond_im2col_rows: src or out is misaligned for its element type");
+	by_f32_bf16(dtype, [&](auto t) {
+		using T = decltype(t);
+		launch_cond_im2col<T>(src, sb, sc, st, nb, Cin, Tin, Tout, taps, stride, pad, Kpad, (T*)out, (hipStream_t)stream);
+	});
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
+}
+
+int ttk_cond_pool_rows(const float* x, int nb, int T, int C, int mode, float* out, void* stream) {
+	TTK_REQUIRE(x && out, TTK_E_ARG, "ttk_cond_pool_rows: null argument");
+	TTK_REQUIRE(nb >= 1 && nb <= 65535 && T >= 1 && C >= 1, TTK_E_ARG, "ttk_cond_pool_rows: nb = %d, T = %d, C = %d out of range (each >= 1, nb <= 65535)", nb, T, C);
+	TTK_REQUIRE(mode == 0 || mode == 1, TTK_E_ARG, "ttk_cond_pool_rows: bad mode %d (0: position 0, 1: mean)", mode);
+	TTK_REQUIRE(aligned_to(x, 4) && aligned_to(out, 4), TTK_E_ARG, "ttk_cond_pool_rows: x or out is misaligned");
+	launch_cond_pool(x, nb, T, C, mode, out, (hipStream_t)stream);
+	TTK_HIP(hipGetLastError());
+	return TTK_OK;
 }
 
 }  // extern "C"

@@ -91,6 +91,17 @@ __global__ __launch_bounds__(256) void k_attn_rowwave(AttnParams p) {
 	for (int e = 0; e < DPL; ++e) op[e] = cvt<T>(o[e] * inv);
 }
 
+// The launches of the two kernels above, each described once: attn_blocks and the entry points on caller-provided operands (cond.hip: ttk_block_gn_rows,
+// ttk_attn_rowwave) both go through them.
+template <typename OT>
+inline void launch_cond_gn(const float* x, int nb, int Tn, int C, int groups, const float* gamma, const float* beta, OT* out, hipStream_t s) {
+	hipLaunchKernelGGL((k_cond_gn<OT>), dim3(groups, nb), dim3(256), 0, s, x, Tn, C, groups, gamma, beta, out);
+}
+template <typename T>
+inline void launch_attn_rowwave(const AttnParams& ap, hipStream_t s) {   // head width 128, ap.T <= kRowWaveMaxT
+	hipLaunchKernelGGL((k_attn_rowwave<T, 128>), dim3((ap.T + 3) / 4, ap.H, ap.nb), dim3(256), (size_t)(4 * ap.T + 4 * 128) * 4, s, ap);
+}
+
 struct Block { float *gn_g = nullptr, *gn_b = nullptr, *relbias = nullptr; Mat qkv, proj; };
 
 inline int gn_groups(int channels) {    // arch_utils.py:27-44
@@ -123,14 +134,14 @@ inline void attn_blocks(int dt, const std::vector<Block>& blocks, float* x, int 
 	const int hd = C / heads;
 	const int64_t rows = (int64_t)b * Tn;
 	for (const Block& B : blocks) {
-		hipLaunchKernelGGL((k_cond_gn<T>), dim3(groups, b), dim3(256), 0, s, x, Tn, C, groups, B.gn_g, B.gn_b, a);
+		launch_cond_gn<T>(x, b, Tn, C, groups, B.gn_g, B.gn_b, a, s);
 		gemm_plain(dt, a, C, B.qkv, (int)rows, nullptr, qkv, 0, s);
 		AttnParams ap = {};
 		ap.qkv = qkv; ap.ld = 3 * C; ap.q_off = 0; ap.k_off = hd; ap.v_off = 2 * hd; ap.head_stride = 3 * hd;   // head-major [H][3][hd], arch_utils.py:79
 		ap.out = ao; ap.ldo = C; ap.nb = b; ap.T = Tn; ap.H = heads; ap.causal = 0; ap.bias = B.relbias;
 		ap.scale = 1.f / sqrtf((float)hd);                                      // (q * hd^-1/4) . (k * hd^-1/4)
 		if (hd == 64) launch_attn_fwd(dt, ap, s);
-		else hipLaunchKernelGGL((k_attn_rowwave<T, 128>), dim3((Tn + 3) / 4, heads, b), dim3(256), (size_t)(4 * Tn + 4 * 128) * 4, s, ap);
+		else launch_attn_rowwave<T>(ap, s);
 		gemm_plain(dt, ao, C, B.proj, (int)rows, x, x, 1, s);
 	}
 }
